@@ -149,6 +149,21 @@ def emit(out: dict) -> None:
     print(contract_line(out), flush=True)
 
 
+# ---------------------------------------------------------------- --dump-outputs: what the timed path returned, so that two builds can be compared
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """DIR/<name>.npy per array, as float32 (exact for the byte values of a proof); refuses more than DUMP_MAX_BYTES in all"""
+    conv = {name: np.asarray(a).astype(np.float32) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ---------------------------------------------------------------- synthetic inputs (no oracle involved)
 def _g1_add(P, S):
     (x1, y1), (x2, y2) = P, S
@@ -342,7 +357,11 @@ def main():
     ap.add_argument("--no-sweep", action="store_true", help="skip create_proof over the reference's 18 benchmark shapes (an extra field, ~25 s)")
     ap.add_argument("--precompute", type=int, default=1, help="1: bases carry precomputed 2^(c*w) window tables (fixed-base SRS, H2HIP_BASES_PRECOMPUTE)")
     ap.add_argument("--batch", type=int, default=4, help="MSM block: MSMs issued per h2hip_msm_g1_batch_dev call (a prover commits several columns per round); 1 = synchronous")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's proof bytes to DIR/proof.npy (float32, one value per byte; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
 
@@ -471,6 +490,8 @@ def main():
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
     seconds = elapsed / args.steps
+    if args.dump_outputs and rank == 0:   # create_proof returns the proof bytes and nothing else
+        dump_outputs(args.dump_outputs, {"proof": np.frombuffer(proof, dtype=np.uint8)})
     if args.pmc_child:   # a rocprofv3 PMC pass of the parent: the timed workload is all it wants
         pk.free()
         kzg.free()
