@@ -28,6 +28,16 @@ pub struct h2hip_base_circuit_params {
     pub num_instance: u32,
     pub lookup_bits: i32,
 }
+/// BasicDynLookupConfig<key_cols>::new(meta, || FirstPhase, lu_sets) + FlexGateConfig (include/h2hip.h states the layout)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct h2hip_dyn_circuit_params {
+    pub k: u32,
+    pub num_advice: u32,
+    pub num_fixed: u32,
+    pub key_cols: u32,
+    pub lu_sets: u32,
+}
 /// state of libh2hip's ready-made array RNG (`h2hip_array_rng_fill` as the `h2hip_rng_fill_fn`)
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -214,6 +224,9 @@ extern "C" {
     pub fn h2hip_plonk_shape_of(params: *const h2hip_base_circuit_params, out: *mut h2hip_plonk_shape) -> c_int;
     pub fn h2hip_plonk_keygen(ctx: *mut h2hip_ctx, params: *const h2hip_base_circuit_params, g: *const h2hip_bases, g_lagrange: *const h2hip_bases,
                               fixed_host: *const *const c_void, copies: *const u32, ncopies: usize, out: *mut *mut h2hip_plonk_pk) -> c_int;
+    pub fn h2hip_plonk_shape_of_dyn(params: *const h2hip_dyn_circuit_params, out: *mut h2hip_plonk_shape) -> c_int;
+    pub fn h2hip_plonk_keygen_dyn(ctx: *mut h2hip_ctx, params: *const h2hip_dyn_circuit_params, g: *const h2hip_bases, g_lagrange: *const h2hip_bases,
+                                  fixed_host: *const *const c_void, copies: *const u32, ncopies: usize, out: *mut *mut h2hip_plonk_pk) -> c_int;
     pub fn h2hip_plonk_pk_free(ctx: *mut h2hip_ctx, pk: *mut h2hip_plonk_pk);
     pub fn h2hip_plonk_pk_commitments(pk: *const h2hip_plonk_pk, fixed_out: *mut c_void, permutation_out: *mut c_void) -> c_int;
     pub fn h2hip_plonk_pk_set_transcript_repr(pk: *mut h2hip_plonk_pk, fr: *const c_void) -> c_int;
@@ -252,6 +265,9 @@ extern "C" {
                                     transcript_repr: *const c_void, g1: *const c_void, g2: *const c_void, s_g2: *const c_void,
                                     instances_host: *const *const c_void, instance_lens: *const usize, proof: *const u8, proof_len: usize,
                                     accepted: *mut c_int) -> c_int;
+    pub fn h2hip_plonk_verify_proof_dyn(params: *const h2hip_dyn_circuit_params, fixed_commitments: *const c_void, permutation_commitments: *const c_void,
+                                        transcript_repr: *const c_void, g1: *const c_void, g2: *const c_void, s_g2: *const c_void, proof: *const u8,
+                                        proof_len: usize, accepted: *mut c_int) -> c_int;
     pub fn h2hip_pairing_check(g1_points: *const c_void, g2_points: *const c_void, n: usize, is_one: *mut c_int) -> c_int;
     pub fn h2hip_blake2b(personal16: *const c_void, digest_len: c_uint, msg: *const c_void, len: usize, out: *mut c_void) -> c_int;
     // timing / diagnostics

@@ -256,6 +256,9 @@ int ntt_run(h2hip_ctx *ctx, Fr *a, uint32_t log_n, const Fr &omega, const Fr *in
             const Fr *out_scale3);
 int ntt_run_batch(h2hip_ctx *ctx, Fr *const *a, const Fr *const *in_override, size_t ncols, uint32_t log_n, const Fr &omega, uint64_t in_len,
                   const Fr *in_scale3, const Fr *out_scale3);   // the same transform over ncols equal-size columns, 32 columns per launch
+// lookup.hip: out[e][i] = Horner_theta(cols[e*width + 0][i], ..., cols[e*width + width-1][i]) for e < count, i < rows (host arrays of device pointers)
+constexpr uint32_t LK_COMPRESS_MAX_EXPRS = 49, LK_COMPRESS_MAX_WIDTH = 5;   // 48 lookups (LK_BATCH) + their table; key_cols <= 4 plus the enable column
+int lookup_compress_batch_dev(h2hip_ctx *ctx, const Fr *const *cols, Fr *const *out, uint32_t count, uint32_t width, size_t rows, const Fr &theta);
 int fr_scatter_rows(h2hip_ctx *ctx, Fr *const *dst, size_t count, const Fr *src, size_t src_stride, size_t len);   // dst[j][i] = src[j*src_stride + i]
 int upload_jobs(h2hip_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes);   // async H2D of a small table through the context's pinned ring
 int exclusive_scan_u32_segments(h2hip_ctx *ctx, const uint32_t *in, uint32_t *out, uint32_t n, uint32_t segments, size_t in_stride,

@@ -343,6 +343,53 @@ static int sort_columns_keys(h2hip_ctx *ctx, const Fr *const *in, uint32_t count
 }
 static int sort_column_keys(h2hip_ctx *ctx, const Fr *in, Key256 *keys, uint32_t u, uint32_t N) { return sort_columns_keys(ctx, &in, 1, keys, u, N); }
 
+// ---- theta compression of multi-column lookups (BasicDynLookupConfig, halo2-base/src/virtual_region/lookups/basic.rs:67-75): expression e of
+// the launch (blockIdx.y) is out_e[i] = Horner_theta(cols_e[0][i], ..., cols_e[w-1][i]) = (..(c_0 theta + c_1) theta + ..) + c_{w-1}, upstream's
+// compress_expressions.  One launch covers every input expression of a proof and its table, on the 2^k Lagrange rows or on the extended coset.
+struct LkCompressArgs {
+    const Fr *cols[LK_COMPRESS_MAX_EXPRS][LK_COMPRESS_MAX_WIDTH];
+    Fr *out[LK_COMPRESS_MAX_EXPRS];
+    uint32_t width;
+    Fr theta;
+};
+__global__ __launch_bounds__(256) void lk_compress_kernel(LkCompressArgs g, size_t rows) {
+    const Fr *const *c = g.cols[blockIdx.y];
+    Fr *__restrict__ o = g.out[blockIdx.y];
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += stride) {
+        Fr acc = c[0][i];
+        for (uint32_t j = 1; j < g.width; ++j) acc = fe_add(fe_mul(acc, g.theta), c[j][i]);
+        o[i] = acc;
+    }
+}
+int lookup_compress_batch_dev(h2hip_ctx *ctx, const Fr *const *cols, Fr *const *out, uint32_t count, uint32_t width, size_t rows, const Fr &theta) {
+    H2_REQUIRE(ctx && cols && out && width >= 1 && width <= LK_COMPRESS_MAX_WIDTH, "lookup_compress_batch_dev: bad argument");
+    if (!rows || !count) return H2HIP_OK;
+    size_t blocks = (rows + 255) / 256;
+    const size_t cap = std::max<size_t>((size_t)ctx->num_cus * 8 / count, 1);   // a few waves per CU over the whole launch
+    blocks = std::min(blocks, cap);
+    prof_begin(ctx, "lk_compress_kernel");
+    for (uint32_t e0 = 0; e0 < count; e0 += LK_COMPRESS_MAX_EXPRS) {
+        const uint32_t cc = std::min<uint32_t>(count - e0, LK_COMPRESS_MAX_EXPRS);
+        LkCompressArgs a;
+        memset((void *)&a, 0, sizeof(a));
+        for (uint32_t e = 0; e < cc; ++e) {
+            for (uint32_t j = 0; j < width; ++j) {
+                a.cols[e][j] = cols[(size_t)(e0 + e) * width + j];
+                H2_REQUIRE(a.cols[e][j], "lookup_compress_batch_dev: NULL column");
+            }
+            a.out[e] = out[e0 + e];
+            H2_REQUIRE(a.out[e], "lookup_compress_batch_dev: NULL output");
+        }
+        a.width = width;
+        a.theta = theta;
+        hipLaunchKernelGGL(lk_compress_kernel, dim3((uint32_t)blocks, cc), dim3(256), 0, ctx->stream, a, rows);
+    }
+    prof_end(ctx);
+    H2_HIPCHK(hipGetLastError());
+    return H2HIP_OK;
+}
+
 }  // namespace h2
 
 using namespace h2;

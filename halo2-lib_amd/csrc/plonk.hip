@@ -64,18 +64,22 @@ static const uint64_t ZETA[4] = {0xb8ca0b2d36636f23ULL, 0xcc37a73fec2bc5e9ULL, 0
 static const uint64_t DELTA[4] = {0x870e56bbe533e9a2ULL, 0x5b5f898e5e963f25ULL, 0x64ec26aad4c86e71ULL, 0x09226b6e22c6f0caULL};           // 7^(2^28)
 
 // ---------------------------------------------------------------------------------------------- constraint-system shape
-struct Lookup {
-    int q_col;   // fixed column of the complex selector, or -1
-    int advice_col, table_col;
-};
 struct ColumnRef {
     int kind;   // 0 = fixed, 1 = advice, 2 = instance
     int index;
+};
+struct Lookup {
+    int q_col;   // fixed column of the complex selector, or -1
+    int advice_col, table_col;
+    std::vector<ColumnRef> in, tab;   // dynamic lookups (q_col = advice_col = table_col = -1): the expressions compressed by theta
 };
 struct Shape {
     h2hip_base_circuit_params p;
     uint32_t k, n;
     bool with_range, single;
+    bool dyn = false;              // BasicDynLookupConfig + FlexGateConfig (init_dyn); otherwise BaseConfig (init)
+    uint32_t key_cols = 0;         // dyn: KEY_COL; lookup expressions have key_cols + 1 columns
+    uint32_t first_gate_advice = 0;   // advice index of gate column 0 (dyn: behind the table and key columns)
     int table_col = -1, q_lookup_col = -1, first_constant_col = -1, first_q_enable_col = -1;
     uint32_t num_advice_total, num_fixed_total;
     std::vector<Lookup> lookups;
@@ -132,6 +136,52 @@ struct Shape {
         num_perm_sets = (uint32_t)((perm_columns.size() + chunk_len - 1) / chunk_len);
         // range/mod.rs:117-121: the table must fit gate.max_rows = 2^k - meta.minimum_rows() = n - (blinding_factors + 3)
         if (bp.lookup_bits >= 0 && with_range) H2_REQUIRE(((uint64_t)1 << bp.lookup_bits) <= n - (blinding_factors + 3), "lookup table is too large for the circuit degree plus blinding factors");
+        return H2HIP_OK;
+    }
+    // BasicDynLookupConfig::new(meta, || FirstPhase, lu_sets) then FlexGateConfig::configure (memory.rs:92-98); include/h2hip.h states the layout
+    int init_dyn(const h2hip_dyn_circuit_params &dp) {
+        H2_REQUIRE(dp.k >= 4 && dp.k <= 26, "k out of range (4..26)");
+        H2_REQUIRE(dp.key_cols >= 1 && dp.key_cols <= 4, "key_cols out of range (1..4)");
+        H2_REQUIRE(dp.lu_sets >= 1 && dp.lu_sets <= 48, "lu_sets out of range (1..48)");
+        H2_REQUIRE(dp.num_advice >= 1 && dp.num_advice <= 1024 && dp.num_fixed <= 16, "column counts out of range");
+        p = h2hip_base_circuit_params{dp.k, dp.num_advice, 0, dp.num_fixed, 0, -1};
+        k = dp.k;
+        n = 1u << k;
+        dyn = true;
+        with_range = single = false;
+        key_cols = dp.key_cols;
+        const uint32_t m = dp.key_cols, L = dp.lu_sets, ndyn = m * (1 + L);
+        first_gate_advice = ndyn;
+        num_advice_total = ndyn + dp.num_advice;
+        first_constant_col = dp.num_fixed ? (int)(1 + L) : -1;
+        first_q_enable_col = (int)(1 + L + dp.num_fixed);
+        num_fixed_total = 1 + L + dp.num_fixed + dp.num_advice;
+        for (uint32_t s = 0; s < L; ++s) {
+            Lookup l{-1, -1, -1, {}, {}};
+            for (uint32_t j = 0; j < m; ++j) {
+                l.in.push_back({1, (int)(m * (1 + s) + j)});
+                l.tab.push_back({1, (int)j});
+            }
+            l.in.push_back({0, (int)(1 + s)});   // key_is_enabled of the set
+            l.tab.push_back({0, 0});             // table_is_enabled
+            lookups.push_back(l);
+        }
+        for (uint32_t c = 0; c < ndyn; ++c) perm_columns.push_back({1, (int)c});
+        for (uint32_t i = 0; i < dp.num_fixed; ++i) perm_columns.push_back({0, first_constant_col + (int)i});
+        for (uint32_t a = 0; a < dp.num_advice; ++a) perm_columns.push_back({1, (int)(ndyn + a)});
+        for (uint32_t c = 0; c < ndyn; ++c) advice_queries.push_back({(int)c, 0});
+        for (uint32_t a = 0; a < dp.num_advice; ++a)
+            for (int r = 0; r < 4; ++r) advice_queries.push_back({(int)(ndyn + a), r});
+        for (uint32_t c = 0; c < num_fixed_total; ++c) fixed_queries.push_back({(int)c, 0});
+        degree = 4;             // max(gate 3, lookup max(4, 2 + 1 + 1))
+        blinding_factors = 6;   // max(3, four queries of a gate column) + 2, as init's
+        H2_REQUIRE(n > blinding_factors + 8, "k too small for the blinding rows");
+        usable_rows = n - (blinding_factors + 1);
+        chunk_len = degree - 2;
+        quotient_pieces = degree - 1;
+        extended_k = k;
+        while (((uint64_t)1 << extended_k) < (uint64_t)n * quotient_pieces) ++extended_k;
+        num_perm_sets = (uint32_t)((perm_columns.size() + chunk_len - 1) / chunk_len);
         return H2HIP_OK;
     }
     uint32_t num_commitments() const {
@@ -413,7 +463,7 @@ static int keygen_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *fi
         pk->sigma_polys.push_back(p);
         pk->sigma_cosets.push_back(e);
     }
-    if (!sh.lookups.empty()) {   // every lookup of a BaseConfig circuit uses the one range table
+    if (!sh.lookups.empty() && !sh.dyn) {   // every lookup of a BaseConfig circuit uses the one range table (a dynamic table is sorted per proof)
         void *ts = nullptr;
         hipError_t e = hipMalloc(&ts, h2hip_lookup_sorted_table_bytes(sh.usable_rows));
         if (e != hipSuccess) {
@@ -763,7 +813,8 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
     // coefficient and extended forms of the columns just committed): they are queued on a side stream (a child context: own NTT scratch and
     // twiddle cache) behind the event the batch MSM records once its accumulations are done, read the Lagrange values the MSM also reads and
     // write NEW buffers, so they run next to the reduction and to the pointwise kernels that follow.  Single GPU only.
-    const bool overlap = !sharded_any && ctx->plonk_tail_overlap != 0;
+    // (dynamic lookups: the permuted columns wait for theta, so the round-1 overlap schedule below does not apply)
+    const bool overlap = !sharded_any && ctx->plonk_tail_overlap != 0 && !sh.dyn;
     // r05, sharded proofs: lagrange_to_coeff (with its all-gather of the coefficient forms when the columns are dealt to the ranks) and the cosets'
     // coeff_to_extended of the FIRST-ROUND columns run on the side context next to round 2's commitments instead of in front of them
     // with RCCL and more than one rank the side stream's all-gather and the main stream's host exchanges would use ONE communicator from
@@ -952,12 +1003,16 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
         bool own_inp;
     };
     std::vector<LookupState> lks(sh.lookups.size());
+    Fr theta = Fr::zero();
+    Fr *dyn_table = nullptr;   // dynamic lookups: the compressed table over the 2^k rows (one table for all sets)
+    const void *table_sorted = pk->table_sorted;
+    auto lookup_table_values = [&](size_t li) -> const Fr * { return sh.dyn ? dyn_table : pk->fixed_values[sh.lookups[li].table_col]; };
     {
         std::vector<const void *> cols(adv.begin(), adv.end());
         for (size_t li = 0; li < sh.lookups.size(); ++li) {
             const Lookup &l = sh.lookups[li];
             LookupState &s = lks[li];
-            s.own_inp = l.q_col >= 0;
+            s.own_inp = l.q_col >= 0 || sh.dyn;
             if (s.own_inp) H2_CHK(sc.take(n, &s.inp));
             else s.inp = adv[l.advice_col];
             H2_CHK(sc.take(n, &s.ap));
@@ -969,7 +1024,7 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
         auto permute_lookups = [&]() -> int {
             for (size_t li = 0; li < sh.lookups.size(); ++li) {
                 const Lookup &l = sh.lookups[li];
-                if (lks[li].own_inp) H2_CHK(h2hip_fr_mul_batch_dev(ctx, lks[li].inp, pk->fixed_values[l.q_col], adv[l.advice_col], n));
+                if (l.q_col >= 0) H2_CHK(h2hip_fr_mul_batch_dev(ctx, lks[li].inp, pk->fixed_values[l.q_col], adv[l.advice_col], n));
             }
             {   // all lookups read the one table column: their multiset checks come back in one host synchronisation
                 std::vector<const void *> ins(lks.size());
@@ -979,7 +1034,7 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
                     aps[li] = lks[li].ap;
                     sps[li] = lks[li].sp;
                 }
-                if (!lks.empty()) H2_CHK(h2hip_lookup_permute_presorted_batch_dev(ctx, ins.data(), pk->table_sorted, u, aps.data(), sps.data(), lks.size()));
+                if (!lks.empty()) H2_CHK(h2hip_lookup_permute_presorted_batch_dev(ctx, ins.data(), table_sorted, u, aps.data(), sps.data(), lks.size()));
             }
             TailRun ta, ts;   // per lookup the staging holds [a' rows][s' rows][2 blinds]
             tails_reserve(ta, lks.size(), 2 * ((size_t)bf + 1) + 2, bf + 1);
@@ -998,12 +1053,47 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
         // r04: the ADVICE columns' commitments do not wait for it — the batch MSM queues them on its lanes first, then calls the permutation (on
         // this stream), then queues the permuted columns behind it (msm_mid_hook): the first accumulation starts ~0.3 ms earlier
         const bool permute_inside = overlap && ctx->plonk_permute_in_commit && !lks.empty() && !adv.empty();
-        if (permute_inside) {
+        if (sh.dyn) {
+            // (below, once theta is known)
+        } else if (permute_inside) {
             ctx->msm_mid_hook = permute_lookups;
             ctx->msm_mid_after = adv.size();
         } else {
             H2_CHK(permute_lookups());
         }
+        if (sh.dyn) {
+            // Dynamic lookups (BasicDynLookupConfig): theta enters the compressed values, so upstream's order is kept literally — the advice
+            // commitments, theta, then the compression of every set's input and of the table in ONE launch, the per-proof sort of the table
+            // and the batched presorted permutation, then the permuted columns' commitments
+            std::vector<const void *> acols(adv.begin(), adv.end());
+            std::vector<G1Affine> apts;
+            H2_CHK(commit_points(pk->g_lagrange, acols, n, apts));
+            for (const G1Affine &p : apts) H2_CHK(tr.write_point(p));
+            theta = tr.squeeze_challenge();
+            H2_CHK(sc.take(n, &dyn_table));
+            const uint32_t w = sh.key_cols + 1;
+            std::vector<const Fr *> ccols;
+            std::vector<Fr *> couts;
+            auto column_lagrange = [&](const ColumnRef &c) -> const Fr * { return c.kind == 0 ? pk->fixed_values[c.index] : adv[c.index]; };
+            for (size_t li = 0; li < lks.size(); ++li) {
+                for (const ColumnRef &c : sh.lookups[li].in) ccols.push_back(column_lagrange(c));
+                couts.push_back(lks[li].inp);
+            }
+            for (const ColumnRef &c : sh.lookups[0].tab) ccols.push_back(column_lagrange(c));
+            couts.push_back(dyn_table);
+            H2_CHK(lookup_compress_batch_dev(ctx, ccols.data(), couts.data(), (uint32_t)couts.size(), w, n, theta));
+            Fr *ts = nullptr;   // sorted keys (Key256, 32 bytes like an Fr) of the compressed table's usable rows
+            H2_CHK(sc.take(h2hip_lookup_sorted_table_bytes(u) / sizeof(Fr), &ts));
+            H2_CHK(h2hip_lookup_table_sort_dev(ctx, dyn_table, u, ts));
+            table_sorted = ts;
+            H2_CHK(permute_lookups());
+            laps.lap(ST_LOOKUP_PERMUTE);
+            std::vector<const void *> lcols(cols.begin() + (long)adv.size(), cols.end());
+            std::vector<G1Affine> lpts;
+            H2_CHK(commit_points(pk->g_lagrange, lcols, n, lpts));
+            for (const G1Affine &p : lpts) H2_CHK(tr.write_point(p));
+            laps.lap(ST_COMMIT_ROUND1);
+        } else {
         laps.lap(ST_LOOKUP_PERMUTE);
         std::vector<G1Affine> pts;
         if (overlap) {   // this round's columns -> coefficient and extended form, next to the commitments' reduction and the grand products
@@ -1026,10 +1116,10 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
         H2_REQUIRE(!ctx->msm_mid_hook && !ctx->msm_col_hook, "internal: the commitment round did not run the lookup permutation / the advice uploads");
         H2_CHK(side_fire_if_pending());
         for (size_t i = 0; i < adv.size(); ++i) H2_CHK(tr.write_point(pts[i]));
-        const Fr theta = tr.squeeze_challenge();
-        (void)theta;
+        theta = tr.squeeze_challenge();   // (BaseConfig: every lookup is a single expression, theta does not enter the values)
         for (size_t i = adv.size(); i < pts.size(); ++i) H2_CHK(tr.write_point(pts[i]));
         laps.lap(ST_COMMIT_ROUND1);
+        }
     }
     const Fr beta = tr.squeeze_challenge();
     const Fr gamma = tr.squeeze_challenge();
@@ -1089,7 +1179,7 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
         }
         for (size_t li = 0; li < lks.size() && m; ++li) {
             LookupState &s = lks[li];
-            H2_CHK(h2hip_lookup_product_terms_dev(ctx, num + (S + li) * m, den + (S + li) * m, s.inp + a, pk->fixed_values[sh.lookups[li].table_col] + a, s.ap + a,
+            H2_CHK(h2hip_lookup_product_terms_dev(ctx, num + (S + li) * m, den + (S + li) * m, s.inp + a, lookup_table_values(li) + a, s.ap + a,
                                                   s.sp + a, m, &beta, &gamma));
         }
         std::vector<Fr> totals(nseg, Fr::one());
@@ -1188,7 +1278,7 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
         const size_t lk0 = merged ? 1 : 0;   // the lookups' first segment
         for (size_t li = 0; li < lks.size(); ++li) {
             LookupState &s = lks[li];
-            H2_CHK(h2hip_lookup_product_terms_dev(ctx, num + (lk0 + li) * (size_t)u, den + (lk0 + li) * (size_t)u, s.inp, pk->fixed_values[sh.lookups[li].table_col],
+            H2_CHK(h2hip_lookup_product_terms_dev(ctx, num + (lk0 + li) * (size_t)u, den + (lk0 + li) * (size_t)u, s.inp, lookup_table_values(li),
                                                   s.ap, s.sp, u, &beta, &gamma));
             H2_CHK(sc.take(n, &s.z));
             lk_z[li] = s.z;
@@ -1359,7 +1449,23 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
             H2_CHK(to_ext(round1, round1_cos, ctx));
         }
     }
+    Fr *dyn_table_cos = nullptr;   // dynamic lookups: the compressed table on the extended domain
     auto lookup_input_cosets = [&]() -> int {
+        if (sh.dyn) {
+            // compressed from the extended-domain forms that h(X) reads anyway (the advice cosets, the key's fixed cosets): one launch, no transform
+            std::vector<const Fr *> ccols;
+            std::vector<Fr *> couts;
+            auto column_coset = [&](const ColumnRef &c) -> const Fr * { return c.kind == 0 ? fixed_cos(c.index) : adv_cos[c.index]; };
+            for (size_t li = 0; li < lks.size(); ++li) {
+                H2_CHK(sc.take(ne_loc, &lk_cos[li].inp));
+                for (const ColumnRef &c : sh.lookups[li].in) ccols.push_back(column_coset(c));
+                couts.push_back(lk_cos[li].inp);
+            }
+            H2_CHK(sc.take(ne_loc, &dyn_table_cos));
+            for (const ColumnRef &c : sh.lookups[0].tab) ccols.push_back(column_coset(c));
+            couts.push_back(dyn_table_cos);
+            return lookup_compress_batch_dev(ctx, ccols.data(), couts.data(), (uint32_t)couts.size(), sh.key_cols + 1, ne_loc, theta);
+        }
         for (size_t li = 0; li < lks.size(); ++li) {
             const Lookup &l = sh.lookups[li];
             LookupCosets &c = lk_cos[li];
@@ -1492,7 +1598,7 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
             std::vector<const void *> gq(sh.p.num_advice), ga(sh.p.num_advice);
             for (uint32_t a = 0; a < sh.p.num_advice; ++a) {
                 gq[a] = fixed_cos(sh.first_q_enable_col + (int)a) + off;
-                ga[a] = adv_cos[a] + off;
+                ga[a] = adv_cos[sh.first_gate_advice + a] + off;
             }
             H2_CHK(h2hip_quotient_flex_gate_batch_dev(ctx, acc_loc + off, gq.data(), ga.data(), gq.size(), ek_, k, &y));
         }
@@ -1521,7 +1627,7 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
                 const LookupCosets &c = lk_cos[li];
                 lz[li] = c.z + off;
                 la[li] = (c.inp ? c.inp : adv_cos[l.advice_col]) + off;
-                ls[li] = fixed_cos(l.table_col) + off;
+                ls[li] = (sh.dyn ? dyn_table_cos : fixed_cos(l.table_col)) + off;
                 lap[li] = c.ap + off;
                 lsp[li] = c.sp + off;
             }
@@ -1574,6 +1680,7 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
         sc.release(c.sp);
         if (c.inp) sc.release(c.inp);
     }
+    if (dyn_table_cos) sc.release(dyn_table_cos);
     for (Fr *p : adv_cos) sc.release(p);
     for (Fr *p : inst_cos) sc.release(p);
     // ---- back to coefficients, split into pieces, commit
@@ -1877,10 +1984,7 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
 
 extern "C" {
 
-int h2hip_plonk_shape_of(const h2hip_base_circuit_params *params, h2hip_plonk_shape *out) {
-    H2_REQUIRE(params && out, "NULL argument");
-    Shape sh;
-    H2_CHK(sh.init(*params));
+static void fill_shape(const Shape &sh, h2hip_plonk_shape *out) {
     out->num_advice_total = sh.num_advice_total;
     out->num_fixed_total = sh.num_fixed_total;
     out->table_col = sh.table_col;
@@ -1897,6 +2001,21 @@ int h2hip_plonk_shape_of(const h2hip_base_circuit_params *params, h2hip_plonk_sh
     out->quotient_pieces = sh.quotient_pieces;
     out->num_commitments = sh.num_commitments();
     out->num_evals = sh.num_evals();
+}
+
+int h2hip_plonk_shape_of(const h2hip_base_circuit_params *params, h2hip_plonk_shape *out) {
+    H2_REQUIRE(params && out, "NULL argument");
+    Shape sh;
+    H2_CHK(sh.init(*params));
+    fill_shape(sh, out);
+    return H2HIP_OK;
+}
+
+int h2hip_plonk_shape_of_dyn(const h2hip_dyn_circuit_params *params, h2hip_plonk_shape *out) {
+    H2_REQUIRE(params && out, "NULL argument");
+    Shape sh;
+    H2_CHK(sh.init_dyn(*params));
+    fill_shape(sh, out);
     return H2HIP_OK;
 }
 
@@ -1934,12 +2053,27 @@ static int check_selectors_stay_apart(const Shape &sh, const void *const *fixed_
     return H2HIP_OK;
 }
 
+static int keygen_common(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const h2hip_bases *g, const h2hip_bases *g_lagrange, const void *const *fixed_host,
+                         const uint32_t *copies, size_t ncopies, int rc, h2hip_plonk_pk **out);
+
 int h2hip_plonk_keygen(h2hip_ctx *ctx, const h2hip_base_circuit_params *params, const h2hip_bases *g, const h2hip_bases *g_lagrange,
                        const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out) {
     H2_DEVICE_GUARD(ctx);
     H2_REQUIRE(ctx && params && g && g_lagrange && fixed_host && out && (ncopies == 0 || copies), "NULL argument");
     h2hip_plonk_pk *pk = new h2hip_plonk_pk();
-    int rc = pk->sh.init(*params);
+    return keygen_common(ctx, pk, g, g_lagrange, fixed_host, copies, ncopies, pk->sh.init(*params), out);
+}
+
+int h2hip_plonk_keygen_dyn(h2hip_ctx *ctx, const h2hip_dyn_circuit_params *params, const h2hip_bases *g, const h2hip_bases *g_lagrange,
+                           const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && params && g && g_lagrange && fixed_host && out && (ncopies == 0 || copies), "NULL argument");
+    h2hip_plonk_pk *pk = new h2hip_plonk_pk();
+    return keygen_common(ctx, pk, g, g_lagrange, fixed_host, copies, ncopies, pk->sh.init_dyn(*params), out);
+}
+
+static int keygen_common(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const h2hip_bases *g, const h2hip_bases *g_lagrange, const void *const *fixed_host,
+                         const uint32_t *copies, size_t ncopies, int rc, h2hip_plonk_pk **out) {
     if (rc == H2HIP_OK && (g->n < pk->sh.n || g_lagrange->n < pk->sh.n)) {
         set_error("h2hip_plonk_keygen: the SRS holds fewer than 2^k bases");
         rc = H2HIP_ERR_INVALID;
@@ -2065,6 +2199,7 @@ int h2hip_plonk_pk_set_sharding(h2hip_plonk_pk *pk, h2hip_comm *comm, const h2hi
     shard_release(pk);
     int world = 1, rank = 0;
     if (comm) H2_CHK(h2hip_comm_info(comm, &world, &rank, nullptr));
+    H2_REQUIRE(!(comm && pk->sh.dyn), "h2hip_plonk_pk_set_sharding: proofs with a dynamic lookup table run on one GPU");
     if (!comm || (world <= 1 && !(flags & H2HIP_SHARD_FORCE))) return H2HIP_OK;
     H2_REQUIRE(g_shard && g_lagrange_shard, "NULL argument");
     H2_REQUIRE(offset <= pk->sh.n && len <= pk->sh.n - offset && g_shard->n >= len && g_lagrange_shard->n >= len, "shard range outside the SRS / shard base sets too small");

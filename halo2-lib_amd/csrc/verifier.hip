@@ -454,24 +454,32 @@ F2 load_f2(const uint8_t *p) {
 
 }  // namespace
 
-extern "C" {
-
-// verify_proof + VerifierSHPLONK + SingleStrategy for a BaseConfig circuit.  fixed_commitments / permutation_commitments: the verifying key
-// (h2hip_plonk_pk_commitments), transcript_repr: the key's hash into the transcript, g1: params.g[0] (the G1 generator of the SRS), g2 / s_g2:
-// 128 bytes each as SerdeFormat::RawBytes stores them (x.c0, x.c1, y.c0, y.c1 Montgomery limbs).  *accepted = 1 iff the proof verifies; a
-// malformed proof is a rejection (accepted = 0, return H2HIP_OK); H2HIP_ERR_INVALID is reserved for bad arguments.
-int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
-                             const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
-                             const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted) {
-    H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
-    *accepted = 0;
+namespace {
+// What the verifier needs of a constraint system: the query lists in the prover's order, the permutation columns, the gates, and every lookup
+// as (input, table) lists of expressions, each expression a product of columns queried at the current row; a lookup's expressions are
+// compressed by Horner in theta (upstream's compress_expressions) — BaseConfig's lookups have one expression each, so theta drops out there.
+struct VCol {
+    int kind;   // 0 = fixed, 1 = advice, 2 = instance
+    int index;
+};
+using VExpr = std::vector<VCol>;   // product of columns at Rotation::cur()
+struct VShape {
     h2hip_plonk_shape sh;
-    H2_CHK(h2hip_plonk_shape_of(params, &sh));
+    uint32_t k, num_instance;
+    std::vector<std::pair<int, int>> adv_q;   // (advice column, rotation)
+    std::vector<int> fixed_q;                 // fixed columns, queried at the current row
+    std::vector<VCol> perm;
+    std::vector<std::pair<int, int>> gates;   // (q_enable fixed column, advice column): q * (a + b*c - d) at rotations 0..3
+    std::vector<std::vector<VExpr>> lk_in, lk_tab;
+};
+
+int verify_impl(const VShape &vs, const void *fixed_commitments, const void *permutation_commitments, const void *transcript_repr, const void *g1,
+                const void *g2, const void *s_g2, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
+                int *accepted) {
+    const h2hip_plonk_shape &sh = vs.sh;
     H2_REQUIRE(sh.num_perm_columns == 0 || permutation_commitments, "NULL argument");
-    H2_REQUIRE(params->num_instance == 0 || (instances_host && instance_lens), "NULL argument");
-    const uint32_t k = params->k, n = 1u << k, bf = sh.blinding_factors;
-    const uint32_t num_advice = params->num_advice, nla = sh.num_advice_total - num_advice;
-    const bool with_range = sh.table_col >= 0, single = sh.q_lookup_col >= 0;
+    H2_REQUIRE(vs.num_instance == 0 || (instances_host && instance_lens), "NULL argument");
+    const uint32_t k = vs.k, n = 1u << k, bf = sh.blinding_factors;
     const uint32_t chunk = sh.degree - 2;
     std::vector<G1Affine> fixed_comm(sh.num_fixed_total), perm_comm(sh.num_perm_columns);
     memcpy(fixed_comm.data(), fixed_commitments, sizeof(G1Affine) * fixed_comm.size());
@@ -495,8 +503,8 @@ int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void
 
     Reader tr(proof, proof_len);
     tr.common_scalar(repr);
-    std::vector<std::vector<Fr>> inst(params->num_instance);
-    for (uint32_t i = 0; i < params->num_instance; ++i) {
+    std::vector<std::vector<Fr>> inst(vs.num_instance);
+    for (uint32_t i = 0; i < vs.num_instance; ++i) {
         if (instance_lens[i] > sh.usable_rows) return H2HIP_OK;   // InstanceTooLarge: rejected
         inst[i].resize(instance_lens[i]);
         if (instance_lens[i]) memcpy(inst[i].data(), instances_host[i], sizeof(Fr) * instance_lens[i]);
@@ -504,7 +512,7 @@ int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void
     }
     std::vector<G1Affine> advice_comm(sh.num_advice_total);
     for (auto &c : advice_comm) c = tr.read_point();
-    (void)tr.squeeze_challenge();   // theta
+    const Fr theta = tr.squeeze_challenge();
     std::vector<G1Affine> lk_a_comm(sh.num_lookups), lk_s_comm(sh.num_lookups), lk_z_comm(sh.num_lookups), permz_comm(sh.num_perm_sets);
     for (uint32_t i = 0; i < sh.num_lookups; ++i) {
         lk_a_comm[i] = tr.read_point();
@@ -519,16 +527,12 @@ int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void
     for (auto &c : h_comm) c = tr.read_point();
     const Fr x = tr.squeeze_challenge();
     // evaluations, in the prover's order
-    const uint32_t n_adv_q = 4 * num_advice + nla;
-    std::vector<Fr> adv_ev(n_adv_q);
+    std::vector<Fr> adv_ev(vs.adv_q.size());
     for (auto &e : adv_ev) e = tr.read_scalar();
-    std::vector<int> fixed_q;   // fixed columns in query order: constants, table, q_lookup, q_enable
-    for (uint32_t i = 0; i < params->num_fixed; ++i) fixed_q.push_back(sh.first_constant_col + (int)i);
-    if (with_range) fixed_q.push_back(sh.table_col);
-    if (single) fixed_q.push_back(sh.q_lookup_col);
-    for (uint32_t i = 0; i < num_advice; ++i) fixed_q.push_back(sh.first_q_enable_col + (int)i);
+    std::map<std::pair<int, int>, Fr> adv_at_q;
+    for (size_t i = 0; i < vs.adv_q.size(); ++i) adv_at_q[vs.adv_q[i]] = adv_ev[i];
     std::vector<Fr> fixed_ev(sh.num_fixed_total, Fr::zero());
-    for (int c : fixed_q) fixed_ev[c] = tr.read_scalar();
+    for (int c : vs.fixed_q) fixed_ev[c] = tr.read_scalar();
     const Fr random_eval = tr.read_scalar();
     std::vector<Fr> sigma_ev(sh.num_perm_columns);
     for (auto &e : sigma_ev) e = tr.read_scalar();
@@ -565,24 +569,30 @@ int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void
         return fe_mul(fe_mul(fe_sub(xn, one), wi), fe_inv(fe_mul(fr_u64(n), fe_sub(x, wi))));
     };
     if (fe_sub(xn, one).is_zero()) return H2HIP_OK;   // x on the domain: negligible; reject rather than divide by zero
-    std::vector<Fr> inst_ev(params->num_instance, Fr::zero());
-    for (uint32_t c = 0; c < params->num_instance; ++c)
+    std::vector<Fr> inst_ev(vs.num_instance, Fr::zero());
+    for (uint32_t c = 0; c < vs.num_instance; ++c)
         for (size_t j = 0; j < inst[c].size(); ++j) inst_ev[c] = fe_add(inst_ev[c], fe_mul(inst[c][j], l_i((int)j)));
     const Fr l_last = l_i(-(int)(bf + 1)), l_0 = l_i(0);
     Fr l_blind = Fr::zero();
     for (uint32_t r = 1; r <= bf; ++r) l_blind = fe_add(l_blind, l_i(-(int)(bf + 1) + (int)r));
     const Fr active = fe_sub(fe_sub(one, l_last), l_blind);
-    auto adv_at = [&](uint32_t col, uint32_t r) -> Fr { return col < num_advice ? adv_ev[4 * col + r] : adv_ev[4 * num_advice + (col - num_advice)]; };
-    auto perm_col_eval = [&](uint32_t pc) -> Fr {   // permutation columns: constants, advice (gate then lookup), instance
-        if (pc < params->num_fixed) return fixed_ev[sh.first_constant_col + (int)pc];
-        pc -= params->num_fixed;
-        if (pc < sh.num_advice_total) return adv_at(pc, 0);
-        return inst_ev[pc - sh.num_advice_total];
+    auto adv_at = [&](int col, int r) -> Fr { return adv_at_q[{col, r}]; };
+    auto col_eval = [&](const VCol &c) -> Fr { return c.kind == 0 ? fixed_ev[c.index] : c.kind == 1 ? adv_at(c.index, 0) : inst_ev[c.index]; };
+    auto compress = [&](const std::vector<VExpr> &exprs) -> Fr {
+        Fr acc = Fr::zero();
+        for (const VExpr &e : exprs) {
+            Fr t = one;
+            for (size_t i = 0; i < e.size(); ++i) t = i ? fe_mul(t, col_eval(e[i])) : col_eval(e[i]);
+            acc = fe_add(fe_mul(acc, theta), t);
+        }
+        return acc;
     };
     Fr expected = Fr::zero();
     auto fold = [&](const Fr &term) { expected = fe_add(fe_mul(expected, y), term); };
-    for (uint32_t a = 0; a < num_advice; ++a)
-        fold(fe_mul(fixed_ev[sh.first_q_enable_col + (int)a], fe_sub(fe_add(adv_at(a, 0), fe_mul(adv_at(a, 1), adv_at(a, 2))), adv_at(a, 3))));
+    for (const auto &g : vs.gates) {
+        const int a = g.second;
+        fold(fe_mul(fixed_ev[g.first], fe_sub(fe_add(adv_at(a, 0), fe_mul(adv_at(a, 1), adv_at(a, 2))), adv_at(a, 3))));
+    }
     if (sh.num_perm_sets) {
         fold(fe_mul(l_0, fe_sub(one, perm_ev[0].e0)));
         const Fr zl = perm_ev[sh.num_perm_sets - 1].e0;
@@ -592,9 +602,9 @@ int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void
             const uint32_t c0 = si * chunk, c1 = std::min<uint32_t>(c0 + chunk, sh.num_perm_columns);
             Fr left = perm_ev[si].e1, right = perm_ev[si].e0;
             Fr cur = fe_mul(fe_mul(beta, x), fe_pow_u64(delta, c0));
-            for (uint32_t c = c0; c < c1; ++c) left = fe_mul(left, fe_add(fe_add(perm_col_eval(c), fe_mul(beta, sigma_ev[c])), gamma));
+            for (uint32_t c = c0; c < c1; ++c) left = fe_mul(left, fe_add(fe_add(col_eval(vs.perm[c]), fe_mul(beta, sigma_ev[c])), gamma));
             for (uint32_t c = c0; c < c1; ++c) {
-                right = fe_mul(right, fe_add(fe_add(perm_col_eval(c), cur), gamma));
+                right = fe_mul(right, fe_add(fe_add(col_eval(vs.perm[c]), cur), gamma));
                 cur = fe_mul(cur, delta);
             }
             fold(fe_mul(active, fe_sub(left, right)));
@@ -602,9 +612,7 @@ int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void
     }
     for (uint32_t li = 0; li < sh.num_lookups; ++li) {
         const LkEv &l = lk_ev[li];
-        const uint32_t acol = single ? 0 : num_advice + li;
-        const Fr inp = single ? fe_mul(fixed_ev[sh.q_lookup_col], adv_at(0, 0)) : adv_at(acol, 0);
-        const Fr tab = fixed_ev[sh.table_col];
+        const Fr inp = compress(vs.lk_in[li]), tab = compress(vs.lk_tab[li]);
         fold(fe_mul(l_0, fe_sub(one, l.pe)));
         fold(fe_mul(l_last, fe_sub(fe_sqr(l.pe), l.pe)));
         fold(fe_mul(active, fe_sub(fe_mul(fe_mul(l.pne, fe_add(l.ae, beta)), fe_add(l.se, gamma)), fe_mul(fe_mul(l.pe, fe_add(inp, beta)), fe_add(tab, gamma)))));
@@ -621,9 +629,7 @@ int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void
     std::vector<VQuery> queries;
     std::vector<int> adv_key(sh.num_advice_total);
     for (uint32_t c = 0; c < sh.num_advice_total; ++c) adv_key[c] = add_comm(advice_comm[c]);
-    for (uint32_t a = 0; a < num_advice; ++a)
-        for (int r = 0; r < 4; ++r) queries.push_back({adv_key[a], rot(r), adv_at(a, (uint32_t)r)});
-    for (uint32_t i = 0; i < nla; ++i) queries.push_back({adv_key[num_advice + i], x, adv_at(num_advice + i, 0)});
+    for (size_t i = 0; i < vs.adv_q.size(); ++i) queries.push_back({adv_key[vs.adv_q[i].first], rot(vs.adv_q[i].second), adv_ev[i]});
     const Fr x_next = rot(1), x_last = rot(-(int)(bf + 1)), x_inv = rot(-1);
     {
         std::vector<VQuery> tail;
@@ -644,7 +650,7 @@ int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void
         queries.push_back({ka, x_inv, l.aie});
         queries.push_back({kz, x_next, l.pne});
     }
-    for (int c : fixed_q) queries.push_back({add_comm(fixed_comm[c]), x, fixed_ev[c]});
+    for (int c : vs.fixed_q) queries.push_back({add_comm(fixed_comm[c]), x, fixed_ev[c]});
     for (uint32_t j = 0; j < sh.num_perm_columns; ++j) queries.push_back({add_comm(perm_comm[j]), x, sigma_ev[j]});
     {   // h commitment = sum_i xn^i H_i
         XYZZ hc = XYZZ::identity();
@@ -710,6 +716,82 @@ int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void
     F12 f = f12_mul(miller_loop(h2, SQ2), miller_loop(right, Q2));
     *accepted = f12_is_one(final_exponentiation(f)) ? 1 : 0;
     return H2HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// verify_proof + VerifierSHPLONK + SingleStrategy for a BaseConfig circuit.  fixed_commitments / permutation_commitments: the verifying key
+// (h2hip_plonk_pk_commitments), transcript_repr: the key's hash into the transcript, g1: params.g[0] (the G1 generator of the SRS), g2 / s_g2:
+// 128 bytes each as SerdeFormat::RawBytes stores them (x.c0, x.c1, y.c0, y.c1 Montgomery limbs).  *accepted = 1 iff the proof verifies; a
+// malformed proof is a rejection (accepted = 0, return H2HIP_OK); H2HIP_ERR_INVALID is reserved for bad arguments.
+int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
+                             const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
+                             const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted) {
+    H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
+    *accepted = 0;
+    VShape vs;
+    H2_CHK(h2hip_plonk_shape_of(params, &vs.sh));
+    const h2hip_plonk_shape &sh = vs.sh;
+    vs.k = params->k;
+    vs.num_instance = params->num_instance;
+    const uint32_t num_advice = params->num_advice, nla = sh.num_advice_total - num_advice;
+    const bool with_range = sh.table_col >= 0, single = sh.q_lookup_col >= 0;
+    for (uint32_t a = 0; a < num_advice; ++a)
+        for (int r = 0; r < 4; ++r) vs.adv_q.push_back({(int)a, r});
+    for (uint32_t i = 0; i < nla; ++i) vs.adv_q.push_back({(int)(num_advice + i), 0});
+    // fixed columns in query order: constants, table, q_lookup, q_enable
+    for (uint32_t i = 0; i < params->num_fixed; ++i) vs.fixed_q.push_back(sh.first_constant_col + (int)i);
+    if (with_range) vs.fixed_q.push_back(sh.table_col);
+    if (single) vs.fixed_q.push_back(sh.q_lookup_col);
+    for (uint32_t i = 0; i < num_advice; ++i) vs.fixed_q.push_back(sh.first_q_enable_col + (int)i);
+    // permutation columns: constants, advice (gate then lookup), instance
+    for (uint32_t i = 0; i < params->num_fixed; ++i) vs.perm.push_back({0, sh.first_constant_col + (int)i});
+    for (uint32_t i = 0; i < sh.num_advice_total; ++i) vs.perm.push_back({1, (int)i});
+    for (uint32_t i = 0; i < params->num_instance; ++i) vs.perm.push_back({2, (int)i});
+    for (uint32_t a = 0; a < num_advice; ++a) vs.gates.push_back({sh.first_q_enable_col + (int)a, (int)a});
+    for (uint32_t li = 0; li < sh.num_lookups; ++li) {
+        vs.lk_in.push_back({single ? VExpr{{0, sh.q_lookup_col}, {1, 0}} : VExpr{{1, (int)(num_advice + li)}}});
+        vs.lk_tab.push_back({VExpr{{0, sh.table_col}}});
+    }
+    return verify_impl(vs, fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2, instances_host, instance_lens, proof, proof_len,
+                       accepted);
+}
+
+// the same for the dynamic-lookup configuration (include/h2hip.h states its layout): the lookups' compressed input and table evaluations are
+// Horner sums in theta of the advice / fixed openings at x
+int h2hip_plonk_verify_proof_dyn(const h2hip_dyn_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
+                                 const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const uint8_t *proof, size_t proof_len,
+                                 int *accepted) {
+    H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
+    *accepted = 0;
+    VShape vs;
+    H2_CHK(h2hip_plonk_shape_of_dyn(params, &vs.sh));
+    const h2hip_plonk_shape &sh = vs.sh;
+    vs.k = params->k;
+    vs.num_instance = 0;
+    const uint32_t m = params->key_cols, L = params->lu_sets, ndyn = m * (1 + L);
+    for (uint32_t c = 0; c < ndyn; ++c) vs.adv_q.push_back({(int)c, 0});
+    for (uint32_t a = 0; a < params->num_advice; ++a)
+        for (int r = 0; r < 4; ++r) vs.adv_q.push_back({(int)(ndyn + a), r});
+    for (uint32_t c = 0; c < sh.num_fixed_total; ++c) vs.fixed_q.push_back((int)c);
+    for (uint32_t c = 0; c < ndyn; ++c) vs.perm.push_back({1, (int)c});
+    for (uint32_t i = 0; i < params->num_fixed; ++i) vs.perm.push_back({0, sh.first_constant_col + (int)i});
+    for (uint32_t a = 0; a < params->num_advice; ++a) vs.perm.push_back({1, (int)(ndyn + a)});
+    for (uint32_t a = 0; a < params->num_advice; ++a) vs.gates.push_back({sh.first_q_enable_col + (int)a, (int)(ndyn + a)});
+    for (uint32_t s = 0; s < L; ++s) {
+        std::vector<VExpr> in, tab;
+        for (uint32_t j = 0; j < m; ++j) {
+            in.push_back(VExpr{{1, (int)(m * (1 + s) + j)}});
+            tab.push_back(VExpr{{1, (int)j}});
+        }
+        in.push_back(VExpr{{0, (int)(1 + s)}});
+        tab.push_back(VExpr{{0, 0}});
+        vs.lk_in.push_back(in);
+        vs.lk_tab.push_back(tab);
+    }
+    return verify_impl(vs, fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2, nullptr, nullptr, proof, proof_len, accepted);
 }
 
 // e(P_0, Q_0) * ... * e(P_{n-1}, Q_{n-1}) == 1 — the "final CPU-side pairing" of the north star as an entry of its own (the verifier above ends in

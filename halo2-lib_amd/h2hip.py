@@ -112,6 +112,8 @@ _PROTOS = {
     "h2hip_lookup_product_terms_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "h2hip_plonk_shape_of": (_int, [_vp, _vp]),
     "h2hip_plonk_keygen": (_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, C.POINTER(_vp)]),
+    "h2hip_plonk_shape_of_dyn": (_int, [_vp, _vp]),
+    "h2hip_plonk_keygen_dyn": (_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, C.POINTER(_vp)]),
     "h2hip_plonk_pk_free": (None, [_vp, _vp]),
     "h2hip_plonk_pk_commitments": (_int, [_vp, _vp, _vp]),
     "h2hip_plonk_pk_set_transcript_repr": (_int, [_vp, _vp]),
@@ -140,6 +142,7 @@ _PROTOS = {
     "h2hip_poseidon_set_spec": (_int, [_vp, _u32, _u32, _u32, _vp, _vp]),
     "h2hip_poseidon_permute_batch_dev": (_int, [_vp, _vp, _vp, _u32, _sz]),
     "h2hip_plonk_verify_proof": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_int)]),
+    "h2hip_plonk_verify_proof_dyn": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_int)]),
     "h2hip_pairing_check": (_int, [_vp, _vp, _sz, C.POINTER(_int)]),
     "h2hip_blake2b": (_int, [_vp, C.c_uint, _vp, _sz, _vp]),
     "h2hip_bench_gather": (_int, [_vp, _u32, _sz, _u32, _u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -36,6 +36,17 @@ class BaseCircuitParams(C.Structure):
         return cls(k, num_advice, num_lookup_advice, num_fixed, num_instance, -1 if lookup_bits is None else lookup_bits)
 
 
+class DynLookupCircuitParams(C.Structure):
+    """h2hip_dyn_circuit_params: BasicDynLookupConfig::<key_cols>::new(meta, || FirstPhase, lu_sets) followed by FlexGateConfig::configure
+    (halo2-base/src/virtual_region/lookups/basic.rs:52-78, the RAMCircuit of virtual_region/tests/lookups/memory.rs:92-98)"""
+    _fields_ = [("k", C.c_uint32), ("num_advice", C.c_uint32), ("num_fixed", C.c_uint32), ("key_cols", C.c_uint32), ("lu_sets", C.c_uint32)]
+    num_instance = 0   # the configuration has no instance columns
+
+    @classmethod
+    def new(cls, k, num_advice, num_fixed, key_cols, lu_sets):
+        return cls(k, num_advice, num_fixed, key_cols, lu_sets)
+
+
 class ConstraintSystemShape(C.Structure):
     """what BaseConfig::configure derives from the params (h2hip_plonk_shape)"""
     _fields_ = [("num_advice_total", C.c_uint32), ("num_fixed_total", C.c_uint32), ("table_col", C.c_int32), ("first_constant_col", C.c_int32),
@@ -44,20 +55,29 @@ class ConstraintSystemShape(C.Structure):
                 ("usable_rows", C.c_uint32), ("quotient_pieces", C.c_uint32), ("num_commitments", C.c_uint32), ("num_evals", C.c_uint32)]
 
 
-def shape_of(ctx: Context, params: BaseCircuitParams) -> ConstraintSystemShape:
+def shape_of(ctx: Context, params) -> ConstraintSystemShape:
     out = ConstraintSystemShape()
-    ctx._chk(ctx.lib.h2hip_plonk_shape_of(C.byref(params), C.byref(out)))
+    fn = ctx.lib.h2hip_plonk_shape_of_dyn if isinstance(params, DynLookupCircuitParams) else ctx.lib.h2hip_plonk_shape_of
+    ctx._chk(fn(C.byref(params), C.byref(out)))
     return out
 
 
-def transcript_repr(params: BaseCircuitParams, fixed_commitments: np.ndarray, permutation_commitments: np.ndarray) -> int:
+def describe(params) -> str:
+    """the key description transcript_repr hashes (one per configuration)"""
+    if isinstance(params, DynLookupCircuitParams):
+        return "halo2-lib_amd BasicDynLookupConfig k=%d advice=%d fixed=%d key_cols=%d lu_sets=%d" % (
+            params.k, params.num_advice, params.num_fixed, params.key_cols, params.lu_sets)
+    return "halo2-lib_amd BaseConfig k=%d advice=%d lookup_advice=%d fixed=%d instance=%d lookup_bits=%s" % (
+        params.k, params.num_advice, params.num_lookup_advice, params.num_fixed, params.num_instance,
+        None if params.lookup_bits < 0 else params.lookup_bits)
+
+
+def transcript_repr(params: BaseCircuitParams | DynLookupCircuitParams, fixed_commitments: np.ndarray, permutation_commitments: np.ndarray) -> int:
     """Stand-in for VerifyingKey::transcript_repr.  Upstream hashes the Rust Debug rendering of the pinned verifying key with
     Blake2b-512("Halo2-Verify-Key"); that rendering belongs to the Rust side of the FFI (the shim passes the value in).  Without Rust
     the same construction is applied to an equivalent description of the key."""
     h = hashlib.blake2b(digest_size=64, person=b"Halo2-Verify-Key")
-    s = ("halo2-lib_amd BaseConfig k=%d advice=%d lookup_advice=%d fixed=%d instance=%d lookup_bits=%s" % (
-        params.k, params.num_advice, params.num_lookup_advice, params.num_fixed, params.num_instance,
-        None if params.lookup_bits < 0 else params.lookup_bits)).encode()
+    s = describe(params).encode()
     h.update(len(s).to_bytes(8, "little") + s)
     q = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
     rinv = pow(1 << 256, -1, q)
@@ -162,8 +182,16 @@ class ProvingKey:
             self.handle = None
 
 
-def perm_column_index(params: BaseCircuitParams, shape: ConstraintSystemShape, kind: str, index: int) -> int:
-    """position of a column among the equality-enabled columns: constants, gate advice, lookup advice, instance"""
+def perm_column_index(params, shape: ConstraintSystemShape, kind: str, index: int) -> int:
+    """position of a column among the equality-enabled columns: constants, gate advice, lookup advice, instance (BaseConfig); the table and
+    key columns, constants, gate advice (DynLookupCircuitParams)"""
+    if isinstance(params, DynLookupCircuitParams):
+        ndyn = params.key_cols * (1 + params.lu_sets)
+        if kind == "fixed":
+            return ndyn + index - shape.first_constant_col
+        if kind == "advice":
+            return index if index < ndyn else ndyn + params.num_fixed + index - ndyn
+        raise ValueError(kind)
     if kind == "fixed":
         return index - shape.first_constant_col
     if kind == "advice":
@@ -173,7 +201,7 @@ def perm_column_index(params: BaseCircuitParams, shape: ConstraintSystemShape, k
     raise ValueError(kind)
 
 
-def keygen(kzg: ParamsKZG, params: BaseCircuitParams, fixed: Sequence[np.ndarray], copies) -> ProvingKey:
+def keygen(kzg: ParamsKZG, params, fixed: Sequence[np.ndarray], copies) -> ProvingKey:
     """keygen_vk + keygen_pk.  fixed: num_fixed_total (n,4) Lagrange columns; copies: (m,4) uint32 (column, row, column, row) over the
     permutation columns, or a list of (((kind, column), row), ((kind, column), row)) in the order the circuit emitted them."""
     ctx = kzg.ctx
@@ -188,7 +216,8 @@ def keygen(kzg: ParamsKZG, params: BaseCircuitParams, fixed: Sequence[np.ndarray
     copies = np.ascontiguousarray(copies, dtype=np.uint32).reshape(-1, 4)
     arr = (_vp * len(cols))(*[_vp(c.ctypes.data) for c in cols])
     out = _vp()
-    ctx._chk(ctx.lib.h2hip_plonk_keygen(ctx.handle, C.byref(params), kzg.g.handle, kzg.g_lagrange.handle, arr, _vp(copies.ctypes.data), len(copies),
+    fn = ctx.lib.h2hip_plonk_keygen_dyn if isinstance(params, DynLookupCircuitParams) else ctx.lib.h2hip_plonk_keygen
+    ctx._chk(fn(ctx.handle, C.byref(params), kzg.g.handle, kzg.g_lagrange.handle, arr, _vp(copies.ctypes.data), len(copies),
                                         C.byref(out)))
     return ProvingKey(ctx, out, params, shape, kzg)
 
@@ -270,6 +299,11 @@ def verify_proof(pk: ProvingKey, instances: Sequence[np.ndarray], proof: bytes) 
     buf = np.frombuffer(bytes(proof), dtype=np.uint8).copy()
     ok = C.c_int(0)
     pc = pk.permutation_commitments if len(pk.permutation_commitments) else np.zeros((1, 8), dtype=np.uint64)
+    if isinstance(pk.params, DynLookupCircuitParams):
+        ctx._chk(ctx.lib.h2hip_plonk_verify_proof_dyn(C.byref(pk.params), _ptr(np.ascontiguousarray(pk.fixed_commitments)), _ptr(np.ascontiguousarray(pc)),
+                                                      _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128),
+                                                      _vp(buf.ctypes.data), len(buf), C.byref(ok)))
+        return bool(ok.value)
     ctx._chk(ctx.lib.h2hip_plonk_verify_proof(C.byref(pk.params), _ptr(np.ascontiguousarray(pk.fixed_commitments)), _ptr(np.ascontiguousarray(pc)),
                                               _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128), ip, il,
                                               _vp(buf.ctypes.data), len(buf), C.byref(ok)))

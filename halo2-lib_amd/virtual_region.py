@@ -455,3 +455,118 @@ def _q(v):
     if isinstance(v, int):
         return Witness(v)
     return v
+
+
+# ---------------------------------------------------------------------------------------------------------------- the dynamic lookup table
+class BasicDynLookupConfig:
+    """virtual_region/lookups/basic.rs:38-199 over this repository's column numbering (include/h2hip.h, h2hip_dyn_circuit_params): advice
+    columns [table t_0..t_{m-1}] [set 0: k_0..k_{m-1}] ... then the gate columns; fixed columns [table_is_enabled] [key_is_enabled per set] ..."""
+
+    def __init__(self, key_cols: int, lu_sets: int):
+        self.key_cols, self.lu_sets = key_cols, lu_sets
+        self.table = list(range(key_cols))
+        self.table_is_enabled = 0
+        self.to_lookup = [(list(range(key_cols * (1 + s), key_cols * (2 + s))), 1 + s) for s in range(lu_sets)]
+
+    def assign_virtual_to_lookup_to_raw(self, region: Region, keys: Sequence[Sequence[AssignedValue]], copy_manager: Optional[CopyConstraintManager],
+                                        offset: int = 0):
+        """basic.rs:115-143: left to right over the sets, then top to bottom; key_is_enabled = 1 on every row used"""
+        lookup_col = 0
+        for key in keys:
+            if lookup_col >= len(self.to_lookup):
+                lookup_col = 0
+                offset += 1
+            key_cols, key_is_enabled = self.to_lookup[lookup_col]
+            region.assign_fixed(key_is_enabled, offset, 1)
+            for cell, column in zip(key, key_cols):
+                bcell = region.assign_advice(column, offset, cell.value)
+                if copy_manager is not None:
+                    constrain_virtual_equals_external(region, cell, bcell, copy_manager)
+            lookup_col += 1
+
+    def assign_virtual_table_to_raw(self, region: Region, rows: Sequence[Sequence[AssignedValue]], copy_manager: Optional[CopyConstraintManager],
+                                    offset: int = 0):
+        """basic.rs:170-198: one enabled row per table row, then ONE disabled all-zero row (a disabled, all-zero key always finds a match)"""
+        for row in rows:
+            region.assign_fixed(self.table_is_enabled, offset, 1)
+            for cell, column in zip(row, self.table):
+                bcell = region.assign_advice(column, offset, cell.value)
+                if copy_manager is not None:
+                    constrain_virtual_equals_external(region, cell, bcell, copy_manager)
+            offset += 1
+        region.assign_fixed(self.table_is_enabled, offset, 0)
+        for column in self.table:
+            region.assign_advice(column, offset, 0)
+
+
+class RAMCircuit:
+    """The RAMCircuit of virtual_region/tests/lookups/memory.rs:30-158: a memory table of (index, value) rows, every access (ptr, memory[ptr])
+    looked up in it, the values summed up on the flex gate.  key_cols = 2 as there; key_cols 1 looks up the index only, key_cols 3 adds
+    (index + value) as a third key column.  `prank` appends memory.rs:174-181's false access (0, 0).
+
+    The cells are laid out as one chain of overlapping gates, | s | v | 1 | s+v | p | 0 | s+v | ..., a gate every third cell, instead of
+    memory.rs's load_witness + add: every gate column then starts with an enabled gate at row 0 (a column break always falls on a gate), so no
+    two q_enable columns are disjoint — the backend keeps one fixed column per gate selector and refuses keys whose selectors halo2's
+    compress_selectors would merge (h2hip_plonk_keygen, include/h2hip.h LIMITS (2))."""
+
+    def __init__(self, memory: Sequence[int], ptrs: Sequence[int], key_cols: int = 2, prank: bool = False):
+        self.memory, self.ptrs, self.key_cols = [m % R_MOD for m in memory], list(ptrs), key_cols
+        self.copy_manager = CopyConstraintManager()
+        self.ctx = Context(False, FIRST_PHASE_TYPE_ID, 0, self.copy_manager)
+        self.mem_access: List[List[AssignedValue]] = []
+        self.sum = self.ctx.load_constant(0)
+        for ptr in self.ptrs:
+            self._access(ptr, self.memory[ptr])
+        if prank:
+            self._access(0, 0)
+
+    def _access(self, ptr: int, value: int):
+        ctx = self.ctx
+        ctx.assign_region([Witness(value), Constant(1), Witness((self.sum.value + value) % R_MOD)], [-1])   # s + v * 1 = s'
+        v, self.sum = ctx.get(-3), ctx.last()
+        extra = {}
+        for name, e in (("p", ptr), ("pv", (ptr + value) % R_MOD))[: 1 if self.key_cols < 3 else 2]:
+            ctx.assign_region([Witness(e), Constant(0), Existing(self.sum)], [-1])                       # s + e * 0 = s
+            extra[name], self.sum = ctx.get(-3), ctx.last()
+        self.mem_access.append([extra["p"], v, extra.get("pv")][: self.key_cols])
+
+    def table_rows(self) -> List[List[AssignedValue]]:
+        rows = []
+        for i, m in enumerate(self.memory):
+            cols = [i, m, (i + m) % R_MOD][: self.key_cols]
+            rows.append([AssignedValue(c, ContextCell(EXTERNAL_CELL_TYPE_ID, j, i)) for j, c in enumerate(cols)])
+        return rows
+
+    def num_advice_needed(self, k: int, blinding_factors: int = 6) -> int:
+        """gate columns the layout fills (a dry run of assign_with_constraints): an empty gate column would have a disjoint selector"""
+        max_rows = (1 << k) - (blinding_factors + 3)
+        cols = len(self.ctx.advice) // max(max_rows - ROTATIONS, 1) + 2
+        return len(assign_with_constraints([self.ctx], list(range(cols)), Region(1 << k, cols), CopyConstraintManager(), max_rows)) + 1
+
+    def synthesize(self, params):
+        """-> (advice, fixed, copies) for plonk.keygen / plonk.create_proof with a DynLookupCircuitParams: memory.rs:115-157 (the gate thread,
+        the table, the accesses, then the copy manager)"""
+        n, m, L = 1 << params.k, params.key_cols, params.lu_sets
+        assert m == self.key_cols
+        ndyn = m * (1 + L)
+        max_rows = n - (6 + 3)   # gate.max_rows = 2^k - minimum_rows, blinding factors 6
+        region = Region(n, ndyn + params.num_advice)
+        gate_cols = list(range(ndyn, ndyn + params.num_advice))
+        self.copy_manager.assigned_advices.clear()
+        self.copy_manager.assigned_constants.clear()
+        assign_with_constraints([self.ctx], gate_cols, region, self.copy_manager, max_rows)
+        cfg = BasicDynLookupConfig(m, L)
+        assert len(self.memory) + 1 <= max_rows and -(-len(self.mem_access) // L) <= max_rows, "the table or the accesses do not fit the rows"
+        cfg.assign_virtual_table_to_raw(region, self.table_rows(), self.copy_manager)
+        cfg.assign_virtual_to_lookup_to_raw(region, self.mem_access, self.copy_manager)
+        constant_cols = list(range(1 + L, 1 + L + params.num_fixed))
+        copy_manager_assign_raw(self.copy_manager, constant_cols, region)
+        fcols: List[Dict[int, int]] = [dict() for _ in range(1 + L + params.num_fixed + params.num_advice)]
+        for c, rows in region.fixed.items():
+            fcols[c].update(rows)
+        for gi, rows in region.selectors.get("q_enable", {}).items():
+            for r in rows:
+                fcols[1 + L + params.num_fixed + gi][r] = 1
+        advice = [_column(n, col) for col in region.advice]
+        fixed = [_column(n, c) for c in fcols]
+        return advice, fixed, list(region.copies)

@@ -405,6 +405,30 @@ typedef struct {
 } h2hip_plonk_shape;
 int h2hip_plonk_shape_of(const h2hip_base_circuit_params *params, h2hip_plonk_shape *out);
 
+/* ---- the dynamic lookup table: BasicDynLookupConfig<KEY_COL>::new(meta, || FirstPhase, num_lu_sets) followed by FlexGateConfig::configure
+ * (reference halo2-base/src/virtual_region/lookups/basic.rs:38-199, the RAMCircuit of virtual_region/tests/lookups/memory.rs:92-98).
+ * LIMITS of this configuration, stated once: key_cols (= KEY_COL) in 1..4, lu_sets (= num_lu_sets) in 1..48, num_advice (gate columns,
+ * phase 0) >= 1, num_fixed (constants) <= 16; no instance columns, no RangeConfig table, one challenge phase; single-GPU only
+ * (h2hip_plonk_pk_set_sharding on such a key returns H2HIP_ERR_INVALID).  Anything else returns H2HIP_ERR_INVALID.
+ * Layout, from the reference's call order (m = key_cols, L = lu_sets):
+ *   advice columns       [table t_0..t_{m-1}] [set 0: k_0..k_{m-1}] ... [set L-1] [gate columns]
+ *   fixed columns        [table_is_enabled] [key_is_enabled per set] [constants] [q_enable per gate column]
+ *   permutation columns  the dynamic advice columns, the constants, the gate advice columns (enable_equality order)
+ *   advice queries       every dynamic column at cur, then per gate column the rotations 0..3; fixed queries in column order
+ *   lookups              one per set: input [k_0..k_{m-1}, key_is_enabled], table [t_0..t_{m-1}, table_is_enabled], compressed by
+ *                        Horner in theta (acc * theta + e), so the permuted columns are computed after theta is squeezed.
+ * Degree max(4, 2 + 1 + 1) = 4; blinding factors 6 (a gate column is queried at four rotations).  A key missing from the table makes
+ * h2hip_plonk_create_proof return H2HIP_ERR_INVALID; the context and the key stay usable. */
+typedef struct h2hip_dyn_circuit_params {
+    uint32_t k;
+    uint32_t num_advice;   /* gate advice columns (num_advice_per_phase[0]) */
+    uint32_t num_fixed;    /* constants columns */
+    uint32_t key_cols;     /* KEY_COL: 1..4 */
+    uint32_t lu_sets;      /* num_lu_sets: 1..48 */
+} h2hip_dyn_circuit_params;
+/* the shape of that constraint system; table_col and q_lookup_col are -1 (the table is made of advice columns) */
+int h2hip_plonk_shape_of_dyn(const h2hip_dyn_circuit_params *params, h2hip_plonk_shape *out);
+
 typedef struct h2hip_plonk_pk h2hip_plonk_pk;
 /* keygen_vk + keygen_pk [UPSTREAM], reference halo2-base/src/utils/testing.rs:224-227.  fixed_host: num_fixed_total columns of 2^k
  * Montgomery Fr (Lagrange values, as the circuit's synthesize assigned them).  copies: ncopies x 4 u32 = (column, row, column, row)
@@ -413,6 +437,10 @@ typedef struct h2hip_plonk_pk h2hip_plonk_pk;
  * Builds sigma polynomials, all coefficient / extended-domain forms and the l_0 / l_last / l_blind cosets on the device. */
 int h2hip_plonk_keygen(h2hip_ctx *ctx, const h2hip_base_circuit_params *params, const h2hip_bases *g, const h2hip_bases *g_lagrange,
                        const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out);
+/* the same for the dynamic-lookup configuration above (fixed_host: num_fixed_total columns in its layout; copies index its permutation columns).
+ * Proofs of such a key go through h2hip_plonk_create_proof: the key carries the shape. */
+int h2hip_plonk_keygen_dyn(h2hip_ctx *ctx, const h2hip_dyn_circuit_params *params, const h2hip_bases *g, const h2hip_bases *g_lagrange,
+                           const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out);
 void h2hip_plonk_pk_free(h2hip_ctx *ctx, h2hip_plonk_pk *pk);
 /* VerifyingKey contents: fixed_commitments (num_fixed_total x 64 B affine) and permutation commitments (num_perm_columns x 64 B) */
 int h2hip_plonk_pk_commitments(const h2hip_plonk_pk *pk, void *fixed_out, void *permutation_out);
@@ -534,6 +562,11 @@ int h2hip_plonk_create_proof(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
 int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
                              const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
                              const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted);
+
+/* h2hip_plonk_verify_proof for the dynamic-lookup configuration: the compressed input and table evaluations come from the openings (no instances) */
+int h2hip_plonk_verify_proof_dyn(const h2hip_dyn_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
+                                 const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const uint8_t *proof, size_t proof_len,
+                                 int *accepted);
 
 /* The final CPU-side pairing check of the north star as an entry of its own: *is_one = 1 iff prod_i e(P_i, Q_i) == 1 in Fq12 (what
  * DualMSM::check / halo2curves' multi_miller_loop + final_exponentiation decide for KZG's two pairs).  g1_points: n x 64 B G1Affine
