@@ -38,6 +38,27 @@ pub struct h2hip_dyn_circuit_params {
     pub key_cols: u32,
     pub lu_sets: u32,
 }
+/// BaseCircuitParams over up to MAX_PHASE = 3 phases, with the challenges squeezed after each phase (include/h2hip.h states the layout)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct h2hip_phased_circuit_params {
+    pub k: u32,
+    pub num_advice_per_phase: [u32; 3],
+    pub num_lookup_advice_per_phase: [u32; 3],
+    pub num_fixed: u32,
+    pub num_instance: u32,
+    pub lookup_bits: i32,
+    pub num_challenges_per_phase: [u32; 3],
+}
+/// a later phase's witness: `fill(user, phase, challenges, num_challenges, columns_dev, num_columns)` (include/h2hip.h states the contract)
+pub type h2hip_phase_witness_fn = Option<unsafe extern "C" fn(user: *mut c_void, phase: u32, challenges_fr: *const c_void, num_challenges: usize,
+                                                              columns_dev: *const *mut c_void, num_columns: usize) -> c_int>;
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct h2hip_phase_witness {
+    pub fill: h2hip_phase_witness_fn,
+    pub user: *mut c_void,
+}
 /// state of libh2hip's ready-made array RNG (`h2hip_array_rng_fill` as the `h2hip_rng_fill_fn`)
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -227,6 +248,9 @@ extern "C" {
     pub fn h2hip_plonk_shape_of_dyn(params: *const h2hip_dyn_circuit_params, out: *mut h2hip_plonk_shape) -> c_int;
     pub fn h2hip_plonk_keygen_dyn(ctx: *mut h2hip_ctx, params: *const h2hip_dyn_circuit_params, g: *const h2hip_bases, g_lagrange: *const h2hip_bases,
                                   fixed_host: *const *const c_void, copies: *const u32, ncopies: usize, out: *mut *mut h2hip_plonk_pk) -> c_int;
+    pub fn h2hip_plonk_shape_of_phased(params: *const h2hip_phased_circuit_params, out: *mut h2hip_plonk_shape) -> c_int;
+    pub fn h2hip_plonk_keygen_phased(ctx: *mut h2hip_ctx, params: *const h2hip_phased_circuit_params, g: *const h2hip_bases, g_lagrange: *const h2hip_bases,
+                                     fixed_host: *const *const c_void, copies: *const u32, ncopies: usize, out: *mut *mut h2hip_plonk_pk) -> c_int;
     pub fn h2hip_plonk_pk_free(ctx: *mut h2hip_ctx, pk: *mut h2hip_plonk_pk);
     pub fn h2hip_plonk_pk_commitments(pk: *const h2hip_plonk_pk, fixed_out: *mut c_void, permutation_out: *mut c_void) -> c_int;
     pub fn h2hip_plonk_pk_set_transcript_repr(pk: *mut h2hip_plonk_pk, fr: *const c_void) -> c_int;
@@ -257,6 +281,10 @@ extern "C" {
     pub fn h2hip_plonk_create_proof(ctx: *mut h2hip_ctx, pk: *mut h2hip_plonk_pk, advice: *const *const c_void, advice_on_device: c_int,
                                     instances_host: *const *const c_void, instance_lens: *const usize, rng: h2hip_rng_fill_fn, rng_user: *mut c_void,
                                     proof_out: *mut u8, proof_cap: usize, proof_len: *mut usize, stage_ms: *mut f64) -> c_int;
+    pub fn h2hip_plonk_create_proof_phased(ctx: *mut h2hip_ctx, pk: *mut h2hip_plonk_pk, advice: *const *const c_void, advice_on_device: c_int,
+                                           instances_host: *const *const c_void, instance_lens: *const usize, rng: h2hip_rng_fill_fn, rng_user: *mut c_void,
+                                           witness: *const h2hip_phase_witness, proof_out: *mut u8, proof_cap: usize, proof_len: *mut usize,
+                                           stage_ms: *mut f64) -> c_int;
     pub fn h2hip_lookup_sorted_table_bytes(usable_rows: usize) -> usize;
     pub fn h2hip_lookup_table_sort_dev(ctx: *mut h2hip_ctx, s_dev: *const c_void, usable_rows: usize, sorted_out_dev: *mut c_void) -> c_int;
     pub fn h2hip_lookup_permute_presorted_dev(ctx: *mut h2hip_ctx, a_dev: *const c_void, sorted_table_dev: *const c_void, usable_rows: usize,
@@ -268,6 +296,10 @@ extern "C" {
     pub fn h2hip_plonk_verify_proof_dyn(params: *const h2hip_dyn_circuit_params, fixed_commitments: *const c_void, permutation_commitments: *const c_void,
                                         transcript_repr: *const c_void, g1: *const c_void, g2: *const c_void, s_g2: *const c_void, proof: *const u8,
                                         proof_len: usize, accepted: *mut c_int) -> c_int;
+    pub fn h2hip_plonk_verify_proof_phased(params: *const h2hip_phased_circuit_params, fixed_commitments: *const c_void, permutation_commitments: *const c_void,
+                                           transcript_repr: *const c_void, g1: *const c_void, g2: *const c_void, s_g2: *const c_void,
+                                           instances_host: *const *const c_void, instance_lens: *const usize, proof: *const u8, proof_len: usize,
+                                           accepted: *mut c_int) -> c_int;
     pub fn h2hip_pairing_check(g1_points: *const c_void, g2_points: *const c_void, n: usize, is_one: *mut c_int) -> c_int;
     pub fn h2hip_blake2b(personal16: *const c_void, digest_len: c_uint, msg: *const c_void, len: usize, out: *mut c_void) -> c_int;
     // timing / diagnostics

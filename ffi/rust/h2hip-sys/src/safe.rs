@@ -301,6 +301,8 @@ pub struct ProvingKeyHip<'b, 'g> {
     be: &'b Backend,
     pk: *mut h2hip_plonk_pk,
     pub params: h2hip_base_circuit_params,
+    /// Some for a circuit with more than one phase or with challenges (h2hip_plonk_keygen_phased)
+    pub phased: Option<h2hip_phased_circuit_params>,
     pub shape: h2hip_plonk_shape,
     _g: &'g ResidentBases<'b>,
     _g_lagrange: &'g ResidentBases<'b>,
@@ -308,17 +310,58 @@ pub struct ProvingKeyHip<'b, 'g> {
 fn invalid(message: String) -> HipError {
     HipError { code: H2HIP_ERR_INVALID, message }
 }
+/// `BaseCircuitParams::num_advice_per_phase` / `num_lookup_advice_per_phase` and the number of `challenge_usable_after(phase)` challenges of
+/// each phase (halo2-base/src/gates/circuit/mod.rs:25-45; MAX_PHASE = 3)
+#[derive(Clone, Debug, Default)]
+pub struct PhaseCounts {
+    pub num_advice_per_phase: Vec<u32>,
+    pub num_lookup_advice_per_phase: Vec<u32>,
+    pub num_challenges_per_phase: Vec<u32>,
+}
+impl PhaseCounts {
+    fn is_first_phase_only(&self) -> bool {
+        self.num_advice_per_phase.len() <= 1 && self.num_lookup_advice_per_phase.len() <= 1 && self.num_challenges_per_phase.iter().all(|&c| c == 0)
+    }
+    fn to_c(&self, params: &h2hip_base_circuit_params) -> Result<h2hip_phased_circuit_params, HipError> {
+        let arr = |v: &[u32], what: &str| -> Result<[u32; 3], HipError> {
+            if v.len() > 3 {
+                return Err(invalid(format!("{what}: {} phases, MAX_PHASE is 3", v.len())));
+            }
+            let mut a = [0u32; 3];
+            a[..v.len()].copy_from_slice(v);
+            Ok(a)
+        };
+        Ok(h2hip_phased_circuit_params {
+            k: params.k,
+            num_advice_per_phase: arr(&self.num_advice_per_phase, "num_advice_per_phase")?,
+            num_lookup_advice_per_phase: arr(&self.num_lookup_advice_per_phase, "num_lookup_advice_per_phase")?,
+            num_fixed: params.num_fixed,
+            num_instance: params.num_instance,
+            lookup_bits: params.lookup_bits,
+            num_challenges_per_phase: arr(&self.num_challenges_per_phase, "num_challenges_per_phase")?,
+        })
+    }
+}
+/// the advice columns of each phase of a multi-phase layout, in index order (include/h2hip.h states the layout)
+fn phase_columns(p: &h2hip_phased_circuit_params) -> Vec<usize> {
+    let (g, la) = (p.num_advice_per_phase, p.num_lookup_advice_per_phase);
+    let range = p.lookup_bits >= 0 && la.iter().sum::<u32>() != 0;
+    let q_lookup = range && g[0] == 1 && la[0] != 0;
+    (0..3).map(|ph| (g[ph] + if !range || (ph == 0 && q_lookup) { 0 } else { la[ph] }) as usize).collect()
+}
 impl<'b, 'g> ProvingKeyHip<'b, 'g> {
     /// `keygen_vk` + `keygen_pk`: `fixed` = the fixed columns after synthesis (table, constants, selector columns), `copies` = the copy
     /// constraints as (permutation column, row, permutation column, row) in emission order.
-    /// `phases` = `BaseCircuitParams::num_advice_per_phase.len()`: libh2hip proves first-phase circuits only (include/h2hip.h, LIMITS).
-    pub fn keygen(be: &'b Backend, params: h2hip_base_circuit_params, phases: usize, g: &'g ResidentBases<'b>, g_lagrange: &'g ResidentBases<'b>,
+    /// `params` carries phase 0's counts; `phases` all of them: a circuit with more than one phase or with challenges goes through
+    /// `h2hip_plonk_keygen_phased` (include/h2hip.h states the layout and the limits).
+    pub fn keygen(be: &'b Backend, params: h2hip_base_circuit_params, phases: &PhaseCounts, g: &'g ResidentBases<'b>, g_lagrange: &'g ResidentBases<'b>,
                   fixed: &[Vec<Fr>], copies: &[[u32; 4]], transcript_repr: impl FnOnce(&[G1Affine], &[G1Affine]) -> Fr) -> Result<Self, HipError> {
-        if phases > 1 {
-            return Err(invalid(format!("libh2hip proves first-phase circuits only; the circuit uses {phases} challenge phases")));
-        }
+        let phased = if phases.is_first_phase_only() { None } else { Some(phases.to_c(&params)?) };
         let mut shape = h2hip_plonk_shape::default();
-        check(unsafe { h2hip_plonk_shape_of(&params, &mut shape) })?;
+        match &phased {
+            Some(pp) => check(unsafe { h2hip_plonk_shape_of_phased(pp, &mut shape) })?,
+            None => check(unsafe { h2hip_plonk_shape_of(&params, &mut shape) })?,
+        }
         // the C side reads num_fixed_total pointers and 2^k elements behind each: check the shapes here, in safe code
         let n = 1usize << params.k;
         if fixed.len() != shape.num_fixed_total as usize {
@@ -332,9 +375,14 @@ impl<'b, 'g> ProvingKeyHip<'b, 'g> {
         }
         let cols: Vec<*const c_void> = fixed.iter().map(|c| c.as_ptr().cast()).collect();
         let mut pk = ptr::null_mut();
-        check(unsafe { h2hip_plonk_keygen(be.ctx, &params, g.h, g_lagrange.h, cols.as_ptr(), copies.as_ptr().cast(), copies.len(), &mut pk) })?;
+        check(unsafe {
+            match &phased {
+                Some(pp) => h2hip_plonk_keygen_phased(be.ctx, pp, g.h, g_lagrange.h, cols.as_ptr(), copies.as_ptr().cast(), copies.len(), &mut pk),
+                None => h2hip_plonk_keygen(be.ctx, &params, g.h, g_lagrange.h, cols.as_ptr(), copies.as_ptr().cast(), copies.len(), &mut pk),
+            }
+        })?;
         // from here on `key`'s Drop frees the handle on every early return and on a panic inside the caller's `transcript_repr`
-        let key = Self { be, pk, params, shape, _g: g, _g_lagrange: g_lagrange };
+        let key = Self { be, pk, params, phased, shape, _g: g, _g_lagrange: g_lagrange };
         let mut fc = vec![G1Affine::default(); shape.num_fixed_total as usize];
         let mut pc = vec![G1Affine::default(); (shape.num_perm_columns as usize).max(1)];
         check(unsafe { h2hip_plonk_pk_commitments(key.pk, fc.as_mut_ptr().cast(), pc.as_mut_ptr().cast()) })?;
@@ -345,14 +393,52 @@ impl<'b, 'g> ProvingKeyHip<'b, 'g> {
     }
     /// `create_proof(params, pk, &[circuit], &[instances], rng, &mut transcript)` after synthesis: returns what
     /// `transcript.finalize()` would.  `rng_fill` is called for every batch of `Fr::random(rng)` draws, in upstream's order.
-    pub fn create_proof<R: FnMut(&mut [Fr])>(&self, advice: &[Vec<Fr>], instances: &[&[Fr]], mut rng_fill: R) -> Result<Vec<u8>, HipError> {
+    /// `advice` holds phase 0's columns; `later_phases(phase, challenges)` synthesises every later phase's columns (gate columns, then
+    /// lookup-advice columns, index order) from the challenges squeezed so far — where halo2-axiom's create_proof runs the next phase's synthesis.
+    pub fn create_proof<R: FnMut(&mut [Fr]), W: FnMut(u32, &[Fr]) -> Result<Vec<Vec<Fr>>, E>, E: std::fmt::Display>(
+        &self, advice: &[Vec<Fr>], instances: &[&[Fr]], mut rng_fill: R, later_phases: W) -> Result<Vec<u8>, HipError> {
         unsafe extern "C" fn trampoline<R: FnMut(&mut [Fr])>(user: *mut c_void, out: *mut c_void, n: usize) {
             let f = &mut *(user as *mut R);
             f(std::slice::from_raw_parts_mut(out as *mut Fr, n));
         }
-        // the C side reads num_advice_total column pointers with usable_rows elements each and num_instance instance arrays
-        if advice.len() != self.shape.num_advice_total as usize {
-            return Err(invalid(format!("create_proof: {} advice columns, the shape has {}", advice.len(), self.shape.num_advice_total)));
+        struct Later<'a, W, E> {
+            f: W,
+            ctx: *mut h2hip_ctx,
+            usable: usize,
+            n: usize,
+            err: &'a mut Option<String>,
+            _e: std::marker::PhantomData<E>,
+        }
+        unsafe extern "C" fn witness<W: FnMut(u32, &[Fr]) -> Result<Vec<Vec<Fr>>, E>, E: std::fmt::Display>(
+            user: *mut c_void, phase: u32, challenges: *const c_void, nch: usize, cols: *const *mut c_void, ncols: usize) -> c_int {
+            let l = &mut *(user as *mut Later<W, E>);
+            let ch = if nch == 0 { &[][..] } else { std::slice::from_raw_parts(challenges as *const Fr, nch) };
+            let got = match (l.f)(phase, ch) {
+                Ok(v) => v,
+                Err(e) => {
+                    *l.err = Some(format!("phase {phase}: {e}"));
+                    return 1;
+                }
+            };
+            if got.len() != ncols || got.iter().any(|c| c.len() < l.usable || c.len() > l.n) {
+                *l.err = Some(format!("phase {phase}: {} columns of usable_rows..2^k rows expected, got {}", ncols, got.len()));
+                return 1;
+            }
+            for (j, c) in got.iter().enumerate() {
+                if h2hip_upload(l.ctx, *cols.add(j), c.as_ptr().cast(), 32 * c.len()) != H2HIP_OK {
+                    *l.err = Some(format!("phase {phase}: upload failed"));
+                    return 1;
+                }
+            }
+            0
+        }
+        // the C side reads the (phase-0) column pointers with usable_rows elements each and num_instance instance arrays
+        let want = match &self.phased {
+            Some(pp) => phase_columns(pp)[0],
+            None => self.shape.num_advice_total as usize,
+        };
+        if advice.len() != want {
+            return Err(invalid(format!("create_proof: {} advice columns, phase 0 has {}", advice.len(), want)));
         }
         if let Some(c) = advice.iter().position(|c| c.len() < self.shape.usable_rows as usize) {
             return Err(invalid(format!("create_proof: advice column {c} has {} rows, fewer than the {} usable rows", advice[c].len(), self.shape.usable_rows)));
@@ -368,21 +454,42 @@ impl<'b, 'g> ProvingKeyHip<'b, 'g> {
         let lens: Vec<usize> = instances.iter().map(|c| c.len()).collect();
         let mut proof = vec![0u8; 32 * (self.shape.num_commitments + self.shape.num_evals) as usize];
         let mut len = 0usize;
-        check(unsafe {
-            h2hip_plonk_create_proof(self.be.ctx, self.pk, adv.as_ptr(), 0, ins.as_ptr(), lens.as_ptr(), Some(trampoline::<R>),
-                                     (&mut rng_fill as *mut R).cast(), proof.as_mut_ptr(), proof.len(), &mut len, ptr::null_mut())
-        })?;
+        let mut err = None;
+        let rc = match &self.phased {
+            None => unsafe {
+                h2hip_plonk_create_proof(self.be.ctx, self.pk, adv.as_ptr(), 0, ins.as_ptr(), lens.as_ptr(), Some(trampoline::<R>),
+                                         (&mut rng_fill as *mut R).cast(), proof.as_mut_ptr(), proof.len(), &mut len, ptr::null_mut())
+            },
+            Some(_) => {
+                let mut later = Later::<W, E> { f: later_phases, ctx: self.be.ctx, usable: self.shape.usable_rows as usize, n: 1usize << self.params.k,
+                                                err: &mut err, _e: std::marker::PhantomData };
+                let w = h2hip_phase_witness { fill: Some(witness::<W, E>), user: (&mut later as *mut Later<W, E>).cast() };
+                unsafe {
+                    h2hip_plonk_create_proof_phased(self.be.ctx, self.pk, adv.as_ptr(), 0, ins.as_ptr(), lens.as_ptr(), Some(trampoline::<R>),
+                                                    (&mut rng_fill as *mut R).cast(), &w, proof.as_mut_ptr(), proof.len(), &mut len, ptr::null_mut())
+                }
+            }
+        };
+        if let Some(message) = err {
+            return Err(HipError { code: rc, message });
+        }
+        check(rc)?;
         proof.truncate(len);
         Ok(proof)
     }
 }
 /// `verify_proof(params, vk, SingleStrategy::new(params), &[instances], &mut Blake2bRead::init(proof))` (check_proof,
 /// halo2-base/src/utils/testing.rs:64-88): `g1` = params.get_g()[0], `g2` / `s_g2` = the verifier half of the SRS in RawBytes form.
-pub fn verify_proof(params: h2hip_base_circuit_params, fixed_commitments: &[G1Affine], permutation_commitments: &[G1Affine], transcript_repr: Fr,
-                    g1: G1Affine, g2: &[u8; 128], s_g2: &[u8; 128], instances: &[&[Fr]], proof: &[u8]) -> Result<bool, HipError> {
+/// `phases`: as for `ProvingKeyHip::keygen` (a circuit with more than one phase or with challenges goes through h2hip_plonk_verify_proof_phased).
+pub fn verify_proof(params: h2hip_base_circuit_params, phases: &PhaseCounts, fixed_commitments: &[G1Affine], permutation_commitments: &[G1Affine],
+                    transcript_repr: Fr, g1: G1Affine, g2: &[u8; 128], s_g2: &[u8; 128], instances: &[&[Fr]], proof: &[u8]) -> Result<bool, HipError> {
+    let phased = if phases.is_first_phase_only() { None } else { Some(phases.to_c(&params)?) };
     // the C side reads num_fixed_total / num_perm_columns commitments and num_instance instance arrays: check the slices first
     let mut shape = h2hip_plonk_shape::default();
-    check(unsafe { h2hip_plonk_shape_of(&params, &mut shape) })?;
+    match &phased {
+        Some(pp) => check(unsafe { h2hip_plonk_shape_of_phased(pp, &mut shape) })?,
+        None => check(unsafe { h2hip_plonk_shape_of(&params, &mut shape) })?,
+    }
     if fixed_commitments.len() != shape.num_fixed_total as usize || permutation_commitments.len() != shape.num_perm_columns as usize {
         return Err(invalid(format!("verify_proof: {} fixed / {} permutation commitments, the shape has {} / {}", fixed_commitments.len(),
                                    permutation_commitments.len(), shape.num_fixed_total, shape.num_perm_columns)));
@@ -394,9 +501,14 @@ pub fn verify_proof(params: h2hip_base_circuit_params, fixed_commitments: &[G1Af
     let lens: Vec<usize> = instances.iter().map(|c| c.len()).collect();
     let mut ok: c_int = 0;
     check(unsafe {
-        h2hip_plonk_verify_proof(&params, fixed_commitments.as_ptr().cast(), permutation_commitments.as_ptr().cast(), fr_ptr(&transcript_repr),
-                                 (&g1 as *const G1Affine).cast(), g2.as_ptr().cast(), s_g2.as_ptr().cast(), ins.as_ptr(), lens.as_ptr(), proof.as_ptr(),
-                                 proof.len(), &mut ok)
+        match &phased {
+            Some(pp) => h2hip_plonk_verify_proof_phased(pp, fixed_commitments.as_ptr().cast(), permutation_commitments.as_ptr().cast(),
+                                                        fr_ptr(&transcript_repr), (&g1 as *const G1Affine).cast(), g2.as_ptr().cast(), s_g2.as_ptr().cast(),
+                                                        ins.as_ptr(), lens.as_ptr(), proof.as_ptr(), proof.len(), &mut ok),
+            None => h2hip_plonk_verify_proof(&params, fixed_commitments.as_ptr().cast(), permutation_commitments.as_ptr().cast(), fr_ptr(&transcript_repr),
+                                             (&g1 as *const G1Affine).cast(), g2.as_ptr().cast(), s_g2.as_ptr().cast(), ins.as_ptr(), lens.as_ptr(),
+                                             proof.as_ptr(), proof.len(), &mut ok),
+        }
     })?;
     Ok(ok != 0)
 }

@@ -80,6 +80,10 @@ struct Shape {
     bool dyn = false;              // BasicDynLookupConfig + FlexGateConfig (init_dyn); otherwise BaseConfig (init)
     uint32_t key_cols = 0;         // dyn: KEY_COL; lookup expressions have key_cols + 1 columns
     uint32_t first_gate_advice = 0;   // advice index of gate column 0 (dyn: behind the table and key columns)
+    bool from_phased = false;      // made by init_phased (h2hip_plonk_keygen_phased)
+    bool phased = false;           // multi-phase BaseConfig (init_phased) with more than one used phase or a challenge
+    std::vector<std::vector<int>> phase_cols;   // phased: the advice columns of every used phase, index order (gate, then lookup advice)
+    uint32_t phase_challenges[H2HIP_MAX_PHASE] = {0, 0, 0};   // phased: challenges squeezed after each phase's commitments
     int table_col = -1, q_lookup_col = -1, first_constant_col = -1, first_q_enable_col = -1;
     uint32_t num_advice_total, num_fixed_total;
     std::vector<Lookup> lookups;
@@ -95,9 +99,16 @@ struct Shape {
         H2_REQUIRE(bp.num_advice >= 1 && bp.num_advice <= 1024 && bp.num_lookup_advice <= 256 && bp.num_fixed <= 16 && bp.num_instance <= 8,
                    "column counts out of range");
         H2_REQUIRE(bp.lookup_bits < (int32_t)k, "lookup_bits must be less than k");
+        const bool range = bp.lookup_bits >= 0 && bp.num_lookup_advice != 0;
+        const bool q_lookup = range && bp.num_advice == 1;   // range/mod.rs:93-95: the lookup sits on the gate column behind a complex selector
+        return layout(bp, range, q_lookup, (q_lookup || !range) ? 0 : bp.num_lookup_advice);
+    }
+    // the columns, lookups and queries of FlexGateConfig + RangeConfig: bp.num_advice gate columns, `nla` dedicated lookup-advice columns,
+    // the table iff `range`, the complex selector q_lookup on gate column 0 iff `q_lookup`
+    int layout(const h2hip_base_circuit_params &bp, bool range, bool q_lookup, uint32_t nla) {
         n = 1u << k;
-        with_range = bp.lookup_bits >= 0 && bp.num_lookup_advice != 0;
-        single = with_range && bp.num_advice == 1;   // range/mod.rs:93-95: the lookup sits on the gate column behind a complex selector
+        with_range = range;
+        single = q_lookup;
         int nf = 0;
         if (with_range) table_col = nf++;            // meta.lookup_table_column() is created first (range/mod.rs:82)
         first_constant_col = bp.num_fixed ? nf : -1;
@@ -108,7 +119,6 @@ struct Shape {
         first_q_enable_col = nf;
         nf += (int)bp.num_advice;
         num_fixed_total = (uint32_t)nf;
-        const uint32_t nla = (single || !with_range) ? 0 : bp.num_lookup_advice;
         num_advice_total = bp.num_advice + nla;
         if (single) lookups.push_back({q_lookup_col, 0, table_col});
         for (uint32_t i = 0; i < nla; ++i) lookups.push_back({-1, (int)(bp.num_advice + i), table_col});
@@ -182,6 +192,60 @@ struct Shape {
         extended_k = k;
         while (((uint64_t)1 << extended_k) < (uint64_t)n * quotient_pieces) ++extended_k;
         num_perm_sets = (uint32_t)((perm_columns.size() + chunk_len - 1) / chunk_len);
+        return H2HIP_OK;
+    }
+    // FlexGateConfig / RangeConfig::configure with num_advice_per_phase / num_lookup_advice_per_phase (flex_gate/mod.rs:121-137,
+    // range/mod.rs:87-108); include/h2hip.h states the layout.  One used phase and no challenge is init() of that phase's BaseCircuitParams.
+    int init_phased(const h2hip_phased_circuit_params &pp) {
+        from_phased = true;
+        const uint32_t *g = pp.num_advice_per_phase, *la = pp.num_lookup_advice_per_phase;
+        uint64_t G = 0, LA = 0, CH = 0;
+        for (int ph = 0; ph < H2HIP_MAX_PHASE; ++ph) {
+            G += g[ph];
+            LA += la[ph];
+            CH += pp.num_challenges_per_phase[ph];
+        }
+        H2_REQUIRE(G >= 1 && G <= 1024 && LA <= 256 && pp.num_fixed <= 16 && pp.num_instance <= 8, "column counts out of range");
+        H2_REQUIRE(CH <= H2HIP_MAX_CHALLENGES, "more than 8 challenges");
+        const bool range = pp.lookup_bits >= 0 && LA != 0;   // gates/circuit/mod.rs:74-85
+        const bool q_lookup = range && g[0] == 1 && la[0] != 0;
+        uint32_t ded[H2HIP_MAX_PHASE], cols[H2HIP_MAX_PHASE];
+        for (int ph = 0; ph < H2HIP_MAX_PHASE; ++ph) {
+            ded[ph] = !range || (ph == 0 && q_lookup) ? 0 : la[ph];   // range/mod.rs:93-95: later phases always get dedicated columns
+            cols[ph] = g[ph] + ded[ph];
+        }
+        uint32_t used = 0;
+        for (int ph = 0; ph < H2HIP_MAX_PHASE; ++ph) {
+            if (cols[ph]) {
+                H2_REQUIRE(ph == 0 || cols[ph - 1], "a phase has advice columns but the phase before it has none (phases must be contiguous)");
+                used = (uint32_t)ph + 1;
+            }
+            H2_REQUIRE(!pp.num_challenges_per_phase[ph] || cols[ph], "a challenge follows a phase that has no advice column");
+        }
+        if (used == 1 && CH == 0) {
+            H2_CHK(init(h2hip_base_circuit_params{pp.k, g[0], la[0], pp.num_fixed, pp.num_instance, pp.lookup_bits}));
+            phase_cols.push_back({});
+            for (uint32_t c = 0; c < num_advice_total; ++c) phase_cols[0].push_back((int)c);
+            return H2HIP_OK;
+        }
+        const uint32_t nd = ded[0] + ded[1] + ded[2];
+        const h2hip_base_circuit_params bp{pp.k, (uint32_t)G, nd, pp.num_fixed, pp.num_instance, pp.lookup_bits};
+        p = bp;
+        k = pp.k;
+        H2_REQUIRE(k >= 4 && k <= 26, "k out of range (4..26)");
+        H2_REQUIRE(pp.lookup_bits < (int32_t)k, "lookup_bits must be less than k");
+        H2_CHK(layout(bp, range, q_lookup, nd));
+        phased = true;
+        uint32_t go = 0, lo = (uint32_t)G;
+        for (uint32_t ph = 0; ph < used; ++ph) {
+            std::vector<int> c;
+            for (uint32_t i = 0; i < g[ph]; ++i) c.push_back((int)(go + i));
+            for (uint32_t i = 0; i < ded[ph]; ++i) c.push_back((int)(lo + i));
+            go += g[ph];
+            lo += ded[ph];
+            phase_cols.push_back(c);
+            phase_challenges[ph] = pp.num_challenges_per_phase[ph];
+        }
         return H2HIP_OK;
     }
     uint32_t num_commitments() const {
@@ -639,7 +703,8 @@ struct Laps {
 };
 
 static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, bool advice_on_device, const void *const *instances,
-                             const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, std::vector<uint8_t> &proof_out, double *stage_ms) {
+                             const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, std::vector<uint8_t> &proof_out, double *stage_ms,
+                             const h2hip_phase_witness *witness = nullptr) {
     const Shape &sh = pk->sh;
     const Domain &dom = pk->dom;
     const uint32_t n = sh.n, k = sh.k, ek = sh.extended_k, bf = sh.blinding_factors, u = sh.usable_rows;
@@ -814,7 +879,8 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
     // twiddle cache) behind the event the batch MSM records once its accumulations are done, read the Lagrange values the MSM also reads and
     // write NEW buffers, so they run next to the reduction and to the pointwise kernels that follow.  Single GPU only.
     // (dynamic lookups: the permuted columns wait for theta, so the round-1 overlap schedule below does not apply)
-    const bool overlap = !sharded_any && ctx->plonk_tail_overlap != 0 && !sh.dyn;
+    // (multi-phase keys: the later phases' columns exist only after the phase boundaries, so neither does the round-1 overlap)
+    const bool overlap = !sharded_any && ctx->plonk_tail_overlap != 0 && !sh.dyn && !sh.phased;
     // r05, sharded proofs: lagrange_to_coeff (with its all-gather of the coefficient forms when the columns are dealt to the ranks) and the cosets'
     // coeff_to_extended of the FIRST-ROUND columns run on the side context next to round 2's commitments instead of in front of them
     // with RCCL and more than one rank the side stream's all-gather and the main stream's host exchanges would use ONE communicator from
@@ -930,7 +996,26 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
     // ---- advice columns: witness rows from the caller, blinding rows from the RNG
     const bool lazy_upload = !advice_on_device && overlap && ctx->plonk_lazy_upload != 0 && sh.num_advice_total >= 2 &&
                              (sh.lookups.empty() || ctx->plonk_permute_in_commit != 0);
-    {
+    // a phase's blinding rows and blinds (multi-phase keys: phase by phase, each once the phase's witness is in its columns)
+    auto blind_phase = [&](const std::vector<int> &pcols) -> int {
+        TailRun tails;
+        tails_reserve(tails, pcols.size(), n - u, n - u);
+        for (int c : pcols) H2_CHK(tails_add(tails, adv[c] + u, draw(n - u)));
+        H2_CHK(tails_flush(tails));
+        draw(pcols.size());   // Blind(Fr::random) per column
+        return H2HIP_OK;
+    };
+    if (sh.phased) {   // `advice` holds phase 0's columns; the later phases' are zeroed here and filled by the witness callback
+        for (uint32_t c = 0; c < sh.num_advice_total; ++c) H2_CHK(sc.take(n, &adv[c]));
+        const std::vector<int> &p0 = sh.phase_cols[0];
+        for (size_t j = 0; j < p0.size(); ++j) {
+            H2_REQUIRE(advice[j], "NULL advice column");
+            H2_HIPCHK(hipMemcpyAsync(adv[p0[j]], advice[j], sizeof(Fr) * u, advice_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        }
+        for (size_t ph = 1; ph < sh.phase_cols.size(); ++ph)
+            for (int c : sh.phase_cols[ph]) H2_HIPCHK(hipMemsetAsync(adv[c], 0, sizeof(Fr) * n, st));
+        H2_CHK(blind_phase(p0));
+    } else {
         TailRun tails;
         tails_reserve(tails, sh.num_advice_total, n - u, n - u);
         for (uint32_t c = 0; c < sh.num_advice_total; ++c) {
@@ -944,8 +1029,8 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
             H2_CHK(tails_add(tails, adv[c] + u, tail));
         }
         H2_CHK(tails_flush(tails));
+        draw(sh.num_advice_total);   // Blind(Fr::random) per column: drawn, unused by KZG
     }
-    draw(sh.num_advice_total);   // Blind(Fr::random) per column: drawn, unused by KZG
     std::vector<std::pair<uint64_t, uint64_t>> rank_ranges;   // sharded: (offset, len) of every rank's coefficient / point range
     if (sharded_any) {
         // every rank must run the same proof: same shape, same RNG stream (a digest of the first column's blinding rows), and point ranges
@@ -1053,15 +1138,51 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
         // r04: the ADVICE columns' commitments do not wait for it — the batch MSM queues them on its lanes first, then calls the permutation (on
         // this stream), then queues the permuted columns behind it (msm_mid_hook): the first accumulation starts ~0.3 ms earlier
         const bool permute_inside = overlap && ctx->plonk_permute_in_commit && !lks.empty() && !adv.empty();
-        if (sh.dyn) {
-            // (below, once theta is known)
+        if (sh.dyn || sh.phased) {
+            // (below, once theta is known / once every phase's columns are)
         } else if (permute_inside) {
             ctx->msm_mid_hook = permute_lookups;
             ctx->msm_mid_after = adv.size();
         } else {
             H2_CHK(permute_lookups());
         }
-        if (sh.dyn) {
+        if (sh.phased) {
+            // Multi-phase keys [UPSTREAM-RECALL: create_proof's per-phase loop]: per phase its columns' commitments as ONE batched MSM call,
+            // the phase's challenges, then the next phase's witness from the caller (at a quiescent point: only the points made the round
+            // trip) and its blinding rows.  The range lookups' permuted columns wait for the last phase and go out after theta, as upstream's.
+            std::vector<Fr> challenges;
+            for (size_t ph = 0; ph < sh.phase_cols.size(); ++ph) {
+                const std::vector<int> &pcols = sh.phase_cols[ph];
+                if (ph > 0) {
+                    H2_HIPCHK(hipStreamSynchronize(st));
+                    if (witness && witness->fill) {
+                        std::vector<void *> dcols;
+                        for (int c : pcols) dcols.push_back(adv[c]);
+                        const int wrc = witness->fill(witness->user, (uint32_t)ph, challenges.data(), challenges.size(), dcols.data(), dcols.size());
+                        if (wrc != 0) {
+                            set_error("create_proof: the witness callback of phase %zu returned %d", ph, wrc);
+                            return H2HIP_ERR_INVALID;
+                        }
+                    }
+                    H2_CHK(blind_phase(pcols));
+                }
+                std::vector<const void *> pc(pcols.size());
+                for (size_t i = 0; i < pcols.size(); ++i) pc[i] = adv[pcols[i]];
+                std::vector<G1Affine> pts;
+                H2_CHK(commit_points(pk->g_lagrange, pc, n, pts));
+                for (const G1Affine &q : pts) H2_CHK(tr.write_point(q));
+                for (uint32_t c = 0; c < sh.phase_challenges[ph]; ++c) challenges.push_back(tr.squeeze_challenge());
+            }
+            laps.lap(ST_COMMIT_ROUND1);
+            theta = tr.squeeze_challenge();
+            H2_CHK(permute_lookups());
+            laps.lap(ST_LOOKUP_PERMUTE);
+            std::vector<const void *> lcols(cols.begin() + (long)adv.size(), cols.end());
+            std::vector<G1Affine> lpts;
+            H2_CHK(commit_points(pk->g_lagrange, lcols, n, lpts));
+            for (const G1Affine &q : lpts) H2_CHK(tr.write_point(q));
+            laps.lap(ST_COMMIT_ROUND1);
+        } else if (sh.dyn) {
             // Dynamic lookups (BasicDynLookupConfig): theta enters the compressed values, so upstream's order is kept literally — the advice
             // commitments, theta, then the compression of every set's input and of the table in ONE launch, the per-proof sort of the table
             // and the batched presorted permutation, then the permuted columns' commitments
@@ -1980,6 +2101,7 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
 }
 
 }  // namespace plonk
+
 }  // namespace h2
 
 extern "C" {
@@ -2015,6 +2137,14 @@ int h2hip_plonk_shape_of_dyn(const h2hip_dyn_circuit_params *params, h2hip_plonk
     H2_REQUIRE(params && out, "NULL argument");
     Shape sh;
     H2_CHK(sh.init_dyn(*params));
+    fill_shape(sh, out);
+    return H2HIP_OK;
+}
+
+int h2hip_plonk_shape_of_phased(const h2hip_phased_circuit_params *params, h2hip_plonk_shape *out) {
+    H2_REQUIRE(params && out, "NULL argument");
+    Shape sh;
+    H2_CHK(sh.init_phased(*params));
     fill_shape(sh, out);
     return H2HIP_OK;
 }
@@ -2070,6 +2200,14 @@ int h2hip_plonk_keygen_dyn(h2hip_ctx *ctx, const h2hip_dyn_circuit_params *param
     H2_REQUIRE(ctx && params && g && g_lagrange && fixed_host && out && (ncopies == 0 || copies), "NULL argument");
     h2hip_plonk_pk *pk = new h2hip_plonk_pk();
     return keygen_common(ctx, pk, g, g_lagrange, fixed_host, copies, ncopies, pk->sh.init_dyn(*params), out);
+}
+
+int h2hip_plonk_keygen_phased(h2hip_ctx *ctx, const h2hip_phased_circuit_params *params, const h2hip_bases *g, const h2hip_bases *g_lagrange,
+                              const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && params && g && g_lagrange && fixed_host && out && (ncopies == 0 || copies), "NULL argument");
+    h2hip_plonk_pk *pk = new h2hip_plonk_pk();
+    return keygen_common(ctx, pk, g, g_lagrange, fixed_host, copies, ncopies, pk->sh.init_phased(*params), out);
 }
 
 static int keygen_common(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const h2hip_bases *g, const h2hip_bases *g_lagrange, const void *const *fixed_host,
@@ -2200,6 +2338,7 @@ int h2hip_plonk_pk_set_sharding(h2hip_plonk_pk *pk, h2hip_comm *comm, const h2hi
     int world = 1, rank = 0;
     if (comm) H2_CHK(h2hip_comm_info(comm, &world, &rank, nullptr));
     H2_REQUIRE(!(comm && pk->sh.dyn), "h2hip_plonk_pk_set_sharding: proofs with a dynamic lookup table run on one GPU");
+    H2_REQUIRE(!(comm && pk->sh.phased), "h2hip_plonk_pk_set_sharding: multi-phase proofs run on one GPU");
     if (!comm || (world <= 1 && !(flags & H2HIP_SHARD_FORCE))) return H2HIP_OK;
     H2_REQUIRE(g_shard && g_lagrange_shard, "NULL argument");
     H2_REQUIRE(offset <= pk->sh.n && len <= pk->sh.n - offset && g_shard->n >= len && g_lagrange_shard->n >= len, "shard range outside the SRS / shard base sets too small");
@@ -2257,9 +2396,9 @@ void h2hip_array_rng_fill(void *user, void *out_fr, size_t n) {
 
 const char *h2hip_plonk_stage_name(int stage) { return stage >= 0 && stage < H2HIP_PLONK_STAGES ? STAGE_NAMES[stage] : ""; }
 
-int h2hip_plonk_create_proof(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, int advice_on_device, const void *const *instances_host,
-                             const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, uint8_t *proof_out, size_t proof_cap,
-                             size_t *proof_len, double *stage_ms) {
+static int create_proof_entry(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, int advice_on_device, const void *const *instances_host,
+                              const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, const h2hip_phase_witness *witness,
+                              uint8_t *proof_out, size_t proof_cap, size_t *proof_len, double *stage_ms) {
     H2_DEVICE_GUARD(ctx);
     H2_REQUIRE(ctx && pk && advice && rng && proof_out && proof_len, "NULL argument");
     H2_REQUIRE(pk->ctx == ctx, "the proving key belongs to another context");
@@ -2273,7 +2412,7 @@ int h2hip_plonk_create_proof(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
         H2_REQUIRE(cr->rounds == 8 || cr->rounds == 12 || cr->rounds == 20, "h2hip_chacha_rng: rounds must be 8, 12 or 20");
     }
     std::vector<uint8_t> proof;
-    int rc = create_proof_impl(ctx, pk, advice, advice_on_device != 0, instances_host, instance_lens, rng, rng_user, proof, stage_ms);
+    int rc = create_proof_impl(ctx, pk, advice, advice_on_device != 0, instances_host, instance_lens, rng, rng_user, proof, stage_ms, witness);
     ctx->msm_tail_hook = nullptr;   // (never leave a hook of this proof behind: it captures the proof's frame)
     ctx->msm_mid_hook = nullptr;
     ctx->msm_col_hook = nullptr;
@@ -2307,4 +2446,35 @@ int h2hip_plonk_create_proof(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
     return H2HIP_OK;
 }
 
+int h2hip_plonk_create_proof(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, int advice_on_device, const void *const *instances_host,
+                             const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, uint8_t *proof_out, size_t proof_cap,
+                             size_t *proof_len, double *stage_ms) {
+    H2_REQUIRE(!pk || pk->sh.phase_cols.size() <= 1, "h2hip_plonk_create_proof: the key has more than one phase (use h2hip_plonk_create_proof_phased)");
+    return create_proof_entry(ctx, pk, advice, advice_on_device, instances_host, instance_lens, rng, rng_user, nullptr, proof_out, proof_cap, proof_len,
+                              stage_ms);
+}
+
+int h2hip_plonk_create_proof_phased(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, int advice_on_device,
+                                    const void *const *instances_host, const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user,
+                                    const h2hip_phase_witness *witness, uint8_t *proof_out, size_t proof_cap, size_t *proof_len, double *stage_ms) {
+    H2_REQUIRE(!pk || pk->sh.from_phased, "h2hip_plonk_create_proof_phased: the key is not of the multi-phase configuration");
+    H2_REQUIRE(!pk || pk->sh.phase_cols.size() <= 1 || (witness && witness->fill), "h2hip_plonk_create_proof_phased: a later phase needs the witness callback");
+    return create_proof_entry(ctx, pk, advice, advice_on_device, instances_host, instance_lens, rng, rng_user, witness, proof_out, proof_cap, proof_len,
+                              stage_ms);
+}
+
 }  // extern "C"
+
+// (declared in internal.h: the verifier reads the multi-phase layout from here)
+int h2::plonk_phased_layout(const h2hip_phased_circuit_params &pp, h2hip_plonk_shape *shape, std::vector<std::vector<int>> *phase_cols,
+                        uint32_t challenges[H2HIP_MAX_PHASE], bool *phased, h2hip_base_circuit_params *bp) {
+    Shape sh;
+    H2_CHK(sh.init_phased(pp));
+    fill_shape(sh, shape);
+    *phased = sh.phased;
+    *bp = sh.p;
+    phase_cols->clear();
+    if (sh.phased) *phase_cols = sh.phase_cols;
+    for (int ph = 0; ph < H2HIP_MAX_PHASE; ++ph) challenges[ph] = sh.phase_challenges[ph];
+    return H2HIP_OK;
+}

@@ -471,6 +471,8 @@ struct VShape {
     std::vector<VCol> perm;
     std::vector<std::pair<int, int>> gates;   // (q_enable fixed column, advice column): q * (a + b*c - d) at rotations 0..3
     std::vector<std::vector<VExpr>> lk_in, lk_tab;
+    std::vector<std::vector<int>> phase_cols;   // multi-phase: the advice columns of each phase, whose commitments come phase by phase
+    uint32_t phase_challenges[H2HIP_MAX_PHASE] = {0, 0, 0};
 };
 
 int verify_impl(const VShape &vs, const void *fixed_commitments, const void *permutation_commitments, const void *transcript_repr, const void *g1,
@@ -511,7 +513,14 @@ int verify_impl(const VShape &vs, const void *fixed_commitments, const void *per
         for (const Fr &v : inst[i]) tr.common_scalar(v);
     }
     std::vector<G1Affine> advice_comm(sh.num_advice_total);
-    for (auto &c : advice_comm) c = tr.read_point();
+    if (vs.phase_cols.empty()) {
+        for (auto &c : advice_comm) c = tr.read_point();
+    } else {   // phase by phase, each followed by its challenges (gates and lookups query none: squeezed for the transcript only)
+        for (size_t ph = 0; ph < vs.phase_cols.size(); ++ph) {
+            for (int c : vs.phase_cols[ph]) advice_comm[c] = tr.read_point();
+            for (uint32_t i = 0; i < vs.phase_challenges[ph]; ++i) (void)tr.squeeze_challenge();
+        }
+    }
     const Fr theta = tr.squeeze_challenge();
     std::vector<G1Affine> lk_a_comm(sh.num_lookups), lk_s_comm(sh.num_lookups), lk_z_comm(sh.num_lookups), permz_comm(sh.num_perm_sets);
     for (uint32_t i = 0; i < sh.num_lookups; ++i) {
@@ -718,6 +727,33 @@ int verify_impl(const VShape &vs, const void *fixed_commitments, const void *per
     return H2HIP_OK;
 }
 
+// FlexGateConfig + RangeConfig: num_advice gate columns, then the dedicated lookup-advice columns; the q_lookup lookup (if any) reads gate column 0
+void base_vshape(VShape &vs, uint32_t k, uint32_t num_advice, uint32_t num_fixed, uint32_t num_instance) {
+    const h2hip_plonk_shape &sh = vs.sh;
+    vs.k = k;
+    vs.num_instance = num_instance;
+    const uint32_t nla = sh.num_advice_total - num_advice;
+    const bool with_range = sh.table_col >= 0, single = sh.q_lookup_col >= 0;
+    for (uint32_t a = 0; a < num_advice; ++a)
+        for (int r = 0; r < 4; ++r) vs.adv_q.push_back({(int)a, r});
+    for (uint32_t i = 0; i < nla; ++i) vs.adv_q.push_back({(int)(num_advice + i), 0});
+    // fixed columns in query order: constants, table, q_lookup, q_enable
+    for (uint32_t i = 0; i < num_fixed; ++i) vs.fixed_q.push_back(sh.first_constant_col + (int)i);
+    if (with_range) vs.fixed_q.push_back(sh.table_col);
+    if (single) vs.fixed_q.push_back(sh.q_lookup_col);
+    for (uint32_t i = 0; i < num_advice; ++i) vs.fixed_q.push_back(sh.first_q_enable_col + (int)i);
+    // permutation columns: constants, advice (gate then lookup), instance
+    for (uint32_t i = 0; i < num_fixed; ++i) vs.perm.push_back({0, sh.first_constant_col + (int)i});
+    for (uint32_t i = 0; i < sh.num_advice_total; ++i) vs.perm.push_back({1, (int)i});
+    for (uint32_t i = 0; i < num_instance; ++i) vs.perm.push_back({2, (int)i});
+    for (uint32_t a = 0; a < num_advice; ++a) vs.gates.push_back({sh.first_q_enable_col + (int)a, (int)a});
+    for (uint32_t li = 0; li < sh.num_lookups; ++li) {
+        const uint32_t ded = li - (single ? 1 : 0);   // index among the dedicated lookup-advice columns
+        vs.lk_in.push_back({single && li == 0 ? VExpr{{0, sh.q_lookup_col}, {1, 0}} : VExpr{{1, (int)(num_advice + ded)}}});
+        vs.lk_tab.push_back({VExpr{{0, sh.table_col}}});
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -733,28 +769,7 @@ int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void
     *accepted = 0;
     VShape vs;
     H2_CHK(h2hip_plonk_shape_of(params, &vs.sh));
-    const h2hip_plonk_shape &sh = vs.sh;
-    vs.k = params->k;
-    vs.num_instance = params->num_instance;
-    const uint32_t num_advice = params->num_advice, nla = sh.num_advice_total - num_advice;
-    const bool with_range = sh.table_col >= 0, single = sh.q_lookup_col >= 0;
-    for (uint32_t a = 0; a < num_advice; ++a)
-        for (int r = 0; r < 4; ++r) vs.adv_q.push_back({(int)a, r});
-    for (uint32_t i = 0; i < nla; ++i) vs.adv_q.push_back({(int)(num_advice + i), 0});
-    // fixed columns in query order: constants, table, q_lookup, q_enable
-    for (uint32_t i = 0; i < params->num_fixed; ++i) vs.fixed_q.push_back(sh.first_constant_col + (int)i);
-    if (with_range) vs.fixed_q.push_back(sh.table_col);
-    if (single) vs.fixed_q.push_back(sh.q_lookup_col);
-    for (uint32_t i = 0; i < num_advice; ++i) vs.fixed_q.push_back(sh.first_q_enable_col + (int)i);
-    // permutation columns: constants, advice (gate then lookup), instance
-    for (uint32_t i = 0; i < params->num_fixed; ++i) vs.perm.push_back({0, sh.first_constant_col + (int)i});
-    for (uint32_t i = 0; i < sh.num_advice_total; ++i) vs.perm.push_back({1, (int)i});
-    for (uint32_t i = 0; i < params->num_instance; ++i) vs.perm.push_back({2, (int)i});
-    for (uint32_t a = 0; a < num_advice; ++a) vs.gates.push_back({sh.first_q_enable_col + (int)a, (int)a});
-    for (uint32_t li = 0; li < sh.num_lookups; ++li) {
-        vs.lk_in.push_back({single ? VExpr{{0, sh.q_lookup_col}, {1, 0}} : VExpr{{1, (int)(num_advice + li)}}});
-        vs.lk_tab.push_back({VExpr{{0, sh.table_col}}});
-    }
+    base_vshape(vs, params->k, params->num_advice, params->num_fixed, params->num_instance);
     return verify_impl(vs, fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2, instances_host, instance_lens, proof, proof_len,
                        accepted);
 }
@@ -792,6 +807,25 @@ int h2hip_plonk_verify_proof_dyn(const h2hip_dyn_circuit_params *params, const v
         vs.lk_tab.push_back(tab);
     }
     return verify_impl(vs, fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2, nullptr, nullptr, proof, proof_len, accepted);
+}
+
+// the same for the multi-phase configuration (include/h2hip.h states its layout): the advice commitments are read phase by phase, each phase's
+// challenges squeezed after them; one used phase without challenges is h2hip_plonk_verify_proof of that phase's BaseCircuitParams
+int h2hip_plonk_verify_proof_phased(const h2hip_phased_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
+                                    const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
+                                    const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted) {
+    H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
+    *accepted = 0;
+    VShape vs;
+    h2hip_base_circuit_params bp;
+    bool phased = false;
+    H2_CHK(plonk_phased_layout(*params, &vs.sh, &vs.phase_cols, vs.phase_challenges, &phased, &bp));
+    if (!phased)
+        return h2hip_plonk_verify_proof(&bp, fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2, instances_host, instance_lens, proof,
+                                        proof_len, accepted);
+    base_vshape(vs, bp.k, bp.num_advice, bp.num_fixed, bp.num_instance);
+    return verify_impl(vs, fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2, instances_host, instance_lens, proof, proof_len,
+                       accepted);
 }
 
 // e(P_0, Q_0) * ... * e(P_{n-1}, Q_{n-1}) == 1 — the "final CPU-side pairing" of the north star as an entry of its own (the verifier above ends in

@@ -114,6 +114,8 @@ _PROTOS = {
     "h2hip_plonk_keygen": (_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, C.POINTER(_vp)]),
     "h2hip_plonk_shape_of_dyn": (_int, [_vp, _vp]),
     "h2hip_plonk_keygen_dyn": (_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, C.POINTER(_vp)]),
+    "h2hip_plonk_shape_of_phased": (_int, [_vp, _vp]),
+    "h2hip_plonk_keygen_phased": (_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, C.POINTER(_vp)]),
     "h2hip_plonk_pk_free": (None, [_vp, _vp]),
     "h2hip_plonk_pk_commitments": (_int, [_vp, _vp, _vp]),
     "h2hip_plonk_pk_set_transcript_repr": (_int, [_vp, _vp]),
@@ -134,6 +136,8 @@ _PROTOS = {
     "h2hip_plonk_stage_name": (C.c_char_p, [_int]),
     "h2hip_plonk_create_proof": (_int, [_vp, _vp, C.POINTER(_vp), _int, C.POINTER(_vp), C.POINTER(_sz), _vp, _vp, _vp, _sz, C.POINTER(_sz),
                                         C.POINTER(C.c_double)]),
+    "h2hip_plonk_create_proof_phased": (_int, [_vp, _vp, C.POINTER(_vp), _int, C.POINTER(_vp), C.POINTER(_sz), _vp, _vp, _vp, _vp, _sz,
+                                                C.POINTER(_sz), C.POINTER(C.c_double)]),
     "h2hip_divide_by_vanishing_poly_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "h2hip_lookup_permute_dev": (_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "h2hip_lookup_sorted_table_bytes": (_sz, [_sz]),
@@ -143,6 +147,7 @@ _PROTOS = {
     "h2hip_poseidon_permute_batch_dev": (_int, [_vp, _vp, _vp, _u32, _sz]),
     "h2hip_plonk_verify_proof": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_int)]),
     "h2hip_plonk_verify_proof_dyn": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_int)]),
+    "h2hip_plonk_verify_proof_phased": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_int)]),
     "h2hip_pairing_check": (_int, [_vp, _vp, _sz, C.POINTER(_int)]),
     "h2hip_blake2b": (_int, [_vp, C.c_uint, _vp, _sz, _vp]),
     "h2hip_bench_gather": (_int, [_vp, _u32, _sz, _u32, _u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

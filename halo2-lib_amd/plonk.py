@@ -20,7 +20,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .h2hip import Context, _fe, _ptr
-from .halo2_proofs import ParamsKZG, R_MOD, fr_limbs
+from .halo2_proofs import ParamsKZG, R_MOD, fr_int, fr_limbs
 
 _vp = C.c_void_p
 PLONK_STAGES = 12
@@ -47,6 +47,43 @@ class DynLookupCircuitParams(C.Structure):
         return cls(k, num_advice, num_fixed, key_cols, lu_sets)
 
 
+class PhasedCircuitParams(C.Structure):
+    """h2hip_phased_circuit_params: BaseCircuitParams with num_advice_per_phase / num_lookup_advice_per_phase of up to MAX_PHASE = 3 entries
+    (gates/flex_gate/mod.rs:28,121-137, gates/range/mod.rs:87-108) and the challenges the circuit declares after each phase
+    (meta.challenge_usable_after(phase)); lookup_bits < 0 means None.  One used phase and no challenge is the BaseConfig of that phase."""
+    _fields_ = [("k", C.c_uint32), ("num_advice_per_phase", C.c_uint32 * 3), ("num_lookup_advice_per_phase", C.c_uint32 * 3), ("num_fixed", C.c_uint32),
+                ("num_instance", C.c_uint32), ("lookup_bits", C.c_int32), ("num_challenges_per_phase", C.c_uint32 * 3)]
+
+    @classmethod
+    def new(cls, k, num_advice_per_phase, num_lookup_advice_per_phase, num_fixed, num_instance=0, lookup_bits: Optional[int] = None,
+            num_challenges_per_phase=()):
+        pad = lambda v: (C.c_uint32 * 3)(*(list(v) + [0] * (3 - len(v))))
+        return cls(k, pad(num_advice_per_phase), pad(num_lookup_advice_per_phase), num_fixed, num_instance, -1 if lookup_bits is None else lookup_bits,
+                   pad(num_challenges_per_phase))
+
+    def phase_columns(self) -> list:
+        """the advice columns of each phase, index order (gate columns of every phase, then the dedicated lookup-advice columns of every phase);
+        trailing phases without columns are dropped"""
+        g, la = list(self.num_advice_per_phase), list(self.num_lookup_advice_per_phase)
+        rng = self.lookup_bits >= 0 and sum(la) != 0
+        q = rng and g[0] == 1 and la[0] != 0
+        ded = [0 if (not rng or (p == 0 and q)) else la[p] for p in range(3)]
+        out, go, lo = [], 0, sum(g)
+        for p in range(3):
+            out.append(list(range(go, go + g[p])) + list(range(lo, lo + ded[p])))
+            go, lo = go + g[p], lo + ded[p]
+        while len(out) > 1 and not out[-1]:
+            out.pop()
+        return out
+
+    def base_params(self) -> Optional[BaseCircuitParams]:
+        """the BaseCircuitParams this is, if it has one used phase and no challenge"""
+        if len(self.phase_columns()) != 1 or any(self.num_challenges_per_phase):
+            return None
+        return BaseCircuitParams(self.k, self.num_advice_per_phase[0], self.num_lookup_advice_per_phase[0], self.num_fixed, self.num_instance,
+                                 self.lookup_bits)
+
+
 class ConstraintSystemShape(C.Structure):
     """what BaseConfig::configure derives from the params (h2hip_plonk_shape)"""
     _fields_ = [("num_advice_total", C.c_uint32), ("num_fixed_total", C.c_uint32), ("table_col", C.c_int32), ("first_constant_col", C.c_int32),
@@ -57,13 +94,20 @@ class ConstraintSystemShape(C.Structure):
 
 def shape_of(ctx: Context, params) -> ConstraintSystemShape:
     out = ConstraintSystemShape()
-    fn = ctx.lib.h2hip_plonk_shape_of_dyn if isinstance(params, DynLookupCircuitParams) else ctx.lib.h2hip_plonk_shape_of
+    fn = {DynLookupCircuitParams: ctx.lib.h2hip_plonk_shape_of_dyn, PhasedCircuitParams: ctx.lib.h2hip_plonk_shape_of_phased}.get(
+        type(params), ctx.lib.h2hip_plonk_shape_of)
     ctx._chk(fn(C.byref(params), C.byref(out)))
     return out
 
 
 def describe(params) -> str:
     """the key description transcript_repr hashes (one per configuration)"""
+    if isinstance(params, PhasedCircuitParams):
+        if params.base_params() is not None:   # one phase, no challenge: the BaseConfig key, the same transcript_repr
+            return describe(params.base_params())
+        return "halo2-lib_amd BaseConfig k=%d advice=%s lookup_advice=%s fixed=%d instance=%d lookup_bits=%s challenges=%s" % (
+            params.k, list(params.num_advice_per_phase), list(params.num_lookup_advice_per_phase), params.num_fixed, params.num_instance,
+            None if params.lookup_bits < 0 else params.lookup_bits, list(params.num_challenges_per_phase))
     if isinstance(params, DynLookupCircuitParams):
         return "halo2-lib_amd BasicDynLookupConfig k=%d advice=%d fixed=%d key_cols=%d lu_sets=%d" % (
             params.k, params.num_advice, params.num_fixed, params.key_cols, params.lu_sets)
@@ -90,6 +134,11 @@ def transcript_repr(params: BaseCircuitParams | DynLookupCircuitParams, fixed_co
 
 
 _RNG_FN = C.CFUNCTYPE(None, _vp, _vp, C.c_size_t)
+_PHASE_FN = C.CFUNCTYPE(C.c_int, _vp, C.c_uint32, _vp, C.c_size_t, C.POINTER(_vp), C.c_size_t)   # h2hip_phase_witness_fn
+
+
+class _PhaseWitness(C.Structure):   # h2hip_phase_witness
+    _fields_ = [("fill", _vp), ("user", _vp)]
 
 
 class _ArrayRngState(C.Structure):   # h2hip_array_rng
@@ -194,7 +243,7 @@ def perm_column_index(params, shape: ConstraintSystemShape, kind: str, index: in
         raise ValueError(kind)
     if kind == "fixed":
         return index - shape.first_constant_col
-    if kind == "advice":
+    if kind == "advice":   # (PhasedCircuitParams: advice indices run over every phase's gate columns, then the lookup-advice columns)
         return params.num_fixed + index
     if kind == "instance":
         return params.num_fixed + shape.num_advice_total + index
@@ -216,20 +265,25 @@ def keygen(kzg: ParamsKZG, params, fixed: Sequence[np.ndarray], copies) -> Provi
     copies = np.ascontiguousarray(copies, dtype=np.uint32).reshape(-1, 4)
     arr = (_vp * len(cols))(*[_vp(c.ctypes.data) for c in cols])
     out = _vp()
-    fn = ctx.lib.h2hip_plonk_keygen_dyn if isinstance(params, DynLookupCircuitParams) else ctx.lib.h2hip_plonk_keygen
+    fn = {DynLookupCircuitParams: ctx.lib.h2hip_plonk_keygen_dyn, PhasedCircuitParams: ctx.lib.h2hip_plonk_keygen_phased}.get(type(params),
+                                                                                                                       ctx.lib.h2hip_plonk_keygen)
     ctx._chk(fn(ctx.handle, C.byref(params), kzg.g.handle, kzg.g_lagrange.handle, arr, _vp(copies.ctypes.data), len(copies),
                                         C.byref(out)))
     return ProvingKey(ctx, out, params, shape, kzg)
 
 
 def create_proof(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarray], rng, timings: Optional[dict] = None,
-                 advice_on_device: bool = False) -> bytes:
+                 advice_on_device: bool = False, phase_witness=None) -> bytes:
     """create_proof for one circuit: advice columns (host (n,4) arrays, or device pointers with advice_on_device), instance columns
-    ((m,4) arrays), rng = ArrayRng / ChaChaRng / CallbackRng.  Returns the proof bytes (Blake2bWrite::finalize)."""
+    ((m,4) arrays), rng = ArrayRng / ChaChaRng / CallbackRng.  Returns the proof bytes (Blake2bWrite::finalize).
+    A PhasedCircuitParams key takes phase 0's columns in `advice`; phase_witness(phase, challenges: list[int]) -> list returns each later
+    phase's columns (host (n,4) arrays or device pointers to n Fr) given every challenge squeezed so far."""
     ctx, sh = pk.ctx, pk.shape
     n = 1 << pk.params.k
-    if len(advice) != sh.num_advice_total:
-        raise ValueError("create_proof: need %d advice columns" % sh.num_advice_total)
+    phased = isinstance(pk.params, PhasedCircuitParams)
+    want = len(pk.params.phase_columns()[0]) if phased else sh.num_advice_total
+    if len(advice) != want:
+        raise ValueError("create_proof: need %d advice columns" % want)
     keep = None
     if advice_on_device:
         adv = (_vp * len(advice))(*[_vp(int(p)) for p in advice])
@@ -255,21 +309,26 @@ def create_proof(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarra
     proof = np.zeros(pk.proof_size(), dtype=np.uint8)
     plen = C.c_size_t(0)
     stage = (C.c_double * PLONK_STAGES)() if timings is not None else None
+    if phased:
+        wit = _phase_witness_trampoline(ctx, n, phase_witness, err)
+        entry = lambda *a: ctx.lib.h2hip_plonk_create_proof_phased(*a[:8], C.byref(wit[0]), *a[8:])
+    else:
+        entry = ctx.lib.h2hip_plonk_create_proof
     if isinstance(rng, ArrayRng):   # libh2hip's own array RNG: no Python frame per draw (a wide shape draws several hundred blinding tails)
         st = _ArrayRngState(rng.values.ctypes.data + 32 * rng.pos, len(rng.values) - rng.pos, 0, 0)
-        rc = ctx.lib.h2hip_plonk_create_proof(ctx.handle, pk.handle, adv, 1 if advice_on_device else 0, ip, il,
+        rc = entry(ctx.handle, pk.handle, adv, 1 if advice_on_device else 0, ip, il,
                                               C.cast(ctx.lib.h2hip_array_rng_fill, _vp), C.cast(C.pointer(st), _vp), _ptr(proof), proof.nbytes,
                                               C.byref(plen), stage)
         rng.pos += st.pos
         if st.exhausted:
             raise RuntimeError("ArrayRng exhausted")
     elif isinstance(rng, ChaChaRng) and rng.device:   # libh2hip's seeded generator: the prover's device path for the large draws
-        rc = ctx.lib.h2hip_plonk_create_proof(ctx.handle, pk.handle, adv, 1 if advice_on_device else 0, ip, il,
+        rc = entry(ctx.handle, pk.handle, adv, 1 if advice_on_device else 0, ip, il,
                                               C.cast(ctx.lib.h2hip_chacha_rng_fill, _vp), C.cast(C.pointer(rng.state), _vp), _ptr(proof), proof.nbytes,
                                               C.byref(plen), stage)
     else:
         cb = _RNG_FN(_fill)
-        rc = ctx.lib.h2hip_plonk_create_proof(ctx.handle, pk.handle, adv, 1 if advice_on_device else 0, ip, il, C.cast(cb, _vp), None, _ptr(proof),
+        rc = entry(ctx.handle, pk.handle, adv, 1 if advice_on_device else 0, ip, il, C.cast(cb, _vp), None, _ptr(proof),
                                               proof.nbytes, C.byref(plen), stage)
     if err:
         raise err[0]
@@ -280,6 +339,36 @@ def create_proof(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarra
             timings[name] = timings.get(name, 0.0) + stage[i]
     del keep
     return proof[: plen.value].tobytes()
+
+
+def _phase_witness_trampoline(ctx: Context, n: int, phase_witness, err: list):
+    """(h2hip_phase_witness, the callback object to keep alive) over phase_witness(phase, challenges) -> list of columns"""
+    one = fr_limbs(1)
+
+    def _fill(_user, phase, chal, nchal, cols, ncols):
+        try:
+            if phase_witness is None:
+                raise ValueError("create_proof: the key has a later phase and no phase_witness was given")
+            ch = np.ctypeslib.as_array(C.cast(chal, C.POINTER(C.c_uint64)), shape=(nchal, 4)).copy() if nchal else np.zeros((0, 4), dtype=np.uint64)
+            got = list(phase_witness(int(phase), [fr_int(r) for r in ch]))
+            if len(got) != ncols:
+                raise ValueError("phase_witness: phase %d has %d columns, got %d" % (phase, ncols, len(got)))
+            for j, col in enumerate(got):
+                if isinstance(col, (int, np.integer)):   # a device pointer to n Fr: y += 1 * x into the zeroed column
+                    ctx._chk(ctx.lib.h2hip_fr_axpy_dev(ctx.handle, _vp(cols[j]), _ptr(one), _vp(int(col)), n))
+                else:
+                    a = _fe(col)
+                    if len(a) > n:
+                        raise ValueError("phase_witness: a column has more than 2^k rows")
+                    ctx._chk(ctx.lib.h2hip_upload(ctx.handle, _vp(cols[j]), _ptr(a), a.nbytes))
+            ctx.sync()
+            return 0
+        except BaseException as e:   # never unwind through the C frames
+            err.append(e)
+            return 1
+
+    cb = _PHASE_FN(_fill)
+    return _PhaseWitness(C.cast(cb, _vp), None), cb
 
 
 def verify_proof(pk: ProvingKey, instances: Sequence[np.ndarray], proof: bytes) -> bool:
@@ -299,6 +388,11 @@ def verify_proof(pk: ProvingKey, instances: Sequence[np.ndarray], proof: bytes) 
     buf = np.frombuffer(bytes(proof), dtype=np.uint8).copy()
     ok = C.c_int(0)
     pc = pk.permutation_commitments if len(pk.permutation_commitments) else np.zeros((1, 8), dtype=np.uint64)
+    if isinstance(pk.params, PhasedCircuitParams):
+        ctx._chk(ctx.lib.h2hip_plonk_verify_proof_phased(C.byref(pk.params), _ptr(np.ascontiguousarray(pk.fixed_commitments)), _ptr(np.ascontiguousarray(pc)),
+                                                         _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128), ip, il,
+                                                         _vp(buf.ctypes.data), len(buf), C.byref(ok)))
+        return bool(ok.value)
     if isinstance(pk.params, DynLookupCircuitParams):
         ctx._chk(ctx.lib.h2hip_plonk_verify_proof_dyn(C.byref(pk.params), _ptr(np.ascontiguousarray(pk.fixed_commitments)), _ptr(np.ascontiguousarray(pc)),
                                                       _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128),

@@ -377,11 +377,10 @@ int h2hip_poseidon_permute_batch_dev(h2hip_ctx *ctx, void *states_dev, const voi
  * prover draws, in upstream's order), the verifying key's transcript representation, and the proof bytes.
  * Everything between — 12 MSMs, ~11 NTTs, the lookup sort, grand products, h(X), evaluations, SHPLONK — runs on the device with
  * every polynomial resident in HBM; the host part is the Blake2b transcript and the O(#openings) bookkeeping of the multiopen. */
-/* LIMITS, stated once: (1) ONE challenge phase.  The reference's params are per-phase vectors with MAX_PHASE = 3
- * (num_advice_per_phase / num_lookup_advice_per_phase, halo2-base/src/gates/flex_gate/mod.rs:28,100,132-137, gates/range/mod.rs:87-108); this
- * struct carries phase 0 only, so a circuit that uses SecondPhase / ThirdPhase columns (none of halo2-ecc's benchmark circuits does) cannot
- * be expressed and must stay on the CPU prover — the Rust shim checks `params.num_advice_per_phase.len() == 1` (ffi/rust/h2hip-sys/src/safe.rs)
- * and returns an error otherwise.  (2) Every gate column's q_enable keeps a fixed column of its own: h2hip_plonk_keygen returns
+/* LIMITS, stated once: (1) This struct carries phase 0 only.  The reference's params are per-phase vectors with MAX_PHASE = 3
+ * (num_advice_per_phase / num_lookup_advice_per_phase, halo2-base/src/gates/flex_gate/mod.rs:28,100,132-137, gates/range/mod.rs:87-108); a
+ * circuit that uses SecondPhase / ThirdPhase columns or challenges goes through h2hip_phased_circuit_params below (the Rust shim routes
+ * `num_advice_per_phase.len() > 1` there, ffi/rust/h2hip-sys/src/safe.rs).  (2) Every gate column's q_enable keeps a fixed column of its own: h2hip_plonk_keygen returns
  * H2HIP_ERR_INVALID for selector activations that upstream's compress_selectors would merge (two gate columns never enabled on a common
  * row, e.g. an empty gate column).  (3) lookup_bits: the table 0..2^lookup_bits must fit 2^k - (blinding_factors + 3) rows, as in
  * RangeConfig::configure (gates/range/mod.rs:117-121). */
@@ -429,6 +428,47 @@ typedef struct h2hip_dyn_circuit_params {
 /* the shape of that constraint system; table_col and q_lookup_col are -1 (the table is made of advice columns) */
 int h2hip_plonk_shape_of_dyn(const h2hip_dyn_circuit_params *params, h2hip_plonk_shape *out);
 
+/* ---- multi-phase BaseConfig: FlexGateConfig with SecondPhase / ThirdPhase gate columns, RangeConfig with phase-1 / 2 lookup-advice columns
+ * (reference halo2-base/src/gates/flex_gate/mod.rs:62-70,121-137, gates/range/mod.rs:87-108,131-150), and the challenges a circuit declares with
+ * meta.challenge_usable_after(phase).  MAX_PHASE = 3 (flex_gate/mod.rs:28).  Layout, from the reference's creation order:
+ *   fixed columns        [table, if any] [constants] [q_lookup, if any] [q_enable per gate column: phase 0's, then 1's, then 2's]
+ *   advice columns       gate columns of phase 0, 1, 2, then the dedicated lookup-advice columns of phase 0, 1, 2
+ *   lookups              the q_lookup lookup (on gate column 0), then one per dedicated lookup-advice column
+ *   permutation columns  constants, gate advice, lookup advice, instance; advice queries: gate columns at 0..3, lookup advice at 0
+ * The table exists iff lookup_bits >= 0 and the lookup-advice counts sum to non-zero (gates/circuit/mod.rs:74-85); q_lookup iff
+ * num_advice_per_phase[0] == 1 and num_lookup_advice_per_phase[0] != 0 (later phases always get dedicated columns, range/mod.rs:93-95).
+ * Protocol: after the instances, for each phase in order: the blinding rows of the phase's columns, one blind per column, the phase's
+ * commitments (index order), then num_challenges_per_phase[p] challenges squeezed (Challenge255); theta and everything after as for BaseConfig.
+ * LIMITS: the column counts summed over the phases are in h2hip_base_circuit_params' ranges; phases are contiguous (a phase with columns
+ * follows a phase with columns); a challenge follows a phase with columns; at most 8 challenges; gates and lookups do not query a challenge
+ * (halo2-base declares none: a challenge reaches the circuit through witness values); single-GPU only (h2hip_plonk_pk_set_sharding on a key
+ * with more than one used phase returns H2HIP_ERR_INVALID).  Anything else returns H2HIP_ERR_INVALID.  One used phase and no challenges IS a
+ * BaseConfig: same shape, key and proof bytes as the h2hip_base_circuit_params of that phase. */
+#define H2HIP_MAX_PHASE 3
+#define H2HIP_MAX_CHALLENGES 8
+typedef struct h2hip_phased_circuit_params {
+    uint32_t k;
+    uint32_t num_advice_per_phase[3];          /* gate columns per phase */
+    uint32_t num_lookup_advice_per_phase[3];   /* lookup-advice columns per phase */
+    uint32_t num_fixed;
+    uint32_t num_instance;
+    int32_t lookup_bits;                       /* < 0: None */
+    uint32_t num_challenges_per_phase[3];      /* challenge_usable_after(phase p): squeezed after phase p's commitments */
+} h2hip_phased_circuit_params;
+int h2hip_plonk_shape_of_phased(const h2hip_phased_circuit_params *params, h2hip_plonk_shape *out);
+/* Supplies the witness of a later phase.  Fills phase `phase`'s advice columns (gate columns, then lookup-advice columns, index order; each n
+ * Fr, zeroed on entry) given every challenge squeezed so far, in squeeze order (num_challenges Montgomery Fr, host memory).  Returns 0, or
+ * non-zero to abort the proof.  Contract: it runs on the calling thread while the library is quiescent on the context's stream; it may write
+ * its columns with h2hip_upload, with `_dev` functions on the same context, or with any device copy it has completed before returning.  Only
+ * rows < usable_rows matter: the library writes the blinding rows afterwards.  A non-zero return makes the proof return H2HIP_ERR_INVALID
+ * (the last error names the phase) after the stream is drained; the key and the context serve the next proof. */
+typedef int (*h2hip_phase_witness_fn)(void *user, uint32_t phase, const void *challenges_fr, size_t num_challenges, void *const *columns_dev,
+                                      size_t num_columns);
+typedef struct h2hip_phase_witness {
+    h2hip_phase_witness_fn fill;
+    void *user;
+} h2hip_phase_witness;
+
 typedef struct h2hip_plonk_pk h2hip_plonk_pk;
 /* keygen_vk + keygen_pk [UPSTREAM], reference halo2-base/src/utils/testing.rs:224-227.  fixed_host: num_fixed_total columns of 2^k
  * Montgomery Fr (Lagrange values, as the circuit's synthesize assigned them).  copies: ncopies x 4 u32 = (column, row, column, row)
@@ -441,6 +481,9 @@ int h2hip_plonk_keygen(h2hip_ctx *ctx, const h2hip_base_circuit_params *params, 
  * Proofs of such a key go through h2hip_plonk_create_proof: the key carries the shape. */
 int h2hip_plonk_keygen_dyn(h2hip_ctx *ctx, const h2hip_dyn_circuit_params *params, const h2hip_bases *g, const h2hip_bases *g_lagrange,
                            const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out);
+/* the same for the multi-phase configuration above (fixed_host and copies in its layout) */
+int h2hip_plonk_keygen_phased(h2hip_ctx *ctx, const h2hip_phased_circuit_params *params, const h2hip_bases *g, const h2hip_bases *g_lagrange,
+                              const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out);
 void h2hip_plonk_pk_free(h2hip_ctx *ctx, h2hip_plonk_pk *pk);
 /* VerifyingKey contents: fixed_commitments (num_fixed_total x 64 B affine) and permutation commitments (num_perm_columns x 64 B) */
 int h2hip_plonk_pk_commitments(const h2hip_plonk_pk *pk, void *fixed_out, void *permutation_out);
@@ -554,6 +597,13 @@ int h2hip_plonk_create_proof(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
                              const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, uint8_t *proof_out, size_t proof_cap,
                              size_t *proof_len, double *stage_ms);
 
+/* create_proof for a key of the multi-phase configuration: `advice` carries phase 0's columns only (gate columns, then lookup-advice columns);
+ * witness->fill supplies every later phase (see h2hip_phase_witness_fn).  witness may be NULL when the key has one phase.  A BaseConfig or
+ * dynamic-lookup key is H2HIP_ERR_INVALID here, and a key with more than one phase is H2HIP_ERR_INVALID for the single-phase entry. */
+int h2hip_plonk_create_proof_phased(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, int advice_on_device,
+                                    const void *const *instances_host, const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user,
+                                    const h2hip_phase_witness *witness, uint8_t *proof_out, size_t proof_cap, size_t *proof_len, double *stage_ms);
+
 /* verify_proof::<KZGCommitmentScheme<Bn256>, VerifierSHPLONK<_>, Challenge255<_>, Blake2bRead<_, _, _>, SingleStrategy<_>> as the reference runs
  * it after every proof (check_proof, halo2-base/src/utils/testing.rs:64-88).  Host code (the reference verifies on the CPU too): transcript
  * replay, the quotient identity rebuilt from the openings, SHPLONK's folded opening and one pairing check.  fixed / permutation commitments:
@@ -567,6 +617,11 @@ int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void
 int h2hip_plonk_verify_proof_dyn(const h2hip_dyn_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
                                  const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const uint8_t *proof, size_t proof_len,
                                  int *accepted);
+
+/* h2hip_plonk_verify_proof for the multi-phase configuration: the advice commitments are read phase by phase and the challenges squeezed */
+int h2hip_plonk_verify_proof_phased(const h2hip_phased_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
+                                    const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
+                                    const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted);
 
 /* The final CPU-side pairing check of the north star as an entry of its own: *is_one = 1 iff prod_i e(P_i, Q_i) == 1 in Fq12 (what
  * DualMSM::check / halo2curves' multi_miller_loop + final_exponentiation decide for KZG's two pairs).  g1_points: n x 64 B G1Affine

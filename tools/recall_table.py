@@ -14,6 +14,7 @@ P, V, L, S = "halo2-lib_amd/csrc/plonk.hip", "halo2-lib_amd/csrc/verifier.hip", 
 OP, OT, OB = "oracle/plonk.py", "oracle/transcript.py", "oracle/bn254.py"
 HP, VR, PL = "halo2-lib_amd/halo2_proofs.py", "halo2-lib_amd/virtual_region.py", "halo2-lib_amd/plonk.py"
 RG, OC = "halo2-lib_amd/csrc/rng.hip", "oracle/chacha.py"
+PO = "tests/phased_oracle.py"
 
 # (item, what is assumed about upstream, [(file, anchor)] product, [(file, anchor)] oracle, how to flip)
 ITEMS = [
@@ -66,6 +67,9 @@ ITEMS = [
     ("`constrain_instance` / `F: Ord`", "an instance copy is recorded as (advice cell, instance cell); constants are sorted by numeric value of the canonical representation",
      [(VR, 'region.constrain_equal(self.copy_manager.assigned_advices[inst.cell], (("instance", col), i))'), (VR, "copy_manager.constant_equalities.sort(key=lambda t: (t[0], t[1]))")], [],
      "`virtual_region.py` (and `host/halo2_proofs.hpp`); affects the sigma polynomials (verifying key), not validity"),
+    ("multi-phase advice order", "after the instances, per phase in order: the blinding rows of the phase's advice columns (column by column, index order), one blind per column, the phase's commitments in index order, then the challenges `challenge_usable_after(phase)` squeezed (Challenge255); the next phase's witness is synthesised with them; theta follows the last phase.  The advice commitments in the proof are grouped by phase, not in column order; the RNG draws the same number of values before the random polynomial",
+     [(P, "// Multi-phase keys [UPSTREAM-RECALL: create_proof's per-phase loop]")], [(PO, "# ---- advice, phase by phase [UPSTREAM-RECALL")],
+     "the phase loop of `create_proof_impl` (and `blind_phase`), the verifier's phase loop in `verify_impl`, and the oracle's block"),
 ]
 
 
