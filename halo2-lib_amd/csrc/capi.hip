@@ -364,46 +364,12 @@ int h2hip_sync(h2hip_ctx *ctx) {
     return H2HIP_OK;
 }
 
+// (the knobs, their legal values and their inheritance: H2_KNOB_TABLE in internal.h)
 static int *param_slot(h2hip_ctx *ctx, const char *name) {
-    if (!strcmp(name, "msm_window_bits")) return &ctx->msm_window_bits;
-    if (!strcmp(name, "msm_chunk")) return &ctx->msm_chunk;
-    if (!strcmp(name, "msm_seg")) return &ctx->msm_seg;
-    if (!strcmp(name, "ntt_tile_bits")) return &ctx->ntt_tile_bits;
-    if (!strcmp(name, "ntt_debug_skip")) return &ctx->ntt_debug_skip;
-    if (!strcmp(name, "ntt_tile_kernel")) return &ctx->ntt_tile_kernel;
-    if (!strcmp(name, "plonk_warm_keygen")) return &ctx->plonk_warm_keygen;
-    if (!strcmp(name, "plonk_tail_overlap")) return &ctx->plonk_tail_overlap;
-    if (!strcmp(name, "plonk_side_on_lanes")) return &ctx->plonk_side_on_lanes;
-    if (!strcmp(name, "kate_coeffs_per_lane")) return &ctx->kate_coeffs_per_lane;
-    if (!strcmp(name, "quotient_29")) return &ctx->quotient_29;
-    if (!strcmp(name, "kate_29")) return &ctx->kate_29;
-    if (!strcmp(name, "host_poll")) return &ctx->host_poll;
-    if (!strcmp(name, "plonk_merge_products")) return &ctx->plonk_merge_products;
-    if (!strcmp(name, "plonk_shard_side")) return &ctx->plonk_shard_side;
-    if (!strcmp(name, "plonk_route_rows")) return &ctx->plonk_route_rows;
-    if (!strcmp(name, "plonk_lazy_upload")) return &ctx->plonk_lazy_upload;
-    if (!strcmp(name, "plonk_early_intt")) return &ctx->plonk_early_intt;
-    if (!strcmp(name, "plonk_gate_before_join")) return &ctx->plonk_gate_before_join;
-    if (!strcmp(name, "msm_stagger_sorts")) return &ctx->msm_stagger_sorts;
-    if (!strcmp(name, "msm_table_split")) return &ctx->msm_table_split;
-    if (!strcmp(name, "clean_on_lane")) return &ctx->clean_on_lane;
-    if (!strcmp(name, "plonk_permute_in_commit")) return &ctx->plonk_permute_in_commit;
-    if (!strcmp(name, "ntt_full_table")) return &ctx->ntt_full_table;
-    if (!strcmp(name, "ntt_min_col_bits")) return &ctx->ntt_min_col_bits;
-    if (!strcmp(name, "msm_lanes")) return &ctx->msm_lanes;
-    if (!strcmp(name, "msm_quad_tails")) return &ctx->msm_quad_tails;
-    if (!strcmp(name, "msm_scatter_split")) return &ctx->msm_scatter_split;
-    if (!strcmp(name, "msm_hist_packed")) return &ctx->msm_hist_packed;
-    if (!strcmp(name, "msm_chunk_lone")) return &ctx->msm_chunk_lone;
-    if (!strcmp(name, "msm_sort_groups")) return &ctx->msm_sort_groups;
-    if (!strcmp(name, "msm_hist_split")) return &ctx->msm_hist_split;
-    if (!strcmp(name, "msm_scatter_full_lds")) return &ctx->msm_scatter_full_lds;
-    if (!strcmp(name, "msm_sort_threads")) return &ctx->msm_sort_threads;
-    if (!strcmp(name, "msm_fuse_cols")) return &ctx->msm_fuse_cols;
-    if (!strcmp(name, "msm_defer_reduce")) return &ctx->msm_defer_reduce;
-    if (!strcmp(name, "msm_quad_seg_max")) return &ctx->msm_quad_seg_max;
-    if (!strcmp(name, "lookup_big_tile_bits")) return &ctx->lookup_big_tile_bits;
-    if (!strcmp(name, "fr_invert_run")) return &ctx->fr_invert_run;
+#define H2_KNOB_SLOT(knob, inherit, legal, domain) \
+    if (!strcmp(name, #knob)) return &ctx->knob;
+    H2_KNOB_TABLE(H2_KNOB_SLOT)
+#undef H2_KNOB_SLOT
     return nullptr;
 }
 int h2hip_set_param(h2hip_ctx *ctx, const char *name, int value) {
@@ -411,17 +377,17 @@ int h2hip_set_param(h2hip_ctx *ctx, const char *name, int value) {
     H2_REQUIRE(ctx && name, "NULL argument");
     int *p = param_slot(ctx, name);
     H2_REQUIRE(p, "unknown parameter name");
-    if (p == &ctx->msm_window_bits) H2_REQUIRE(value == 0 || (value >= 4 && value <= 16), "msm_window_bits must be 0 (auto) or 4..16 (a window's histogram lives in LDS; at most 64 windows)");
-    if (p == &ctx->msm_chunk) H2_REQUIRE(value == 0 || (value >= 2 && value <= 4096), "msm_chunk must be 0 (auto) or 2..4096");
-    if (p == &ctx->msm_seg) H2_REQUIRE(value >= 1 && value <= 1024 && (value & (value - 1)) == 0, "msm_seg must be a power of two <= 1024");
-    if (p == &ctx->msm_fuse_cols) H2_REQUIRE(value >= 0 && value <= (int)MSM_MAX_COLS, "msm_fuse_cols must be 0 (auto) or 1..32");
-    if (p == &ctx->fr_invert_run) H2_REQUIRE(value >= 0 && value <= 1024, "fr_invert_run must be 0 (auto) or 1..1024");
-    if (p == &ctx->lookup_big_tile_bits) H2_REQUIRE(value >= 12 && value <= 28, "lookup_big_tile_bits must be 12..28");
-    if (p == &ctx->msm_sort_threads) H2_REQUIRE(value == 256 || value == 512 || value == 1024, "msm_sort_threads must be 256, 512 or 1024");
-    if (p == &ctx->msm_scatter_split) H2_REQUIRE(value >= 0 && value <= 64 && (value & (value - 1)) == 0, "msm_scatter_split must be 0 or a power of two <= 64");
-    if (p == &ctx->msm_lanes) H2_REQUIRE(value >= 0 && value <= 4, "msm_lanes must be 0 (auto) or 1..4");
-    if (p == &ctx->ntt_min_col_bits) H2_REQUIRE(value >= 0 && value <= 5, "ntt_min_col_bits must be 0..5");
-    if (p == &ctx->ntt_tile_bits) H2_REQUIRE(value >= 4 && value <= 10, "ntt_tile_bits must be 4..10");
+    // a value outside the knob's domain is refused and the stored value stays
+#define H2_KNOB_CHECK(knob, inherit, legal, domain)                                                     \
+    if (p == &ctx->knob) {                                                                              \
+        const int v = value;                                                                            \
+        if (!(legal)) {                                                                                 \
+            set_error("h2hip_set_param: invalid argument: " #knob " = %d: must be " domain, value);   \
+            return H2HIP_ERR_INVALID;                                                                   \
+        }                                                                                               \
+    }
+    H2_KNOB_TABLE(H2_KNOB_CHECK)
+#undef H2_KNOB_CHECK
     *p = value;
     return H2HIP_OK;
 }

@@ -192,8 +192,9 @@ __global__ __launch_bounds__(256, 3) void ntt_round_probe_kernel(Fr *__restrict_
 // (division steps, modinv.cuh) per lane.  [UPSTREAM ff::BatchInvert / halo2 batch_invert_assigned; denominators come from
 // reference halo2-base/src/gates/flex_gate/mod.rs:677-681,791-795]
 // (r06) src -> dst: out of place when they differ — the grand products invert their denominators straight out of the factor array instead of
-// copying it first (a 32 MiB device copy per proof at k = 19, on the critical path between the factors and the prefix products)
-__global__ __launch_bounds__(256) void fr_batch_invert_kernel(const Fr *__restrict__ src, Fr *__restrict__ dst, Fr *__restrict__ scratch, size_t n) {
+// copying it first (a 32 MiB device copy per proof at k = 19, on the critical path between the factors and the prefix products).  In place
+// (h2hip_fr_batch_invert_dev) src == dst, so neither carries __restrict__ (finding 4): a lane reads src[i] before it writes dst[i].
+__global__ __launch_bounds__(256) void fr_batch_invert_kernel(const Fr *src, Fr *dst, Fr *__restrict__ scratch, size_t n) {
     const size_t T = (size_t)gridDim.x * blockDim.x, t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
     Fr acc = Fr::one();

@@ -177,32 +177,64 @@ struct h2hip_ctx {
 };
 
 namespace h2 {
-// every tuning knob a child context (a batch lane, the prover's side context) takes from its parent — ADVICE r05: host_poll and the r05
-// scheduling knobs did not reach the children, so an A/B through h2hip_set_param switched only part of a proof
+inline bool knob_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+}  // namespace h2
+// Every tuning knob of h2hip_set_param / h2hip_get_param, one entry each: K(member of h2hip_ctx (= the name the API takes), inheritance, whether
+// the value v is legal, the legal values as text).  param_slot, the domain check of h2hip_set_param and h2::inherit_knobs are generated from it
+// (a hand-written copy list missed knobs twice, so an A/B through h2hip_set_param switched only part of a proof).
+// INHERITED: child contexts (batch lanes, the prover's side context) take the parent's value; PARENT_ONLY("why"): the knob is read on the
+// caller's context only.  The defaults stay with the members above.
+#define H2_INHERITED true
+#define H2_PARENT_ONLY(why) false
+#define H2_KNOB_TABLE(K)                                                                                                                          \
+    K(msm_window_bits, H2_INHERITED, v == 0 || (v >= 4 && v <= 16), "0 (auto) or 4..16")                                                         \
+    K(msm_chunk, H2_INHERITED, v == 0 || (v >= 2 && v <= 4096), "0 (auto) or 2..4096")                                                          \
+    K(msm_chunk_lone, H2_INHERITED, v >= -1 && v <= 4096, "-1 (auto), 0 (the batch rule) or 1..4096")                                          \
+    K(msm_seg, H2_INHERITED, h2::knob_pow2(v) && v <= 1024, "a power of two <= 1024")                                                          \
+    K(msm_quad_tails, H2_INHERITED, v == 0 || v == 1, "0 or 1")                                                                                 \
+    K(msm_quad_seg_max, H2_INHERITED, v >= 0, ">= 0")                                                                                           \
+    K(msm_sort_threads, H2_INHERITED, v == 256 || v == 512 || v == 1024, "256, 512 or 1024")                                                   \
+    K(msm_sort_groups, H2_INHERITED, v >= 0 && v <= 1024, "0 (auto) or 1..1024")                                                               \
+    K(msm_hist_split, H2_INHERITED, v == 0 || (h2::knob_pow2(v) && v <= 64), "0 or a power of two <= 64")                                      \
+    K(msm_hist_packed, H2_INHERITED, v == 0 || v == 1, "0 or 1")                                                                                \
+    K(msm_scatter_split, H2_INHERITED, v == 0 || (h2::knob_pow2(v) && v <= 64), "0 (auto) or a power of two <= 64")                            \
+    K(msm_scatter_full_lds, H2_INHERITED, v == 0 || v == 1, "0 or 1")                                                                           \
+    K(msm_table_split, H2_INHERITED, v == 0 || v == 1, "0 or 1")                                                                                \
+    K(msm_lanes, H2_PARENT_ONLY("read only by the batch driver, on the caller's context"), v >= 0 && v <= 4, "0 (auto) or 1..4")              \
+    K(msm_stagger_sorts, H2_PARENT_ONLY("read only by the batch driver, on the caller's context"), v >= -1 && v <= 1, "-1 (auto), 0 or 1")     \
+    K(msm_fuse_cols, H2_PARENT_ONLY("read only by the batch driver, on the caller's context"), v >= 0 && v <= (int)h2::MSM_MAX_COLS,           \
+      "0 (auto) or 1..32")                                                                                                                        \
+    K(msm_defer_reduce, H2_PARENT_ONLY("read only by the batch driver, on the caller's context"), v == 0 || v == 1, "0 or 1")                  \
+    K(clean_on_lane, H2_PARENT_ONLY("read only by the batch driver, on the caller's context"), v == 0 || v == 1, "0 or 1")                     \
+    K(ntt_tile_bits, H2_INHERITED, v >= 4 && v <= 10, "4..10")                                                                                  \
+    K(ntt_min_col_bits, H2_INHERITED, v >= 0 && v <= 5, "0..5")                                                                                 \
+    K(ntt_full_table, H2_INHERITED, v == 0 || v == 1, "0 or 1")                                                                                 \
+    K(ntt_tile_kernel, H2_INHERITED, v == 0 || v == 1, "0 or 1")                                                                                \
+    K(ntt_debug_skip, H2_INHERITED, v >= 0 && v <= 2, "0, 1 or 2")                                                                              \
+    K(quotient_29, H2_INHERITED, v == 0 || v == 1, "0 or 1")                                                                                    \
+    K(kate_29, H2_INHERITED, v == 0 || v == 1, "0 or 1")                                                                                        \
+    K(kate_coeffs_per_lane, H2_INHERITED, v == 0 || v == 1 || v == 2 || v == 4 || v == 8, "0 (by length), 1, 2, 4 or 8")                       \
+    K(fr_invert_run, H2_INHERITED, v >= 0 && v <= 1024, "0 (auto) or 1..1024")                                                                 \
+    K(lookup_big_tile_bits, H2_INHERITED, v >= 12 && v <= 28, "12..28")                                                                         \
+    K(host_poll, H2_INHERITED, v == 0 || v == 1, "0 or 1")                                                                                      \
+    K(plonk_warm_keygen, H2_PARENT_ONLY("read only by h2hip_plonk_keygen"), v == 0 || v == 1, "0 or 1")                                       \
+    K(plonk_tail_overlap, H2_PARENT_ONLY("read only by create_proof, on the caller's context"), v == 0 || v == 1, "0 or 1")                    \
+    K(plonk_side_on_lanes, H2_PARENT_ONLY("read only by create_proof, on the caller's context"), v == 0 || v == 1, "0 or 1")                   \
+    K(plonk_permute_in_commit, H2_PARENT_ONLY("read only by create_proof, on the caller's context"), v == 0 || v == 1, "0 or 1")               \
+    K(plonk_merge_products, H2_PARENT_ONLY("read only by create_proof, on the caller's context"), v == 0 || v == 1, "0 or 1")                  \
+    K(plonk_shard_side, H2_PARENT_ONLY("read only by create_proof, on the caller's context"), v >= 0 && v <= 2, "0, 1 or 2 (forced)")          \
+    K(plonk_route_rows, H2_PARENT_ONLY("read only by create_proof, on the caller's context"), v == 0 || v == 1, "0 or 1")                      \
+    K(plonk_lazy_upload, H2_PARENT_ONLY("read only by create_proof, on the caller's context"), v == 0 || v == 1, "0 or 1")                     \
+    K(plonk_early_intt, H2_PARENT_ONLY("read only by create_proof, on the caller's context"), v == 0 || v == 1, "0 or 1")                      \
+    K(plonk_gate_before_join, H2_PARENT_ONLY("read only by create_proof, on the caller's context"), v == 0 || v == 1, "0 or 1")
+
+namespace h2 {
+// the knobs a child context (a batch lane, the prover's side context) takes from its parent: every H2_INHERITED entry of H2_KNOB_TABLE
 inline void inherit_knobs(h2hip_ctx *c, const h2hip_ctx *p) {
-    c->msm_window_bits = p->msm_window_bits;
-    c->msm_chunk = p->msm_chunk;
-    c->msm_seg = p->msm_seg;
-    c->msm_scatter_split = p->msm_scatter_split;
-    c->msm_scatter_full_lds = p->msm_scatter_full_lds;
-    c->msm_hist_packed = p->msm_hist_packed;
-    c->msm_sort_groups = p->msm_sort_groups;
-    c->msm_hist_split = p->msm_hist_split;
-    c->msm_sort_threads = p->msm_sort_threads;
-    c->msm_quad_tails = p->msm_quad_tails;
-    c->msm_quad_seg_max = p->msm_quad_seg_max;
-    c->msm_seg = p->msm_seg;
-    c->ntt_tile_bits = p->ntt_tile_bits;
-    c->ntt_min_col_bits = p->ntt_min_col_bits;
-    c->ntt_full_table = p->ntt_full_table;
-    c->ntt_tile_kernel = p->ntt_tile_kernel;
-    c->quotient_29 = p->quotient_29;
-    c->kate_29 = p->kate_29;
-    c->kate_coeffs_per_lane = p->kate_coeffs_per_lane;
-    c->fr_invert_run = p->fr_invert_run;
-    c->lookup_big_tile_bits = p->lookup_big_tile_bits;
-    c->host_poll = p->host_poll;
-    c->plonk_route_rows = p->plonk_route_rows;
+#define H2_KNOB_INHERIT(name, inherit, legal, domain) \
+    if (inherit) c->name = p->name;
+    H2_KNOB_TABLE(H2_KNOB_INHERIT)
+#undef H2_KNOB_INHERIT
     c->profiling = p->profiling;
     c->prof_filter = p->prof_filter;
     c->prof_ref = p->prof_ref;   // launch spans of all children share the parent's time origin

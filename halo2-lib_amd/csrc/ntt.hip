@@ -576,13 +576,16 @@ int ntt_run_batch(h2hip_ctx *ctx, Fr *const *a, const Fr *const *in_override, si
         sc.out3[i] = out_scale3 ? out_scale3[i] : Fr::one();
     }
     uint32_t LT = (uint32_t)ctx->ntt_tile_bits;
-    uint32_t mlist[8], P;
+    uint32_t mlist[28], P;   // (at least one stage per pass: P <= log_n <= 28)
     auto plan = [&](uint32_t lt) {
         if (log_n <= lt) {
             P = 1;
             mlist[0] = log_n;
         } else {
-            uint32_t maxm = lt - (uint32_t)ctx->ntt_min_col_bits;   // at least 2^min_col_bits adjacent columns per tile (row segments of 32 B each)
+            // at least 2^min_col_bits adjacent columns per tile (row segments of 32 B each) — but at least one stage per pass: with
+            // ntt_min_col_bits >= ntt_tile_bits the difference was 0 (a division by zero here) or wrapped round (no pass at all)
+            const uint32_t mcb = (uint32_t)ctx->ntt_min_col_bits < lt ? (uint32_t)ctx->ntt_min_col_bits : lt - 1;
+            uint32_t maxm = lt - mcb;
             P = (log_n + maxm - 1) / maxm;
             for (uint32_t i = 0; i < P; ++i) mlist[i] = log_n / P + (i < log_n % P ? 1 : 0);
         }

@@ -1042,8 +1042,13 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
         me.len = pk->shard_len;
         me.rank = pk->shard_rank;
         me.k = k;
+        // + the stages sharded and whether the grand products' rows are routed by an all-to-all (plonk_route_rows, which only acts with
+        // shard_ntt): the exchange schedule depends on them, and ranks that disagree would issue different collectives (finding 2).
+        // (plonk_shard_side is not folded in: it moves the first-round transforms' all-gather to another stream, but every rank still issues the
+        // same collectives in the same host order.)
+        const bool route_rows = pk->shard_ntt && ctx->plonk_route_rows != 0;
         me.ncols = (uint64_t)sh.num_advice_total | (uint64_t)(pk->shard_quotient ? 1 : 0) << 32 | (uint64_t)(pk->shard_products ? 1 : 0) << 33 |
-                   (uint64_t)(pk->shard_ntt ? 1 : 0) << 34;   // + the stages sharded: the exchange schedule depends on them
+                   (uint64_t)(pk->shard_ntt ? 1 : 0) << 34 | (uint64_t)(route_rows ? 1 : 0) << 35;
         {
             Blake2b h(32, "h2hip-shard-rng");
             h.update(pk->host_stage, sizeof(Fr) * (size_t)(n - u));   // the first draw of this proof sits at the start of the staging buffer
@@ -1059,7 +1064,7 @@ static int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *con
             Hello o;
             memcpy(&o, all.data() + (size_t)r * (8 + sizeof(Hello)) + 8, sizeof(Hello));
             if (o.k != me.k || o.ncols != me.ncols || memcmp(o.digest, me.digest, 32) != 0 || o.rank != r) {
-                set_error("create_proof: rank %u of the sharded proof runs a different proof (shape, rank order or RNG stream differ)", r);
+                set_error("create_proof: rank %u of the sharded proof runs a different proof (shape, sharded stages, row routing, rank order or RNG stream differ)", r);
                 return H2HIP_ERR_INVALID;
             }
             ranges.push_back({o.offset, o.len});

@@ -58,28 +58,36 @@ int h2hip_device_count(int *count);
 int h2hip_init(int device, void *hip_stream, h2hip_ctx **out);
 void h2hip_destroy(h2hip_ctx *ctx);
 int h2hip_sync(h2hip_ctx *ctx);
-/* tuning knobs (defaults are the tuned values): "msm_window_bits" (0 = auto), "msm_chunk" (0 = auto), "msm_seg",
- * "msm_scatter_split" (0 = auto), "msm_lanes", "msm_quad_tails", "msm_fuse_cols", "msm_defer_reduce", "ntt_tile_bits" (10),
- * "ntt_tile_kernel" (1 = the specialised full-tile pass kernel, 0 = the generic one), "ntt_min_col_bits", "ntt_full_table",
- * "msm_scatter_full_lds", "msm_sort_threads", "msm_quad_seg_max", "fr_invert_run" (0 = auto), "lookup_big_tile_bits",
- * "kate_coeffs_per_lane" (0 = by length); arithmetic form of the pointwise kernels: "quotient_29", "kate_29" (1 = unsaturated 9 x 29-bit
- * limbs, 0 = the saturated kernels: same results); the prover's scheduling: "plonk_tail_overlap", "plonk_side_on_lanes",
- * "plonk_permute_in_commit", "plonk_warm_keygen", "clean_on_lane" (1 everywhere: 0 switches the overlap off, same proof bytes);
- * r05: "host_poll" (1: results of a round come back through a host-mapped flag instead of hipMemcpyAsync + hipStreamSynchronize),
- * "msm_table_split" (1: base sets uploaded / generated AFTER the call get 128-byte table entries pre-split into 9 x 29-bit limbs),
- * "plonk_merge_products" (1: one batched inversion / prefix product for the permutation set and the lookups when nothing chains),
- * "plonk_shard_side" (1: sharded proofs run the first-round columns' transforms and all-gather on a side stream),
- * "plonk_early_intt" (1: the grand products' lagrange_to_coeff is queued on the side context in front of their commitment round),
- * "plonk_gate_before_join" (0; 1: the quotient's gate identities start before the grand products' transforms are joined — measured neutral),
- * "msm_stagger_sorts" (-1 = auto: two-lane batches; 1 / 0: a batch's lanes start their first sorts one behind the other / together),
- * r06: "msm_hist_packed" (1: the sort's LDS histogram as 16-bit counter pairs whenever a chunk holds < 2^16 scalars), "msm_scatter_full_lds"
- * (0: the scatter declares its cursors only, so that it fits beside running accumulations), "msm_hist_split" (0 / 1 = the whole window per
- * histogram workgroup; n = n bucket sub-ranges), "msm_sort_groups" (0 = auto), "msm_chunk_lone" (-1 = auto: a lone MSM keeps the longer
- * entries-per-lane rule, batch lanes the shorter one), "plonk_lazy_upload" (1: host-resident advice columns 1.. are uploaded inside round 1's
- * commitment batch, each right before its MSM is queued), "plonk_route_rows" (1: sharded proofs route the grand products' rows to the column
- * owners by h2hip_comm_alltoall_dev instead of all-gathering them; same proof bytes);
- * profiling aid: "ntt_debug_skip" (produces wrong results).  The variants r01-r03 measured slower (two-level sort, bucket-major sort,
- * split streams, split windows, accumulation builds 2/5/6/7, radix-8 and wave-local NTT passes) were removed in r04, r05's (two-wave
+/* tuning knobs (defaults are the tuned values; every knob claims the same results at every legal value).  h2hip_set_param refuses a value
+ * outside the knob's legal domain with H2HIP_ERR_INVALID and keeps the stored value.  Child contexts (batch lanes, the prover's side context)
+ * take every knob from their parent except the batch driver's and create_proof's, which only the caller's context reads.  Legal values:
+ * MSM: "msm_window_bits" 0 (auto) or 4..16, "msm_chunk" 0 (auto) or 2..4096 (entries per accumulation lane), "msm_chunk_lone" -1 (auto: a
+ * lone MSM keeps the longer entries-per-lane rule, batch lanes the shorter one), 0 (the batch rule) or 1..4096, "msm_seg" a power of two
+ * <= 1024 (buckets per running-sum segment), "msm_quad_tails" 0 / 1, "msm_quad_seg_max" >= 0 (quad-lane bucket reduction up to this many
+ * segments), "msm_sort_threads" 256, 512 or 1024, "msm_sort_groups" 0 (auto = 32) or 1..1024 (chunks per window of the counting sort),
+ * "msm_hist_split" 0 or a power of two <= 64 (0 / 1 = the whole window per histogram workgroup, else that many bucket sub-ranges, at most
+ * the window's bucket count), "msm_hist_packed" 0 / 1 (r06, 1: the sort's LDS histogram as 16-bit counter pairs whenever a chunk holds
+ * < 2^16 scalars), "msm_scatter_split" 0 (auto) or a power of two <= 64, "msm_scatter_full_lds" 0 / 1 (0: the scatter declares its cursors
+ * only, so that it fits beside running accumulations), "msm_table_split" 0 / 1 (r05, 1: base sets uploaded / generated AFTER the call get
+ * 128-byte table entries pre-split into 9 x 29-bit limbs);
+ * the batch driver (h2hip_msm_g1_batch_dev / _multi_dev): "msm_lanes" 0 (auto) or 1..4, "msm_stagger_sorts" -1 (auto: two-lane batches),
+ * 0 or 1 (a batch's lanes start their first sorts together / one behind the other), "msm_fuse_cols" 0 (auto) or 1..32, "msm_defer_reduce"
+ * 0 / 1, "clean_on_lane" 0 / 1 (the bucket zero-fill on the first lane's stream);
+ * NTT: "ntt_tile_bits" 4..10, "ntt_min_col_bits" 0..5 (at least 2^bits adjacent columns per tile, as far as the tile leaves room for one
+ * stage), "ntt_full_table" 0 / 1, "ntt_tile_kernel" 0 / 1 (1 = the specialised full-tile pass kernel, 0 = the generic one);
+ * arithmetic form of the pointwise kernels: "quotient_29", "kate_29" 0 / 1 (1 = unsaturated 9 x 29-bit limbs, 0 = the saturated kernels),
+ * "kate_coeffs_per_lane" 0 (by length), 1, 2, 4 or 8, "fr_invert_run" 0 (auto) or 1..1024, "lookup_big_tile_bits" 12..28;
+ * r05: "host_poll" 0 / 1 (1: results of a round come back through a host-mapped flag instead of hipMemcpyAsync + hipStreamSynchronize);
+ * the prover's scheduling, all 0 / 1 and the same proof bytes either way: "plonk_tail_overlap", "plonk_side_on_lanes",
+ * "plonk_permute_in_commit", "plonk_warm_keygen", "plonk_merge_products" (1: one batched inversion / prefix product for the permutation set
+ * and the lookups when nothing chains), "plonk_early_intt" (1: the grand products' lagrange_to_coeff is queued on the side context in front
+ * of their commitment round), "plonk_gate_before_join" (0; 1: the quotient's gate identities start before the grand products' transforms
+ * are joined — measured neutral), "plonk_lazy_upload" (1: host-resident advice columns 1.. are uploaded inside round 1's commitment batch,
+ * each right before its MSM is queued), "plonk_route_rows" (1: sharded proofs route the grand products' rows to the column owners by
+ * h2hip_comm_alltoall_dev instead of all-gathering them; every rank of a sharded proof must use the same value); "plonk_shard_side" 0, 1
+ * or 2 (1: sharded proofs run the first-round columns' transforms and all-gather on a side stream where the transport allows it, 2: always);
+ * profiling aid: "ntt_debug_skip" 0, 1 or 2 (produces wrong results).  The variants r01-r03 measured slower (two-level sort, bucket-major
+ * sort, split streams, split windows, accumulation builds 2/5/6/7, radix-8 and wave-local NTT passes) were removed in r04, r05's (two-wave
  * accumulation, sort-first batches, split lone commitments) in r05, r05's wave-owned radix-8 NTT pass ("ntt_w8") and the 48-byte NTT tile
  * layout in r06 (tools/probes/); their A/B logs stay under profiles/. */
 int h2hip_set_param(h2hip_ctx *ctx, const char *name, int value);

@@ -207,6 +207,18 @@ def _worker_scenarios(rank, world, port, q):
             ctx.set_param("plonk_route_rows", 0)
             out[name + "_allgather_rows"] = PL.create_proof(pk, circ.advice, circ.instances, PreDrawnRng(budget, 9)) == single
             ctx.set_param("plonk_route_rows", 1)
+            if name == "multi" and full:
+                # ranks that disagree on plonk_route_rows would issue different collectives (all-to-all against all-gather): the hello exchange
+                # refuses the proof on EVERY rank (finding 2), and the next proof with matching settings goes through
+                ctx.set_param("plonk_route_rows", rank % 2)
+                try:
+                    PL.create_proof(pk, circ.advice, circ.instances, PreDrawnRng(budget, 9))
+                    out["route_mismatch"] = "no error"
+                except H.H2HipError as e:
+                    out["route_mismatch"] = (e.code, "different proof" in str(e))
+                finally:
+                    ctx.set_param("plonk_route_rows", 1)
+                out["after_route_mismatch"] = PL.create_proof(pk, circ.advice, circ.instances, PreDrawnRng(budget, 9)) == single
             if name == "multi":
                 # the exchange schedule libh2hip reports for that proof (bench.py --gpus N prints it): 13 host exchanges with every stage sharded,
                 # the status-only go-aheads at their places, the SHPLONK carry slots at a fixed 64 x 32 bytes
@@ -284,3 +296,5 @@ def test_sharded_create_proof_scenarios(world):
         assert o["multi_allgather_rows"] and o.get("single_allgather_rows", True), (r, o)   # r06: rows routed by all-to-all (default) == rows all-gathered
         assert o["fail"] == (-1 if r == world - 1 else -5), (r, o)     # H2HIP_ERR_INVALID where the witness is wrong, H2HIP_ERR_PEER elsewhere
         assert o["rng"] == -1, (r, o)                                   # every rank sees the mismatch in the hello exchange
+        if world == 2:
+            assert o["route_mismatch"] == (-1, True) and o["after_route_mismatch"], (r, o)   # refused on both ranks, nobody hangs

@@ -625,3 +625,45 @@ def test_flex_gate_reference_kats_emulated(ctx):
         add, sub, mul, mul_add, invert = (staticmethod(f) for f in (ctx.fr_add, ctx.fr_sub, ctx.fr_mul, ctx.fr_mul_add, ctx.fr_batch_invert))
 
     assert GK.check_all(B) == 31
+
+
+# ---- the tuning knobs at their non-default values, against the oracle (tests/knob_checks.py; the GPU suite runs the same at real sizes)
+def test_knobs_msm_sort_geometry_emulated(ctx):
+    """20 000 points: five counting-sort chunks per window at the default chunk count; windows 4 and 6 take the clamp of the larger splits to B"""
+    from tests import knob_checks as K
+
+    assert K.check_msm_sort_geometry(ctx, 20000, (4, 6, 0), threads=4) >= 49
+
+
+def test_knobs_msm_accumulation_and_reduction_emulated(ctx):
+    from tests import knob_checks as K
+
+    K.check_msm_chunk_lone(ctx, 20000, threads=4)
+    assert K.check_msm_quad_seg_max(ctx, 5000, 8, threads=4) == 32 * 32
+    K.check_msm_table_split(ctx, 3000, 8, threads=4)
+
+
+def test_knobs_msm_batch_driver_emulated(ctx):
+    from tests import knob_checks as K
+
+    K.check_msm_batch_driver(ctx, 3000, threads=4)
+
+
+@pytest.mark.parametrize("log_n,ext", [(12, 2), (13, 1)])
+def test_knobs_ntt_emulated(ctx, log_n, ext):
+    """ntt_min_col_bits >= ntt_tile_bits - 2 once divided by zero on the host or planned more passes than the plan holds"""
+    from tests import knob_checks as K
+
+    K.check_ntt_knobs(ctx, log_n, ext, threads=4)
+
+
+def test_knobs_kate_division_emulated(ctx):
+    from tests import knob_checks as K
+
+    K.check_kate_knobs(ctx)
+
+
+def test_knobs_batch_inversion_emulated(ctx):
+    from tests import knob_checks as K
+
+    K.check_invert_run(ctx, (1, 2, 1000, 3001))

@@ -516,3 +516,50 @@ def test_full_range_field_inputs_pointwise(ctx):
     F.check_pointwise(ctx, 100003)
     F.check_inverse_and_products(ctx, [1, 257, 70001, 1 << 19])
     F.check_eval_and_division(ctx, [1, 2049, 1 << 19, (1 << 21) + 5])
+
+
+# ---- the tuning knobs at their non-default values, against the oracle or the known-dlog closed form (tests/knob_checks.py; the CPU suite
+# runs the same on the emulated build at small sizes).  Only legal values are set: the domains are tests/test_knobs.py's (emulated) business.
+def test_knobs_msm_sort_geometry(ctx):
+    """2^20 + 3 points (a last chunk of 3 scalars), windows 4, 6, 16 (the largest B) and auto"""
+    from tests import knob_checks as K
+
+    K.check_msm_sort_geometry(ctx, (1 << 20) + 3, (4, 6, 16, 0), threads=NT, exact=False)
+
+
+def test_knobs_packed_counter_boundary(ctx):
+    from tests import knob_checks as K
+
+    K.check_packed_counter_boundary(ctx, (1 << 21, 33 * 65535, 33 * 65535 + 1), threads=NT)
+
+
+def test_knobs_msm_accumulation_and_reduction(ctx):
+    from tests import knob_checks as K
+
+    K.check_msm_chunk_lone(ctx, (1 << 20) + 3, threads=NT, exact=False)
+    assert K.check_msm_quad_seg_max(ctx, (1 << 20) + 3, 16, threads=NT, exact=False) == 16 * 8192
+    K.check_msm_table_split(ctx, (1 << 16) + 1, 16, threads=NT)
+
+
+def test_knobs_msm_batch_driver(ctx):
+    from tests import knob_checks as K
+
+    K.check_msm_batch_driver(ctx, (1 << 18) + 5, threads=NT, exact=False)
+
+
+def test_knobs_ntt(ctx):
+    from tests import knob_checks as K
+
+    K.check_ntt_knobs(ctx, 20, 1, threads=NT)
+
+
+def test_knobs_kate_division(ctx):
+    from tests import knob_checks as K
+
+    K.check_kate_knobs(ctx, threads=NT)
+
+
+def test_knobs_batch_inversion(ctx):
+    from tests import knob_checks as K
+
+    K.check_invert_run(ctx, (1, 1000, 70001, (1 << 19) + 7))

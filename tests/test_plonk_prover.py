@@ -213,10 +213,14 @@ def test_create_proof_schedule_switches_emulated():
         sh, kzg, params, circ, gpk = _setup(ctx, 6, 2, 2, 1, 0, 4, 1, 1, True)
         rng = lambda: PreDrawnRng(_rng_budget(sh), 1)
         plain = PL.create_proof(gpk, circ.advice, circ.instances, rng())
-        names = ("plonk_early_intt", "msm_stagger_sorts", "msm_fuse_cols", "plonk_gate_before_join")
+        inst = [O.limbs_to_ints(v, R) for v in circ.instances]
+        assert plain == P.create_proof(params, _oracle_pk(sh, params, circ, 4), circ.advice, inst, rng(), 4), "proof bytes differ from the oracle prover's"
+        # + the round trips through the runtime's copy and wait (host_poll = 0) and the batch's bucket clean-up on the context's clean stream
+        # (clean_on_lane = 0)
+        names = ("plonk_early_intt", "msm_stagger_sorts", "msm_fuse_cols", "plonk_gate_before_join", "host_poll", "clean_on_lane")
         old = {n: ctx.get_param(n) for n in names}
         try:
-            for vals in ((1, 0, 0, 0), (0, 1, 1, 1), (1, 1, 1, 1), (0, 0, 0, 0)):
+            for vals in ((1, 0, 0, 0, 0, 1), (0, 1, 1, 1, 1, 0), (1, 1, 1, 1, 0, 0), (0, 0, 0, 0, 1, 1)):
                 for n, v in zip(names, vals):
                     ctx.set_param(n, v)
                 assert PL.create_proof(gpk, circ.advice, circ.instances, rng()) == plain, vals
@@ -225,6 +229,15 @@ def test_create_proof_schedule_switches_emulated():
                 ctx.set_param(n, v)
         gpk.free()
         kzg.free()
+        # msm_table_split is read when the base sets are made: the SRS set up (and the key made) under 0 proves the same bytes
+        ctx.set_param("msm_table_split", 0)
+        try:
+            sh2, kzg2, _, circ2, gpk2 = _setup(ctx, 6, 2, 2, 1, 0, 4, 1, 1, True)
+            assert PL.create_proof(gpk2, circ2.advice, circ2.instances, rng()) == plain
+            gpk2.free()
+            kzg2.free()
+        finally:
+            ctx.set_param("msm_table_split", 1)
     finally:
         ctx.close()
 

@@ -62,6 +62,13 @@ def _prove_both_ways(ctx, shape, make_comm, precompute, seed=4):
     for flags in (SHARD_QUOTIENT | SHARD_PRODUCTS | SHARD_NTT_COLUMNS | SHARD_FORCE, SHARD_FORCE):   # every sharded stage / commitments, evaluations and SHPLONK only
         ctx._chk(ctx.lib.h2hip_plonk_pk_set_sharding(pk.handle, comm, kzg.g.handle, kzg.g_lagrange.handle, 0, n, flags))
         assert PL.create_proof(pk, circ.advice, circ.instances, PreDrawnRng(budget, 9)) == single, flags
+        # the first-round columns' transforms (and their all-gather) on the main stream instead of the side stream: the same bytes
+        old_side = ctx.get_param("plonk_shard_side")
+        try:
+            ctx.set_param("plonk_shard_side", 0)
+            assert PL.create_proof(pk, circ.advice, circ.instances, PreDrawnRng(budget, 9)) == single, (flags, "plonk_shard_side = 0")
+        finally:
+            ctx.set_param("plonk_shard_side", old_side)
     ctx._chk(ctx.lib.h2hip_plonk_pk_set_sharding(pk.handle, None, None, None, 0, 0, 0))
     assert PL.create_proof(pk, circ.advice, circ.instances, PreDrawnRng(budget, 9)) == single
     assert PL.verify_proof(pk, circ.instances, single)
