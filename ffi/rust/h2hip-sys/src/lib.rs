@@ -59,6 +59,20 @@ pub struct h2hip_phase_witness {
     pub fill: h2hip_phase_witness_fn,
     pub user: *mut c_void,
 }
+/// one failure of h2hip_plonk_check_witness: kind H2HIP_WITNESS_GATE (column = advice index of the gate column), _LOOKUP (column = lookup
+/// index) or _COPY (column, row = permutation column and row; peer_* = sigma of that cell)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct h2hip_witness_failure {
+    pub kind: u32,
+    pub column: u32,
+    pub row: u32,
+    pub peer_column: u32,
+    pub peer_row: u32,
+}
+pub const H2HIP_WITNESS_GATE: u32 = 1;
+pub const H2HIP_WITNESS_LOOKUP: u32 = 2;
+pub const H2HIP_WITNESS_COPY: u32 = 3;
 /// state of libh2hip's ready-made array RNG (`h2hip_array_rng_fill` as the `h2hip_rng_fill_fn`)
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -285,6 +299,9 @@ extern "C" {
                                            instances_host: *const *const c_void, instance_lens: *const usize, rng: h2hip_rng_fill_fn, rng_user: *mut c_void,
                                            witness: *const h2hip_phase_witness, proof_out: *mut u8, proof_cap: usize, proof_len: *mut usize,
                                            stage_ms: *mut f64) -> c_int;
+    pub fn h2hip_plonk_check_witness(ctx: *mut h2hip_ctx, pk: *const h2hip_plonk_pk, advice: *const *const c_void, advice_on_device: c_int,
+                                     instances_host: *const *const c_void, instance_lens: *const usize, failures_out: *mut h2hip_witness_failure,
+                                     max_failures: usize, num_failures: *mut usize) -> c_int;
     pub fn h2hip_lookup_sorted_table_bytes(usable_rows: usize) -> usize;
     pub fn h2hip_lookup_table_sort_dev(ctx: *mut h2hip_ctx, s_dev: *const c_void, usable_rows: usize, sorted_out_dev: *mut c_void) -> c_int;
     pub fn h2hip_lookup_permute_presorted_dev(ctx: *mut h2hip_ctx, a_dev: *const c_void, sorted_table_dev: *const c_void, usable_rows: usize,

@@ -391,6 +391,44 @@ impl<'b, 'g> ProvingKeyHip<'b, 'g> {
         check(unsafe { h2hip_plonk_pk_set_transcript_repr(key.pk, fr_ptr(&repr)) })?;
         Ok(key)
     }
+    /// `MockProver::run(k, &circuit, instances).verify()` on the GPU with this key (h2hip_plonk_check_witness): `advice` holds EVERY advice
+    /// column of the key's layout (all phases, index order), at least usable_rows rows each.  Returns the exact number of failures and the
+    /// first `max_failures` of them in canonical order (gate, lookup, copy; by column, then row).
+    pub fn check_witness(&self, advice: &[Vec<Fr>], instances: &[&[Fr]], max_failures: usize)
+                         -> Result<(usize, Vec<h2hip_witness_failure>), HipError> {
+        if advice.len() != self.shape.num_advice_total as usize {
+            return Err(invalid(format!("check_witness: {} advice columns, the key has {}", advice.len(), self.shape.num_advice_total)));
+        }
+        if let Some(c) = advice.iter().position(|c| c.len() < self.shape.usable_rows as usize) {
+            return Err(invalid(format!("check_witness: advice column {c} has fewer than the {} usable rows", self.shape.usable_rows)));
+        }
+        if instances.len() != self.params.num_instance as usize {
+            return Err(invalid(format!("check_witness: {} instance columns, the circuit has {}", instances.len(), self.params.num_instance)));
+        }
+        let adv: Vec<*const c_void> = advice.iter().map(|c| c.as_ptr().cast()).collect();
+        let ins: Vec<*const c_void> = instances.iter().map(|c| c.as_ptr().cast()).collect();
+        let lens: Vec<usize> = instances.iter().map(|c| c.len()).collect();
+        let mut out = vec![h2hip_witness_failure::default(); max_failures];
+        let mut total = 0usize;
+        check(unsafe {
+            h2hip_plonk_check_witness(self.be.ctx, self.pk, adv.as_ptr(), 0, ins.as_ptr(), lens.as_ptr(),
+                                      if max_failures == 0 { ptr::null_mut() } else { out.as_mut_ptr() }, max_failures, &mut total)
+        })?;
+        out.truncate(total.min(max_failures));
+        Ok((total, out))
+    }
+    /// `MockProver::assert_satisfied`: panics with one line per failure (at most 16) when the witness does not satisfy the circuit
+    pub fn assert_satisfied(&self, advice: &[Vec<Fr>], instances: &[&[Fr]]) {
+        let (total, fails) = self.check_witness(advice, instances, 16).expect("check_witness");
+        if total > 0 {
+            let lines: Vec<String> = fails.iter().map(|f| match f.kind {
+                H2HIP_WITNESS_GATE => format!("gate column {} not satisfied at row {}", f.column, f.row),
+                H2HIP_WITNESS_LOOKUP => format!("lookup {}: input at row {} is not in the table", f.column, f.row),
+                _ => format!("copy: permutation column {} row {} != column {} row {}", f.column, f.row, f.peer_column, f.peer_row),
+            }).collect();
+            panic!("witness not satisfied: {total} failures\n{}", lines.join("\n"));
+        }
+    }
     /// `create_proof(params, pk, &[circuit], &[instances], rng, &mut transcript)` after synthesis: returns what
     /// `transcript.finalize()` would.  `rng_fill` is called for every batch of `Fr::random(rng)` draws, in upstream's order.
     /// `advice` holds phase 0's columns; `later_phases(phase, challenges)` synthesises every later phase's columns (gate columns, then

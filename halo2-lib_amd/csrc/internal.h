@@ -324,4 +324,26 @@ int comm_reserve_alltoall_dev(h2hip_comm *c, size_t bytes);
 int plonk_phased_layout(const h2hip_phased_circuit_params &pp, h2hip_plonk_shape *shape, std::vector<std::vector<int>> *phase_cols,
                         uint32_t challenges[H2HIP_MAX_PHASE], bool *phased, h2hip_base_circuit_params *bp);
 int msm_reduce_cols(h2hip_ctx *ctx, const h2hip_bases *bases, uint32_t window_bits, const XYZZ29 *buckets, uint32_t ncols, XYZZ *out_dev);
+// lookup.hip: the key count a sort of u keys pads to (a power of two, at least one tile), and the bitonic network over N = lookup_padded_keys(u)
+// caller-made 32-byte keys (ascending by limb 7 .. 0; the caller pads with all-ones)
+uint32_t lookup_padded_keys(uint32_t u);
+int lookup_sort_keys_dev(h2hip_ctx *ctx, void *keys, uint32_t N);
+// witness_check.hip: the kernels of h2hip_plonk_check_witness over a layout plonk.hip derives from the key.  Columns are named by a flat index
+// into `cols` (device values, usable rows read); every failure is one bit of a mask over (gate columns + lookups + permutation columns) x rows.
+struct WitnessCheckJob {
+    uint32_t u = 0;                             // usable rows
+    std::vector<const Fr *> cols;               // every column's values on the device
+    std::vector<uint32_t> gate_adv, gate_q;     // per gate column: its advice column, its q_enable (flat indices)
+    std::vector<uint32_t> gate_report;          // per gate column: the advice index a failure names
+    std::vector<uint32_t> lk_in, lk_q;          // range lookups: the input column, the complex selector (WC_NONE: none) per lookup
+    const void *table_sorted = nullptr;         // range lookups: the table's sorted canonical keys (h2hip_lookup_table_sort_dev)
+    uint32_t dyn_width = 0;                     // dynamic lookups: columns per tuple (0: range lookups)
+    std::vector<uint32_t> dyn_in, dyn_tab;      // dynamic lookups: [lookup][dyn_width] input tuples, [dyn_width] the table tuple
+    uint32_t num_lookups = 0;
+    std::vector<uint32_t> perm_col;             // every permutation column (flat index)
+    const uint16_t *sigma_c = nullptr;          // [perm column][u]: sigma of every usable cell (device)
+    const uint32_t *sigma_r = nullptr;
+};
+constexpr uint32_t WC_NONE = 0xFFFFFFFFu;
+int witness_check_run(h2hip_ctx *ctx, const WitnessCheckJob &job, h2hip_witness_failure *failures_out, size_t max_failures, size_t *num_failures);
 }  // namespace h2

@@ -389,6 +389,8 @@ int lookup_compress_batch_dev(h2hip_ctx *ctx, const Fr *const *cols, Fr *const *
     H2_HIPCHK(hipGetLastError());
     return H2HIP_OK;
 }
+uint32_t lookup_padded_keys(uint32_t u) { return padded_keys(u); }
+int lookup_sort_keys_dev(h2hip_ctx *ctx, void *keys, uint32_t N) { return bitonic_sort(ctx, (Key256 *)keys, N); }
 
 }  // namespace h2
 

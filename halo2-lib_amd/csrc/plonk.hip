@@ -366,6 +366,12 @@ struct h2hip_plonk_pk {
     hipEvent_t side_ev = nullptr, side_ev1 = nullptr;   // side_ev: everything queued on the side stream so far; side_ev1: the first-round columns' transforms
     Fr *host_stage = nullptr;   // pinned staging for the RNG-drawn scalars (the n coefficients of the random polynomial, the blinding rows)
     size_t host_stage_elems = 0;
+    // the copy cycles for h2hip_plonk_check_witness: sigma(c, r) = (sigma_c, sigma_r)[c * usable_rows + r] over the usable rows (copies stay in
+    // them, so every other cell maps to itself).  Kept on the host; uploaded by the first check into buffers the key owns.
+    std::vector<uint16_t> sigma_c_host;
+    std::vector<uint32_t> sigma_r_host;
+    uint16_t *sigma_c_dev = nullptr;
+    uint32_t *sigma_r_dev = nullptr;
 };
 
 namespace h2 {
@@ -508,6 +514,15 @@ static int keygen_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *fi
         H2_REQUIRE(c[1] < sh.usable_rows && c[3] < sh.usable_rows, "copy constraint outside the usable rows (NotEnoughRowsAvailable)");
         as.copy(c[0], c[1], c[2], c[3]);
     }
+    H2_REQUIRE(m <= 65536, "more than 65536 permutation columns");
+    pk->sigma_c_host.resize((size_t)m * sh.usable_rows);
+    pk->sigma_r_host.resize((size_t)m * sh.usable_rows);
+    for (uint32_t c = 0; c < m; ++c)
+        for (uint32_t r = 0; r < sh.usable_rows; ++r) {
+            const size_t i = (size_t)c * n + r, o = (size_t)c * sh.usable_rows + r;
+            pk->sigma_c_host[o] = (uint16_t)as.map_c[i];
+            pk->sigma_r_host[o] = as.map_r[i];
+        }
     std::vector<Fr> wpow(n), dpow(m ? m : 1), col(n);
     wpow[0] = Fr::one();
     for (uint32_t j = 1; j < n; ++j) wpow[j] = fe_mul(wpow[j - 1], pk->dom.omega);
@@ -2466,6 +2481,97 @@ int h2hip_plonk_create_proof_phased(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const vo
     H2_REQUIRE(!pk || pk->sh.phase_cols.size() <= 1 || (witness && witness->fill), "h2hip_plonk_create_proof_phased: a later phase needs the witness callback");
     return create_proof_entry(ctx, pk, advice, advice_on_device, instances_host, instance_lens, rng, rng_user, witness, proof_out, proof_cap, proof_len,
                               stage_ms);
+}
+
+// MockProver's verdict on the GPU (include/h2hip.h): the key's layout as a WitnessCheckJob for witness_check.hip
+int h2hip_plonk_check_witness(h2hip_ctx *ctx, const h2hip_plonk_pk *pk_in, const void *const *advice, int advice_on_device,
+                              const void *const *instances_host, const size_t *instance_lens, h2hip_witness_failure *failures_out,
+                              size_t max_failures, size_t *num_failures) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && pk_in && advice && num_failures, "NULL argument");
+    H2_REQUIRE(failures_out || max_failures == 0, "failures_out is NULL and max_failures > 0");
+    h2hip_plonk_pk *pk = const_cast<h2hip_plonk_pk *>(pk_in);   // (its buffer pool and the one-time upload of the cycles)
+    H2_REQUIRE(pk->ctx == ctx, "the proving key belongs to another context");
+    const Shape &sh = pk->sh;
+    const uint32_t n = sh.n, u = sh.usable_rows, F = sh.num_fixed_total, A = sh.num_advice_total, I = sh.p.num_instance;
+    H2_REQUIRE(I == 0 || instance_lens, "instance_lens is required");
+    for (uint32_t c = 0; c < A; ++c) H2_REQUIRE(advice[c], "NULL advice column");
+    for (uint32_t i = 0; i < I; ++i) {
+        H2_REQUIRE(instance_lens[i] <= u, "InstanceTooLarge");
+        H2_REQUIRE(instance_lens[i] == 0 || (instances_host && instances_host[i]), "NULL instance column");
+    }
+    *num_failures = 0;
+    hipStream_t st = ctx->stream;
+    const uint32_t m = (uint32_t)sh.perm_columns.size();
+    if (m && !pk->sigma_c_dev) {
+        void *c = nullptr, *r = nullptr;
+        H2_HIPCHK(hipMalloc(&c, sizeof(uint16_t) * pk->sigma_c_host.size()));
+        pk->owned.push_back(c);
+        H2_HIPCHK(hipMalloc(&r, sizeof(uint32_t) * pk->sigma_r_host.size()));
+        pk->owned.push_back(r);
+        H2_HIPCHK(hipMemcpyAsync(c, pk->sigma_c_host.data(), sizeof(uint16_t) * pk->sigma_c_host.size(), hipMemcpyHostToDevice, st));
+        H2_HIPCHK(hipMemcpyAsync(r, pk->sigma_r_host.data(), sizeof(uint32_t) * pk->sigma_r_host.size(), hipMemcpyHostToDevice, st));
+        H2_HIPCHK(hipStreamSynchronize(st));
+        pk->sigma_c_dev = (uint16_t *)c;
+        pk->sigma_r_dev = (uint32_t *)r;
+    }
+    Scope sc(&pk->pool);
+    WitnessCheckJob job;
+    job.u = u;
+    for (uint32_t c = 0; c < F; ++c) job.cols.push_back(pk->fixed_values[c]);
+    int rc = H2HIP_OK;
+    for (uint32_t c = 0; c < A && rc == H2HIP_OK; ++c) {
+        if (advice_on_device) {
+            job.cols.push_back((const Fr *)advice[c]);
+            continue;
+        }
+        Fr *d = nullptr;
+        rc = sc.take(n, &d);
+        if (rc == H2HIP_OK && hipMemcpyAsync(d, advice[c], sizeof(Fr) * u, hipMemcpyHostToDevice, st) != hipSuccess) {
+            set_error("h2hip_plonk_check_witness: advice upload failed");
+            rc = H2HIP_ERR_HIP;
+        }
+        job.cols.push_back(d);
+    }
+    for (uint32_t i = 0; i < I && rc == H2HIP_OK; ++i) {   // zero-padded as create_proof pads them
+        Fr *d = nullptr;
+        rc = sc.take(n, &d);
+        if (rc == H2HIP_OK && (hipMemsetAsync(d, 0, sizeof(Fr) * u, st) != hipSuccess ||
+                               (instance_lens[i] && hipMemcpyAsync(d, instances_host[i], sizeof(Fr) * instance_lens[i], hipMemcpyHostToDevice, st) != hipSuccess))) {
+            set_error("h2hip_plonk_check_witness: instance upload failed");
+            rc = H2HIP_ERR_HIP;
+        }
+        job.cols.push_back(d);
+    }
+    if (rc == H2HIP_OK) {
+        auto flat = [&](const ColumnRef &c) -> uint32_t { return c.kind == 0 ? (uint32_t)c.index : c.kind == 1 ? F + (uint32_t)c.index : F + A + (uint32_t)c.index; };
+        for (uint32_t g = 0; g < sh.p.num_advice; ++g) {
+            job.gate_report.push_back(sh.first_gate_advice + g);
+            job.gate_adv.push_back(F + sh.first_gate_advice + g);
+            job.gate_q.push_back((uint32_t)sh.first_q_enable_col + g);
+        }
+        job.num_lookups = (uint32_t)sh.lookups.size();
+        if (sh.dyn) {
+            job.dyn_width = sh.key_cols + 1;
+            for (const Lookup &l : sh.lookups)
+                for (const ColumnRef &c : l.in) job.dyn_in.push_back(flat(c));
+            if (!sh.lookups.empty())
+                for (const ColumnRef &c : sh.lookups[0].tab) job.dyn_tab.push_back(flat(c));
+        } else {
+            for (const Lookup &l : sh.lookups) {
+                job.lk_in.push_back(F + (uint32_t)l.advice_col);
+                job.lk_q.push_back(l.q_col >= 0 ? (uint32_t)l.q_col : WC_NONE);
+            }
+            job.table_sorted = pk->table_sorted;
+        }
+        for (const ColumnRef &c : sh.perm_columns) job.perm_col.push_back(flat(c));
+        job.sigma_c = pk->sigma_c_dev;
+        job.sigma_r = pk->sigma_r_dev;
+        rc = witness_check_run(ctx, job, failures_out, max_failures, num_failures);
+    }
+    hipStreamSynchronize(st);   // nothing of the check may still read buffers that go back to the pool
+    if (rc != H2HIP_OK) *num_failures = 0;
+    return rc;
 }
 
 }  // extern "C"

@@ -145,6 +145,7 @@ _PROTOS = {
     "h2hip_lookup_permute_presorted_dev": (_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "h2hip_poseidon_set_spec": (_int, [_vp, _u32, _u32, _u32, _vp, _vp]),
     "h2hip_poseidon_permute_batch_dev": (_int, [_vp, _vp, _vp, _u32, _sz]),
+    "h2hip_plonk_check_witness": (_int, [_vp, _vp, C.POINTER(_vp), _int, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_sz)]),
     "h2hip_plonk_verify_proof": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_int)]),
     "h2hip_plonk_verify_proof_dyn": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_int)]),
     "h2hip_plonk_verify_proof_phased": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_int)]),
@@ -156,6 +157,13 @@ _PROTOS = {
 }
 # symbols added by later translation units register themselves here (see fr_ops section below)
 EXPORTED_SYMBOLS = list(_PROTOS)
+
+WITNESS_GATE, WITNESS_LOOKUP, WITNESS_COPY = 1, 2, 3   # H2HIP_WITNESS_*
+
+
+class WitnessFailureStruct(C.Structure):
+    """h2hip_witness_failure: one failure of h2hip_plonk_check_witness"""
+    _fields_ = [("kind", C.c_uint32), ("column", C.c_uint32), ("row", C.c_uint32), ("peer_column", C.c_uint32), ("peer_row", C.c_uint32)]
 
 
 class H2HipError(RuntimeError):

@@ -15,11 +15,11 @@ from __future__ import annotations
 
 import ctypes as C
 import hashlib
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from .h2hip import Context, _fe, _ptr
+from .h2hip import WITNESS_COPY, WITNESS_GATE, WITNESS_LOOKUP, Context, WitnessFailureStruct, _fe, _ptr
 from .halo2_proofs import ParamsKZG, R_MOD, fr_int, fr_limbs
 
 _vp = C.c_void_p
@@ -402,3 +402,65 @@ def verify_proof(pk: ProvingKey, instances: Sequence[np.ndarray], proof: bytes) 
                                               _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128), ip, il,
                                               _vp(buf.ctypes.data), len(buf), C.byref(ok)))
     return bool(ok.value)
+
+
+class WitnessFailure(NamedTuple):
+    """one failure of check_witness (h2hip_witness_failure): kind = "gate" (column = advice index of the gate column), "lookup" (column = lookup
+    index in the key's order) or "copy" (column, row = permutation column and row; peer_* = sigma of that cell); row = the gate's / input's row"""
+    kind: str
+    column: int
+    row: int
+    peer_column: int = 0
+    peer_row: int = 0
+
+    def __str__(self) -> str:
+        if self.kind == "gate":
+            return "gate column %d not satisfied at row %d" % (self.column, self.row)
+        if self.kind == "lookup":
+            return "lookup %d: input at row %d is not in the table" % (self.column, self.row)
+        return "copy: permutation column %d row %d != column %d row %d" % (self.column, self.row, self.peer_column, self.peer_row)
+
+
+_KINDS = {WITNESS_GATE: "gate", WITNESS_LOOKUP: "lookup", WITNESS_COPY: "copy"}
+
+
+def check_witness(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarray] = (), max_failures: int = 64,
+                  advice_on_device: bool = False) -> tuple:
+    """MockProver::run(k, &circuit, instances).verify() for the key's configuration, on the GPU (h2hip_plonk_check_witness): every advice
+    column of the key (all phases of a PhasedCircuitParams key, advice index order; host (n,4) arrays or device pointers with advice_on_device),
+    the instance columns.  Returns (exact number of failures, the first max_failures of them in canonical order: gate, lookup, copy; by column,
+    then row)."""
+    ctx, sh = pk.ctx, pk.shape
+    n = 1 << pk.params.k
+    if len(advice) != sh.num_advice_total:
+        raise ValueError("check_witness: need %d advice columns" % sh.num_advice_total)
+    keep = None
+    if advice_on_device:
+        adv = (_vp * len(advice))(*[_vp(int(p)) for p in advice])
+    else:
+        keep = [_fe(c) for c in advice]
+        if any(len(c) != n for c in keep):
+            raise ValueError("check_witness: advice columns must have 2^k elements")
+        adv = (_vp * len(keep))(*[_vp(c.ctypes.data) for c in keep])
+    inst = [_fe(c) for c in instances]
+    if len(inst) != pk.params.num_instance:
+        raise ValueError("check_witness: need %d instance columns" % pk.params.num_instance)
+    ip = (_vp * max(len(inst), 1))(*[_vp(c.ctypes.data) for c in inst])
+    il = (C.c_size_t * max(len(inst), 1))(*[len(c) for c in inst])
+    out = (WitnessFailureStruct * max(max_failures, 1))()
+    total = C.c_size_t(0)
+    ctx._chk(ctx.lib.h2hip_plonk_check_witness(ctx.handle, pk.handle, adv, 1 if advice_on_device else 0, ip, il,
+                                               C.cast(out, _vp) if max_failures else None, max_failures, C.byref(total)))
+    del keep
+    got = [WitnessFailure(_KINDS[f.kind], f.column, f.row, f.peer_column, f.peer_row) for f in out[: min(total.value, max_failures)]]
+    return total.value, got
+
+
+def assert_satisfied(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarray] = (), max_failures: int = 16,
+                     advice_on_device: bool = False) -> None:
+    """MockProver::assert_satisfied: raises AssertionError naming the first failures (kind, column, row) when the witness does not satisfy the
+    key's circuit"""
+    total, fails = check_witness(pk, advice, instances, max_failures, advice_on_device)
+    if total:
+        more = "" if total <= len(fails) else "\n... and %d more" % (total - len(fails))
+        raise AssertionError("witness not satisfied: %d failure%s\n" % (total, "" if total == 1 else "s") + "\n".join(map(str, fails)) + more)

@@ -612,6 +612,30 @@ int h2hip_plonk_create_proof_phased(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const vo
                                     const void *const *instances_host, const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user,
                                     const h2hip_phase_witness *witness, uint8_t *proof_out, size_t proof_cap, size_t *proof_len, double *stage_ms);
 
+/* ---- witness check: what MockProver::run(k, &circuit, instances).verify() answers (halo2-base/src/utils/testing.rs:183-188), specialised to the
+ * one gate form and the lookup forms of the three configurations above; not a generic expression evaluator.  Over the usable rows r < usable_rows,
+ * exactly in Fr (advice rows >= usable_rows are ignored, as create_proof ignores them):
+ *   GATE    gate column g, row r with q_enable_g[r] != 0: q * (a[r] + b[r+1] * c[r+2] - d[r+3]) == 0 (the prover's quotient term); a row with
+ *           r + 3 >= usable_rows fails whatever the values (those cells are blinding rows: MockProver reports them unassigned)
+ *   LOOKUP  every row's input expression (q_lookup * a, a lookup-advice column a, or the dynamic tuple [k_0..k_{m-1}, key_is_enabled]) occurs
+ *           among the table expression's values at rows < usable_rows (a tuple: exact membership of every component)
+ *   COPY    every permutation column c, row r: the cell equals sigma(c, r), the next cell of its cycle (constants from the key, instances
+ *           zero-padded as create_proof pads them)
+ * advice: every advice column of the key's layout (all phases of a multi-phase key, advice index order), host or device (advice_on_device)
+ * pointers, usable_rows rows read; instances as for create_proof.  *num_failures = the exact number of failures; failures_out[0 ..
+ * min(max_failures, total)) = the first ones in canonical order (gate, then lookup, then copy; by column or lookup index, then by row);
+ * failures_out may be NULL when max_failures == 0.  A witness with failures is not an error (H2HIP_OK).  Synchronous; a sharded key is checked
+ * locally.  The key and the context serve the next create_proof unchanged. */
+#define H2HIP_WITNESS_GATE 1   /* column = gate column (advice index), row = the gate's row */
+#define H2HIP_WITNESS_LOOKUP 2 /* column = lookup index (shape order), row = the input row */
+#define H2HIP_WITNESS_COPY 3   /* column, row = permutation column and row; peer_* = sigma of that cell */
+typedef struct h2hip_witness_failure {
+    uint32_t kind, column, row, peer_column, peer_row;
+} h2hip_witness_failure;
+int h2hip_plonk_check_witness(h2hip_ctx *ctx, const h2hip_plonk_pk *pk, const void *const *advice, int advice_on_device,
+                              const void *const *instances_host, const size_t *instance_lens, h2hip_witness_failure *failures_out,
+                              size_t max_failures, size_t *num_failures);
+
 /* verify_proof::<KZGCommitmentScheme<Bn256>, VerifierSHPLONK<_>, Challenge255<_>, Blake2bRead<_, _, _>, SingleStrategy<_>> as the reference runs
  * it after every proof (check_proof, halo2-base/src/utils/testing.rs:64-88).  Host code (the reference verifies on the CPU too): transcript
  * replay, the quotient identity rebuilt from the openings, SHPLONK's folded opening and one pairing check.  fixed / permutation commitments:
