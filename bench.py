@@ -6,13 +6,19 @@ One step = ONE `create_proof` for the configuration BASELINE.json's metric is qu
 halo2-ecc/configs/secp256k1/bench_ecdsa.config:1 (`h2hip_plonk_create_proof`: Blake2b transcript, 12 MSMs of 2^19 points, the lookup sort, grand
 products, h(X) over the 2^21-point extended domain, evaluations, SHPLONK; proof bytes out).  Inputs are resident in HBM when the
 timed region starts: SRS tables, proving key and the advice column (`advice_on_device`); the blinding scalars come from the host RNG callback as
-in the reference.  The same call with the advice column in host memory (the Vec the Rust prover fills; its 16 MiB upload inside the call) is
-timed beside it: `seconds_per_proof_host_advice`, the PCIe-inclusive rate.
+in the reference.
+
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` if asked and prints the result line: the metric and its value, the
+configuration and the HBM roofline of the dominant kernel from the timed steps' own HIP events.  `--full` adds everything else below, all of it
+after the timed steps: the checks of the timed proof (verified, the same bytes from host-resident advice and from every RNG path), the further
+timings, the rooflines and accounts that take runs of their own, the CPU baseline and the side blocks.
 
   value        = constraints/s = assigned advice cells of the circuit / seconds per proof
   roofline     = the proof's dominant kernel, msm_accum_kernel: algorithmic 96 B x 2^19 per launch over its mean duration inside the timed
-                 region (HIP events on the launch streams); `roofline_int`: the same launch against the binding roof, the 254-bit
-                 multiplier peak measured in the same run; `roofline_proof`: the whole proof's algorithmic products / bytes over its wall time
+                 region (HIP events on the launch streams); with --full, `roofline_int`: the same launch against the binding roof, the 254-bit
+                 multiplier peak measured in the same run; `roofline_proof`: the whole proof's algorithmic products / bytes over its wall time;
+                 `seconds_per_proof_host_advice`: the same call with the advice column in host memory (the Vec the Rust prover fills; its
+                 16 MiB upload inside the call), the PCIe-inclusive rate
   cpu_baseline = the oracle's restatement of the same prover ("port": identical step list, C kernels) on the box's host cores, one full
                  proof, whose BYTES are compared with the GPU proof's
   msm_2_20     = the other half of the metric (BASELINE configs[1]): G1-adds/s of 2^20-point MSMs with its own roofline and CPU line;
@@ -65,7 +71,8 @@ def _pick(d, *keys):
 
 def contract_line(out: dict, extra_file: str = "bench_extra.json") -> str:
     """The ONE line the driver parses: the contract keys + roofline / roofline_int / roofline_proof / cpu_baseline and a few headline figures of
-    the side blocks, strict JSON, < CONTRACT_LINE_MAX_BYTES.  Everything else of `out` lives in `extra_file` (and on an earlier stdout line)."""
+    the side blocks, strict JSON, < CONTRACT_LINE_MAX_BYTES.  Everything else of `out` lives in `extra_file` (and on an earlier stdout line);
+    a plain run writes no such file and passes extra_file=None.  Blocks that `out` does not hold are left out (a plain run's roofline_int)."""
     cfg = out.get("config", {})
     line = _pick(out, "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")
     line["metric"] = str(line.get("metric", ""))[:160]
@@ -76,9 +83,10 @@ def contract_line(out: dict, extra_file: str = "bench_extra.json") -> str:
     rf = out.get("roofline", {})
     line["roofline"] = {**_pick(rf, "bound", "achieved", "peak", "unit", "frac", "traffic", "frac_of_binding_roof", "algorithmic_bytes_per_launch",
                                 "avg_launch_ms", "launches"), "kernel": str(rf.get("kernel", ""))[:80]}
-    ri = out.get("roofline_int", {})
-    line["roofline_int"] = {**_pick(ri, "achieved", "peak", "unit", "frac", "algorithmic_products_per_launch", "window_bits", "windows"),
-                            "kernel": str(ri.get("kernel", ""))[:40]}
+    ri = out.get("roofline_int")
+    if ri:   # --full only: the multiplier peak takes a run of its own
+        line["roofline_int"] = {**_pick(ri, "achieved", "peak", "unit", "frac", "algorithmic_products_per_launch", "window_bits", "windows"),
+                                "kernel": str(ri.get("kernel", ""))[:40]}
     rp = out.get("roofline_proof", {})
     if rp:
         line["roofline_proof"] = {"products": rp.get("algorithmic", {}).get("products"), "bytes": rp.get("algorithmic", {}).get("bytes"),
@@ -121,7 +129,8 @@ def contract_line(out: dict, extra_file: str = "bench_extra.json") -> str:
     ip = out.get("independent_proofs_per_gpu")
     if isinstance(ip, dict):
         line["independent_proofs_per_gpu"] = _pick(ip, "ms_per_step", "value", "unit", "scaling")
-    line["extra"] = extra_file
+    if extra_file:
+        line["extra"] = extra_file
     text = json.dumps(_sig(line), allow_nan=False, separators=(",", ":"))
     if len(text) >= CONTRACT_LINE_MAX_BYTES:   # never happens with the caps above; if it does, drop the side blocks rather than the contract keys
         for k in ("independent_proofs_per_gpu", "comm", "ntt_2_22", "msm_2_20", "create_proof_k21_pairing_shape", "roofline_proof"):
@@ -332,6 +341,52 @@ def measure_hbm_traffic(k, kernel="msm_accum_kernel"):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def headline(args, world, sharded, sh, cells, seconds, proof_bytes, msm_n, k_ms, k_cnt, k_busy_ms):
+    """the result line's own fields, the same in a plain and a --full run: the metric and its value from the timed steps, the configuration, and
+    the HBM roofline of the dominant kernel from the HIP events the timed steps carry (k_ms / k_cnt / k_busy_ms: h2hip_profile_get(_busy))"""
+    k, n = args.k, 1 << args.k
+    proofs_per_step = 1 if (world == 1 or sharded) else world
+    k_avg_s = k_ms / max(k_cnt, 1) * 1e-3
+    alg_bytes = 96.0 * msm_n
+    return {
+        "metric": ("create_proof constraints/sec (k=19 ECDSA configuration, halo2-ecc/configs/secp256k1/bench_ecdsa.config:1); MSM G1-adds/sec in `msm_2_%d`" % args.log_n) if k == 19 else
+                  ("create_proof constraints/sec (--k %d: bench_ecdsa.config:1's 1 + 1 + 1 COLUMN SHAPE at another k — not a configuration of the reference; the k=21 "
+                   "reference configuration is the pairing shape in `create_proof_k21_pairing_shape`); MSM G1-adds/sec in `msm_2_%d`" % (k, args.log_n)),
+        "value": proofs_per_step * cells / seconds,
+        "unit": "constraints/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": seconds * 1e3,
+        "higher_is_better": True,
+        "scaling": ("strong" if sharded else "weak") if world > 1 else args.scaling,   # N = 1: the mode the N > 1 lines of the same command use
+        "vs_baseline": None,
+        "dtype": "u32 (254-bit Montgomery integers as 8x32 / 9x29-bit limbs)",
+        "data": "synthetic",
+        "config": {"workload": "BASELINE configs[3]: h2hip_plonk_create_proof for the k=%d secp256k1-ECDSA configuration (bench_ecdsa.config:1: 1 advice column with the "
+                               "lookup behind q_lookup, 1 constants column, lookup_bits %d, no instances), synthetic circuit-like witness (halo2_lib_amd/testing.py: "
+                               "every gate satisfied, 0/1 / small / full-width cells, range-checked cells, copy constraints); one step = one proof: host wall clock "
+                               "around the C call with the advice column resident in HBM (advice_on_device), incl. the generation of the 2^k blinding scalars (ChaCha12 "
+                               "Fr::random stream of StdRng::seed_from_u64(0), on the device) and the proof bytes coming back; `seconds_per_proof_host_advice` = the same with the advice column staged from host "
+                               "memory inside the call; witness generation (CPU gadgets, Rust) excluded" % (k, k - 1),
+                   "workload_short": "BASELINE configs[3]: h2hip_plonk_create_proof, k=%d secp256k1-ECDSA shape (bench_ecdsa.config:1: 1 advice + 1 lookup + 1 constants column, "
+                                     "lookup_bits %d), synthetic circuit-like witness resident in HBM; 1 step = 1 proof, bytes back on the host" % (k, k - 1),
+                   "value_is": "constraints / seconds_per_proof with the advice column RESIDENT IN HBM when the timed region starts (the bench contract); the like-for-like "
+                               "figure against a CPU prover (witness in host memory, its 16 MiB upload inside the call) is seconds_per_proof_host_advice / "
+                               "value_host_advice — what speedup_vs_cpu_port is computed from",
+                   "constraints_per_proof": cells, "constraints_definition": "assigned advice cells (SURVEY.md §8d)", "msm_count": sh.num_commitments, "msm_size": n,
+                   "extended_k": sh.extended_k, "degree": sh.degree, "proof_bytes": proof_bytes,
+                   "sharding": ("ONE proof per step over %d GPUs: commitments point-range sharded (2^%d / %d points per GPU), see DESIGN.md §6" % (world, k, world)) if sharded else
+                               ("none (1 GPU)" if world == 1 else "%d independent proofs per step, one per GPU (replicas, no exchange)" % world)},
+        "seconds_per_proof": seconds,
+        "roofline": {"bound": "hbm", "kernel": "msm_accum_kernel (2^%d points per launch, %d launches per proof)" % (int(np.log2(msm_n)), round(k_cnt / args.steps)),
+                     "achieved": alg_bytes / k_avg_s / 1e9 if k_avg_s > 0 else 0.0, "peak": 8000.0, "unit": "GB/s",
+                     "frac": alg_bytes / k_avg_s / 8e12 if k_avg_s > 0 else 0.0,
+                     "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": k_avg_s * 1e3, "launches": int(k_cnt),
+                     "busy_ms_per_launch": k_busy_ms / max(k_cnt, 1)},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -359,6 +414,9 @@ def main():
     ap.add_argument("--batch", type=int, default=4, help="MSM block: MSMs issued per h2hip_msm_g1_batch_dev call (a prover commits several columns per round); 1 = synchronous")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the last timed step's proof bytes to DIR/proof.npy (float32, one value per byte; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also check the proof and run every further measurement (host-resident advice, RNG paths, kernel "
+                         "account, rooflines, PMC traffic, CPU baseline, side blocks) and write bench_extra.json; the --no-* switches trim this")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -420,15 +478,6 @@ def main():
         t0 = time.perf_counter()
         pk = PL.keygen(kzg, bp, circ.fixed, circ.copies)
         keygen_s = time.perf_counter() - t0
-        # the prover's randomness: the reference hands create_proof `StdRng::seed_from_u64(0)` (halo2-base/src/utils/testing.rs:38) = ChaCha12 in
-        # counter mode.  libh2hip's seeded generator reproduces that Fr::random stream and the prover generates its 2^k blinding scalars ON THE
-        # DEVICE inside the timed call (PL.ChaChaRng, csrc/rng.hip).  `draws` = the same stream as an array (generated by the same kernel, once):
-        # what the pre-drawn-array comparison figure and the CPU baseline consume, so that all of them produce the SAME proof bytes.
-        rng_seed = PL.ChaChaRng(ctx.lib, 0, 12).state.seed
-        d_draws = ctx.malloc(32 * (n + 4096))
-        ctx._chk(ctx.lib.h2hip_rng_chacha_fill_dev(ctx.handle, d_draws, n + 4096, rng_seed, 12, 0))
-        draws = ctx.download(d_draws, (n + 4096, 4))
-        ctx.free(d_draws)
     except Exception as e:
         if world == 1:
             raise
@@ -461,9 +510,6 @@ def main():
     # next to it (`seconds_per_proof_host_advice`).  The RNG stream is a host callback in both, as it is in the reference.
     adv_dev = [ctx.to_device(np.ascontiguousarray(c)) for c in circ.advice]
     prove = lambda stages=None: PL.create_proof(pk, adv_dev, circ.instances, PL.ChaChaRng(ctx.lib, 0, 12), stages, advice_on_device=True)
-    prove_host = lambda: PL.create_proof(pk, circ.advice, circ.instances, PL.ChaChaRng(ctx.lib, 0, 12))
-    prove_array = lambda: PL.create_proof(pk, adv_dev, circ.instances, PL.ArrayRng(draws), advice_on_device=True)
-    prove_host_rng = lambda: PL.create_proof(pk, adv_dev, circ.instances, PL.ChaChaRng(ctx.lib, 0, 12, device=False), advice_on_device=True)
     t0 = time.perf_counter()
     first = prove()                      # the cold first proof after keygen (allocates the key's buffer pool, builds twiddle tables)
     cold_s = time.perf_counter() - t0
@@ -499,6 +545,38 @@ def main():
         return
     if proof != first:
         raise SystemExit("bench.py: create_proof is not repeatable for a fixed RNG stream — refusing to report a number")
+    # the timed steps' HIP events around msm_accum_kernel (profiling is off from here on, so later proofs add nothing to them)
+    k_ms, k_cnt = ctx.profile_get("msm_accum_kernel")
+    k_busy_ms = ctx.profile_get_busy("msm_accum_kernel")
+    cells = 4 * (sh.usable_rows // 4)    # assigned advice cells: `constraints` of SURVEY.md §8d (total_advice of the circuit)
+    msm_n = n // world if sharded else n
+    if not args.full:   # a plain run: the result line and nothing else
+        if rank == 0:
+            print(contract_line(headline(args, world, sharded, sh, cells, seconds, len(proof), msm_n, k_ms, k_cnt, k_busy_ms), extra_file=None), flush=True)
+        if sk is not None:
+            sk.free()
+        pk.free()
+        kzg.free()
+        if comm is not None:
+            comm.destroy()
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ------------------------------------------------------------------ --full: everything below runs after the timed steps
+    # the prover's randomness: the reference hands create_proof `StdRng::seed_from_u64(0)` (halo2-base/src/utils/testing.rs:38) = ChaCha12 in
+    # counter mode.  libh2hip's seeded generator reproduces that Fr::random stream and the prover generates its 2^k blinding scalars ON THE
+    # DEVICE inside the timed call (PL.ChaChaRng, csrc/rng.hip).  `draws` = the same stream as an array (generated by the same kernel, once):
+    # what the pre-drawn-array comparison figure and the CPU baseline consume, so that all of them produce the SAME proof bytes.
+    rng_seed = PL.ChaChaRng(ctx.lib, 0, 12).state.seed
+    d_draws = ctx.malloc(32 * (n + 4096))
+    ctx._chk(ctx.lib.h2hip_rng_chacha_fill_dev(ctx.handle, d_draws, n + 4096, rng_seed, 12, 0))
+    draws = ctx.download(d_draws, (n + 4096, 4))
+    ctx.free(d_draws)
+    prove_host = lambda: PL.create_proof(pk, circ.advice, circ.instances, PL.ChaChaRng(ctx.lib, 0, 12))
+    prove_array = lambda: PL.create_proof(pk, adv_dev, circ.instances, PL.ArrayRng(draws), advice_on_device=True)
+    prove_host_rng = lambda: PL.create_proof(pk, adv_dev, circ.instances, PL.ChaChaRng(ctx.lib, 0, 12, device=False), advice_on_device=True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         proof_host = prove_host()        # every rank: a sharded proof has collectives inside
@@ -529,10 +607,7 @@ def main():
 
     out = None
     ctx.profile_filter("")
-    if rank == 0:
-        k_ms, k_cnt = ctx.profile_get("msm_accum_kernel")
-        k_busy_ms = ctx.profile_get_busy("msm_accum_kernel")
-        k_avg_s = k_ms / max(k_cnt, 1) * 1e-3
+    k_avg_s = k_ms / max(k_cnt, 1) * 1e-3
     # outside the timed region: the same call with every kernel bracketed (the per-kernel account; ~200 launches x 2 events cost ~1 ms per proof),
     # then with per-stage laps (a stream synchronisation per stage)
     acct_proofs = 5
@@ -553,11 +628,8 @@ def main():
         mm_ms, mm_n = ctx.bench_modmul(16384, 256, 2, unsaturated=True)
         modmul_peak = mm_n / (mm_ms * 1e-3)
         work = proof_algorithmic_work(ctx, bp, sh)
-        msm_n = n // world if sharded else n
         c19, W19 = window_for(ctx, msm_n)
-        cells = 4 * (sh.usable_rows // 4)    # assigned advice cells: `constraints` of SURVEY.md §8d (total_advice of the circuit)
         proofs_per_step = 1 if (world == 1 or sharded) else world
-        alg_bytes = 96.0 * msm_n
         traffic_prof = None
         pmc_path = os.path.join(ROOT, "profiles", "r06_create_proof_k19_pmc_hbm.json")
         if not os.path.exists(pmc_path):
@@ -572,37 +644,20 @@ def main():
         traffic_live, traffic_err = (None, "skipped (--no-pmc-traffic)")
         if world == 1 and not args.no_pmc_traffic:
             traffic_live, traffic_err = measure_hbm_traffic(k)
-        out = {
-            "metric": ("create_proof constraints/sec (k=19 ECDSA configuration, halo2-ecc/configs/secp256k1/bench_ecdsa.config:1); MSM G1-adds/sec in `msm_2_%d`" % args.log_n) if k == 19 else
-                      ("create_proof constraints/sec (--k %d: bench_ecdsa.config:1's 1 + 1 + 1 COLUMN SHAPE at another k — not a configuration of the reference; the k=21 "
-                       "reference configuration is the pairing shape in `create_proof_k21_pairing_shape`); MSM G1-adds/sec in `msm_2_%d`" % (k, args.log_n)),
-            "value": proofs_per_step * cells / seconds,
-            "unit": "constraints/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": seconds * 1e3,
-            "higher_is_better": True,
-            "scaling": ("strong" if sharded else "weak") if world > 1 else args.scaling,   # N = 1: the mode the N > 1 lines of the same command use
-            "vs_baseline": None,
-            "dtype": "u32 (254-bit Montgomery integers as 8x32 / 9x29-bit limbs)",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE configs[3]: h2hip_plonk_create_proof for the k=%d secp256k1-ECDSA configuration (bench_ecdsa.config:1: 1 advice column with the "
-                                   "lookup behind q_lookup, 1 constants column, lookup_bits %d, no instances), synthetic circuit-like witness (halo2_lib_amd/testing.py: "
-                                   "every gate satisfied, 0/1 / small / full-width cells, range-checked cells, copy constraints); one step = one proof: host wall clock "
-                                   "around the C call with the advice column resident in HBM (advice_on_device), incl. the generation of the 2^k blinding scalars (ChaCha12 "
-                                   "Fr::random stream of StdRng::seed_from_u64(0), on the device) and the proof bytes coming back; `seconds_per_proof_host_advice` = the same with the advice column staged from host "
-                                   "memory inside the call; witness generation (CPU gadgets, Rust) excluded" % (k, k - 1),
-                       "workload_short": "BASELINE configs[3]: h2hip_plonk_create_proof, k=%d secp256k1-ECDSA shape (bench_ecdsa.config:1: 1 advice + 1 lookup + 1 constants column, "
-                                         "lookup_bits %d), synthetic circuit-like witness resident in HBM; 1 step = 1 proof, bytes back on the host" % (k, k - 1),
-                       "value_is": "constraints / seconds_per_proof with the advice column RESIDENT IN HBM when the timed region starts (the bench contract); the like-for-like "
-                                   "figure against a CPU prover (witness in host memory, its 16 MiB upload inside the call) is seconds_per_proof_host_advice / "
-                                   "value_host_advice — what speedup_vs_cpu_port is computed from",
-                       "constraints_per_proof": cells, "constraints_definition": "assigned advice cells (SURVEY.md §8d)", "msm_count": sh.num_commitments, "msm_size": n,
-                       "extended_k": sh.extended_k, "degree": sh.degree, "proof_bytes": len(proof),
-                       "sharding": ("ONE proof per step over %d GPUs: commitments point-range sharded (2^%d / %d points per GPU), see DESIGN.md §6" % (world, k, world)) if sharded else
-                                   ("none (1 GPU)" if world == 1 else "%d independent proofs per step, one per GPU (replicas, no exchange)" % world)},
-            "seconds_per_proof": seconds, "seconds_per_proof_host_advice": host_advice_s, "value_host_advice": proofs_per_step * cells / host_advice_s,
+        out = headline(args, world, sharded, sh, cells, seconds, len(proof), msm_n, k_ms, k_cnt, k_busy_ms)
+        out["roofline"].update({
+            "bound_note": "bound / achieved / peak / unit / frac are the HBM figures the bench contract asks for (algorithmic bytes over the launch duration against "
+                          "8 TB/s); the roof that BINDS this kernel is the 254-bit integer multiplier: `frac_of_binding_roof` = `roofline_int.frac`",
+            "frac_of_binding_roof": (10.0 * msm_n * W19 / k_avg_s / modmul_peak) if k_avg_s > 0 else 0.0,
+            "traffic": traffic_live["bytes_per_launch"] if traffic_live else None,
+            "traffic_measurement": traffic_live if traffic_live else {"error": traffic_err},
+            "traffic_note": "HBM bytes per launch from the PMC counters of two rocprofv3 child runs inside this run (null if rocprofv3 is unavailable: the "
+                            "separately collected, committed figure is under `traffic_from_profiles` with the file's git blob hash)",
+            "traffic_from_profiles": traffic_prof,
+            "note": "algorithmic bytes = 96 B per (scalar, base) pair (SURVEY.md §8d); avg_launch_ms = mean duration of the kernel's launches inside the "
+                    "timed region, HIP events on the launch streams (h2hip_profile_*); the binding roof of this kernel is the integer multiplier: `roofline_int`"})
+        out.update({
+            "seconds_per_proof_host_advice": host_advice_s, "value_host_advice": proofs_per_step * cells / host_advice_s,
             "seconds_per_proof_with_rng": {"device_generated_chacha12": seconds, "host_generated_chacha12_one_thread": host_rng_s, "predrawn_array_outside_the_call": array_rng_s,
                                            "proof_bytes_identical": True,
                                            "note": "the headline (`value`, seconds_per_proof) draws its blinding from `StdRng::seed_from_u64(0)`'s Fr::random stream (ChaCha12, "
@@ -614,21 +669,6 @@ def main():
             "kernel_ms_per_proof": account, "gpu_busy_ms_per_proof": busy_all_ms,
             "kernel_account_note": "kernel_ms_per_proof / gpu_busy_ms_per_proof: %d further proofs with every launch bracketed by HIP events (not the timed region: the events of "
                                    "~200 launches add ~1 ms per proof); ms = sum of launch durations (launches of concurrent MSM lanes overlap), busy_ms = union of their spans" % acct_proofs,
-            "roofline": {"bound": "hbm",
-                         "bound_note": "bound / achieved / peak / unit / frac are the HBM figures the bench contract asks for (algorithmic bytes over the launch duration against "
-                                       "8 TB/s); the roof that BINDS this kernel is the 254-bit integer multiplier: `frac_of_binding_roof` = `roofline_int.frac`",
-                         "frac_of_binding_roof": (10.0 * msm_n * W19 / k_avg_s / modmul_peak) if k_avg_s > 0 else 0.0,
-                         "kernel": "msm_accum_kernel (2^%d points per launch, %d launches per proof)" % (int(np.log2(msm_n)), round(k_cnt / args.steps)),
-                         "achieved": alg_bytes / k_avg_s / 1e9 if k_avg_s > 0 else 0.0, "peak": 8000.0, "unit": "GB/s",
-                         "frac": alg_bytes / k_avg_s / 8e12 if k_avg_s > 0 else 0.0, "traffic": traffic_live["bytes_per_launch"] if traffic_live else None,
-                         "traffic_measurement": traffic_live if traffic_live else {"error": traffic_err},
-                         "traffic_note": "HBM bytes per launch from the PMC counters of two rocprofv3 child runs inside this run (null if rocprofv3 is unavailable: the "
-                                         "separately collected, committed figure is under `traffic_from_profiles` with the file's git blob hash)",
-                         "traffic_from_profiles": traffic_prof,
-                         "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": k_avg_s * 1e3, "launches": int(k_cnt),
-                         "busy_ms_per_launch": k_busy_ms / max(k_cnt, 1),
-                         "note": "algorithmic bytes = 96 B per (scalar, base) pair (SURVEY.md §8d); avg_launch_ms = mean duration of the kernel's launches inside the "
-                                 "timed region, HIP events on the launch streams (h2hip_profile_*); the binding roof of this kernel is the integer multiplier: `roofline_int`"},
             "roofline_int": {"bound": "integer multiplier (v_mad_u64_u32, 4 cycles per wave64)", "kernel": "msm_accum_kernel",
                              "achieved": 10.0 * msm_n * W19 / k_avg_s if k_avg_s > 0 else 0.0, "peak": modmul_peak, "unit": "modmul/s",
                              "frac": (10.0 * msm_n * W19 / k_avg_s / modmul_peak) if k_avg_s > 0 else 0.0,
@@ -642,7 +682,7 @@ def main():
                                "hbm": {"achieved": work["bytes"] / seconds / 1e9, "peak": 8000.0, "unit": "GB/s", "frac": work["bytes"] / seconds / 8e12},
                                "note": "whole proof: (sum of the algorithmic products of its MSMs and transforms) / seconds_per_proof against the multiplier peak measured in "
                                        "this run; recompute from `algorithmic`, `seconds_per_proof` and `roofline_int.peak`"},
-        }
+        })
         if not args.no_cpu_baseline:   # N > 1 as well: rank 0's host cores, the other ranks wait at the next barrier
             try:
                 cb = cpu_baseline_create_proof(ctx, kzg, pk, circ, draws, proof, k, s_toxic)

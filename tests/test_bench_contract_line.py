@@ -3,6 +3,7 @@ here on the canned output of a real run (profiles/r05_bench.json) and on degener
 import json
 import math
 import os
+import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -76,6 +77,35 @@ def test_contract_line_multi_gpu_fields():
     assert line["comm"] == {"transport": "RCCL (ncclAllGather ...)", "distinct_gpus": 8, "ranks": 8}
     assert line["independent_proofs_per_gpu"]["scaling"] == "weak" and line["sharded_bytes_equal_unsharded"] is True
     assert line["create_proof_k21_pairing_shape"]["sharded"]["seconds"] == 0.013
+
+
+def test_plain_run_line_carries_the_headline_alone():
+    """A run without --full builds its line from bench.headline() alone: the headline fields as a --full run words and computes them, the
+    roofline from the timed steps' events, and none of the blocks that need runs of their own."""
+    import argparse
+    import types
+
+    args = argparse.Namespace(k=19, log_n=20, steps=20, warmup=5, scaling="strong")
+    sh = types.SimpleNamespace(num_commitments=12, extended_k=21, degree=5)
+    cells, seconds = 524000, 0.013
+    out = bench.headline(args, 1, False, sh, cells, seconds, 2400, 1 << 19, k_ms=24.0, k_cnt=240, k_busy_ms=23.0)
+    canned = json.load(open(os.path.join(ROOT, "profiles", "r06_bench.json")))   # the last committed line of a full run
+    line = _strict(bench.contract_line(out, extra_file=None))
+    for k in CONTRACT_KEYS:
+        if k != "cpu_baseline":
+            assert k in line, k
+    for k in ("cpu_baseline", "roofline_int", "roofline_proof", "msm_2_20", "ntt_2_22", "create_proof_k21_pairing_shape", "extra"):
+        assert k not in line, k
+    assert line["metric"] == canned["metric"] and line["unit"] == canned["unit"] and line["dtype"] == canned["dtype"]
+    assert line["higher_is_better"] is True and line["value"] == float("%.6g" % (cells / seconds))
+    assert line["ms_per_step"] == 13.0 and line["steps"] == 20 and line["warmup"] == 5
+    rf = line["roofline"]
+    assert rf["bound"] == "hbm" and rf["launches"] == 240 and rf["avg_launch_ms"] == 0.1 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-6
+
+
+def test_full_is_an_option():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout, r.stderr
 
 
 def test_sig_rounding():

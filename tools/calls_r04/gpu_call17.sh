@@ -7,5 +7,5 @@ timeout 300 rocprofv3 --kernel-trace -d $O/p19 -o t -- python $REPO/tools/prove_
 cd $REPO
 python tools/rocprof_timeline.py $(find $O/p19 -name "*.db" | head -1) modmul_bench 99 20000 > $O/timeline_k19.md 2>&1
 rm -rf $O/p19
-( time timeout 900 python bench.py > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.log
+( time timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.log
 tail -3 $O/bench_time.log; grep -c "|" $O/timeline_k19.md; grep "create_proof rep" $O/prove.log

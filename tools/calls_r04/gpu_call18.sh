@@ -12,5 +12,5 @@ timeout 300 rocprofv3 --kernel-trace -d $O/p19 -o t -- python $REPO/tools/prove_
 cd $REPO
 python tools/rocprof_timeline.py $(find $O/p19 -name "*.db" | head -1) modmul_bench 99 20000 > $O/timeline_k19.md 2>&1
 rm -rf $O/p19
-timeout 600 python bench.py --no-sweep --no-pmc-traffic 2>/dev/null | tail -1 | head -c 600 > $O/bench_head.json
+timeout 600 python bench.py --full --no-sweep --no-pmc-traffic 2>/dev/null | tail -1 | head -c 600 > $O/bench_head.json
 tail -2 $O/pytest.log; for f in ab_k19 ov_k19 ov_k21 ov_k15; do echo "== $f"; cat $O/$f.log; done; cat $O/bench_head.json; echo; grep "create_proof rep" $O/prove.log

@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/c4; O=gpurun_out/c4
 timeout 300 python -m pytest tests/test_rng_chacha.py tests/test_gpu_parity.py -m gpu -q -x -k "rng or chacha or ntt or coset" > $O/pytest.log 2>&1
 timeout 300 python tools/ntt_r04.py ntt_tile_kernel=1:0 > $O/ntt.log 2>&1
-timeout 600 python bench.py --no-sweep > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --full --no-sweep > $O/bench.json 2> $O/bench.err
 timeout 200 python tools/prove_time.py 19 1 1 1 0 18 8 > $O/prove19.log 2>&1
 tail -3 $O/pytest.log; cat $O/ntt.log | cut -c1-330; tail -3 $O/bench.err; python - <<'PY'
 import json

@@ -5,7 +5,7 @@ timeout 900 python -m pytest tests/test_plonk_prover.py tests/test_rng_chacha.py
 timeout 200 python tools/prove_time.py 19 1 1 1 0 18 8 --ab=plonk_tail_overlap > $O/prove19.log 2>&1
 timeout 300 python tools/prove_time.py 21 2 1 1 0 20 5 --ab=plonk_tail_overlap > $O/prove21.log 2>&1
 timeout 200 python tools/prove_time.py 15 17 3 1 0 14 8 --ab=plonk_tail_overlap > $O/prove15.log 2>&1
-timeout 300 python bench.py --no-sweep --no-replay > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --full --no-sweep --no-replay > $O/bench.json 2> $O/bench.err
 tail -4 $O/pytest.log; grep "plonk_tail_overlap=" $O/prove19.log $O/prove21.log $O/prove15.log; tail -14 $O/prove19.log; tail -2 $O/bench.err
 python - <<'PY'
 import json

@@ -5,8 +5,8 @@ set -u
 O=$PWD/gpurun_out/r05c01; mkdir -p $O; REPO=$PWD
 ( time timeout 1200 python -m pytest tests/test_sharded_multirank_gpu.py -m gpu -x -q --durations=5 ) > $O/multirank.log 2>&1
 tail -15 $O/multirank.log
-timeout 600 python bench.py 2>$O/bench.err | tail -1 > $O/bench.json
-timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --share-device --dist-backend gloo --steps 5 --warmup 2 --no-sweep --shard-ntt-columns on 2> $O/bench_2rank.err | tail -1 > $O/bench_2rank_shared_gpu_gloo.json
+timeout 600 python bench.py --full 2>$O/bench.err | tail -1 > $O/bench.json
+timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --share-device --dist-backend gloo --steps 5 --warmup 2 --no-sweep --shard-ntt-columns on 2> $O/bench_2rank.err | tail -1 > $O/bench_2rank_shared_gpu_gloo.json
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/p19 -o t -- python $REPO/tools/prove_time.py 19 1 1 1 0 18 5 > $O/prove_time_k19.log 2>&1
 cd $REPO

@@ -8,7 +8,7 @@ timeout 600 python -m pytest tests/test_gpu_parity.py tests/test_plonk_prover.py
 timeout 300 python tools/prove_time.py 19 1 1 1 0 18 3 --ab=host_poll:0,1 > $O/poll_ab_k19.log 2>&1; grep "host_poll=" $O/poll_ab_k19.log
 timeout 300 python tools/prove_time.py 15 17 3 1 0 14 3 --ab=host_poll:0,1 > $O/poll_ab_k15.log 2>&1; grep "host_poll=" $O/poll_ab_k15.log
 timeout 300 python tools/ntt_r04.py > $O/ntt_times.log 2>&1; cat $O/ntt_times.log
-timeout 600 python bench.py --no-sweep 2>$O/bench.err | tail -1 > $O/bench.json
+timeout 600 python bench.py --full --no-sweep 2>$O/bench.err | tail -1 > $O/bench.json
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/tr -o t -- python $REPO/bench.py --pmc-child --steps 6 --warmup 2 > $O/trace.log 2>&1
 cd $REPO

@@ -7,7 +7,7 @@ O=$PWD/gpurun_out/r05c04; mkdir -p $O
 ( time timeout 1200 python -m pytest tests/test_sharded_multirank_gpu.py tests/test_sharded_single_rank.py -m gpu -x -q -s --durations=5 ) > $O/sharded.log 2>&1
 grep -E "passed|failed|measured|error" $O/sharded.log | tail -8
 timeout 600 python -m pytest tests/test_reference_shapes_golden.py -m gpu -x -q -k "ecdsa-19 or pairing-21" > $O/golden_forced.log 2>&1; tail -2 $O/golden_forced.log
-timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --share-device --dist-backend gloo --steps 5 --warmup 2 --no-sweep --shard-ntt-columns on 2> $O/bench_2rank.err | tail -1 > $O/bench_2rank_shared_gpu_gloo_pairing21.json
+timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --share-device --dist-backend gloo --steps 5 --warmup 2 --no-sweep --shard-ntt-columns on 2> $O/bench_2rank.err | tail -1 > $O/bench_2rank_shared_gpu_gloo_pairing21.json
 python - <<'PY'
 import json
 e=json.load(open("gpurun_out/r05c04/bench_2rank_shared_gpu_gloo_pairing21.json"))

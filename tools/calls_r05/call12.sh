@@ -5,8 +5,8 @@ O=$PWD/gpurun_out/r05c12; mkdir -p $O
 ( time timeout 1500 python -m pytest tests -m gpu -q --durations=8 ) > $O/pytest_gpu.log 2>&1; tail -14 $O/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke OK')" >> $O/pytest_gpu.log 2>&1; tail -1 $O/pytest_gpu.log
 ( time H2HIP_GOLDEN_BIG=1 timeout 1500 python -m pytest tests/test_reference_shapes_golden.py -m gpu -q -k "msm-L8 or msm-L9 or msm-L13" --durations=4 ) > $O/pytest_big.log 2>&1; tail -9 $O/pytest_big.log
-timeout 900 python bench.py 2>$O/bench.err | tail -1 > $O/bench.json
-timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --share-device --dist-backend gloo --steps 5 --warmup 2 --no-sweep --shard-ntt-columns on 2> $O/bench_2rank.err | tail -1 > $O/bench_2rank_shared_gpu_gloo_pairing21.json
+timeout 900 python bench.py --full 2>$O/bench.err | tail -1 > $O/bench.json
+timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --share-device --dist-backend gloo --steps 5 --warmup 2 --no-sweep --shard-ntt-columns on 2> $O/bench_2rank.err | tail -1 > $O/bench_2rank_shared_gpu_gloo_pairing21.json
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/r05c12/bench.json"))

@@ -6,4 +6,4 @@ O=$PWD/gpurun_out/r05c25; mkdir -p $O
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke OK')" >> $O/pytest_gpu.log 2>&1; tail -1 $O/pytest_gpu.log
 H2HIP_FUZZ_KNOBS=1 timeout 500 python tools/fuzz_shapes.py 400 21 > $O/fuzz_knobs.log 2>&1; tail -1 $O/fuzz_knobs.log
 H2HIP_FUZZ_KNOBS=1 timeout 400 python tools/fuzz_shapes.py 300 22 13 17 > $O/fuzz_knobs_mid.log 2>&1; tail -1 $O/fuzz_knobs_mid.log
-( time timeout 900 python bench.py 2>$O/bench.err | tail -1 > $O/bench.json ) 2> $O/time.log; tail -3 $O/time.log; head -c 400 $O/bench.json; echo
+( time timeout 900 python bench.py --full 2>$O/bench.err | tail -1 > $O/bench.json ) 2> $O/time.log; tail -3 $O/time.log; head -c 400 $O/bench.json; echo

@@ -2,7 +2,7 @@
 # r06 GPU call 1: the default bench line as the driver runs it (the compact last line must parse: VERDICT r05 #1), then the partition state (read-only)
 set -u
 O=$PWD/gpurun_out/r06c01; mkdir -p $O; REPO=$PWD
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.stdout 2>$O/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.stdout 2>$O/bench.err; echo "bench rc=$?"
 tail -1 $O/bench.stdout > $O/bench_line.json; wc -c $O/bench_line.json; wc -l $O/bench.stdout
 python - <<'PY'
 import json

@@ -11,11 +11,11 @@ if [ "$SKIP_TESTS" != "1" ]; then
 timeout 1500 python -m pytest tests -m gpu -q -x 2>&1 | tail -8 > $OUT/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke OK')" > $OUT/smoke.log 2>&1
 fi
-timeout 900 python bench.py 2>$OUT/bench.err | tail -1 > $OUT/bench.json
+timeout 900 python bench.py --full 2>$OUT/bench.err | tail -1 > $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python $REPO/bench.py --no-cpu-baseline --no-replay --steps 64 > $OUT/trace.log 2>&1
-timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o f -- python $REPO/bench.py --no-cpu-baseline --no-replay --steps 8 > $OUT/pmc_fetch.log 2>&1
-timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o w -- python $REPO/bench.py --no-cpu-baseline --no-replay --steps 8 > $OUT/pmc_write.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python $REPO/bench.py --full --no-cpu-baseline --no-replay --steps 64 > $OUT/trace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o f -- python $REPO/bench.py --full --no-cpu-baseline --no-replay --steps 8 > $OUT/pmc_fetch.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o w -- python $REPO/bench.py --full --no-cpu-baseline --no-replay --steps 8 > $OUT/pmc_write.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/ptrace -o t -- python $REPO/tools/prove_time.py 19 1 1 1 0 18 4 > $OUT/prove_time.log 2>&1
 cd $REPO
 python tools/rocprof_proof.py $(find $OUT/ptrace -name "*.db" | head -1) > $OUT/create_proof_kernels.md 2>&1

@@ -6,11 +6,11 @@ set -u
 OUT=$PWD/gpurun_out/final
 mkdir -p $OUT
 REPO=$PWD
-timeout 900 python bench.py 2>$OUT/bench.err | tail -1 > $OUT/bench.json
+timeout 900 python bench.py --full 2>$OUT/bench.err | tail -1 > $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python $REPO/bench.py --no-cpu-baseline --no-replay --no-sweep --steps 20 > $OUT/trace.log 2>&1
-timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o f -- python $REPO/bench.py --no-cpu-baseline --no-replay --no-sweep --steps 4 > $OUT/pmc_fetch.log 2>&1
-timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o w -- python $REPO/bench.py --no-cpu-baseline --no-replay --no-sweep --steps 4 > $OUT/pmc_write.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python $REPO/bench.py --full --no-cpu-baseline --no-replay --no-sweep --steps 20 > $OUT/trace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o f -- python $REPO/bench.py --full --no-cpu-baseline --no-replay --no-sweep --steps 4 > $OUT/pmc_fetch.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o w -- python $REPO/bench.py --full --no-cpu-baseline --no-replay --no-sweep --steps 4 > $OUT/pmc_write.log 2>&1
 cd $REPO
 python tools/rocprof_summary.py $(ls $OUT/trace/*.db | head -1) > $OUT/kernel_trace.md 2>&1
 python tools/rocprof_proof.py $(ls $OUT/trace/*.db | head -1) > $OUT/create_proof_kernels.md 2>&1

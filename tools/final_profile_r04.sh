@@ -13,7 +13,7 @@ mkdir -p $OUT
 REPO=$PWD
 ( time timeout 1500 python -m pytest tests -m gpu -q --durations=12 ) > $OUT/pytest_gpu.log 2>&1
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke OK')" >> $OUT/pytest_gpu.log 2>&1
-timeout 900 python bench.py 2>$OUT/bench.err | tail -1 > $OUT/bench.json
+timeout 900 python bench.py --full 2>$OUT/bench.err | tail -1 > $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python $REPO/bench.py --pmc-child --steps 20 --warmup 3 > $OUT/trace.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o f -- python $REPO/bench.py --pmc-child --steps 4 --warmup 1 > $OUT/pmc_fetch.log 2>&1
@@ -42,5 +42,5 @@ rm -rf $OUT/trace $OUT/pmc_fetch $OUT/pmc_write $OUT/p19 $OUT/p21
 timeout 300 python tools/ntt_r04.py ntt_tile_kernel=1:0 > $OUT/ntt_times.log 2>&1
 timeout 300 python tools/msm_r03.py 19,20 > $OUT/msm_breakdown.log 2>&1
 timeout 900 python tools/config_sweep.py all 5 > $OUT/config_sweep.md 2> $OUT/config_sweep.err
-timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --share-device --dist-backend gloo --k 21 --steps 3 --warmup 1 --no-replay --no-sweep --no-pmc-traffic --shard-ntt-columns on 2> $OUT/bench_2rank.err | tail -1 > $OUT/bench_2rank_shared_gpu_gloo_k21.json
+timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --share-device --dist-backend gloo --k 21 --steps 3 --warmup 1 --no-replay --no-sweep --no-pmc-traffic --shard-ntt-columns on 2> $OUT/bench_2rank.err | tail -1 > $OUT/bench_2rank_shared_gpu_gloo_k21.json
 tail -24 $OUT/pytest_gpu.log; head -c 700 $OUT/bench.json; echo; head -14 $OUT/kernel_trace.md; head -8 $OUT/pmc_hbm.md; head -30 $OUT/create_proof_k19_kernels.md; head -c 600 $OUT/bench_2rank_shared_gpu_gloo_k21.json; tail -3 $OUT/bench_2rank.err

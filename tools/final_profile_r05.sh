@@ -15,7 +15,7 @@ mkdir -p $OUT
 REPO=$PWD
 ( time timeout 1500 python -m pytest tests -m gpu -q --durations=12 ) > $OUT/pytest_gpu.log 2>&1
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke OK')" >> $OUT/pytest_gpu.log 2>&1
-timeout 900 python bench.py 2>$OUT/bench.err | tail -1 > $OUT/bench.json
+timeout 900 python bench.py --full 2>$OUT/bench.err | tail -1 > $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python $REPO/bench.py --pmc-child --steps 20 --warmup 3 > $OUT/trace.log 2>&1
 python $REPO/tools/rocprof_proof.py $(find $OUT/trace -name "*.db" | head -1) > $OUT/bench_proof_k19_kernels.md 2>&1
@@ -53,5 +53,5 @@ H2HIP_FUZZ_KNOBS=1 timeout 300 python tools/fuzz_shapes.py 120 6 > $OUT/fuzz_kno
 timeout 300 python tools/fuzz_shapes.py 100 5 13 16 > $OUT/fuzz_mid.log 2>&1
 timeout 400 python tools/soak.py 200 > $OUT/soak.log 2>&1
 ( tail -2 $OUT/fuzz_small.log; tail -2 $OUT/fuzz_knobs.log; tail -2 $OUT/fuzz_mid.log; tail -3 $OUT/soak.log ) > $OUT/fuzz_soak.log 2>&1
-timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --share-device --dist-backend gloo --steps 5 --warmup 2 --no-sweep --shard-ntt-columns on 2> $OUT/bench_2rank.err | tail -1 > $OUT/bench_2rank_shared_gpu_gloo_pairing21.json
+timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --share-device --dist-backend gloo --steps 5 --warmup 2 --no-sweep --shard-ntt-columns on 2> $OUT/bench_2rank.err | tail -1 > $OUT/bench_2rank_shared_gpu_gloo_pairing21.json
 tail -24 $OUT/pytest_gpu.log; head -c 700 $OUT/bench.json; echo; head -14 $OUT/kernel_trace.md; head -8 $OUT/pmc_hbm.md; head -30 $OUT/create_proof_k19_kernels.md; head -c 600 $OUT/bench_2rank_shared_gpu_gloo_pairing21.json; tail -3 $OUT/bench_2rank.err

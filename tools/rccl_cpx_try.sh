@@ -20,7 +20,7 @@ if [ "${N:-1}" -gt 1 ] 2>/dev/null; then
   for W in 2 4 8; do
     [ $W -le $N ] || continue
     echo "== bench.py --gpus $W over RCCL on $N logical devices" >> $LOG
-    timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $W --master-addr 127.0.0.1 --master-port $((29600+W)) bench.py --gpus $W --steps 5 --warmup 2 --no-sweep --dist-backend nccl 2>>${LOG%.log}_bench_$W.err | tail -1 > ${LOG%.log}_bench_$W.json
+    timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $W --master-addr 127.0.0.1 --master-port $((29600+W)) bench.py --full --gpus $W --steps 5 --warmup 2 --no-sweep --dist-backend nccl 2>>${LOG%.log}_bench_$W.err | tail -1 > ${LOG%.log}_bench_$W.json
     echo "rc=$? $(head -c 600 ${LOG%.log}_bench_$W.json)" >> $LOG
   done
   echo "== tests/test_sharded_multirank_gpu.py with the RCCL transport on distinct logical devices" >> $LOG
