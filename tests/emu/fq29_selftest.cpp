@@ -83,14 +83,213 @@ static void field_checks(const char *name) {
     printf("%s field checks done\n", name);
 }
 
+// ---- zero tests at every multiple of the modulus, in the limb form the callers pass (ec29.cuh, quad29.cuh) ----------------------------------
+// plain integer helpers on normalised limbs (no table of multiples, no modular arithmetic): the expected side of the checks below
+template <class P29>
+static F29<P29> int_add(const F29<P29> &a, const F29<P29> &b) {
+    return f29_norm(f29_add(a, b));
+}
+template <class P29>
+static F29<P29> int_sub(const F29<P29> &a, const F29<P29> &b) {   // a >= b
+    F29<P29> r;
+    int64_t borrow = 0;
+    for (int i = 0; i < 9; ++i) {
+        int64_t v = (int64_t)a.l[i] - (int64_t)b.l[i] - borrow;
+        borrow = v < 0;
+        if (v < 0) v += (int64_t)1 << 29;
+        r.l[i] = (uint32_t)v;
+    }
+    if (borrow) {
+        printf("FAIL int_sub: negative\n");
+        ++fails;
+    }
+    return r;
+}
+template <class P29>
+static bool int_ge(const F29<P29> &a, const F29<P29> &b) {   // both normalised, top limbs included
+    for (int i = 8; i >= 0; --i)
+        if (a.l[i] != b.l[i]) return a.l[i] > b.l[i];
+    return true;
+}
+template <class P29>
+static F29<P29> modulus() {
+    F29<P29> q;
+    for (int i = 0; i < 9; ++i) q.l[i] = P29::p(i);
+    return q;
+}
+template <class P29>
+static F29<P29> times_q(int j) {
+    F29<P29> r = F29<P29>::zero();
+    for (int i = 0; i < j; ++i) r = int_add(r, modulus<P29>());
+    return r;
+}
+template <class P29>
+static F29<P29> small_int(uint32_t v) {
+    F29<P29> r = F29<P29>::zero();
+    r.l[0] = v;
+    return r;
+}
+template <class P29>
+static F29<P29> rnd_below_q() {   // a normalised integer < 2^252 < q
+    F29<P29> r;
+    for (int i = 0; i < 9; ++i) r.l[i] = (uint32_t)sm() & MASK29;
+    r.l[8] &= (1u << 20) - 1;   // 8 * 29 + 20 = 252 bits
+    return r;
+}
+
+template <int K, class P29>
+static void zero_test_checks() {
+    const F29<P29> q = modulus<P29>(), one = small_int<P29>(1);
+    // every multiple j q, 0 <= j <= K, and its two neighbours
+    for (int j = 0; j <= K; ++j) {
+        const F29<P29> m = times_q<P29>(j);
+        CHECK(f29_is_zero_mod_q<K>(m));
+        CHECK(!f29_is_zero_mod_q<K>(int_add(m, one)));
+        if (j) CHECK(!f29_is_zero_mod_q<K>(int_sub(m, one)));
+        for (int it = 0; it < 50; ++it) {   // j q + d for 0 < d < q
+            F29<P29> d = rnd_below_q<P29>();
+            if (d.is_zero_exact()) d = one;
+            if (j < K) CHECK(!f29_is_zero_mod_q<K>(int_add(m, d)));
+        }
+    }
+    // the top of the stated ranges: (K + 0.01) q for K = 7, (K + 0.05) q for K = 3 — K q + q / 100 resp. K q + q / 20 and the values around them
+    {
+        F29<P29> frac = F29<P29>::zero();   // floor(q / 2^7) < 0.01 q resp. floor(q / 2^5) < 0.05 q, from the limbs
+        const int sh = K == 7 ? 7 : 5;
+        for (int i = 0; i < 9; ++i) frac.l[i] = ((q.l[i] >> sh) | (i < 8 ? q.l[i + 1] << (29 - sh) : 0)) & MASK29;
+        const F29<P29> top = int_add(times_q<P29>(K), frac);
+        CHECK(!f29_is_zero_mod_q<K>(top));
+        CHECK(!f29_is_zero_mod_q<K>(int_add(top, one)));
+        CHECK(!f29_is_zero_mod_q<K>(int_sub(top, one)));
+    }
+    for (int it = 0; it < 300; ++it) {
+        const F29<P29> a0 = rnd_below_q<P29>();
+        if (K == 7) {
+            // f29_sub<6>(a, b) = a - b + 6 q (xyzz29_add_affine's Pd): j q for 1 <= j <= 6 from b = a + (6 - j) q, 7 q from a = b + q
+            for (int j = 1; j <= 7; ++j) {
+                F29<P29> a = a0, b = int_add(a0, times_q<P29>(6 - (j <= 6 ? j : 6)));
+                if (j == 7) {
+                    b = a0;
+                    b.l[8] = 0;
+                    b.l[7] &= 0xffff;   // < 0.01 q, as the callers' bounds have it
+                    a = int_add(b, q);
+                }
+                const F29<P29> d = f29_sub<6>(a, b);
+                CHECK(int_ge(d, times_q<P29>(j)) && int_ge(times_q<P29>(j), d));   // the integer j q
+                CHECK(f29_is_zero_mod_q<7>(d));
+                CHECK(!f29_is_zero_mod_q<7>(f29_sub<6>(int_add(a, one), b)));
+                if (j < 7) CHECK(!f29_is_zero_mod_q<7>(f29_sub<6>(a, int_add(b, one))));
+            }
+            // f29_signed_sub4(a, neg, b) = (neg ? 2 q - a : a) - b + 4 q (its Rd): plain, j q for 1 <= j <= 5; negated, for 2 <= j <= 5
+            for (int j = 1; j <= 5; ++j) {
+                F29<P29> a = a0, b = int_add(a0, times_q<P29>(4 - (j <= 4 ? j : 4)));
+                if (j == 5) a = int_add(a0, q);   // a = b + q < 2 q
+                const F29<P29> d = f29_signed_sub4(a, false, b);
+                CHECK(int_ge(d, times_q<P29>(j)) && int_ge(times_q<P29>(j), d));
+                CHECK(f29_is_zero_mod_q<7>(d));
+                CHECK(!f29_is_zero_mod_q<7>(f29_signed_sub4(a, false, int_add(b, one))));
+                CHECK(!f29_is_zero_mod_q<7>(f29_signed_sub4(a, true, int_add(b, one))));
+            }
+            for (int j = 2; j <= 5; ++j) {   // a + b = (6 - j) q
+                const F29<P29> a = a0, b = int_sub(times_q<P29>(6 - j), a0);
+                const F29<P29> d = f29_signed_sub4(a, true, b);
+                CHECK(int_ge(d, times_q<P29>(j)) && int_ge(times_q<P29>(j), d));
+                CHECK(f29_is_zero_mod_q<7>(d));
+            }
+        } else {
+            // f29_sub<2>(a, b) = a - b + 2 q (xyzz29_add's and quad_xyzz_add's Pd, Rd): q from b = a + q, 2 q from b = a, 3 q from a = b + q
+            for (int j = 1; j <= 3; ++j) {
+                const F29<P29> a = j == 3 ? int_add(a0, q) : a0, b = j == 1 ? int_add(a0, q) : a0;
+                const F29<P29> d = f29_sub<2>(a, b);
+                CHECK(int_ge(d, times_q<P29>(j)) && int_ge(times_q<P29>(j), d));
+                CHECK(f29_is_zero_mod_q<3>(d));
+                CHECK(!f29_is_zero_mod_q<3>(f29_sub<2>(int_add(a, one), b)));
+                CHECK(!f29_is_zero_mod_q<3>(f29_sub<2>(a, int_add(b, one))));
+            }
+        }
+    }
+}
+
 static bool same_point(const XYZZ &p, const XYZZ &q) {
     G1Affine a = xyzz_to_affine(p), b = xyzz_to_affine(q);
     return a.x == b.x && a.y == b.y;
 }
 
+// The additions' equal-x / equal-y decisions at EVERY multiple of q their differences can take.  The accumulator is the point 2^i G with a random
+// Z and with its coordinates moved to other representatives of the same residues (X + m q < 5.25 q, Y + m' q < 3.3 q: the bounds of ec29.cuh); the
+// point added is the same point or its negative, so every call must take the doubling or the cancelling branch.  Pd = 7 q needs
+// U2 = x2 * ZZ >= q as an integer (a few products in a thousand) and the representative X = U2 - q < 0.01 q.
+static void exceptional_branch_checks(const G1Affine *pts, int npts) {
+    const Fq29 q = modulus<Q29P>();
+    int hits_pd[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hits_add[4] = {0, 0, 0, 0};
+    for (int it = 0; it < 60000 && fails <= 5; ++it) {
+        const G1Affine p = pts[it % npts];
+        const G1Affine29 p29 = g1affine29_from_sat(p);
+        const Fq29 z = f29_from_sat(rnd<FqP>());
+        XYZZ29 base;
+        base.zz = f29_sqr(z);
+        base.zzz = f29_mul(base.zz, z);
+        const Fq29 U2 = f29_mul(p29.x, base.zz), S2 = f29_mul(p29.y, base.zzz);
+        const XYZZ dbl = xyzz_double(XYZZ::from_affine(p));
+        const int m = (int)(sm() % 7) - 1, my = (int)(sm() % 3);   // X = U2 + m q (m = -1: only when U2 >= q), Y = S2 + my q
+        if (m < 0 && !int_ge(U2, q)) continue;
+        base.x = m < 0 ? int_sub(U2, q) : int_add(U2, times_q<Q29P>(m));
+        if (m == 5) {   // Pd = q: X = U2 + 5 q stays below 5.25 q only for U2 < q / 4
+            const Fq29 x2 = int_add(base.x, base.x);
+            if (int_ge(int_add(x2, x2), times_q<Q29P>(21))) continue;
+        }
+        base.y = int_add(S2, times_q<Q29P>(my));
+        ++hits_pd[6 - m];
+        for (int neg = 0; neg < 2; ++neg) {
+            XYZZ29 a = base;
+            xyzz29_add_affine(a, p29.x, p29.y, neg != 0);
+            CHECK(a.is_identity() == (neg != 0));
+            if (!neg && !a.is_identity()) CHECK(same_point(xyzz29_to_sat(a), dbl));
+            XYZZ29 b = base;
+            bool empty = false;
+            xyzz29_add_affine_flag(b, empty, p29.x, p29.y, neg != 0);
+            CHECK(empty == (neg != 0));
+            if (!neg && !empty) CHECK(same_point(xyzz29_to_sat(b), dbl));
+        }
+        // the full addition: the same point under another Z, either sign; its Pd = U2' - U1' + 2 q is q, 2 q or 3 q
+        const Fq29 z2 = f29_from_sat(rnd<FqP>());
+        XYZZ29 other;
+        other.zz = f29_sqr(z2);
+        other.zzz = f29_mul(other.zz, z2);
+        other.x = int_add(f29_mul(p29.x, other.zz), times_q<Q29P>((int)(sm() % 5)));
+        const Fq29 oy = f29_mul(p29.y, other.zzz);
+        if (m < 0 || m == 5) continue;   // (the full addition is checked on the common representatives)
+        {
+            const Fq29 U1 = f29_mul(base.x, other.zz), V2 = f29_mul(other.x, base.zz);
+            const Fq29 Pd = f29_sub<2>(V2, U1);
+            for (int j = 1; j <= 3; ++j)
+                if (int_ge(Pd, times_q<Q29P>(j)) && int_ge(times_q<Q29P>(j), Pd)) ++hits_add[j];
+        }
+        for (int neg = 0; neg < 2; ++neg) {
+            other.y = neg ? f29_neg<2>(oy) : int_add(oy, times_q<Q29P>(my));
+            XYZZ29 a = base;
+            xyzz29_add(a, other);
+            CHECK(a.is_identity() == (neg != 0));
+            if (!neg && !a.is_identity()) CHECK(same_point(xyzz29_to_sat(a), dbl));
+            XYZZ29 id = XYZZ29::identity(), c = base;   // identity operands on either side
+            xyzz29_add(c, id);
+            xyzz29_add(id, base);
+            CHECK(same_point(xyzz29_to_sat(c), XYZZ::from_affine(p)) && same_point(xyzz29_to_sat(id), XYZZ::from_affine(p)));
+        }
+    }
+    for (int j = 1; j <= 7; ++j) CHECK(hits_pd[j] > 0);    // every multiple the mixed additions' Pd can be was reached
+    for (int j = 1; j <= 3; ++j) CHECK(hits_add[j] > 0);   // and every one of the full addition's
+    printf("exceptional branches: Pd = j q reached %d %d %d %d %d %d %d times (j = 1..7); full add %d %d %d (j = 1..3)\n", hits_pd[1], hits_pd[2],
+           hits_pd[3], hits_pd[4], hits_pd[5], hits_pd[6], hits_pd[7], hits_add[1], hits_add[2], hits_add[3]);
+}
+
 int main() {
     field_checks<Q29P, FqP>("Fq");
     field_checks<R29P, FrP>("Fr");
+    zero_test_checks<7, Q29P>();
+    zero_test_checks<3, Q29P>();
+    zero_test_checks<7, R29P>();
+    zero_test_checks<3, R29P>();
     // points: G = (1, 2) and multiples built with the saturated formulas
     G1Affine G;
     G.x = from_u64<FqP>(1);
@@ -106,6 +305,7 @@ int main() {
         acc = xyzz_double(acc);
         xyzz_add_affine(acc, G.x, G.y);
     }
+    exceptional_branch_checks(pts, 64);
     // random walks of mixed adds (both signs), full adds and doublings, including P+P, P-P and identity operands
     XYZZ s = XYZZ::identity();
     XYZZ29 s29 = XYZZ29::identity();

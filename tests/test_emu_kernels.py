@@ -667,3 +667,57 @@ def test_knobs_batch_inversion_emulated(ctx):
     from tests import knob_checks as K
 
     K.check_invert_run(ctx, (1, 2, 1000, 3001))
+
+
+# ---- curve arithmetic on degenerate base sets (small multiples of one point, identities, negatives): the exceptional branches of every
+# addition routine through every MSM path, against the C oracle AND the closed form (tests/degenerate_group_checks.py; the GPU suite runs
+# the same at real sizes)
+def test_degenerate_bases_msm_paths_emulated(ctx):
+    """sizes around a wave (63 .. 65), a workgroup (255 .. 257), just above a sort chunk (4097) and 20 011; at each size a rotating quarter of
+    the (base set, scalar kind) cases under one of the (msm_table_split, plain / precomputed) combinations — a call of the emulated build costs
+    ~0.1 s whatever its size, so the cross product is spread over the sizes (the GPU suite runs it whole)"""
+    from tests import degenerate_group_checks as D
+
+    assert D.check_msm_paths(ctx, [1, 2, 3, 63, 64, 65, 255, 256, 257, 3000, 4097, 20011], threads=4, thin=4) == 69
+    D.check_prefix_of_bases(ctx, 700, threads=4)
+
+
+def test_degenerate_bases_msm_batch_emulated(ctx):
+    from tests import degenerate_group_checks as D
+
+    D.check_msm_batch(ctx, 300, threads=4, base_kind=1)
+    D.check_msm_batch(ctx, 2500, threads=4, base_kind=6)
+    D.check_msm_multi(ctx, 2000, threads=4)
+
+
+def test_degenerate_bases_dense_then_cancelling_emulated(ctx):
+    from tests import degenerate_group_checks as D
+
+    D.check_dense_then_cancelling(ctx, 2000, threads=4)
+
+
+def test_degenerate_bases_msm_knobs_emulated(ctx):
+    """three cases (long runs, pairwise cancelling, late cancelling) x 35 knob settings; windows 4, 7 and 12"""
+    from tests import degenerate_group_checks as D
+
+    assert D.check_msm_knobs(ctx, 2000, threads=4, exact_cases=3) == 3 * 35
+
+
+def test_degenerate_bases_msm_g2_emulated(ctx):
+    """n up to 3000: the reference is one G2 scalar multiplication per case whatever n is, the emulated kernels set the size"""
+    from tests import degenerate_group_checks as D
+
+    assert D.check_msm_g2(ctx, [1, 2, 65, 300, 3000]) == 5 * 13
+
+
+def test_degenerate_srs_g1_to_lagrange_emulated(ctx):
+    from tests import degenerate_group_checks as D
+
+    D.check_g1_to_lagrange(ctx, [1, 2, 3, 5, 8], threads=4)
+
+
+def test_degenerate_point_sums_and_fixed_base_products_emulated(ctx):
+    from tests import degenerate_group_checks as D
+
+    D.check_g1_sum_jacobian(ctx)
+    D.check_g1_fixed_base_mul(ctx)

@@ -563,3 +563,67 @@ def test_knobs_batch_inversion(ctx):
     from tests import knob_checks as K
 
     K.check_invert_run(ctx, (1, 1000, 70001, (1 << 19) + 7))
+
+
+# ---- curve arithmetic on degenerate base sets (tests/degenerate_group_checks.py; the CPU suite runs the same on the emulated build at
+# small sizes): every base a small multiple of one point, so that P + P, P + (-P) and identity + P occur in every bucket, run and merge
+# level; every case against the C oracle bit for bit AND the closed form (sum s_i k_i) P
+def test_degenerate_bases_msm_paths(ctx):
+    """every (base set, scalar kind) case under every (msm_table_split, plain / precomputed) combination at every size"""
+    from tests import degenerate_group_checks as D
+
+    sizes = [1, 2, 3, 63, 64, 65, 255, 256, 257, 3000, 4097, 20011, (1 << 16) + 3]
+    assert D.check_msm_paths(ctx, sizes, threads=NT) == 23 * len(sizes)
+    D.check_prefix_of_bases(ctx, 70001, threads=NT)
+
+
+@pytest.mark.parametrize("n", [1 << 19, 1 << 20])
+def test_degenerate_bases_msm_large(ctx, n):
+    from tests import degenerate_group_checks as D
+
+    combos = [(6, "few"), (6, "cancel"), (1, "cancel_late"), (1, "rand"), ("alternating", "few"), ("equal", "full_range"), ("identity", "rand"),
+              ("last", "rand"), (6, "circuit")]
+    D.check_msm_large(ctx, n, NT, combos)
+
+
+def test_degenerate_bases_msm_batch(ctx):
+    from tests import degenerate_group_checks as D
+
+    for n, M in ((1, 6), (2, 1), (65, 1), (257, 6), (4097, 1), (20011, 6), ((1 << 16) + 3, 6), (1 << 19, 1)):
+        D.check_msm_batch(ctx, n, threads=NT, base_kind=M)
+    for n in (3, 257, 20011, (1 << 16) + 3):
+        D.check_msm_multi(ctx, n, threads=NT)
+
+
+def test_degenerate_bases_dense_then_cancelling(ctx):
+    from tests import degenerate_group_checks as D
+
+    for n in (65, 4097, (1 << 16) + 3, 1 << 19):
+        D.check_dense_then_cancelling(ctx, n, threads=NT)
+
+
+@pytest.mark.parametrize("n,windows", [(257, (4, 7, 12)), (20011, (4, 7, 12)), ((1 << 16) + 3, (5, 9, 16)), (1 << 19, (6, 13, 16))])
+def test_degenerate_bases_msm_knobs(ctx, n, windows):
+    from tests import degenerate_group_checks as D
+
+    assert D.check_msm_knobs(ctx, n, threads=NT, windows=windows) == 7 * 35
+
+
+def test_degenerate_bases_msm_g2(ctx):
+    """n up to 2^16 + 3: the reference is one G2 scalar multiplication per case whatever n is"""
+    from tests import degenerate_group_checks as D
+
+    assert D.check_msm_g2(ctx, [1, 2, 65, 300, 5000, (1 << 16) + 3]) == 6 * 13
+
+
+def test_degenerate_srs_g1_to_lagrange(ctx):
+    from tests import degenerate_group_checks as D
+
+    D.check_g1_to_lagrange(ctx, [1, 2, 3, 5, 8, 10, 12], threads=NT)
+
+
+def test_degenerate_point_sums_and_fixed_base_products(ctx):
+    from tests import degenerate_group_checks as D
+
+    D.check_g1_sum_jacobian(ctx)
+    D.check_g1_fixed_base_mul(ctx, threads=NT)
