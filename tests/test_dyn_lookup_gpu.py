@@ -35,6 +35,23 @@ def test_ram_prover_shape(ctx):
         kzg.free()
 
 
+@pytest.mark.parametrize("k", [12, 13])
+def test_multi_tile_sort_against_test_prover(ctx, k):
+    """a table of 2^k - 11 rows and 2^k accesses over 2 lookup sets, 2 key columns: the theta-compressed keys are full-width, and their sort
+    spans 4 (k = 12) and 8 (k = 13) LDS tiles with two and three merge steps of global stages.  Byte for byte against the test-side prover,
+    whose time was measured on a CPU at 1.7 s (k = 12) and 2.7 s (k = 13) for keygen and proof together."""
+    from tests.lookup_key_checks import MIN_TILE, padded_keys
+
+    gpk, kzg, params, vk, got, want, sh, _ = prove_both(ctx, k, 1 << k, (1 << k) - 9 - 2, 2, 2, seed=60 + k, threads=8)
+    try:
+        assert padded_keys(sh.usable_rows) == (1 << k) >= 4 * MIN_TILE
+        assert got == want, "proof bytes differ from the test prover's"
+        assert PL.verify_proof(gpk, [], got) and oracle_verify(params, vk, got)
+    finally:
+        gpk.free()
+        kzg.free()
+
+
 def test_large_table_k17(ctx):
     """k = 17, a table of 2^17 - 11 rows (the last usable row holds the disabled zero row) and 4 lookup sets: the per-proof sort of the
     compressed table runs the bitonic network's global passes.  Verified by both verifiers; two proofs from one RNG stream are identical."""

@@ -721,3 +721,64 @@ def test_degenerate_point_sums_and_fixed_base_products_emulated(ctx):
 
     D.check_g1_sum_jacobian(ctx)
     D.check_g1_fixed_base_mul(ctx)
+
+
+# ---- the lookup permutation on full-width keys through every sort path (tests/lookup_key_checks.py; the GPU suite runs the same at proof
+# sizes): every case against oracle.bn254.permute_expression_pair, A' and S' equal element by element
+LOOKUP_KEY_SIZES = [1, 2, 3, 1000, 1024, 1025, 4000, 5000]   # padded key counts: one tile (with and without padding), 2 (mostly padding), 4 and 8 tiles
+
+
+def test_lookup_full_width_key_families_emulated(ctx):
+    """28 key families (uniform, one word decides x 16, all 16 in one set, stored-small, edges, four multiplicity shapes, four input shapes) at
+    every size, plain and with a presorted table"""
+    from tests import lookup_key_checks as L
+
+    L.check_padded_keys_mirror(ctx)
+    assert [L.padded_keys(u) // L.MIN_TILE for u in LOOKUP_KEY_SIZES] == [1, 1, 1, 1, 1, 2, 4, 8]
+    assert L.check_families(ctx, LOOKUP_KEY_SIZES) == len(LOOKUP_KEY_SIZES) * 28
+    L.check_edges_next_to_padding(ctx, 1000)
+    L.check_edges_next_to_padding(ctx, 1025)
+
+
+def test_lookup_full_width_keys_both_tile_sizes_emulated(ctx):
+    """the same inputs through the 4096-key LDS tile (lookup_big_tile_bits = 12: 1, 2 and 8 such tiles) and through the 1024-key tile (the knob
+    as it stands: 4, 8 and 32 tiles, up to five global stages per merge step)"""
+    from tests import lookup_key_checks as L
+
+    assert ctx.get_param("lookup_big_tile_bits") == 19
+    assert L.check_families(ctx, [4000, 5000, 20000], tile_bits=(12, None)) == 3 * 28
+    assert ctx.get_param("lookup_big_tile_bits") == 19
+
+
+def test_lookup_full_width_keys_batch_emulated(ctx):
+    from tests import lookup_key_checks as L
+
+    fams = ("uniform", "one_word_all", "stored_small", "edges", "one_value", "sorted", "reverse", "bitonic") + L.ONE_WORD[6:12]
+    assert L.check_families_batch(ctx, 1000, fams) == 14
+    assert L.check_families_batch(ctx, 5000, fams) == 14
+    with L.knobs(ctx, lookup_big_tile_bits=12):
+        assert L.check_families_batch(ctx, 5000, fams, seed=1) == 14
+
+
+def test_lookup_routing_thresholds_emulated(ctx):
+    """largest keys 2^22 - 2, 2^22 - 1 (counting sort), 2^22, 2^32 - 1, 2^32, 2^224 + 5 (bitonic network) in one column; a batch with both
+    sorters; 49 and 97 columns; a missing full-width value"""
+    from tests import lookup_key_checks as L
+
+    assert L.check_thresholds(ctx, 300) == 12
+    assert L.check_thresholds(ctx, 2500, seed=1) == 12
+    L.check_batch_mixed_sorters(ctx, 1500)
+    L.check_batch_many_columns(ctx, 200)
+    L.check_missing_value(ctx, 1500)
+    L.check_missing_value(ctx, 5000, seed=1)
+
+
+def test_lookup_batch_histogram_limit_emulated(ctx):
+    """31 columns with a key of 2^22 - 1 take the batched counting sort (31 histograms of 2^22 bins), 32 exceed 1 GiB and go column by column;
+    both counts come from the predicate.  Measured on the emulated build: 5.2 s and 2.8 s."""
+    from tests import lookup_key_checks as L
+
+    batched, per_column = L.fallback_counts()
+    assert (batched, per_column) == (31, 32) and per_column <= L.BATCH
+    L.check_batch_histogram_limit(ctx, 64, per_column)
+    L.check_batch_histogram_limit(ctx, 64, batched)

@@ -627,3 +627,81 @@ def test_degenerate_point_sums_and_fixed_base_products(ctx):
 
     D.check_g1_sum_jacobian(ctx)
     D.check_g1_fixed_base_mul(ctx, threads=NT)
+
+
+# ---- the lookup permutation on full-width keys through every sort path (tests/lookup_key_checks.py, shared with the emulated build): every
+# case against oracle.bn254.permute_expression_pair, A' and S' equal element by element
+@pytest.mark.gpu
+def test_lookup_full_width_key_families(ctx):
+    from tests import lookup_key_checks as L
+    from tests.test_emu_kernels import LOOKUP_KEY_SIZES
+
+    L.check_padded_keys_mirror(ctx)
+    assert L.check_families(ctx, LOOKUP_KEY_SIZES + [20000]) == (len(LOOKUP_KEY_SIZES) + 1) * 28
+    L.check_edges_next_to_padding(ctx, 1000)
+    L.check_edges_next_to_padding(ctx, 1025)
+    assert L.check_families(ctx, [4000, 5000, 20000], tile_bits=(12,)) == 3 * 28   # the 4096-key tile on 1, 2 and 8 tiles
+
+
+@pytest.mark.gpu
+def test_lookup_full_width_keys_2_17_both_tile_sizes(ctx):
+    """2^17 - 20 keys (128 tiles of 1024 keys, 32 of 4096) under both tile sizes"""
+    from tests import lookup_key_checks as L
+
+    assert ctx.get_param("lookup_big_tile_bits") == 19
+    assert L.check_families(ctx, [(1 << 17) - 20], families=L.FAMILIES, tile_bits=(None, 12)) == len(L.FAMILIES)
+    assert ctx.get_param("lookup_big_tile_bits") == 19
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("u,families", [((1 << 19) - 6, ("uniform", "one_word_all", "stored_small", "edges", "one_value", "permutation", "three_five", "runs",
+                                                          "sorted", "reverse", "bitonic", "valley")),
+                                        ((1 << 20) - 7, ("uniform", "one_word_all", "stored_small", "edges", "runs", "reverse"))],
+                         ids=["2^19-6", "2^20-7"])
+def test_lookup_full_width_keys_big_tile_sizes(ctx, u, families):
+    """the sizes that take the 4096-key tile (128 KiB of LDS) by default, with global stages up to a partner distance of 2^19 keys.  The
+    reference costs ~3 s (2^19) and ~6 s (2^20) per case: every family at 2^19 - 6, six of them at 2^20 - 7."""
+    from tests import lookup_key_checks as L
+
+    assert L.padded_keys(u) >= 1 << ctx.get_param("lookup_big_tile_bits")
+    assert L.check_families(ctx, [u], families=families) == len(families)
+
+
+@pytest.mark.gpu
+def test_lookup_full_width_keys_batch(ctx):
+    from tests import lookup_key_checks as L
+
+    fams = ("uniform", "one_word_all", "stored_small", "edges", "one_value", "sorted", "reverse", "bitonic") + L.ONE_WORD[6:12]
+    assert L.check_families_batch(ctx, 1000, fams) == 14
+    assert L.check_families_batch(ctx, 5000, fams) == 14
+    assert L.check_families_batch(ctx, 70000, fams, seed=2) == 14
+    with L.knobs(ctx, lookup_big_tile_bits=12):
+        assert L.check_families_batch(ctx, 70000, fams, seed=1) == 14
+    assert L.check_families_batch(ctx, (1 << 19) - 6, ("uniform", "one_word_all", "reverse")) == 3
+
+
+@pytest.mark.gpu
+def test_lookup_routing_thresholds(ctx):
+    from tests import lookup_key_checks as L
+
+    assert L.check_thresholds(ctx, 300) == 12
+    assert L.check_thresholds(ctx, 2500, seed=1) == 12
+    assert L.check_thresholds(ctx, (1 << 17) - 20, seed=2) == 12
+    L.check_batch_mixed_sorters(ctx, 1500)
+    L.check_batch_mixed_sorters(ctx, 70000, seed=1)
+    L.check_batch_many_columns(ctx, 200)
+    L.check_batch_many_columns(ctx, 3001, bits=9, seed=1)
+    L.check_missing_value(ctx, 1500)
+    L.check_missing_value(ctx, 70000, seed=1)
+
+
+@pytest.mark.gpu
+def test_lookup_batch_histogram_limit(ctx):
+    """both sides of sort_columns_keys' 1 GiB predicate with a key of 2^22 - 1: 31 columns batched, 32 column by column"""
+    from tests import lookup_key_checks as L
+
+    batched, per_column = L.fallback_counts()
+    assert (batched, per_column) == (31, 32) and per_column <= L.BATCH
+    for u in (64, 3001):
+        L.check_batch_histogram_limit(ctx, u, per_column)
+        L.check_batch_histogram_limit(ctx, u, batched)
