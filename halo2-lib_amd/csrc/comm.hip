@@ -112,7 +112,7 @@ static int comm_dev_stage(h2hip_comm *c, size_t bytes) {
 }
 
 // every fallible preparation of a later h2hip_comm_allgather_dev(bytes per rank) — the callback transport's pinned staging area — done NOW, so
-// that a caller can put it before the go-ahead exchange that precedes the collective (plonk.hip: the coset all-gather)
+// that a caller can put it before the go-ahead exchange that precedes the collective (plonk_prove.hip: the coset all-gather)
 int h2::comm_reserve_allgather_dev(h2hip_comm *c, size_t bytes) {
     H2_REQUIRE(c, "NULL argument");
     if (c->nccl || !bytes) return H2HIP_OK;

@@ -114,7 +114,7 @@ struct h2hip_ctx {
     size_t job_ring_off = 0;
     // One-shot hook of the batch MSM (set by the prover before a commitment round): called on the host right after the lanes' accumulations and
     // merges have been joined into `stream` — `ev` is recorded there at that point — and BEFORE the latency-bound bucket reduction is queued, so
-    // that work the caller queues on another stream behind `ev` runs next to the reduction's few waves instead of after them (plonk.hip: the
+    // that work the caller queues on another stream behind `ev` runs next to the reduction's few waves instead of after them (plonk_prove.hip: the
     // round's challenge-independent transforms).  Cleared before it is called; left set if the call took a path without lanes.
     // a batch MSM whose LAST columns are still being produced when it is called (round 1 of create_proof: the permuted lookup columns): the
     // batch queues its first msm_mid_after columns on the lanes, calls the hook — the caller queues the producing work on this context's stream,
@@ -319,7 +319,7 @@ int rng_chacha_fill_dev(h2hip_ctx *ctx, Fr *out_dev, size_t n, const uint8_t see
 // comm.hip: the fallible preparations of a later h2hip_comm_allgather_dev of `bytes` per rank, done ahead of time
 int comm_reserve_allgather_dev(h2hip_comm *comm, size_t bytes);
 int comm_reserve_alltoall_dev(h2hip_comm *c, size_t bytes);
-// plonk.hip: the multi-phase layout (Shape::init_phased) for the verifier: the shape, each used phase's advice columns and challenges, whether
+// plonk.hip: the multi-phase layout (Shape::init_phased, plonk_internal.h) for the verifier: the shape, each used phase's advice columns and challenges, whether
 // the key is multi-phase at all (otherwise it proves as the BaseConfig of `bp`), and the BaseCircuitParams of the gate / lookup-advice totals
 int plonk_phased_layout(const h2hip_phased_circuit_params &pp, h2hip_plonk_shape *shape, std::vector<std::vector<int>> *phase_cols,
                         uint32_t challenges[H2HIP_MAX_PHASE], bool *phased, h2hip_base_circuit_params *bp);

@@ -2,7 +2,7 @@
 // (halo2-base/src/utils/testing.rs:64-88: verify_proof::<KZGCommitmentScheme<Bn256>, VerifierSHPLONK<_>, Challenge255<_>, Blake2bRead<_, _, _>,
 // SingleStrategy<_>>).  Host code (the reference verifies on the CPU as well): Blake2b transcript replay, the quotient identity rebuilt from the
 // openings, SHPLONK's folded opening and ONE pairing check e(h2, s*g2) == e(right, g2).  [UPSTREAM-RECALL for the protocol order, like
-// plonk.hip.]  The pairing is the plain ate pairing f_{t-1,Q}(P)^((q^12-1)/r) over the tower Fq2 = Fq[u]/(u^2+1), Fq6 = Fq2[v]/(v^3 - (9+u)),
+// plonk_prove.hip.]  The pairing is the plain ate pairing f_{t-1,Q}(P)^((q^12-1)/r) over the tower Fq2 = Fq[u]/(u^2+1), Fq6 = Fq2[v]/(v^3 - (9+u)),
 // Fq12 = Fq6[w]/(w^2 - v) — any non-degenerate pairing decides e(L, sQ) == e(R, Q), which is all a KZG verifier needs.
 #include <mutex>
 #include <algorithm>
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "blake2b.h"
+#include "host_field.h"
 #include "internal.h"
 
 namespace h2 {
@@ -253,17 +254,6 @@ static G1Affine g1_neg(const G1Affine &p) {
 
 // ---------------------------------------------------------------------------------------------- transcript (Blake2bRead)
 static const unsigned SIGN_BIT = 6, INF_BIT = 7;
-static void fr_repr(const Fr &a, uint8_t out[32]) {
-    Fr c = fe_from_mont(a);
-    memcpy(out, c.l, 32);
-}
-static Fr fr_from_uniform_bytes(const uint8_t b[64]) {
-    Fr d0, d1;
-    memcpy(d0.l, b, 32);
-    memcpy(d1.l, b + 32, 32);
-    const Fr r2 = Fr::r2(), r3 = fe_mul(r2, r2);
-    return fe_add(fe_mul(d0, r2), fe_mul(d1, r3));
-}
 template <class P>
 static bool canonical(const Fe<P> &a) {
     unsigned br = 0;
@@ -352,13 +342,6 @@ struct Reader {
         return fr_from_uniform_bytes(d);
     }
 };
-
-static int fr_cmp(const Fr &a, const Fr &b) {
-    Fr x = fe_from_mont(a), y = fe_from_mont(b);
-    for (int i = 7; i >= 0; --i)
-        if (x.l[i] != y.l[i]) return x.l[i] < y.l[i] ? -1 : 1;
-    return 0;
-}
 
 }  // namespace verifier
 }  // namespace h2

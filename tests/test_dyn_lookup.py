@@ -54,9 +54,11 @@ def test_ram_circuit_proof_emulated(key_cols):
 
     ctx = emu_context()
     try:
-        gpk, kzg, params, vk, got, want, sh, _ = prove_both(ctx, 5, 50, 16, key_cols, 3, seed=key_cols)
+        gpk, kzg, params, vk, got, want, sh, advice = prove_both(ctx, 5, 50, 16, key_cols, 3, seed=key_cols)
         try:
             assert got == want, "proof bytes differ from the test prover's"
+            if key_cols == 1:   # a timed run (a stream synchronisation per stage) of the same RNG stream gives the same bytes
+                assert PL.create_proof(gpk, advice, [], PreDrawnRng(rng_budget(sh), 1000 + key_cols), {}) == got, "the timed proof differs"
             assert oracle_verify(params, vk, got), "the test verifier rejects the proof"
             assert PL.verify_proof(gpk, [], got), "h2hip_plonk_verify_proof_dyn rejects the proof"
             first_eval = 32 * (sh.num_advice_total + 3 * len(sh.lookups) + sh.num_perm_sets + 1 + sh.quotient_poly_degree)

@@ -70,6 +70,10 @@ def test_phased_proof_emulated(ctx, name, k):
     try:
         circ, got = r["circ"], r["got"]
         assert got == r["want"], "proof bytes differ from the test prover's"
+        if name == "a":   # a timed run (a stream synchronisation per stage) of the same RNG stream gives the same bytes
+            timed = PL.create_proof(r["gpk"], circ.advice0(), circ.instance_arrays(), PreDrawnRng(r["budget"], 1000 + k + ord(name)), {},
+                                    phase_witness=circ.witness)
+            assert timed == got, "the timed proof differs"
         if params.num_challenges_per_phase[0]:
             assert r["seen"][0][0] == 1 and len(r["seen"][0][1]) == 1   # phase 1 received the challenge squeezed after phase 0
         instances = circ.instances

@@ -1,4 +1,4 @@
-"""create_proof for halo2-base circuits (include/h2hip.h "a1", halo2-lib_amd/csrc/plonk.hip) against the oracle's restatement
+"""create_proof for halo2-base circuits (include/h2hip.h "a1", halo2-lib_amd/csrc/plonk_prove.hip) against the oracle's restatement
 (oracle/plonk.py) of what the reference runs at halo2-base/src/utils/testing.rs:32-50 (prove) and :64-88 (verify):
 
   * proof BYTES equal to the oracle prover's on the same SRS, circuit and RNG stream (BASELINE.json: "proof bytes equal to CPU");
@@ -84,7 +84,8 @@ def _check(ctx, k, na, nl, nf, ni, lb, seed=3, threads=4, oracle_prover=True, pr
         ref_rng, arr_rng = PreDrawnRng(budget, 1000 + seed), None
         arr_rng = PL.ArrayRng(ref_rng.values)
         assert PL.create_proof(gpk, circ.advice, circ.instances, arr_rng) == got
-        PL.create_proof(gpk, circ.advice, circ.instances, ref_rng)
+        # ... and the untimed run of the same stream: the stage laps' synchronisations (and the late join they switch off) leave the bytes alone
+        assert PL.create_proof(gpk, circ.advice, circ.instances, ref_rng) == got, "the timed proof differs from the untimed one"
         assert arr_rng.pos == ref_rng.pos > 0
         # a second proof from the same key (pooled buffers reused) with another RNG stream: different bytes, still valid
         if second_proof:
