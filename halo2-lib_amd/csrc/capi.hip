@@ -627,8 +627,6 @@ void h2hip_bases_free(h2hip_ctx *ctx, h2hip_bases *bases) {
 size_t h2hip_bases_len(const h2hip_bases *bases) { return bases ? bases->n : 0; }
 
 static int finish_point(h2hip_ctx *ctx, char *outbuf, int point_format, void *out_host);
-static int msm_batch_impl(h2hip_ctx *ctx, const h2hip_bases *bases, const h2hip_bases *const *bases_per_col, const void *const *scalars_in,
-                          bool scalars_on_host, size_t n, size_t count, int point_format, void *out_host);
 int h2hip_msm_g1_dev(h2hip_ctx *ctx, const h2hip_bases *bases, const void *scalars_dev, size_t n, int point_format, void *out_host) {
     H2_DEVICE_GUARD(ctx);
     H2_REQUIRE(ctx && bases && out_host && (n == 0 || scalars_dev), "NULL argument");
@@ -638,6 +636,8 @@ int h2hip_msm_g1_dev(h2hip_ctx *ctx, const h2hip_bases *bases, const void *scala
     H2_CHK(msm_run(ctx, bases, (const Fr *)scalars_dev, n, (XYZZ *)outbuf));
     return finish_point(ctx, outbuf, point_format, out_host);
 }
+}  // extern "C"
+namespace h2 {
 // Several independent MSMs over the same bases (e.g. the h(X) pieces, or all advice columns of a phase): MSM j runs
 // on lane j mod 2 — a child context with its own stream and scratch — so the latency-bound tail of one MSM (merge,
 // bucket reduction) overlaps the multiplier-bound accumulation of the next.
@@ -664,9 +664,9 @@ static void join_lanes(h2hip_ctx *ctx, int nl) {
         }                         \
     } while (0)
 // bases_per_col (optional): a base set per column — columns over different sets (e.g. a Lagrange-basis and a monomial-basis commitment of
-// the same prover round) share the lanes and, when their window tables match, the deferred bucket reduction
-static int msm_batch_impl(h2hip_ctx *ctx, const h2hip_bases *bases, const h2hip_bases *const *bases_per_col, const void *const *scalars_in,
-                          bool scalars_on_host, size_t n, size_t count, int point_format, void *out_host) {
+// the same prover round) share the lanes and, when their window tables match, the deferred bucket reduction.  hooks (optional): BatchMsmHooks, internal.h
+int msm_batch(h2hip_ctx *ctx, const h2hip_bases *bases, const h2hip_bases *const *bases_per_col, const void *const *scalars_in, bool scalars_on_host,
+              size_t n, size_t count, int point_format, void *out_host, const BatchMsmHooks *hooks) {
     if (bases_per_col && count) bases = bases_per_col[0];
     H2_REQUIRE(ctx && bases && (count == 0 || (scalars_in && out_host)), "NULL argument");
     bool mixed = false;
@@ -772,22 +772,18 @@ static int msm_batch_impl(h2hip_ctx *ctx, const h2hip_bases *bases, const h2hip_
     // (two other schedules were built, measured slower and removed in r04: every accumulation on one stream with all sorts / merges on a
     // second, higher-priority one — 2^19 1.00 vs 0.95 ms per MSM, tools/batch_ab.py in r02 — and a column's windows dealt to two lanes —
     // the k = 19 proof 15.7-15.8 vs 14.7 ms, profiles/archive/r03_msm_split_windows_ab.log)
-    // late columns (msm_mid_hook, internal.h): the hook runs once, before the first group that holds a column >= msm_mid_after
-    std::function<int()> mid_hook;
-    mid_hook.swap(ctx->msm_mid_hook);
-    const size_t mid_after = ctx->msm_mid_after;
+    const BatchMsmHooks none;
+    const BatchMsmHooks &hk = hooks ? *hooks : none;
+    // late columns (BatchMsmHooks::mid): the hook runs once, before the first group that holds a column >= mid_after
+    bool mid_pending = (bool)hk.mid;
     auto run_mid = [&]() -> int {
-        if (!mid_hook) return H2HIP_OK;
-        std::function<int()> f;
-        f.swap(mid_hook);
-        H2_CHK(f());
+        mid_pending = false;
+        H2_CHK(hk.mid());
         if (!ctx->fork_ev2) H2_HIPCHK(hipEventCreateWithFlags(&ctx->fork_ev2, hipEventDisableTiming));
         H2_HIPCHK(hipEventRecord(ctx->fork_ev2, ctx->stream));   // what the hook queued on the caller's stream produces the remaining columns
         for (int l = 0; l < NL; ++l) H2_HIPCHK(hipStreamWaitEvent(ctx->lane[l]->stream, ctx->fork_ev2, 0));
         return H2HIP_OK;
     };
-    std::function<int(size_t)> col_hook;   // columns that arrive one by one (msm_col_hook, internal.h)
-    col_hook.swap(ctx->msm_col_hook);
     const size_t ngroups = groups.size();
     // (r05, last: the lanes' streams created with the lowest / the highest HIP priority — either way 7 - 10 % slower at k = 17 / 19, profiles/r05_lane_priority_ab.log; removed)
     // (r05 built and measured a third schedule — the sorts of a round of columns queued on ALL lanes before any of their accumulations, so that no
@@ -796,20 +792,21 @@ static int msm_batch_impl(h2hip_ctx *ctx, const h2hip_bases *bases, const h2hip_
     for (size_t g = 0; g < ngroups; ++g) {
         const size_t j0 = groups[g].first, gsize = groups[g].second;
         h2hip_ctx *c = ctx->lane[g % NL];
-        if (col_hook)   // the group's columns are produced now, on the caller's stream (before the mid hook: what it queues may read them)
-            for (size_t j = j0; j < j0 + gsize; ++j) H2_LANES_RC(col_hook(j));
-        if (mid_hook && j0 + gsize > mid_after) H2_LANES_RC(run_mid());
-        if (col_hook) {   // the lane waits for them
+        if (hk.col)   // the group's columns are produced now, on the caller's stream (before the mid hook: what it queues may read them)
+            for (size_t j = j0; j < j0 + gsize; ++j) H2_LANES_RC(hk.col(j));
+        if (mid_pending && j0 + gsize > hk.mid_after) H2_LANES_RC(run_mid());
+        if (hk.col) {   // the lane waits for them
             if (!ctx->fork_ev3) H2_LANES(hipEventCreateWithFlags(&ctx->fork_ev3, hipEventDisableTiming));
             H2_LANES(hipEventRecord(ctx->fork_ev3, ctx->stream));
             H2_LANES(hipStreamWaitEvent(c->stream, ctx->fork_ev3, 0));
         }
         const h2hip_bases *gb = bases_of(j0);
+        hipEvent_t sorted_ev = nullptr;   // what this group's MSM records behind its scatter
         if ((ctx->msm_stagger_sorts > 0 || (ctx->msm_stagger_sorts < 0 && NL == 2)) && precomp && fuse == 1 && g < (size_t)NL) {   // the first round of columns: lane g sorts behind lane g - 1's sort
             if (g > 0 && ctx->lane[g - 1]->sorted_ev) H2_LANES(hipStreamWaitEvent(c->stream, ctx->lane[g - 1]->sorted_ev, 0));
             if (g + 1 < (size_t)NL && g + 1 < ngroups) {
                 if (!c->sorted_ev) H2_LANES(hipEventCreateWithFlags(&c->sorted_ev, hipEventDisableTiming));
-                c->sorted_arm = true;
+                sorted_ev = c->sorted_ev;
             }
         }
         for (size_t j = j0; j < j0 + gsize; ++j) {
@@ -818,7 +815,7 @@ static int msm_batch_impl(h2hip_ctx *ctx, const h2hip_bases *bases, const h2hip_
         char *outbuf = nullptr;
         H2_LANES_RC(ws_reserve(c, h2hip_ctx::WS_OUT, sizeof(XYZZ) * MSM_MAX_COLS, (void **)&outbuf));
         H2_LANES_RC(msm_run_cols(c, gb, (const Fr *const *)(scalars_dev + j0), (uint32_t)gsize, n, (XYZZ *)outbuf,
-                                 deferred ? all_buckets + keys_per_col * j0 : nullptr, buckets_zeroed));
+                                 deferred ? all_buckets + keys_per_col * j0 : nullptr, buckets_zeroed, sorted_ev));
         if (!deferred) {   // the group's results, one lane each, into their slots of the batch's result array
             prof_begin(c, "point_finish_kernel");
             hipLaunchKernelGGL(point_finish_slot_kernel, dim3((uint32_t)gsize), dim3(64), 0, c->stream, (const XYZZ *)outbuf,
@@ -827,7 +824,7 @@ static int msm_batch_impl(h2hip_ctx *ctx, const h2hip_bases *bases, const h2hip_
         }
         H2_LANES(hipGetLastError());
     }
-    if (mid_hook) H2_LANES_RC(run_mid());   // (no column behind msm_mid_after: the hook still runs, before the join)
+    if (mid_pending) H2_LANES_RC(run_mid());   // (no column behind mid_after: the hook still runs, before the join)
     for (int l = 0; l < NL; ++l) {
         H2_HIPCHK(hipEventRecord(ctx->lane_ev[l], ctx->lane[l]->stream));
         H2_HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->lane_ev[l], 0));
@@ -838,12 +835,10 @@ static int msm_batch_impl(h2hip_ctx *ctx, const h2hip_bases *bases, const h2hip_
     // profiles/archive/r04_timeline_k19.md: issued after the tail and the result copy had been queued, the side transforms started 20 us after that
     // copy FINISHED — the runtime resolved the cross-stream wait against what the stream held at the time of the wait, not of the record)
     int hook_rc = H2HIP_OK;
-    if (ctx->msm_tail_hook) {
-        std::function<int(hipEvent_t)> tail_hook;
-        tail_hook.swap(ctx->msm_tail_hook);
+    if (hk.tail) {
         if (!ctx->tail_ev) H2_HIPCHK(hipEventCreateWithFlags(&ctx->tail_ev, hipEventDisableTiming));
         H2_HIPCHK(hipEventRecord(ctx->tail_ev, ctx->stream));
-        hook_rc = tail_hook(ctx->tail_ev);
+        hook_rc = hk.tail(ctx->tail_ev);
     }
     if (deferred) {   // one bucket reduction per 64 columns, on the caller's stream
         XYZZ *sums = nullptr;
@@ -862,26 +857,27 @@ static int msm_batch_impl(h2hip_ctx *ctx, const h2hip_bases *bases, const h2hip_
     // (the hook works on the last lane's): a fill that waits for the reduction must not sit in front of that work in a shared hardware queue
     if (deferred) H2_CHK(buckets_clean_after_use(ctx, 1, all_buckets, sizeof(XYZZ29) * keys_per_col * count, ctx->clean_on_lane ? ctx->lane[0]->stream : nullptr));
     H2_CHK(sync_results(ctx, out_host, results, psz * count));   // the commitments come back (r05: through the host-mapped flag, no runtime wait)
-    H2_CHK(hook_rc);
-    return H2HIP_OK;   // (the lanes' kernel timers are folded into this context's table when it is read: prof_collect_all)
+    return hook_rc;   // (the lanes' kernel timers are folded into this context's table when it is read: prof_collect_all)
 }
+}  // namespace h2
+extern "C" {
 
 int h2hip_msm_g1_batch_dev(h2hip_ctx *ctx, const h2hip_bases *bases, const void *const *scalars_dev, size_t n, size_t count, int point_format,
                            void *out_host) {
     H2_DEVICE_GUARD(ctx);
-    return msm_batch_impl(ctx, bases, nullptr, scalars_dev, false, n, count, point_format, out_host);
+    return msm_batch(ctx, bases, nullptr, scalars_dev, false, n, count, point_format, out_host, nullptr);
 }
 int h2hip_msm_g1_multi_dev(h2hip_ctx *ctx, const h2hip_bases *const *bases_per_column, const void *const *scalars_dev, size_t n, size_t count,
                            int point_format, void *out_host) {
     H2_DEVICE_GUARD(ctx);
     H2_REQUIRE(ctx && (count == 0 || bases_per_column), "NULL argument");
     if (!count) return H2HIP_OK;
-    return msm_batch_impl(ctx, nullptr, bases_per_column, scalars_dev, false, n, count, point_format, out_host);
+    return msm_batch(ctx, nullptr, bases_per_column, scalars_dev, false, n, count, point_format, out_host, nullptr);
 }
 int h2hip_msm_g1_batch(h2hip_ctx *ctx, const h2hip_bases *bases, const void *const *scalars_host, size_t n, size_t count, int point_format,
                        void *out_host) {
     H2_DEVICE_GUARD(ctx);
-    return msm_batch_impl(ctx, bases, nullptr, scalars_host, true, n, count, point_format, out_host);
+    return msm_batch(ctx, bases, nullptr, scalars_host, true, n, count, point_format, out_host, nullptr);
 }
 
 int h2hip_msm_g1(h2hip_ctx *ctx, const h2hip_bases *bases, const void *scalars_host, size_t n, int point_format, void *out_host) {

@@ -897,7 +897,7 @@ int buckets_clean_after_use(h2hip_ctx *ctx, int which, void *buf, size_t bytes, 
 }
 
 int msm_run_cols(h2hip_ctx *ctx, const h2hip_bases *bases, const Fr *const *scalars, uint32_t ncols, size_t n, XYZZ *out, XYZZ29 *ext_buckets,
-                 bool ext_buckets_zeroed) {
+                 bool ext_buckets_zeroed, hipEvent_t sorted_ev) {
     H2_REQUIRE(ncols >= 1 && ncols <= MSM_MAX_COLS, "1..32 columns per fused MSM");
     H2_REQUIRE(n <= bases->n, "more scalars than resident bases");
     H2_REQUIRE(bases->pts29 != nullptr || bases->n == 0, "bases are not prepared");
@@ -1031,10 +1031,7 @@ int msm_run_cols(h2hip_ctx *ctx, const h2hip_bases *bases, const Fr *const *scal
                        (const uint32_t *)bhist, sval);
     prof_end(ctx);
     H2_HIPCHK(hipGetLastError());
-    if (ctx->sorted_arm) {   // (msm_stagger_sorts) the next lane's sort may start
-        ctx->sorted_arm = false;
-        H2_HIPCHK(hipEventRecord(ctx->sorted_ev, st));
-    }
+    if (sorted_ev) H2_HIPCHK(hipEventRecord(sorted_ev, st));   // (msm_stagger_sorts) the next lane's sort may start
 
     // ---- accumulate (+ wave-level merge), then the block-level merge of the wave-boundary partials
     {

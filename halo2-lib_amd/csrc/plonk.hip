@@ -243,8 +243,6 @@ static int check_selectors_stay_apart(const Shape &sh, const void *const *fixed_
 
 static int keygen_common(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const h2hip_bases *g, const h2hip_bases *g_lagrange, const void *const *fixed_host,
                          const uint32_t *copies, size_t ncopies, int rc, h2hip_plonk_pk **out);
-// the MSM hooks of a proof capture its ProofRun: never leave one on the context once the proof has returned
-static void clear_proof_hooks(h2hip_ctx *ctx) { ctx->msm_tail_hook = nullptr, ctx->msm_mid_hook = nullptr, ctx->msm_col_hook = nullptr; }
 static void sync_proof_streams(h2hip_ctx *ctx, h2hip_plonk_pk *pk) {
     if (pk->copy_stream) hipStreamSynchronize(pk->copy_stream);
     if (pk->side) hipStreamSynchronize(pk->side->stream);
@@ -322,7 +320,6 @@ static int keygen_common(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const h2hip_bases *
             pk->transcript_repr = Fr::zero();
             const int wrc = create_proof_impl(ctx, pk, adv.data(), true, inst.data(), inst_len.data(), h2hip_chacha_rng_fill, &wr, throwaway, nullptr);
             pk->transcript_repr = saved;
-            clear_proof_hooks(ctx);
             sync_proof_streams(ctx, pk);
             if (wrc != H2HIP_OK) set_error("");   // not the caller's error
         }
@@ -473,7 +470,6 @@ static int create_proof_entry(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *co
     }
     std::vector<uint8_t> proof;
     int rc = create_proof_impl(ctx, pk, advice, advice_on_device != 0, instances_host, instance_lens, rng, rng_user, proof, stage_ms, witness);
-    clear_proof_hooks(ctx);
     if (pk->side && ctx->profiling && ctx->prof_filter.empty()) prof_fold_child(ctx, pk->side);   // (the lanes' timers are folded when the table is read)
     if (rc != H2HIP_OK) {
         sync_proof_streams(ctx, pk);   // nothing of the failed proof may still run on buffers that go back to the pool

@@ -337,7 +337,7 @@ static inline G1Affine jacobian_to_affine(const G1Jac &p) {
     return r;
 }
 
-// plonk_prove.hip: one proof.  The hooks it leaves on the context capture the run: the caller clears them after every proof.
+// plonk_prove.hip: one proof.  Nothing of the run stays on the context: its callbacks into the batch MSM are arguments of the commitment calls.
 int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, bool advice_on_device, const void *const *instances,
                       const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, std::vector<uint8_t> &proof_out, double *stage_ms,
                       const h2hip_phase_witness *witness = nullptr);

@@ -271,9 +271,10 @@ struct Commit {
     h2hip_plonk_pk *pk;
     ShardLink *link;
     Transcript *tr;
-    // `bases_per_col`: empty = all columns over `bases`
+    // `bases_per_col`: empty = all columns over `bases`.  `hooks` (optional; BatchMsmHooks, internal.h): every hook given to a commitment that
+    // succeeds has run exactly once when it returns
     int points_multi(const h2hip_bases *bases, const std::vector<const h2hip_bases *> &bases_per_col, const std::vector<const void *> &cols, size_t len,
-                     std::vector<G1Affine> &pts) {
+                     std::vector<G1Affine> &pts, const BatchMsmHooks *hooks = nullptr) {
         std::vector<G1Jac> jac(cols.size());
         const bool sharded = link->on();
         std::vector<const h2hip_bases *> bpc(cols.size());
@@ -290,10 +291,17 @@ struct Commit {
         // (r05 ran a lone commitment — SHPLONK's W and W' — as 2 / 4 point-range parts on the batch API's lanes, co-running accumulations and shorter
         // sorts against one more join: the k = 19 proof 13.2-13.4 / 13.5-13.7 vs 13.0-13.1 ms, k = 21 51.6-52.5 vs 49.8-51.8: slower, removed —
         // profiles/r05_split_single_msm_ab.log)
-        if (cols.size() == 1)
-            H2_CHK(h2hip_msm_g1_dev(ctx, bpc[0], local[0], hi - lo, H2HIP_POINT_JACOBIAN, jac.data()));
-        else if (!cols.empty())
-            H2_CHK(h2hip_msm_g1_multi_dev(ctx, bpc.data(), local.data(), hi - lo, cols.size(), H2HIP_POINT_JACOBIAN, jac.data()));
+        if (cols.size() >= 2) {
+            H2_CHK(msm_batch(ctx, nullptr, bpc.data(), local.data(), false, hi - lo, cols.size(), H2HIP_POINT_JACOBIAN, jac.data(), hooks));
+        } else {   // the lone MSM has no lanes to join: `tail` runs behind what the main stream holds after it
+            H2_REQUIRE(!hooks || (!hooks->mid && !hooks->col), "internal: `mid` / `col` need a batch of two or more columns");
+            if (cols.size() == 1) H2_CHK(h2hip_msm_g1_dev(ctx, bpc[0], local[0], hi - lo, H2HIP_POINT_JACOBIAN, jac.data()));
+            if (hooks && hooks->tail) {
+                if (!ctx->tail_ev) H2_HIPCHK(hipEventCreateWithFlags(&ctx->tail_ev, hipEventDisableTiming));
+                H2_HIPCHK(hipEventRecord(ctx->tail_ev, ctx->stream));
+                H2_CHK(hooks->tail(ctx->tail_ev));
+            }
+        }
         pts.resize(cols.size());
         if (sharded) {
             std::vector<uint8_t> all;
@@ -321,8 +329,8 @@ struct Commit {
         for (size_t i = 0; i < jac.size(); ++i) pts[i] = jacobian_to_affine(jac[i]);
         return H2HIP_OK;
     }
-    int points(const h2hip_bases *bases, const std::vector<const void *> &cols, size_t len, std::vector<G1Affine> &pts) {
-        return points_multi(bases, std::vector<const h2hip_bases *>(), cols, len, pts);
+    int points(const h2hip_bases *bases, const std::vector<const void *> &cols, size_t len, std::vector<G1Affine> &pts, const BatchMsmHooks *hooks = nullptr) {
+        return points_multi(bases, std::vector<const h2hip_bases *>(), cols, len, pts, hooks);
     }
     int batch(const h2hip_bases *bases, const std::vector<const void *> &cols, size_t len) {   // ... each point written to the transcript
         std::vector<G1Affine> pts;
@@ -379,10 +387,10 @@ struct SideStream {
         busy = true;
         return H2HIP_OK;
     }
-    // queues `fn` on the side stream behind the batch MSM's accumulations (or, if the commitment took a path without lanes, behind what
-    // the main stream holds after it) — `arm` before the commitment, `fire_if_pending` after it
-    void arm(std::function<int()> fn, bool first_round = false) {
-        ctx->msm_tail_hook = [this, fn, first_round](hipEvent_t ev) -> int {
+    // a commitment's BatchMsmHooks::tail that queues `fn` on the side stream behind the batch MSM's accumulations (or, if the commitment took
+    // a path without lanes, behind what the main stream holds after it)
+    std::function<int(hipEvent_t)> behind_commit(std::function<int()> fn, bool first_round = false) {
+        return [this, fn, first_round](hipEvent_t ev) -> int {
             H2_CHK(pick(ctx->lane[2]));
             H2_HIPCHK(hipStreamWaitEvent(c->stream, ev, 0));
             H2_CHK(fn());
@@ -394,14 +402,6 @@ struct SideStream {
             busy = true;
             return H2HIP_OK;
         };
-    }
-    int fire_if_pending() {
-        if (!ctx->msm_tail_hook) return H2HIP_OK;
-        std::function<int(hipEvent_t)> hook;
-        hook.swap(ctx->msm_tail_hook);
-        if (!ctx->tail_ev) H2_HIPCHK(hipEventCreateWithFlags(&ctx->tail_ev, hipEventDisableTiming));
-        H2_HIPCHK(hipEventRecord(ctx->tail_ev, ctx->stream));
-        return hook(ctx->tail_ev);
     }
     int join() {   // the main stream continues after everything queued on the side stream
         if (busy) H2_HIPCHK(hipStreamWaitEvent(ctx->stream, pk->side_ev, 0));
@@ -629,7 +629,7 @@ struct ProofRun {
         for (uint32_t c = 0; c < sh.num_advice_total; ++c) {
             H2_REQUIRE(advice[c], "NULL advice column");
             H2_CHK(sc.take(n, &adv[c].lagrange));
-            // r06: host-resident columns behind the first are uploaded INSIDE round 1's commitment batch (msm_col_hook in round1_base), each right before its
+            // r06: host-resident columns behind the first are uploaded INSIDE round 1's commitment batch (`col` in round1_base), each right before its
             // MSM is queued: the pageable copy blocks the host, not the GPU, which is working on the columns before it by then
             if (!(lazy_upload && c >= 1)) H2_HIPCHK(hipMemcpyAsync(adv[c].lagrange, advice[c], sizeof(Fr) * u, kind, st));
             const Fr *tail = stage.draw(n - u);
@@ -746,11 +746,12 @@ struct ProofRun {
     // values: the permuted columns are computed before the advice commitments are out, and all of this round's and the next round's
     // commitments go through ONE batched MSM call (the transcript still sees them in upstream's order)
     int round1_base(const std::vector<const void *> &cols) {
+        BatchMsmHooks hooks;
         // r04: the ADVICE columns' commitments do not wait for the permutation — the batch MSM queues them on its lanes first, then calls the
-        // permutation (on this stream), then queues the permuted columns behind it (msm_mid_hook): the first accumulation starts ~0.3 ms earlier
+        // permutation (on this stream), then queues the permuted columns behind it (`mid`): the first accumulation starts ~0.3 ms earlier
         if (overlap && ctx->plonk_permute_in_commit && !lks.empty() && !adv.empty()) {
-            ctx->msm_mid_hook = [this]() -> int { return permute_lookups(); };
-            ctx->msm_mid_after = adv.size();
+            hooks.mid = [this]() -> int { return permute_lookups(); };
+            hooks.mid_after = adv.size();
         } else {
             H2_CHK(permute_lookups());
         }
@@ -758,17 +759,15 @@ struct ProofRun {
         std::vector<G1Affine> pts;
         if (overlap) {   // this round's columns -> coefficient and extended form, next to the commitments' reduction and the grand products
             r1.src = lagrange_of(first_round_columns());
-            side.arm([this]() -> int { return side.transforms(r1); }, true);
+            hooks.tail = side.behind_commit([this]() -> int { return side.transforms(r1); }, true);
         }
         if (lazy_upload) {
-            ctx->msm_col_hook = [this](size_t j) -> int {
+            hooks.col = [this](size_t j) -> int {
                 if (j >= 1 && j < adv.size()) H2_HIPCHK(hipMemcpyAsync(adv[j].lagrange, advice[j], sizeof(Fr) * u, hipMemcpyHostToDevice, st));
                 return H2HIP_OK;
             };
         }
-        H2_CHK(commit.points(pk->g_lagrange, cols, n, pts));
-        H2_REQUIRE(!ctx->msm_mid_hook && !ctx->msm_col_hook, "internal: the commitment round did not run the lookup permutation / the advice uploads");
-        H2_CHK(side.fire_if_pending());
+        H2_CHK(commit.points(pk->g_lagrange, cols, n, pts, &hooks));
         for (size_t i = 0; i < adv.size(); ++i) H2_CHK(tr.write_point(pts[i]));
         theta = tr.squeeze_challenge();   // (BaseConfig: every lookup is a single expression, theta does not enter the values)
         for (size_t i = adv.size(); i < pts.size(); ++i) H2_CHK(tr.write_point(pts[i]));
@@ -1148,6 +1147,7 @@ struct ProofRun {
         cols.push_back(random_poly);
         bases.push_back(pk->g);
         std::vector<G1Affine> pts;
+        BatchMsmHooks hooks;
         if (overlap) {   // the grand products' coefficient and extended forms do not depend on y: next to this round's reduction
             r3.src = zs;
             if (ctx->plonk_early_intt) {
@@ -1157,12 +1157,11 @@ struct ProofRun {
                 H2_CHK(side.wait_for_main());
                 H2_CHK(side.to_coeff(r3));
                 H2_CHK(side.queued());
-                side.arm([this]() -> int { return side.to_ext(r3); });
+                hooks.tail = side.behind_commit([this]() -> int { return side.to_ext(r3); });
             } else
-                side.arm([this]() -> int { return side.transforms(r3); });
+                hooks.tail = side.behind_commit([this]() -> int { return side.transforms(r3); });
         }
-        H2_CHK(commit.points_multi(nullptr, bases, cols, n, pts));
-        H2_CHK(side.fire_if_pending());
+        H2_CHK(commit.points_multi(nullptr, bases, cols, n, pts, &hooks));
         for (size_t i = 0; i + 1 < pts.size(); ++i) H2_CHK(tr.write_point(pts[i]));
         laps.lap(ST_COMMIT_PRODUCTS);
         H2_CHK(tr.write_point(pts.back()));   // the random polynomial's commitment

@@ -243,6 +243,51 @@ def test_create_proof_schedule_switches_emulated():
         ctx.close()
 
 
+def _failed_commitment_round_leaves_context_usable(ctx, shape, precompute):
+    """a proof that fails inside the commitment round's callback — a value of the dedicated lookup-advice column is missing from the table,
+    which the lookup permutation reports while it runs INSIDE round 1's batch MSM (plonk_permute_in_commit, the default) — leaves the context
+    and the key usable: the next proof gives the bytes of the one before.  Then the same with the permutation in front of the commitment."""
+    sh, kzg, params, circ, gpk = _setup(ctx, *shape, 1, 1, precompute)
+    try:
+        rng = lambda: PreDrawnRng(_rng_budget(sh), 1)
+        first = PL.create_proof(gpk, circ.advice, circ.instances, rng())
+        missing = [np.array(c) for c in circ.advice]
+        missing[sh.lookup_advice[0]][0] = O.ints_to_limbs([(1 << sh.lookup_bits) + 5], R)[0]
+        old = ctx.get_param("plonk_permute_in_commit")
+        assert old == 1
+        try:
+            for in_commit in (1, 0):
+                ctx.set_param("plonk_permute_in_commit", in_commit)
+                with pytest.raises(H.H2HipError):
+                    PL.create_proof(gpk, missing, circ.instances, rng())
+                assert PL.create_proof(gpk, circ.advice, circ.instances, rng()) == first, in_commit
+        finally:
+            ctx.set_param("plonk_permute_in_commit", old)
+    finally:
+        gpk.free()
+        kzg.free()
+
+
+def test_failed_commitment_round_leaves_context_usable_emulated():
+    """(two advice columns: the lazy upload's per-column callback is engaged too)"""
+    from tests.emu_util import emu_context
+
+    ctx = emu_context()
+    try:
+        _failed_commitment_round_leaves_context_usable(ctx, (6, 2, 1, 1, 0, 4), False)
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_failed_commitment_round_leaves_context_usable_gpu():
+    ctx = H.Context()
+    try:
+        _failed_commitment_round_leaves_context_usable(ctx, (9, 2, 1, 1, 0, 8), True)
+    finally:
+        ctx.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(9, 1, 1, 1, 0, 8), (12, 1, 1, 1, 1, 11), (12, 2, 1, 1, 1, 11), (13, 4, 2, 2, 2, 10), (10, 1, 0, 1, 0, None),
                                    (11, 20, 4, 2, 1, 10), (9, 1, 1, 0, 0, 7), (9, 2, 0, 0, 1, None), (10, 1, 2, 1, 0, 8)])   # (11, 20, 4, ...): a wide shape like the reference's low-k configurations (13 chained permutation sets); then: no constants column, no range chip with an instance column, one advice column with num_lookup_advice > 1
