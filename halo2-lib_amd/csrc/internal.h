@@ -261,6 +261,19 @@ struct alignas(128) TableEntry29 {
 };
 static_assert(sizeof(TableEntry29) == 128, "one entry per 128-byte line");
 int ws_reserve(h2hip_ctx *ctx, int slot, size_t bytes, void **out);
+// workgroups of 256 lanes for n elements at per_lane elements each, at most eight per CU (the kernels stride over the rest)
+inline uint32_t grid_for(const h2hip_ctx *ctx, size_t n, size_t per_lane = 1) {
+    size_t blocks = (n / per_lane + 255) / 256, cap = (size_t)ctx->num_cus * 8;
+    if (blocks > cap) blocks = cap;
+    return (uint32_t)(blocks ? blocks : 1);
+}
+inline Fr ld_fr(const void *p) {   // a field element out of the caller's (possibly unaligned) memory
+    Fr r;
+    memcpy(&r, p, sizeof(Fr));
+    return r;
+}
+struct OmegaTable;   // fr29.cuh
+int ntt_pow_table(h2hip_ctx *ctx, uint32_t log_n, const Fr &omega, OmegaTable *out);   // ntt.hip: the cached (log_n, omega) power table for pow_lookup
 
 // RAII-less kernel timer: prof_begin/prof_end bracket one launch with events when ctx->profiling.
 void prof_begin(h2hip_ctx *ctx, const char *name);

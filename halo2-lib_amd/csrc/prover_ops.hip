@@ -8,39 +8,9 @@
 
 namespace h2 {
 
-int ntt_pow_table(h2hip_ctx *ctx, uint32_t log_n, const Fr &omega, OmegaTable *out);   // ntt.hip
-
 constexpr int PP_MAX_COLS = 8;
-struct PermProductArgs {
-    const Fr *cols[PP_MAX_COLS], *sigmas[PP_MAX_COLS];
-    uint32_t ncols;
-    Fr beta, gamma, delta;
-    Fr x0;      // beta * delta^(first column index of the set): the identity-permutation term at row 0
-    Fr omega;   // row generator
-    Fr xstep;   // omega^(grid stride)
-};
-// num[i] = prod_j (v_j[i] + beta*delta^(c0+j)*omega^i + gamma),  den[i] = prod_j (v_j[i] + beta*sigma_j[i] + gamma),  i < rows
-__global__ __launch_bounds__(256) void perm_product_terms_kernel(Fr *__restrict__ num, Fr *__restrict__ den, PermProductArgs g, size_t rows) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i0 >= rows) return;
-    Fr xbase = fe_mul(g.x0, fe_pow_u64(g.omega, (uint64_t)i0));
-    for (size_t i = i0; i < rows; i += stride, xbase = fe_mul(xbase, g.xstep)) {
-        Fr nu = Fr::one(), de = Fr::one(), xterm = xbase;
-        for (uint32_t j = 0; j < g.ncols; ++j) {
-            Fr v = g.cols[j][i];
-            Fr a = fe_add(fe_add(v, xterm), g.gamma);
-            Fr b = fe_add(fe_add(v, fe_mul(g.beta, g.sigmas[j][i])), g.gamma);
-            nu = j ? fe_mul(nu, a) : a;
-            de = j ? fe_mul(de, b) : b;
-            xterm = fe_mul(xterm, g.delta);
-        }
-        num[i] = nu;
-        den[i] = de;
-    }
-}
-
-// The same factors for SEVERAL consecutive sets per launch (a wide shape has ~80 sets of three 2^14-row columns): set s of the launch owns
+// num[i] = prod_j (v_j[i] + beta*delta^(c0+j)*omega^i + gamma),  den[i] = prod_j (v_j[i] + beta*sigma_j[i] + gamma),  i < rows,
+// for SEVERAL consecutive sets per launch (a wide shape has ~80 sets of three 2^14-row columns): set s of the launch owns
 // columns [s*chunk, (s+1)*chunk) of the launch's column table and rows [s*rows, (s+1)*rows) of num / den; omega^i is computed once per row.
 constexpr uint32_t PP_BATCH_COLS = 64;
 struct PermProductBatchArgs {
@@ -123,17 +93,6 @@ struct SmallPoly {
 __global__ void fr_sub_low_kernel(Fr *__restrict__ y, SmallPoly p, uint32_t m) {
     uint32_t i = threadIdx.x;
     if (i < m) y[i] = fe_sub(y[i], p.c[i]);
-}
-
-static uint32_t grid_rows(h2hip_ctx *ctx, size_t n, size_t per_lane) {
-    size_t blocks = (n / per_lane + 255) / 256, cap = (size_t)ctx->num_cus * 8;
-    if (blocks > cap) blocks = cap;
-    return (uint32_t)(blocks ? blocks : 1);
-}
-static Fr ld(const void *p) {
-    Fr r;
-    memcpy(&r, p, sizeof(Fr));
-    return r;
 }
 
 }  // namespace h2
@@ -223,56 +182,17 @@ __global__ __launch_bounds__(256) void coset_combine_kernel(Fr *__restrict__ out
     });
 }
 
-extern "C" {
-
-int h2hip_permutation_product_terms_dev(h2hip_ctx *ctx, void *num_dev, void *den_dev, const void *const *cols_dev, const void *const *sigmas_dev,
-                                        uint32_t ncols, uint32_t first_col_index, size_t rows, const void *beta, const void *gamma, const void *delta,
-                                        const void *omega) {
-    H2_DEVICE_GUARD(ctx);
-    H2_REQUIRE(ctx && beta && gamma && delta && omega && cols_dev && sigmas_dev && (rows == 0 || (num_dev && den_dev)), "NULL argument");
-    H2_REQUIRE(ncols >= 1 && ncols <= PP_MAX_COLS, "1..8 columns per permutation set");
-    if (!rows) return H2HIP_OK;
-    PermProductArgs g;
-    memset(&g, 0, sizeof(g));
-    for (uint32_t j = 0; j < ncols; ++j) {
-        H2_REQUIRE(cols_dev[j] && sigmas_dev[j], "NULL column");
-        g.cols[j] = (const Fr *)cols_dev[j];
-        g.sigmas[j] = (const Fr *)sigmas_dev[j];
-    }
-    g.ncols = ncols;
-    g.beta = ld(beta); g.gamma = ld(gamma); g.delta = ld(delta); g.omega = ld(omega);
-    g.x0 = fe_mul(g.beta, fe_pow_u64(g.delta, first_col_index));
-    uint32_t grid = grid_rows(ctx, rows, 4);
-    g.xstep = fe_pow_u64(g.omega, (uint64_t)grid * 256);
-    prof_begin(ctx, "perm_product_terms_kernel");
-    hipLaunchKernelGGL(perm_product_terms_kernel, dim3(grid), dim3(256), 0, ctx->stream, (Fr *)num_dev, (Fr *)den_dev, g, rows);
-    prof_end(ctx);
-    H2_HIPCHK(hipGetLastError());
-    return H2HIP_OK;
-}
-
-// every set of the permutation argument: set s owns columns [s*chunk_len, (s+1)*chunk_len) and rows [s*rows, (s+1)*rows) of num / den
-int h2hip_permutation_product_terms_sets_dev(h2hip_ctx *ctx, void *num_dev, void *den_dev, const void *const *cols_dev, const void *const *sigmas_dev,
-                                             uint32_t num_columns, uint32_t chunk_len, size_t rows, const void *beta, const void *gamma,
-                                             const void *delta, const void *omega) {
-    return h2hip_permutation_product_terms_rows_dev(ctx, num_dev, den_dev, cols_dev, sigmas_dev, num_columns, chunk_len, 0, rows, beta, gamma, delta, omega);
-}
-// the same for the ROW RANGE [row0, row0 + rows) of the columns (the multi-GPU prover: a rank forms the factors of its rows only); num / den: set s
-// at [s * rows, (s + 1) * rows)
-int h2hip_permutation_product_terms_rows_dev(h2hip_ctx *ctx, void *num_dev, void *den_dev, const void *const *cols_dev, const void *const *sigmas_dev,
-                                             uint32_t num_columns, uint32_t chunk_len, size_t row0, size_t rows, const void *beta, const void *gamma,
-                                             const void *delta, const void *omega) {
-    H2_DEVICE_GUARD(ctx);
-    H2_REQUIRE(ctx && beta && gamma && delta && omega && (num_columns == 0 || (cols_dev && sigmas_dev)) && (rows == 0 || num_columns == 0 || (num_dev && den_dev)),
-               "NULL argument");
-    H2_REQUIRE(chunk_len >= 1 && chunk_len <= PP_MAX_COLS, "1..8 columns per permutation set");
-    if (!rows || !num_columns) return H2HIP_OK;
-    for (uint32_t c = 0; c < num_columns; ++c) H2_REQUIRE(cols_dev[c] && sigmas_dev[c], "NULL column");
+namespace h2 {
+// the factors of every set over columns [0, num_columns) — set s owns columns [s*chunk_len, (s+1)*chunk_len), the first of them has index
+// first_col_index in the permutation argument — for the rows [row0, row0 + rows): whole sets of up to PP_BATCH_COLS columns per launch
+static int perm_product_terms_run(h2hip_ctx *ctx, Fr *num, Fr *den, const void *const *cols_dev, const void *const *sigmas_dev, uint32_t num_columns,
+                                  uint32_t chunk_len, uint32_t first_col_index, size_t row0, size_t rows, const void *beta, const void *gamma,
+                                  const void *delta, const void *omega) {
     PermProductBatchArgs g;
     memset(&g, 0, sizeof(g));
     g.chunk = chunk_len;
-    g.beta = ld(beta); g.gamma = ld(gamma); g.delta = ld(delta); g.omega = ld(omega);
-    const uint32_t grid = grid_rows(ctx, rows, rows >= ((size_t)1 << 16) ? 4 : 1);   // long columns: four rows per lane amortise the omega^i start-up
+    g.beta = ld_fr(beta); g.gamma = ld_fr(gamma); g.delta = ld_fr(delta); g.omega = ld_fr(omega);
+    const uint32_t grid = grid_for(ctx, rows, rows >= ((size_t)1 << 16) ? 4 : 1);   // long columns: four rows per lane amortise the omega^i start-up
     g.xstep = fe_pow_u64(g.omega, (uint64_t)grid * 256);
     OmegaTable pw = {nullptr, nullptr, 0};
     if (ctx->quotient_29) {
@@ -281,7 +201,7 @@ int h2hip_permutation_product_terms_rows_dev(h2hip_ctx *ctx, void *num_dev, void
         H2_CHK(ntt_pow_table(ctx, log_rows, g.omega, &pw));
     }
     const uint32_t per_launch = PP_BATCH_COLS / chunk_len * chunk_len;   // whole sets
-    Fr x0 = fe_mul(g.beta, fe_pow_u64(g.omega, (uint64_t)row0));
+    Fr x0 = fe_mul(fe_mul(g.beta, fe_pow_u64(g.delta, first_col_index)), fe_pow_u64(g.omega, (uint64_t)row0));
     for (uint32_t c0 = 0; c0 < num_columns; c0 += per_launch) {
         g.ncols = num_columns - c0 < per_launch ? num_columns - c0 : per_launch;
         g.x0 = x0;
@@ -301,16 +221,50 @@ int h2hip_permutation_product_terms_rows_dev(h2hip_ctx *ctx, void *num_dev, void
             k29.gamma32 = r29_load(fe_x32(g.gamma));
             k29.one = r29_load(Fr::one());
             k29.pw = pw;
-            hipLaunchKernelGGL(perm_product_terms_batch29_kernel, dim3(grid), dim3(256), 0, ctx->stream, (Fr *)num_dev + first_set * rows,
-                               (Fr *)den_dev + first_set * rows, g, k29, rows);
+            hipLaunchKernelGGL(perm_product_terms_batch29_kernel, dim3(grid), dim3(256), 0, ctx->stream, num + first_set * rows, den + first_set * rows, g, k29,
+                               rows);
         } else {
-            hipLaunchKernelGGL(perm_product_terms_batch_kernel, dim3(grid), dim3(256), 0, ctx->stream, (Fr *)num_dev + first_set * rows,
-                               (Fr *)den_dev + first_set * rows, g, rows);
+            hipLaunchKernelGGL(perm_product_terms_batch_kernel, dim3(grid), dim3(256), 0, ctx->stream, num + first_set * rows, den + first_set * rows, g, rows);
         }
         prof_end(ctx);
     }
     H2_HIPCHK(hipGetLastError());
     return H2HIP_OK;
+}
+}  // namespace h2
+
+extern "C" {
+
+// one set: its columns have the indices first_col_index ... in the permutation argument
+int h2hip_permutation_product_terms_dev(h2hip_ctx *ctx, void *num_dev, void *den_dev, const void *const *cols_dev, const void *const *sigmas_dev,
+                                        uint32_t ncols, uint32_t first_col_index, size_t rows, const void *beta, const void *gamma, const void *delta,
+                                        const void *omega) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && beta && gamma && delta && omega && cols_dev && sigmas_dev && (rows == 0 || (num_dev && den_dev)), "NULL argument");
+    H2_REQUIRE(ncols >= 1 && ncols <= PP_MAX_COLS, "1..8 columns per permutation set");
+    if (!rows) return H2HIP_OK;
+    for (uint32_t j = 0; j < ncols; ++j) H2_REQUIRE(cols_dev[j] && sigmas_dev[j], "NULL column");
+    return perm_product_terms_run(ctx, (Fr *)num_dev, (Fr *)den_dev, cols_dev, sigmas_dev, ncols, ncols, first_col_index, 0, rows, beta, gamma, delta, omega);
+}
+
+// every set of the permutation argument: set s owns columns [s*chunk_len, (s+1)*chunk_len) and rows [s*rows, (s+1)*rows) of num / den
+int h2hip_permutation_product_terms_sets_dev(h2hip_ctx *ctx, void *num_dev, void *den_dev, const void *const *cols_dev, const void *const *sigmas_dev,
+                                             uint32_t num_columns, uint32_t chunk_len, size_t rows, const void *beta, const void *gamma,
+                                             const void *delta, const void *omega) {
+    return h2hip_permutation_product_terms_rows_dev(ctx, num_dev, den_dev, cols_dev, sigmas_dev, num_columns, chunk_len, 0, rows, beta, gamma, delta, omega);
+}
+// the same for the ROW RANGE [row0, row0 + rows) of the columns (the multi-GPU prover: a rank forms the factors of its rows only); num / den: set s
+// at [s * rows, (s + 1) * rows)
+int h2hip_permutation_product_terms_rows_dev(h2hip_ctx *ctx, void *num_dev, void *den_dev, const void *const *cols_dev, const void *const *sigmas_dev,
+                                             uint32_t num_columns, uint32_t chunk_len, size_t row0, size_t rows, const void *beta, const void *gamma,
+                                             const void *delta, const void *omega) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && beta && gamma && delta && omega && (num_columns == 0 || (cols_dev && sigmas_dev)) && (rows == 0 || num_columns == 0 || (num_dev && den_dev)),
+               "NULL argument");
+    H2_REQUIRE(chunk_len >= 1 && chunk_len <= PP_MAX_COLS, "1..8 columns per permutation set");
+    if (!rows || !num_columns) return H2HIP_OK;
+    for (uint32_t c = 0; c < num_columns; ++c) H2_REQUIRE(cols_dev[c] && sigmas_dev[c], "NULL column");
+    return perm_product_terms_run(ctx, (Fr *)num_dev, (Fr *)den_dev, cols_dev, sigmas_dev, num_columns, chunk_len, 0, row0, rows, beta, gamma, delta, omega);
 }
 
 int h2hip_lookup_product_terms_dev(h2hip_ctx *ctx, void *num_dev, void *den_dev, const void *a_dev, const void *s_dev, const void *a_perm_dev,
@@ -319,8 +273,8 @@ int h2hip_lookup_product_terms_dev(h2hip_ctx *ctx, void *num_dev, void *den_dev,
     H2_REQUIRE(ctx && beta && gamma && (rows == 0 || (num_dev && den_dev && a_dev && s_dev && a_perm_dev && s_perm_dev)), "NULL argument");
     if (!rows) return H2HIP_OK;
     prof_begin(ctx, "lookup_product_terms_kernel");
-    hipLaunchKernelGGL(lookup_product_terms_kernel, dim3(grid_rows(ctx, rows, 1)), dim3(256), 0, ctx->stream, (Fr *)num_dev, (Fr *)den_dev,
-                       (const Fr *)a_dev, (const Fr *)s_dev, (const Fr *)a_perm_dev, (const Fr *)s_perm_dev, ld(beta), ld(gamma), rows);
+    hipLaunchKernelGGL(lookup_product_terms_kernel, dim3(grid_for(ctx, rows, 1)), dim3(256), 0, ctx->stream, (Fr *)num_dev, (Fr *)den_dev,
+                       (const Fr *)a_dev, (const Fr *)s_dev, (const Fr *)a_perm_dev, (const Fr *)s_perm_dev, ld_fr(beta), ld_fr(gamma), rows);
     prof_end(ctx);
     H2_HIPCHK(hipGetLastError());
     return H2HIP_OK;
@@ -417,7 +371,7 @@ int h2hip_fr_coset_combine_dev(h2hip_ctx *ctx, void *out_dev, const void *in_dev
     CosetCombineArgs a;
     memset((void *)&a, 0, sizeof(a));
     for (uint32_t c = 0; c < C; ++c) a.slot[c] = slots[c];
-    const Fr r = ld(rho_inv), zn = ld(zeta_n_inv);
+    const Fr r = ld_fr(rho_inv), zn = ld_fr(zeta_n_inv);
     Fr p = Fr::one();
     for (uint32_t j = 0; j < C / 2; ++j) {
         a.tw[j] = p;

@@ -256,7 +256,8 @@ int h2hip_fr_grand_products_dev(h2hip_ctx *ctx, void *const *z_dev, const void *
 /* factors of ONE permutation set's grand product over rows [0, rows) (columns = the equality-enabled columns of
  * halo2-base's configs, flex_gate/mod.rs:69,124-128, range/mod.rs:104):  num[i] = prod_j (v_j[i] + beta*delta^(first_col_index+j)*omega^i
  * + gamma),  den[i] = prod_j (v_j[i] + beta*sigma_j[i] + gamma);  cols / sigmas: host arrays of ncols (<= 8) device pointers.
- * z = h2hip_fr_grand_product_dev(num, den), scaled by the previous set's last value. */
+ * z = h2hip_fr_grand_product_dev(num, den), scaled by the previous set's last value.  One set of the _sets_dev form below: the same
+ * kernels, on unsaturated limbs or saturated as the knob quotient_29 says. */
 int h2hip_permutation_product_terms_dev(h2hip_ctx *ctx, void *num_dev, void *den_dev, const void *const *cols_dev, const void *const *sigmas_dev,
                                         uint32_t ncols, uint32_t first_col_index, size_t rows, const void *beta, const void *gamma, const void *delta,
                                         const void *omega);
@@ -301,7 +302,8 @@ int h2hip_fr_kate_division_range_dev(h2hip_ctx *ctx, void *q_dev, const void *co
 
 /* ---- K6: the halo2-base custom gate's term of the quotient numerator on the extended domain:
  *      acc[i] = acc[i]*y + q[i]*(a[i] + a[i+s]*a[i+2s] - a[i+3s]), s = 2^(ext_k-k)
- *      (gate q*(a+b*c-d) at rotations 0..3, reference halo2-base/src/gates/flex_gate/mod.rs:80-91) ----- */
+ *      (gate q*(a+b*c-d) at rotations 0..3, reference halo2-base/src/gates/flex_gate/mod.rs:80-91).
+ *      One column of the _batch_dev form: the same kernels, on unsaturated limbs or saturated as the knob quotient_29 says ----- */
 int h2hip_quotient_flex_gate_dev(h2hip_ctx *ctx, void *acc_dev, const void *q_dev, const void *a_dev, uint32_t ext_k, uint32_t k,
                                  const void *y);
 
@@ -311,7 +313,8 @@ int h2hip_divide_by_vanishing_poly_dev(h2hip_ctx *ctx, void *a_dev, uint32_t ext
 
 /* Lookup argument's five identities, folded in upstream's order: l0*(1-z); l_last*(z^2-z);
  * active*(z(wX)(a'+beta)(s'+gamma) - z(a+beta)(s+gamma)); l0*(a'-s'); active*(a'-s')(a'-a'(w^-1 X)); active = 1-(l_last+l_blind).
- * All arrays: 2^ext_k extended-domain evaluations (halo2-base's lookups: halo2-base/src/gates/range/mod.rs:131-150). */
+ * All arrays: 2^ext_k extended-domain evaluations (halo2-base's lookups: halo2-base/src/gates/range/mod.rs:131-150).
+ * One lookup of h2hip_quotient_lookups_dev: the same kernels, on unsaturated limbs or saturated as the knob quotient_29 says. */
 int h2hip_quotient_lookup_dev(h2hip_ctx *ctx, void *acc_dev, const void *z_dev, const void *a_dev, const void *s_dev, const void *a_perm_dev,
                               const void *s_perm_dev, const void *l0_dev, const void *l_last_dev, const void *l_blind_dev, uint32_t ext_k,
                               uint32_t k, const void *beta, const void *gamma, const void *y);

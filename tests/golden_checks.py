@@ -105,38 +105,51 @@ def check_prover_steps(ctx, n, seed=5):
     got = to_i(ctx.assigned_resolve(num, den))
     ni, di = to_i(num), to_i(den)
     assert got == [a * (O.inv_mod(d, R) if d else 0) % R for a, d in zip(ni, di)]
-    # permutation set factors
+    # permutation set factors, on unsaturated limbs (the default) and in saturated arithmetic
     beta, gamma = [int(v) for v in g.integers(1, 1 << 62, size=2)]
     omega = O.omega_for(max(1, (n - 1).bit_length()))
+    wpows = [1] * n
+    for i in range(1, n):
+        wpows[i] = wpows[i - 1] * omega % R
+
+    def factors(col, sig, index):   # one column's factors of num / den, the column having `index` in the permutation argument
+        bd = beta * pow(O.DELTA, index, R) % R
+        return [(c + bd * w + gamma) % R for c, w in zip(col, wpows)], [(c + beta * s_ + gamma) % R for c, s_ in zip(col, sig)]
+
+    def set_factors(fs):            # the products over a set's columns, as limbs
+        wn, wd = list(fs[0][0]), list(fs[0][1])
+        for fn, fd in fs[1:]:
+            wn, wd = [x * y_ % R for x, y_ in zip(wn, fn)], [x * y_ % R for x, y_ in zip(wd, fd)]
+        return fr(wn), fr(wd)
+
     cols, sigs = [rand_fr(n, seed + 10 + j) for j in range(3)], [rand_fr(n, seed + 20 + j) for j in range(3)]
     first = 2
-    gn, gd = ctx.permutation_product_terms(cols, sigs, first, fr([beta]), fr([gamma]), fr([O.DELTA]), fr([omega]))
-    ci, si = [to_i(c) for c in cols], [to_i(c) for c in sigs]
-    wn, wd, wpow = [], [], 1
-    for i in range(n):
-        a = b = 1
-        for j in range(3):
-            a = a * (ci[j][i] + beta * pow(O.DELTA, first + j, R) % R * wpow + gamma) % R
-            b = b * (ci[j][i] + beta * si[j][i] + gamma) % R
-        wn.append(a)
-        wd.append(b)
-        wpow = wpow * omega % R
-    assert to_i(gn) == wn and to_i(gd) == wd
+    wn, wd = set_factors([factors(to_i(cols[j]), to_i(sigs[j]), first + j) for j in range(3)])
     # all sets at once (chunks of 3 and 2 columns, a ragged last set; 70 columns cross the 64-column launch boundary)
     many_c = [rand_fr(n, seed + 300 + j) for j in range(70 if n <= 64 else 7)]
     many_s = [rand_fr(n, seed + 400 + j) for j in range(len(many_c))]
-    for chunk in (3, 2):
-        nums, dens = ctx.permutation_product_terms_sets(many_c, many_s, chunk, fr([beta]), fr([gamma]), fr([O.DELTA]), fr([omega]))
-        for si in range(len(nums)):
-            c0, c1 = si * chunk, min((si + 1) * chunk, len(many_c))
-            wn1, wd1 = ctx.permutation_product_terms(many_c[c0:c1], many_s[c0:c1], c0, fr([beta]), fr([gamma]), fr([O.DELTA]), fr([omega]))
-            assert np.array_equal(nums[si], wn1) and np.array_equal(dens[si], wd1), (chunk, si)
-        # a row range of the same columns (the sharded prover's form) = those rows of the whole-column factors
-        if n >= 5:
-            r0, rn = n // 3, n - n // 3 - 1
-            pn, pd = ctx.permutation_product_terms_sets(many_c, many_s, chunk, fr([beta]), fr([gamma]), fr([O.DELTA]), fr([omega]), row0=r0, rows=rn)
-            for si in range(len(nums)):
-                assert np.array_equal(pn[si], nums[si][r0:r0 + rn]) and np.array_equal(pd[si], dens[si][r0:r0 + rn]), (chunk, si)
+    many_f = [factors(to_i(many_c[j]), to_i(many_s[j]), j) for j in range(len(many_c))]
+    many_w = {chunk: [set_factors(many_f[c0:c0 + chunk]) for c0 in range(0, len(many_c), chunk)] for chunk in (3, 2)}   # big-int, first = c0
+    for q29 in (1, 0):
+        ctx.set_param("quotient_29", q29)
+        try:
+            gn, gd = ctx.permutation_product_terms(cols, sigs, first, fr([beta]), fr([gamma]), fr([O.DELTA]), fr([omega]))
+            assert np.array_equal(gn, wn) and np.array_equal(gd, wd), q29
+            for chunk in (3, 2):
+                nums, dens = ctx.permutation_product_terms_sets(many_c, many_s, chunk, fr([beta]), fr([gamma]), fr([O.DELTA]), fr([omega]))
+                for si in range(len(nums)):
+                    c0, c1 = si * chunk, min((si + 1) * chunk, len(many_c))
+                    wn1, wd1 = ctx.permutation_product_terms(many_c[c0:c1], many_s[c0:c1], c0, fr([beta]), fr([gamma]), fr([O.DELTA]), fr([omega]))
+                    assert np.array_equal(nums[si], wn1) and np.array_equal(dens[si], wd1), (q29, chunk, si)
+                    assert np.array_equal(nums[si], many_w[chunk][si][0]) and np.array_equal(dens[si], many_w[chunk][si][1]), (q29, chunk, si)
+                # a row range of the same columns (the sharded prover's form) = those rows of the whole-column factors
+                if n >= 5:
+                    r0, rn = n // 3, n - n // 3 - 1
+                    pn, pd = ctx.permutation_product_terms_sets(many_c, many_s, chunk, fr([beta]), fr([gamma]), fr([O.DELTA]), fr([omega]), row0=r0, rows=rn)
+                    for si in range(len(nums)):
+                        assert np.array_equal(pn[si], nums[si][r0:r0 + rn]) and np.array_equal(pd[si], dens[si][r0:r0 + rn]), (q29, chunk, si)
+        finally:
+            ctx.set_param("quotient_29", 1)
     # lookup factors
     a_, s_, ap, sp = (rand_fr(n, seed + 30 + j) for j in range(4))
     gn, gd = ctx.lookup_product_terms(a_, s_, ap, sp, fr([beta]), fr([gamma]))
@@ -265,8 +278,9 @@ def check_ntt_batches(ctx, ks=(3, 11), ncols=35):
 
 def check_quotient_batches(ctx, k=3, gate_cols=67, lookups=34, perm_cols=40, chunk_len=3):
     """the batched quotient entries (64 gate columns / 32 lookups / 12 (set, term) jobs per launch: the counts cross every group boundary,
-    the last permutation set is ragged) against the one-identity-per-call entries the other tests pin to the big-int formulae, folded in
-    evaluate_h's order"""
+    the last permutation set is ragged) against the one-identity-per-call entries, folded in evaluate_h's order, and against independent
+    arithmetic folded the same way: the C oracle's field operations for the gate term, big-int formulae for the lookup and permutation terms"""
+    from oracle import c_oracle as CO
     from tests.util import rand_fr
 
     ek = k + 2
@@ -280,14 +294,30 @@ def check_quotient_batches(ctx, k=3, gate_cols=67, lookups=34, perm_cols=40, chu
     want = acc0
     for q, a in zip(qs, advs):
         want = ctx.quotient_flex_gate(want, q, a, ek, k, y)
-    assert np.array_equal(ctx.quotient_flex_gate_batch(acc0, qs, advs, ek, k, y), want)
+    got = ctx.quotient_flex_gate_batch(acc0, qs, advs, ek, k, y)
+    assert np.array_equal(got, want)
+    step = 1 << (ek - k)
+    rot = lambda v, r: np.roll(v, -r * step, axis=0)
+    yrep = np.repeat(y, ne, axis=0)
+    want = acc0
+    for q, a in zip(qs, advs):
+        want = CO.fr_add(CO.fr_mul(want, yrep), CO.fr_mul(q, CO.fr_sub(CO.fr_add(a, CO.fr_mul(rot(a, 1), rot(a, 2))), rot(a, 3))))
+    assert np.array_equal(got, want)
     assert np.array_equal(ctx.quotient_flex_gate_batch(acc0, [], [], ek, k, y), acc0)
     # lookups
     cols5 = [[col(400 + 40 * t + j) for j in range(lookups)] for t in range(5)]
     want = acc0
     for j in range(lookups):
         want = ctx.quotient_lookup(want, *[cols5[t][j] for t in range(5)], l0, l_last, l_blind, ek, k, beta, gamma, y)
-    assert np.array_equal(ctx.quotient_lookups(acc0, *cols5, l0, l_last, l_blind, ek, k, beta, gamma, y), want)
+    got = ctx.quotient_lookups(acc0, *cols5, l0, l_last, l_blind, ek, k, beta, gamma, y)
+    assert np.array_equal(got, want)
+    to_i = lambda a: O.limbs_to_ints(a, R)
+    (yi,), (bi,), (gi,) = to_i(y), to_i(beta), to_i(gamma)
+    acc0i, l0i, lli, lbi = to_i(acc0), to_i(l0), to_i(l_last), to_i(l_blind)
+    wi = acc0i
+    for j in range(lookups):
+        wi = O.quotient_lookup_terms(wi, *[to_i(cols5[t][j]) for t in range(5)], l0i, lli, lbi, step, bi, gi, yi)
+    assert to_i(got) == wi
     # permutation argument
     from halo2_lib_amd.h2hip import PERM_CHAIN, PERM_FIRST, PERM_LAST, PERM_PRODUCT
 
@@ -297,6 +327,7 @@ def check_quotient_batches(ctx, k=3, gate_cols=67, lookups=34, perm_cols=40, chu
         sets = (ncols + chunk_len - 1) // chunk_len
         zs = [col(800 + j) for j in range(sets)]
         pc, ps = [col(900 + j) for j in range(ncols)], [col(1000 + j) for j in range(ncols)]
+        zsi, pci, psi = [to_i(c) for c in zs], [to_i(c) for c in pc], [to_i(c) for c in ps]
         last_rot = -3
 
         def one(acc, si, terms):
@@ -304,18 +335,25 @@ def check_quotient_batches(ctx, k=3, gate_cols=67, lookups=34, perm_cols=40, chu
             return ctx.quotient_permutation_set(acc, zs[si], zs[si - 1] if si else None, pc[c0:c1], ps[c0:c1], c0, l0, l_last, l_blind, ek, k, terms,
                                                 last_rot, beta, gamma, delta, zeta, ext_omega, y)
 
-        want = acc0
-        if sets == 1:
-            want = one(want, 0, PERM_FIRST | PERM_LAST | PERM_PRODUCT)
-        else:
-            want = one(want, 0, PERM_FIRST)
-            want = one(want, sets - 1, PERM_LAST)
+        def one_bigint(acc, si, terms):
+            c0, c1 = si * chunk_len, min((si + 1) * chunk_len, ncols)
+            return O.quotient_permutation_set_terms(acc, zsi[si], zsi[si - 1] if si else None, pci[c0:c1], psi[c0:c1], c0, l0i, lli, lbi, step, terms,
+                                                    last_rot % (1 << k), bi, gi, O.DELTA, O.ZETA, O.omega_for(ek), yi)
+
+        def fold(acc, f):   # evaluate_h's order
+            if sets == 1:
+                return f(acc, 0, PERM_FIRST | PERM_LAST | PERM_PRODUCT)
+            acc = f(acc, 0, PERM_FIRST)
+            acc = f(acc, sets - 1, PERM_LAST)
             for si in range(1, sets):
-                want = one(want, si, PERM_CHAIN)
+                acc = f(acc, si, PERM_CHAIN)
             for si in range(sets):
-                want = one(want, si, PERM_PRODUCT)
+                acc = f(acc, si, PERM_PRODUCT)
+            return acc
+
         got = ctx.quotient_permutation_sets(acc0, zs, pc, ps, chunk_len, l0, l_last, l_blind, ek, k, last_rot, beta, gamma, delta, zeta, ext_omega, y)
-        assert np.array_equal(got, want), ncols
+        assert np.array_equal(got, fold(acc0, one)), ncols
+        assert to_i(got) == fold(acc0i, one_bigint), ncols
 
 
 def check_lookup_permute_batch(ctx, u=700, bits=6, count=5):
@@ -344,3 +382,31 @@ def check_lookup_permute_batch(ctx, u=700, bits=6, count=5):
         pass
     else:
         raise AssertionError("a value outside the table went unnoticed")
+
+
+def check_quotient_flex_gate(ctx, k, ek):
+    """the gate term of one column, on random inputs and on the edge limb patterns of tests/util.edge_fr_values (built the way
+    test_emu_kernels._quotient_identity_checks builds its columns), against the C oracle's field arithmetic"""
+    from oracle import c_oracle as CO
+    from tests.util import edge_fr_values, rand_fr
+
+    ne, step = 1 << ek, 1 << (ek - k)
+    rinv = O.inv_mod(pow(2, 256, R), R)
+    edge = [e * rinv % R for e in edge_fr_values()]
+    es = lambda seed: fr([edge[(i * (2 * seed + 1) + seed) % len(edge)] for i in range(ne)])
+    rot = lambda v, r: np.roll(v, -r * step, axis=0)
+    y = rand_fr(1, 4)
+    for acc, q, a in ((rand_fr(ne, 1), rand_fr(ne, 2), rand_fr(ne, 3)), (es(1), es(2), es(3))):
+        got = ctx.quotient_flex_gate(acc, q, a, ek, k, y)
+        gate = CO.fr_mul(q, CO.fr_sub(CO.fr_add(a, CO.fr_mul(rot(a, 1), rot(a, 2))), rot(a, 3)))
+        assert np.array_equal(got, CO.fr_add(CO.fr_mul(acc, np.repeat(y, ne, axis=0)), gate))
+
+
+def check_eval_polynomial(ctx, n):
+    """h2hip_fr_eval_polynomial_dev at the lengths where its two stages can go wrong (a tile is 256 x 32 = 8192 coefficients; from
+    8192 x 256 + 1 coefficients on a lane of the final stage handles two tile values) against the C oracle"""
+    from oracle import c_oracle as CO
+    from tests.util import rand_fr
+
+    c, x = rand_fr(n, 4242 + n % 1000), rand_fr(1, 99)
+    assert np.array_equal(ctx.fr_eval_polynomial(c, x), CO.fr_eval_polynomial(c, x))

@@ -187,6 +187,18 @@ def test_eval_polynomial_and_kate_division(ctx, n):
         assert np.array_equal(ctx.fr_kate_division(c, x), CO.fr_kate_division(c, x))
 
 
+@pytest.mark.parametrize("unsaturated", [1, 0])
+@pytest.mark.parametrize("n", [0, 1, 8191, 8192, 8193])
+def test_eval_polynomial_tile_boundaries(ctx, n, unsaturated):
+    from tests.golden_checks import check_eval_polynomial
+
+    ctx.set_param("kate_29", unsaturated)
+    try:
+        check_eval_polynomial(ctx, n)
+    finally:
+        ctx.set_param("kate_29", 1)
+
+
 @pytest.mark.parametrize("t,r_p", [(3, 57), (5, 60)])
 def test_poseidon_batch_matches_reference_kat(ctx, t, r_p):
     from oracle.poseidon import Spec
@@ -209,15 +221,15 @@ def test_poseidon_batch_matches_reference_kat(ctx, t, r_p):
     assert [O.limbs_to_ints(g, R) for g in got1] == [spec.absorb_and_permute(s, i[:1]) for s, i in zip(states[:5], inputs[:5])]
 
 
-def test_quotient_flex_gate(ctx):
-    k, ek = 6, 8
-    ne, step = 1 << ek, 1 << (ek - k)
-    acc, q, a, y = rand_fr(ne, 1), rand_fr(ne, 2), rand_fr(ne, 3), rand_fr(1, 4)
-    got = ctx.quotient_flex_gate(acc, q, a, ek, k, y)
-    rot = lambda v, r: np.roll(v, -r * step, axis=0)
-    gate = CO.fr_mul(q, CO.fr_sub(CO.fr_add(a, CO.fr_mul(rot(a, 1), rot(a, 2))), rot(a, 3)))
-    want = CO.fr_add(CO.fr_mul(acc, np.repeat(y, ne, axis=0)), gate)
-    assert np.array_equal(got, want)
+@pytest.mark.parametrize("unsaturated", [1, 0])
+def test_quotient_flex_gate(ctx, unsaturated):
+    from tests.golden_checks import check_quotient_flex_gate
+
+    ctx.set_param("quotient_29", unsaturated)
+    try:
+        check_quotient_flex_gate(ctx, 6, 8)
+    finally:
+        ctx.set_param("quotient_29", 1)
 
 
 def test_msm_batch_pipelined(ctx):

@@ -8,7 +8,7 @@
 // w' = W * (-r^-1) mod 2^261 (one low-half product) — because w * 2^261 = w' * r + W.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I halo2-lib_amd/csrc -I include tools/probes/shoup_probe.hip -o /tmp/shoup_probe && /tmp/shoup_probe
 // prints: a correctness check (2^20 random pairs: canonical(shoup(x, w)) == canonical(montgomery(x, W))) and the products/s of both forms in the
-// dependent-chain loop the library's multiplier roof is measured with (modmul29_bench_kernel in csrc/fr_ops.hip).
+// dependent-chain loop the library's multiplier roof is measured with (modmul29_bench_kernel in csrc/probes.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>

@@ -21,7 +21,7 @@ PO = "tests/phased_oracle.py"
 ITEMS = [
     ("y-fold order of h(X)", "evaluate_h folds: every gate column's `q*(a+b*c-d)`, then the permutation argument (l_0(1-z_0), l_last(z_last^2-z_last), the chain terms, the product terms), then per lookup its five identities — `acc = acc*y + term`",
      [(PP, "int quotient_pass(size_t off")], [(OP, "# ---- evaluate_h on the extended domain")],
-     "reorder the three calls inside `ProofRun::quotient_pass` (and the job order inside `h2hip_quotient_permutation_sets_dev`, fr_ops.hip `items.push_back`) and the oracle's block alike; verifier: `verifier.hip` expression list"),
+     "reorder the three calls inside `ProofRun::quotient_pass` (and the job order inside `h2hip_quotient_permutation_sets_dev`, quotient.hip `items.push_back`) and the oracle's block alike; verifier: `verifier.hip` expression list"),
     ("order of the evaluations in the proof", "advice queries, fixed queries, random poly, sigma polys, permutation sets (z(x), z(wx), z(w^last x) except the last set), lookups (z(x), z(wx), a'(x), a'(w^-1 x), s'(x)); h(x) is NOT written",
      [(PP, "std::vector<Query> evq;")], [(OP, "def create_proof(params: Params, pk: ProvingKey")],
      "permute the `want(...)` calls; the multiopen's query order is the separate `ask(...)` list just below"),
