@@ -311,6 +311,7 @@ int h2hip_fr_coset_scale_batch_dev(h2hip_ctx *ctx, void *const *outs_dev, const 
     H2_DEVICE_GUARD(ctx);
     H2_REQUIRE(ctx && s && (count == 0 || (outs_dev && ins_dev)), "NULL argument");
     if (!n) return H2HIP_OK;
+    for (size_t c = 0; c < count; ++c) H2_REQUIRE(ins_dev[c] && outs_dev[c], "NULL column");   // before the first launch: a rejected call scales nothing
     Fr sv;
     memcpy(&sv, s, sizeof(Fr));
     for (size_t c0 = 0; c0 < count; c0 += COSET_BATCH) {
@@ -319,7 +320,6 @@ int h2hip_fr_coset_scale_batch_dev(h2hip_ctx *ctx, void *const *outs_dev, const 
         for (uint32_t j = 0; j < COSET_BATCH; ++j) {
             g.in[j] = j < cc ? (const Fr *)ins_dev[c0 + j] : nullptr;
             g.out[j] = j < cc ? (Fr *)outs_dev[c0 + j] : nullptr;
-            H2_REQUIRE(j >= cc || (g.in[j] && g.out[j]), "NULL column");
         }
         g.sblock = Fr::one();
         prof_begin(ctx, "coset_scale_kernel");

@@ -872,6 +872,32 @@ class Context:
             for p in dc + ds + [dn, dd]:
                 self.free(p)
 
+    # -- cosets of the extended domain (the sharded prover's device steps): thin wrappers over device pointers, nothing is allocated or copied
+    def fr_coset_scale_batch_dev(self, out_dptrs, in_dptrs, n: int, s: np.ndarray):
+        """out_j[t] = in_j[t] * s^t, t < n, for every column j (out_j may be in_j); a pointer of 0 / None is passed on as NULL"""
+        assert len(out_dptrs) == len(in_dptrs)
+        count = len(in_dptrs)
+        o = (_vp * max(count, 1))(*[_vp(d) for d in out_dptrs])
+        i = (_vp * max(count, 1))(*[_vp(d) for d in in_dptrs])
+        self._chk(self.lib.h2hip_fr_coset_scale_batch_dev(self.handle, o, i, count, n, _ptr(_fe(s))))
+
+    def fr_coset_gather_dev(self, out_dptr: int, in_dptr: int, cosets, log_cosets: int, n: int):
+        """out[m * n + j] = in[(j << log_cosets) + cosets[m]], j < n"""
+        count = len(cosets)
+        arr = (_u32 * max(count, 1))(*[int(c) for c in cosets])
+        self._chk(self.lib.h2hip_fr_coset_gather_dev(self.handle, _vp(out_dptr), _vp(in_dptr), arr, count, log_cosets, n))
+
+    def fr_coset_interleave_dev(self, out_dptr: int, in_dptr: int, slots, log_cosets: int, n: int):
+        """out[(j << log_cosets) + c] = in[slots[c] * n + j], j < n, c < 2^log_cosets (the entry reads 2^log_cosets slots)"""
+        arr = (_u32 * max(len(slots), 1))(*[int(c) for c in slots])
+        self._chk(self.lib.h2hip_fr_coset_interleave_dev(self.handle, _vp(out_dptr), _vp(in_dptr), arr, log_cosets, n))
+
+    def fr_coset_combine_dev(self, out_dptr: int, in_dptr: int, slots, log_cosets: int, n: int, rho_inv: np.ndarray, zeta_n_inv: np.ndarray):
+        """out[q * n + t] = zeta_n_inv^q / C * sum_c in[slots[c] * n + t] * rho_inv^(c q), C = 2^log_cosets"""
+        arr = (_u32 * max(len(slots), 1))(*[int(c) for c in slots])
+        self._chk(self.lib.h2hip_fr_coset_combine_dev(self.handle, _vp(out_dptr), _vp(in_dptr), arr, log_cosets, n, _ptr(_fe(rho_inv)),
+                                                      _ptr(_fe(zeta_n_inv))))
+
     def lookup_permute_batch(self, inputs, table: np.ndarray, usable_rows: int):
         """[(a_perm, s_perm)] for several input columns against one table (sorted once): h2hip_lookup_permute_presorted_batch_dev"""
         table = _fe(table)

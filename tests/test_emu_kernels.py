@@ -794,3 +794,57 @@ def test_lookup_batch_histogram_limit_emulated(ctx):
     assert (batched, per_column) == (31, 32) and per_column <= L.BATCH
     L.check_batch_histogram_limit(ctx, 64, per_column)
     L.check_batch_histogram_limit(ctx, 64, batched)
+
+
+# ---- the device steps of the sharded prover against their definitions (tests/sharded_step_checks.py; the GPU suite runs the same plus one
+# longer size each): big-int arithmetic or the C oracle's fr_mul / fr_add, never another entry of the library
+SHARDED_SHAPES = [(log_c, n) for log_c in range(5) for n in (1, 255, 256, 257)]
+
+
+def test_sharded_coset_scale_emulated(ctx):
+    """ten lengths around the lane tail and the 1024-coefficient workgroup, 1 / 32 / 33 / 70 columns, six scale factors, out of place and in place"""
+    from tests import sharded_step_checks as S
+
+    assert S.check_coset_scale(ctx) == len(S.SCALE_CASES) * 6 * 2
+
+
+def test_sharded_coset_gather_interleave_emulated(ctx):
+    """log_cosets 0 .. 4 x n in 1, 255, 256, 257: gather lists of 1 .. 16 indices (scrambled, subsets, repeats); identity, scrambled and the prover's
+    slot tables for world 1 .. 4 with poisoned unused slots; the round trip"""
+    from tests import sharded_step_checks as S
+
+    assert S.check_coset_gather(ctx, SHARDED_SHAPES) >= len(SHARDED_SHAPES) * 17
+    assert S.check_coset_interleave(ctx, SHARDED_SHAPES) == len(SHARDED_SHAPES) * 6
+    S.check_gather_interleave_round_trip(ctx, SHARDED_SHAPES)
+
+
+def test_sharded_coset_combine_emulated(ctx):
+    """coset_combine_kernel<1 .. 4> at n in 1, 64, 255, 256, 257 under four slot tables; zn = 1 and r - 1 on zero, all r - 1 and uniform h"""
+    from tests import sharded_step_checks as S
+
+    S.check_coset_combine_reference_forms()
+    shapes = [(log_c, n) for log_c in (1, 2, 3, 4) for n in (1, 64, 255, 256, 257)]
+    assert S.check_coset_combine(ctx, shapes) == len(shapes) * 4
+    assert S.check_coset_combine_special(ctx, 257) == 4 * 2 * 4
+
+
+def test_sharded_perm_row_ranges_emulated(ctx):
+    """row ranges of 2^10-row columns, four (beta, gamma) pairs, both arithmetic forms"""
+    from tests import sharded_step_checks as S
+
+    assert S.check_perm_row_ranges(ctx, 10) == 4 * 2 * (8 + 3)
+    assert ctx.get_param("quotient_29") == 1
+
+
+def test_sharded_perm_rows_long_emulated(ctx):
+    """the four-rows-per-lane launch (2^16 + 5 rows from row 2^16 - 7) and the last one-row size (2^16 - 1 rows).  The emulated device has 8 CUs,
+    so both launches also stride: a lane takes up to five rows here, at most four on the GPU."""
+    from tests import sharded_step_checks as S
+
+    S.check_perm_rows_long(ctx)
+
+
+def test_sharded_step_argument_errors_emulated(ctx):
+    from tests import sharded_step_checks as S
+
+    S.check_argument_errors(ctx)

@@ -718,3 +718,58 @@ def test_lookup_batch_histogram_limit(ctx):
     for u in (64, 3001):
         L.check_batch_histogram_limit(ctx, u, per_column)
         L.check_batch_histogram_limit(ctx, u, batched)
+
+
+# ---- the device steps of the sharded prover against their definitions (tests/sharded_step_checks.py: big-int arithmetic or the C oracle's fr_mul /
+# fr_add, never another entry of the library): the emulated suite's cases plus one longer size each
+SHARDED_SHAPES = [(log_c, n) for log_c in range(5) for n in (1, 255, 256, 257)]
+
+
+def test_sharded_coset_scale(ctx):
+    """the emulated suite's ten lengths and 1 / 32 / 33 / 70 columns, and 2^16 + 3 coefficients (65 workgroups, a last lane with three)"""
+    from tests import sharded_step_checks as S
+
+    cases = S.SCALE_CASES + S.SCALE_CASES_LONG
+    assert S.check_coset_scale(ctx, cases) == len(cases) * 6 * 2
+
+
+def test_sharded_coset_gather_interleave(ctx):
+    """also 2^16 + 1 elements per coset with eight cosets"""
+    from tests import sharded_step_checks as S
+
+    shapes = SHARDED_SHAPES + [(3, (1 << 16) + 1)]
+    assert S.check_coset_gather(ctx, shapes) >= len(SHARDED_SHAPES) * 17 + 4
+    assert S.check_coset_interleave(ctx, shapes) == len(shapes) * 6
+    S.check_gather_interleave_round_trip(ctx, shapes)
+
+
+def test_sharded_coset_combine(ctx):
+    """also coset_combine_kernel<4> on 2^14 + 1 elements per coset"""
+    from tests import sharded_step_checks as S
+
+    shapes = [(log_c, n) for log_c in (1, 2, 3, 4) for n in (1, 64, 255, 256, 257)]
+    assert S.check_coset_combine(ctx, shapes) == len(shapes) * 4
+    assert S.check_coset_combine_special(ctx, 257) == 4 * 2 * 4
+    S.check_coset_combine_long(ctx, 4, (1 << 14) + 1)
+
+
+def test_sharded_perm_row_ranges(ctx):
+    """row ranges of 2^12-row columns"""
+    from tests import sharded_step_checks as S
+
+    assert S.check_perm_row_ranges(ctx, 12) == 4 * 2 * (8 + 3)
+    assert ctx.get_param("quotient_29") == 1
+
+
+def test_sharded_perm_rows_long(ctx):
+    """2^16 + 5 rows from row 2^16 - 7 (65 workgroups of four-row lanes, the stride between a lane's rows, a 2^17-entry power table for 2^16 + 5
+    rows) and 2^16 - 1 rows (the last one-row launch)"""
+    from tests import sharded_step_checks as S
+
+    S.check_perm_rows_long(ctx)
+
+
+def test_sharded_step_argument_errors(ctx):
+    from tests import sharded_step_checks as S
+
+    S.check_argument_errors(ctx)
