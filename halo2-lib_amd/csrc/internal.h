@@ -32,13 +32,15 @@ void set_error(const char *fmt, ...);
         if (r__ != H2HIP_OK) return r__;  \
     } while (0)
 
-#define H2_REQUIRE(cond, msg)                                        \
-    do {                                                             \
-        if (!(cond)) {                                               \
-            h2::set_error("%s: invalid argument: %s", __func__, msg); \
-            return H2HIP_ERR_INVALID;                                \
-        }                                                            \
+// (_AS: a check that moved into a helper keeps reporting under its driver's name — the messages are part of the C ABI's behaviour)
+#define H2_REQUIRE_AS(func, cond, msg)                           \
+    do {                                                         \
+        if (!(cond)) {                                           \
+            h2::set_error("%s: invalid argument: %s", func, msg); \
+            return H2HIP_ERR_INVALID;                            \
+        }                                                        \
     } while (0)
+#define H2_REQUIRE(cond, msg) H2_REQUIRE_AS(__func__, cond, msg)
 
 // growable device scratch buffer owned by the context
 struct DevBuf {
@@ -294,8 +296,7 @@ int exclusive_scan_u32_segments(h2hip_ctx *ctx, const uint32_t *in, uint32_t *ou
                                 size_t out_stride);   // `segments` independent scans of n elements, in_stride / out_stride elements apart
 int exclusive_scan_u32(h2hip_ctx *ctx, const uint32_t *in, uint32_t *out, uint32_t n);   // out[i] = sum_{j<i} in[j]; in != out
 int batch_normalize_jac(h2hip_ctx *ctx, const G1Jac *tmp, G1Affine *out, uint32_t n);   // msm_tables.hip
-uint32_t pick_window(size_t n, bool precomp = false);   // Pippenger window width for n points (msm_tables.hip)
-int msm_prepare_bases(h2hip_ctx *ctx, h2hip_bases *bases, bool precompute);
+int msm_prepare_bases(h2hip_ctx *ctx, h2hip_bases *bases, bool precompute);   // msm_tables.hip (the window: pick_window, msm_plan.h)
 int msm_run(h2hip_ctx *ctx, const h2hip_bases *bases, const Fr *scalars_dev, size_t n, XYZZ *out_dev);
 constexpr uint32_t MSM_MAX_COLS = 32;   // columns one fused multi-column MSM handles
 // ext_buckets != nullptr: stop after the merge and leave the columns' buckets ([col][windows][B]; zeroed here unless ext_buckets_zeroed) there for msm_reduce_cols
@@ -318,7 +319,7 @@ struct BatchMsmHooks {
     // reduction's few waves instead of after them (plonk_prove.hip: the round's challenge-independent transforms).
     std::function<int(hipEvent_t ev)> tail;
 };
-// capi.hip: the batch MSM behind h2hip_msm_g1_batch_dev / _multi_dev / _batch (no hooks); bases_per_col, hooks: optional
+// msm_batch.hip: the batch MSM behind h2hip_msm_g1_batch_dev / _multi_dev / _batch (no hooks); bases_per_col, hooks: optional
 int msm_batch(h2hip_ctx *ctx, const h2hip_bases *bases, const h2hip_bases *const *bases_per_col, const void *const *scalars_in, bool scalars_on_host,
               size_t n, size_t count, int point_format, void *out_host, const BatchMsmHooks *hooks);
 // zero-fill-after-use of the bucket arrays (see h2hip_ctx::clean_*): is the buffer's head already (scheduled to be) zero?  (a true answer

@@ -26,7 +26,7 @@
 // Bases stay resident in HBM (h2hip_bases); with H2HIP_BASES_PRECOMPUTE the table also holds 2^(c*w)*P_i for
 // every window (16x the memory — sized for 288 GB HBM), so all windows share one bucket set per index and the
 // serial 2^(c*w) fold disappears.  Signs are applied inside the mixed addition (no negated copy of y).
-#include "internal.h"
+#include "msm_plan.h"
 #ifndef H2_HIPEMU
 #include <hip/hip_ext.h>
 #endif
@@ -52,7 +52,6 @@ namespace h2 {
 
 
 constexpr uint32_t KEY_INVALID = 0xFFFFFFFFu;
-constexpr uint32_t MAX_LDS_BUCKETS = 1u << 15;   // 128 KiB of u32 counters
 
 // ------------------------------------------------------------------ 1. digits
 // blockIdx.y = column of a fused multi-column MSM (column col's digits follow column col-1's: window col*W + w)
@@ -64,6 +63,7 @@ struct DigitCols {
 // r06: a digit travels as a 16-BIT CODE — 0 = no entry, 1 .. B = +d, B + 1 .. 2B - 1 = -d (a negative digit is at most B - 1: v = B stays positive),
 // 2B - 1 = 65535 at c = 16 — so the digits array, written once and read by the histogram and by the scatter, moves half the bytes
 typedef uint16_t digit_t;
+static_assert(sizeof(digit_t) == MSM_DIGIT_BYTES, "MsmPlan sizes the digits array");
 __device__ __forceinline__ uint32_t digit_bucket(uint32_t code, uint32_t B) { return code > B ? code - B : code; }   // 1-based bucket of a non-zero code
 __global__ __launch_bounds__(256) void msm_digits_kernel(DigitCols cols, uint32_t n, uint32_t c, uint32_t W, digit_t *__restrict__ digits,
                                                          uint32_t *__restrict__ counts_tail, uint32_t *__restrict__ offsets_tail) {
@@ -96,15 +96,7 @@ __global__ __launch_bounds__(256) void msm_digits_kernel(DigitCols cols, uint32_
     }
 }
 
-// workgroup -> (window, chunk).  Workgroups are dealt round-robin to the 8 XCDs, each XCD works through its own sequence in order: the first
-// 8 * floor(total / 8) windows are pinned — window w lives on XCD (w mod 8), its G chunk workgroups run together there, one window after the
-// other — so that a window's slice of the sorted array stays in ONE 4 MiB L2 while it is written.  The total % 8 windows left over (17 windows:
-// one) are dealt chunk by chunk over all XCDs: pinned too, the 17th window was a third round on XCD 0 alone with seven XCDs idle (2.1 rounds of
-// work in the time of 3); its 4-byte writes now combine per XCD only (1/17 of the entries).
-H2_HD uint32_t sort_grid_size(uint32_t total, uint32_t G) {
-    const uint32_t full = total / 8u, rem = total - 8u * full;
-    return 8u * (full * G + (rem * G + 7u) / 8u);
-}
+// workgroup -> (window, chunk): the inverse of sort_grid_size's dealing (msm_plan.h)
 __device__ __forceinline__ void block_to_window_chunk(uint32_t L, uint32_t G, uint32_t total, uint32_t &w, uint32_t &g) {
     const uint32_t x = L & 7u, q = L >> 3, full = total / 8u;
     if (q < full * G) {
@@ -896,105 +888,56 @@ int buckets_clean_after_use(h2hip_ctx *ctx, int which, void *buf, size_t bytes, 
     return H2HIP_OK;
 }
 
-int msm_run_cols(h2hip_ctx *ctx, const h2hip_bases *bases, const Fr *const *scalars, uint32_t ncols, size_t n, XYZZ *out, XYZZ29 *ext_buckets,
-                 bool ext_buckets_zeroed, hipEvent_t sorted_ev) {
-    H2_REQUIRE(ncols >= 1 && ncols <= MSM_MAX_COLS, "1..32 columns per fused MSM");
-    H2_REQUIRE(n <= bases->n, "more scalars than resident bases");
-    H2_REQUIRE(bases->pts29 != nullptr || bases->n == 0, "bases are not prepared");
-    H2_REQUIRE(n < (1u << 27), "n too large for 32-bit entry indices");
-    hipStream_t st = ctx->stream;
-    if (n == 0) {
-        H2_REQUIRE(!ext_buckets, "empty MSM in a deferred-reduction batch");
-        H2_HIPCHK(hipMemsetAsync(out, 0, sizeof(XYZZ) * ncols, st));
-        return H2HIP_OK;
-    }
-    const bool precomp = bases->tables > 1;
-    H2_REQUIRE(ncols == 1 || precomp, "a fused multi-column MSM needs precomputed bases");
-    const uint32_t c = precomp ? bases->window_bits : (ctx->msm_window_bits ? (uint32_t)ctx->msm_window_bits : pick_window(n));
-    H2_REQUIRE(c >= 2 && c <= 16, "window bits must be 2..16 (a window's bucket histogram lives in LDS)");
-    const uint32_t Wcol = (255 + c - 1) / c;   // windows of one column
-    H2_REQUIRE(Wcol <= 64, "too many windows");
-    H2_REQUIRE(!precomp || bases->tables >= Wcol, "precomputed table has too few windows");
-    const uint32_t W = Wcol * ncols;           // windows the sort / accumulation see
-    const G1Affine *table = (const G1Affine *)bases->pts29;
-    const uint32_t B = 1u << (c - 1);
-    const uint32_t nkeys = W * B;              // keys of the counting sort = run keys of the accumulation = bucket slots
-    const uint64_t emax = (uint64_t)n * W;
-    H2_REQUIRE(emax < 0xFFFFFFF0ull, "n*W overflows 32 bits");
-    uint32_t K1 = (uint32_t)ctx->msm_chunk;
-    if (K1 == 0) {   // auto: as long as possible (fewer shared runs to merge) while the grid is still several waves per SIMD
-        // Measured at 2^19 / 17 windows (tools/msm_r03.py): 34 entries per lane = 4096 waves 0.72 ms; 32 = 4352 waves 0.81 ms; 64 = 2176 waves
-        // 0.98 ms; ONE exact round of two waves per SIMD (68 entries = 2048 waves) 0.72 ms although its wave-level merge is a single
-        // addition per lane — with one round the kernel ends with its slowest wave, shorter lanes in several rounds balance themselves.
-        // r06, re-measured in whole proofs with the sort kernels running beside the accumulations (profiles/r06_msm_chunk_ab.log): shorter lanes — more,
-        // shorter accumulation workgroups, whose retiring gives the next column's sort its slots sooner — win up to 2^20 points: 24 entries per lane
-        // -0.7 ... -1.3 % at k = 19, -1.6 % at k = 18, -3 % at k = 17 (four fused columns), -4 % at k = 16; 2^20 points: 32 (-1.5 ... -3 %; 48: +3 %); from 2^21
-        // points the longest lanes stay best (56 / 48 / 32: +1 % / neutral / +1.3 %)
-        uint64_t k = emax / 262144;
-        K1 = k < 8 ? 8u : k > 64 ? 64u : (uint32_t)k;
-        const bool lone = !ctx->is_lane && ctx->msm_chunk_lone != 0;   // a lone MSM (SHPLONK's W, W'): no other column's sort waits for its slots
-        if (lone) {   // r05's rule stays: alone, 34 entries per lane are 1 - 3 % faster than 24 at 2^19 points (warm: sync MSM 1.09 - 1.12 vs 1.12 - 1.13 ms, accumulation 0.70 vs 0.72 - 0.78)
-            if (ctx->msm_chunk_lone > 0) K1 = (uint32_t)ctx->msm_chunk_lone;
-        } else if (emax >= 25000000ull) K1 = 64;
-        else if (emax >= 12000000ull) K1 = 32;
-        else if (emax >= 4000000ull) K1 = 24;
-    }
-    // chunking of the counting sort: about 32 chunks per window, 4Ki..64Ki scalars each.  32 = the CUs of an XCD: the (window, chunk)
-    // workgroups of one window run together on the window's XCD, one per CU (tried: chunks sized for ONE round over the whole chip,
-    // W * G <= CUs — 2^19: scatter 0.081 -> 0.145 ms, 2^20: 0.154 -> 0.242 ms: half of every XCD's CUs idle and three windows' slices
-    // competing for one 4 MiB L2).
-    // (r06 tried choosing the chunk count so that windows x chunks fills whole rounds of the chip's 2 x CUs sort-workgroup slots — 30 at 17 windows: 510
-    // workgroups instead of 544 — on the theory that the 32 left-over workgroups cost a round: warm, a synchronous 2^19-point MSM is 1.08 ms either way
-    // and whole proofs do not move (profiles/r06_sort_groups_ab.log; the first sweep's 1.20 -> 1.09 ms was the tool's cold first measurement).  The
-    // knob stays: msm_sort_groups, 0 = 32.)
-    const uint32_t sort_groups = ctx->msm_sort_groups > 0 ? (uint32_t)ctx->msm_sort_groups : 32u;
-    uint32_t chunk = (uint32_t)((n + sort_groups - 1) / sort_groups);
-    if (chunk < 4096) chunk = 4096;
-    const uint32_t chunk_cap = ctx->msm_hist_packed ? 65535u : 65536u;   // (r06) a packed histogram counter holds at most 65535: 2^21 points sort as 33 chunks
-    if (chunk > chunk_cap) chunk = chunk_cap;
-    const uint32_t G = (uint32_t)((n + chunk - 1) / chunk);
-
-    // The one-pass LDS-histogram counting sort is the only sort.  r03 also built a two-level sort with only coalesced writes (0.124 -> 0.087 ms
-    // at 2^19 on uniform scalars) that lost inside the proofs — 5-9 % slower accumulation on its entry order, 15-20 % behind on 0/1-heavy columns
-    // at k >= 20 — a bucket-major sort with one bucket set per column (msm_fold_windows: the wave-level merge of its 16x longer runs cost more
-    // than the presum it saved) and a column's windows dealt to two lanes; all three were removed in r04, their A/B logs are
-    // profiles/archive/r03_msm_sort_ab.log, r03_msm_reorder.log, r02_msm_fold_windows_ab.log, r03_msm_split_windows_ab.log.
+// ---- msm_run_cols, stage by stage: every size, grid and knob decision is MsmPlan's (msm_plan.h); the stages below only reserve and launch
+struct MsmScratch {
     digit_t *digits;
     uint32_t *bhist, *counts, *offsets, *sval, *pkey[2];
     XYZZ29 *buckets, *pval[2];
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_DIGITS, sizeof(digit_t) * emax, (void **)&digits));
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_CURSOR, sizeof(uint32_t) * (size_t)W * G * B, (void **)&bhist));
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_COUNTS, sizeof(uint32_t) * ((size_t)nkeys + 1), (void **)&counts));
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_OFFSETS, sizeof(uint32_t) * ((size_t)nkeys + 2), (void **)&offsets));
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_SVAL, sizeof(uint32_t) * (emax + 4), (void **)&sval));   // + 4: the accumulation reads aligned 16-byte groups
-    if (ext_buckets) buckets = ext_buckets;
-    else H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_BUCKETS, sizeof(XYZZ29) * nkeys, (void **)&buckets));
-    const uint32_t T1 = (uint32_t)((emax + K1 - 1) / K1);
-    const uint32_t accum_blocks = (T1 + 255) / 256;
-    const uint32_t len1 = 8 * accum_blocks, blocks1 = (len1 + 255) / 256;   // the accumulation leaves two partial slots per wave (4 waves per workgroup)
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_PKEY0, sizeof(uint32_t) * (size_t)len1, (void **)&pkey[0]));
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_PVAL0, sizeof(XYZZ29) * (size_t)len1, (void **)&pval[0]));
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_PKEY1, sizeof(uint32_t) * 2 * (size_t)blocks1, (void **)&pkey[1]));
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_PVAL1, sizeof(XYZZ29) * 2 * (size_t)blocks1, (void **)&pval[1]));
-
-    // ---- sort
-    if (ext_buckets) {   // a batch's shared array: zeroed by the batch (after its previous use) or here
-        if (!ext_buckets_zeroed) H2_HIPCHK(hipMemsetAsync(buckets, 0, sizeof(XYZZ29) * nkeys, st));
-    } else if (buckets_prezeroed(ctx, 0, buckets, sizeof(XYZZ29) * nkeys)) {
-        H2_HIPCHK(hipStreamWaitEvent(st, ctx->clean_ev, 0));
+};
+// The one-pass LDS-histogram counting sort is the only sort.  r03 also built a two-level sort with only coalesced writes (0.124 -> 0.087 ms
+// at 2^19 on uniform scalars) that lost inside the proofs — 5-9 % slower accumulation on its entry order, 15-20 % behind on 0/1-heavy columns
+// at k >= 20 — a bucket-major sort with one bucket set per column (msm_fold_windows: the wave-level merge of its 16x longer runs cost more
+// than the presum it saved) and a column's windows dealt to two lanes; all three were removed in r04, their A/B logs are
+// profiles/archive/r03_msm_sort_ab.log, r03_msm_reorder.log, r02_msm_fold_windows_ab.log, r03_msm_split_windows_ab.log.
+static int msm_reserve(h2hip_ctx *ctx, const MsmPlan &p, XYZZ29 *ext_buckets, MsmScratch *s) {
+    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_DIGITS, p.digits_bytes, (void **)&s->digits));
+    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_CURSOR, p.bhist_bytes, (void **)&s->bhist));
+    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_COUNTS, p.counts_bytes, (void **)&s->counts));
+    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_OFFSETS, p.offsets_bytes, (void **)&s->offsets));
+    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_SVAL, p.sval_bytes, (void **)&s->sval));
+    if (ext_buckets) s->buckets = ext_buckets;
+    else H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_BUCKETS, p.buckets_bytes, (void **)&s->buckets));
+    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_PKEY0, p.pkey0_bytes, (void **)&s->pkey[0]));
+    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_PVAL0, p.pval0_bytes, (void **)&s->pval[0]));
+    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_PKEY1, p.pkey1_bytes, (void **)&s->pkey[1]));
+    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_PVAL1, p.pval1_bytes, (void **)&s->pval[1]));
+    return H2HIP_OK;
+}
+// the accumulation needs zeroed buckets: a batch's shared array was zeroed by the batch (after its previous use) or is zeroed here; the
+// context's own array waits for the fill queued behind its last reduction, if that fill covered it
+static int zero_or_await_buckets(h2hip_ctx *ctx, const MsmPlan &p, XYZZ29 *buckets, bool external, bool external_zeroed) {
+    if (external) {
+        if (!external_zeroed) H2_HIPCHK(hipMemsetAsync(buckets, 0, p.buckets_bytes, ctx->stream));
+    } else if (buckets_prezeroed(ctx, 0, buckets, p.buckets_bytes)) {
+        H2_HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->clean_ev, 0));
     } else {
-        H2_HIPCHK(hipMemsetAsync(buckets, 0, sizeof(XYZZ29) * nkeys, st));
+        H2_HIPCHK(hipMemsetAsync(buckets, 0, p.buckets_bytes, ctx->stream));
     }
+    return H2HIP_OK;
+}
+// digits, histogram, its scans, scatter: s.sval holds the entries in bucket order, s.offsets the buckets' boundaries
+static int msm_sort(h2hip_ctx *ctx, const MsmPlan &p, const Fr *const *scalars, const MsmScratch &s, hipEvent_t sorted_ev) {
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)p.n;
     DigitCols dcols;
     for (uint32_t col = 0; col < MSM_MAX_COLS; ++col) {
-        H2_REQUIRE(col >= ncols || scalars[col], "NULL scalar column");
-        dcols.scalars[col] = col < ncols ? scalars[col] : nullptr;
+        H2_REQUIRE_AS("msm_run_cols", col >= p.ncols || scalars[col], "NULL scalar column");
+        dcols.scalars[col] = col < p.ncols ? scalars[col] : nullptr;
     }
     prof_begin(ctx, "msm_digits_kernel");
-    hipLaunchKernelGGL(msm_digits_kernel, dim3((uint32_t)((n + 255) / 256), ncols), dim3(256), 0, st, dcols, (uint32_t)n, c, Wcol, digits, counts + nkeys,
-                       offsets + nkeys + 1);   // + the sentinels counts[nkeys], offsets[nkeys + 1]
+    hipLaunchKernelGGL(msm_digits_kernel, dim3((uint32_t)((p.n + 255) / 256), p.ncols), dim3(256), 0, st, dcols, n, p.c, p.Wcol, s.digits, s.counts + p.nkeys,
+                       s.offsets + p.nkeys + 1);   // + the sentinels counts[nkeys], offsets[nkeys + 1]
     prof_end(ctx);
-    const uint32_t sort_threads = (uint32_t)ctx->msm_sort_threads;
     if (!ctx->msm_lds_attr_set) {   // dynamic LDS above 64 KiB has to be enabled per kernel (and device) once
         H2_HIPCHK(hipFuncSetAttribute((const void *)msm_hist_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(uint32_t) * MAX_LDS_BUCKETS)));
         H2_HIPCHK(hipFuncSetAttribute((const void *)msm_hist_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(uint32_t) * MAX_LDS_BUCKETS)));
@@ -1002,84 +945,87 @@ int msm_run_cols(h2hip_ctx *ctx, const h2hip_bases *bases, const Fr *const *scal
         ctx->msm_lds_attr_set = true;
     }
     prof_begin(ctx, "msm_hist_kernel");
-    const bool hist_packed = ctx->msm_hist_packed != 0 && chunk < 65536u && B >= 2;   // (a counter holds at most `chunk`)
-    // bucket sub-ranges per window (msm_hist_split, default 1): two 32 KiB sub-ranges at c = 16 would fit one retiring accumulation workgroup's slot where
-    // the 64 KiB window needs two — measured: k = 21 / 22 proofs unchanged, k = 20 +0.5 %, a synchronous 2^20-point MSM +4 % (profiles/r06_hist_split_ab.log)
-    uint32_t HS = ctx->msm_hist_split > 0 ? (uint32_t)ctx->msm_hist_split : 1u;
-    if (HS > B) HS = B;
-    const uint32_t hist_grid = sort_grid_size(W * HS, G);
-    if (hist_packed)
-        hipLaunchKernelGGL(msm_hist_kernel<true>, dim3(hist_grid), dim3(sort_threads), sizeof(uint32_t) * ((B / HS + 1) / 2), st, (const digit_t *)digits, (uint32_t)n, W, B, G, chunk, HS, bhist);
-    else
-        hipLaunchKernelGGL(msm_hist_kernel<false>, dim3(hist_grid), dim3(sort_threads), sizeof(uint32_t) * (B / HS), st, (const digit_t *)digits, (uint32_t)n, W, B, G, chunk, HS, bhist);
+    hipLaunchKernelGGL(p.hist_packed ? msm_hist_kernel<true> : msm_hist_kernel<false>, dim3(p.hist_grid), dim3(p.sort_threads), p.hist_lds, st, (const digit_t *)s.digits, n,
+                       p.W, p.B, p.G, p.chunk, p.HS, s.bhist);
     prof_end(ctx);
     prof_begin(ctx, "msm_hist_scan_kernel");
-    hipLaunchKernelGGL(msm_hist_scan_kernel, dim3((nkeys + 255) / 256), dim3(256), 0, st, bhist, W, B, G, counts);
+    hipLaunchKernelGGL(msm_hist_scan_kernel, dim3((p.nkeys + 255) / 256), dim3(256), 0, st, s.bhist, p.W, p.B, p.G, s.counts);
     prof_end(ctx);
     H2_HIPCHK(hipGetLastError());
-    H2_CHK(exclusive_scan_u32(ctx, counts, offsets, nkeys + 1));
+    H2_CHK(exclusive_scan_u32(ctx, s.counts, s.offsets, p.nkeys + 1));
     prof_begin(ctx, "msm_scatter_kernel");
-    uint32_t S = (uint32_t)ctx->msm_scatter_split;   // sub-ranges per window: keep a segment's output slice (n*4/S bytes) within ~2 MiB
-    if (S == 0) {
-        S = 1;
-        while (S < 4 && S * 2 <= B && ((uint64_t)n * 4) / S > (2u << 20)) S *= 2;
-    }
-    if (S > B) S = B;
-    const uint32_t scatter_grid = sort_grid_size(W * S, G);
-    hipLaunchKernelGGL(msm_scatter_kernel, dim3(scatter_grid), dim3(sort_threads), ctx->msm_scatter_full_lds ? sizeof(uint32_t) * MAX_LDS_BUCKETS : sizeof(uint32_t) * (B / S), st,   // full 128 KiB: one workgroup per CU keeps a segment's writes on one XCD
-                       (const digit_t *)digits, (uint32_t)n, W, B, G, chunk, S, precomp ? (uint32_t)bases->n : 0u, Wcol, (const uint32_t *)offsets,
-                       (const uint32_t *)bhist, sval);
+    hipLaunchKernelGGL(msm_scatter_kernel, dim3(p.scatter_grid), dim3(p.sort_threads), p.scatter_lds, st, (const digit_t *)s.digits, n, p.W, p.B, p.G, p.chunk, p.S,
+                       p.table_stride, p.Wcol, (const uint32_t *)s.offsets, (const uint32_t *)s.bhist, s.sval);
     prof_end(ctx);
     H2_HIPCHK(hipGetLastError());
     if (sorted_ev) H2_HIPCHK(hipEventRecord(sorted_ev, st));   // (msm_stagger_sorts) the next lane's sort may start
-
-    // ---- accumulate (+ wave-level merge), then the block-level merge of the wave-boundary partials
-    {
-        // (profiled launches carry their events themselves: hipExtLaunchKernelGGL — separate records around the twelve accumulations of a proof
-        // cost it ~0.3 ms)
-        hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    return H2HIP_OK;
+}
+// ev_a != nullptr: a profiled launch that records its two events itself
+template <bool SPLIT>
+static void launch_accum(h2hip_ctx *ctx, const h2hip_bases *bases, const MsmPlan &p, const MsmScratch &s, hipEvent_t ev_a, hipEvent_t ev_b) {
+    const G1Affine *table = (const G1Affine *)bases->pts29;
 #ifndef H2_HIPEMU
-        if (prof_launch_events(ctx, "msm_accum_kernel", &ev_a, &ev_b)) {
-            if (bases->split)
-                hipExtLaunchKernelGGL(msm_accum_kernel<true>, dim3(accum_blocks), dim3(256), 0, st, ev_a, ev_b, 0, (const uint32_t *)sval, table,
-                                      (const uint32_t *)offsets, nkeys, K1, buckets, pkey[0], pval[0], T1);
-            else
-                hipExtLaunchKernelGGL(msm_accum_kernel<false>, dim3(accum_blocks), dim3(256), 0, st, ev_a, ev_b, 0, (const uint32_t *)sval, table,
-                                      (const uint32_t *)offsets, nkeys, K1, buckets, pkey[0], pval[0], T1);
-        } else
-#endif
-        {
-            prof_begin(ctx, "msm_accum_kernel");   // (a no-op unless profiling without launch events: the emulated build)
-            if (bases->split)
-                hipLaunchKernelGGL(msm_accum_kernel<true>, dim3(accum_blocks), dim3(256), 0, st, (const uint32_t *)sval, table, (const uint32_t *)offsets, nkeys, K1,
-                                   buckets, pkey[0], pval[0], T1);
-            else
-                hipLaunchKernelGGL(msm_accum_kernel<false>, dim3(accum_blocks), dim3(256), 0, st, (const uint32_t *)sval, table, (const uint32_t *)offsets, nkeys, K1,
-                                   buckets, pkey[0], pval[0], T1);
-            prof_end(ctx);
-        }
-        (void)ev_a;
-        (void)ev_b;
+    if (ev_a) {
+        hipExtLaunchKernelGGL(msm_accum_kernel<SPLIT>, dim3(p.accum_blocks), dim3(256), 0, ctx->stream, ev_a, ev_b, 0, (const uint32_t *)s.sval, table,
+                              (const uint32_t *)s.offsets, p.nkeys, p.K1, s.buckets, s.pkey[0], s.pval[0], p.T1);
+        return;
     }
+#endif
+    prof_begin(ctx, "msm_accum_kernel");   // (a no-op unless profiling without launch events: the emulated build)
+    hipLaunchKernelGGL(msm_accum_kernel<SPLIT>, dim3(p.accum_blocks), dim3(256), 0, ctx->stream, (const uint32_t *)s.sval, table, (const uint32_t *)s.offsets, p.nkeys,
+                       p.K1, s.buckets, s.pkey[0], s.pval[0], p.T1);
+    prof_end(ctx);
+}
+// accumulation (+ wave-level merge): complete runs go to their buckets, the wave-boundary partials to pkey[0] / pval[0]
+static int msm_accumulate(h2hip_ctx *ctx, const h2hip_bases *bases, const MsmPlan &p, const MsmScratch &s) {
+    // (profiled launches carry their events themselves: hipExtLaunchKernelGGL — separate records around the twelve accumulations of a proof
+    // cost it ~0.3 ms)
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+#ifndef H2_HIPEMU
+    prof_launch_events(ctx, "msm_accum_kernel", &ev_a, &ev_b);
+#endif
+    if (bases->split) launch_accum<true>(ctx, bases, p, s, ev_a, ev_b);
+    else launch_accum<false>(ctx, bases, p, s, ev_a, ev_b);
     H2_HIPCHK(hipGetLastError());
-    uint32_t len = len1;
+    return H2HIP_OK;
+}
+// block-level merge of the partials, level by level until one workgroup holds what is left
+static int msm_merge_partials(h2hip_ctx *ctx, const MsmPlan &p, const MsmScratch &s) {
+    uint32_t len = p.len1;
     int src = 0;
     for (;;) {
         const uint32_t blocks = (len + 255) / 256;
         const uint32_t final_level = blocks == 1 ? 1u : 0u;
         prof_begin(ctx, "msm_merge_kernel");
-        hipLaunchKernelGGL(msm_merge_kernel, dim3(blocks), dim3(256), 0, st, (const uint32_t *)pkey[src], (const XYZZ29 *)pval[src], len, buckets,
-                           pkey[src ^ 1], pval[src ^ 1], final_level);
+        hipLaunchKernelGGL(msm_merge_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t *)s.pkey[src], (const XYZZ29 *)s.pval[src], len, s.buckets,
+                           s.pkey[src ^ 1], s.pval[src ^ 1], final_level);
         prof_end(ctx);
         H2_HIPCHK(hipGetLastError());
-        if (final_level) break;
+        if (final_level) return H2HIP_OK;
         len = 2 * blocks;
         src ^= 1;
     }
+}
 
+int msm_run_cols(h2hip_ctx *ctx, const h2hip_bases *bases, const Fr *const *scalars, uint32_t ncols, size_t n, XYZZ *out, XYZZ29 *ext_buckets,
+                 bool ext_buckets_zeroed, hipEvent_t sorted_ev) {
+    MsmPlan p;
+    H2_CHK(msm_plan(*ctx, *bases, n, ncols, &p));
+    if (n == 0) {
+        H2_REQUIRE(!ext_buckets, "empty MSM in a deferred-reduction batch");
+        H2_HIPCHK(hipMemsetAsync(out, 0, sizeof(XYZZ) * ncols, ctx->stream));
+        return H2HIP_OK;
+    }
+    MsmScratch s;
+    H2_CHK(msm_reserve(ctx, p, ext_buckets, &s));
+    H2_CHK(zero_or_await_buckets(ctx, p, s.buckets, ext_buckets != nullptr, ext_buckets_zeroed));
+    H2_CHK(msm_sort(ctx, p, scalars, s, sorted_ev));
+    H2_CHK(msm_accumulate(ctx, bases, p, s));
+    H2_CHK(msm_merge_partials(ctx, p, s));
     if (ext_buckets) return H2HIP_OK;   // the caller reduces several MSMs' buckets together
-    H2_CHK(msm_reduce_cols(ctx, bases, c, buckets, ncols, out));
-    return buckets_clean_after_use(ctx, 0, buckets, sizeof(XYZZ29) * nkeys);
+    H2_CHK(msm_reduce_cols(ctx, bases, p.c, s.buckets, ncols, out));
+    return buckets_clean_after_use(ctx, 0, s.buckets, p.buckets_bytes);
 }
 
 int msm_run(h2hip_ctx *ctx, const h2hip_bases *bases, const Fr *scalars, size_t n, XYZZ *out) {

@@ -2,7 +2,7 @@
 // H2HIP_BASES_PRECOMPUTE, the window table 2^(c*w) * P_i for every window w — the device side of what halo2's
 // ParamsKZG keeps as `g` / `g_lagrange` [UPSTREAM halo2-axiom 0.5.3 poly/kzg/commitment.rs; the reference holds them behind
 // gen_srs, /root/reference/halo2-base/src/utils/mod.rs:441].  Built once per SRS (h2hip_bases_create), never in a proof.
-#include "internal.h"
+#include "msm_plan.h"
 #include "ec29.cuh"
 
 namespace h2 {
@@ -99,29 +99,6 @@ __global__ __launch_bounds__(256) void bases_to_29_split_kernel(const G1Affine *
         }
     }
     out[i] = e;
-}
-
-// Window size by a cost model in field multiplications.  Plain bases: every window has its own bucket set, reduced at
-// ~28 multiplications per bucket.  Precomputed tables: ONE bucket set, but its reduction is a chain of dependent
-// additions whose latency is worth ~150 multiplications of the (parallel) accumulation per bucket — fitted to the
-// measured optimum c = 13/14 at 2^16, 15/16 at 2^18, 16 at 2^19 and above (tools/c_sweep.sh).
-uint32_t pick_window(size_t n, bool precomp) {
-    uint32_t best = 4;
-    double best_cost = 1e300;
-    for (uint32_t c = 4; c <= 16; ++c) {
-        double W = (double)((255 + c - 1) / c);
-        // precomputed tables: W*n mixed additions; every (window, bucket) pair costs a full addition in the per-index presum plus its share of
-        // the run boundaries, zero fill and merge (~34 products' worth, fitted on proofs of 2^14..2^17-row shapes: tools/prove_time.py
-        // --param=msm_window_bits=..); the running sums over one bucket set per column come last
-        const double B = (double)(1u << (c - 1));
-        double cost = precomp ? W * 10.0 * (double)n + W * B * 34.0 + 60.0 * B
-                              : W * (10.0 * (double)n + 28.0 * B + 400.0 * c);
-        if (cost < best_cost) {
-            best_cost = cost;
-            best = c;
-        }
-    }
-    return best;
 }
 
 // (re)builds bases->pts29, the unsaturated copy every MSM reads; with `precompute` it holds W levels

@@ -668,3 +668,107 @@ int ntt_run(h2hip_ctx *ctx, Fr *a, uint32_t log_n, const Fr &omega, const Fr *in
 }
 
 }  // namespace h2
+
+using namespace h2;
+
+// ------------------------------------------------------------------ C ABI: host-buffer and device-pointer entry points
+extern "C" {
+
+static int stage_in(h2hip_ctx *ctx, const void *host, size_t elems, Fr **dev) {
+    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_STAGE, sizeof(Fr) * elems, (void **)dev));
+    H2_HIPCHK(hipMemcpyAsync(*dev, host, sizeof(Fr) * elems, hipMemcpyHostToDevice, ctx->stream));
+    return H2HIP_OK;
+}
+static int stage_out(h2hip_ctx *ctx, void *host, const Fr *dev, size_t elems) {
+    H2_HIPCHK(hipMemcpyAsync(host, dev, sizeof(Fr) * elems, hipMemcpyDeviceToHost, ctx->stream));
+    H2_HIPCHK(hipStreamSynchronize(ctx->stream));
+    return H2HIP_OK;
+}
+
+int h2hip_best_fft_dev(h2hip_ctx *ctx, void *a_dev, const void *omega, uint32_t log_n) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && a_dev && omega, "NULL argument");
+    return ntt_run(ctx, (Fr *)a_dev, log_n, ld_fr(omega), nullptr, 0, nullptr, nullptr);
+}
+int h2hip_best_fft(h2hip_ctx *ctx, void *a_host, const void *omega, uint32_t log_n) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && a_host && omega && log_n <= 28, "bad argument");
+    Fr *d = nullptr;
+    H2_CHK(stage_in(ctx, a_host, (size_t)1 << log_n, &d));
+    H2_CHK(h2hip_best_fft_dev(ctx, d, omega, log_n));
+    return stage_out(ctx, a_host, d, (size_t)1 << log_n);
+}
+int h2hip_ifft_dev(h2hip_ctx *ctx, void *a_dev, const void *omega_inv, uint32_t log_n, const void *divisor) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && a_dev && omega_inv && divisor, "NULL argument");
+    Fr d = ld_fr(divisor);
+    Fr out3[3] = {d, d, d};
+    return ntt_run(ctx, (Fr *)a_dev, log_n, ld_fr(omega_inv), nullptr, 0, nullptr, out3);
+}
+int h2hip_ifft(h2hip_ctx *ctx, void *a_host, const void *omega_inv, uint32_t log_n, const void *divisor) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && a_host && omega_inv && divisor && log_n <= 28, "bad argument");
+    Fr *d = nullptr;
+    H2_CHK(stage_in(ctx, a_host, (size_t)1 << log_n, &d));
+    H2_CHK(h2hip_ifft_dev(ctx, d, omega_inv, log_n, divisor));
+    return stage_out(ctx, a_host, d, (size_t)1 << log_n);
+}
+int h2hip_coeff_to_extended_dev(h2hip_ctx *ctx, const void *coeffs_dev, uint32_t k, void *out_dev, uint32_t ext_k, const void *ext_omega,
+                                const void *zeta) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && coeffs_dev && out_dev && ext_omega && zeta, "NULL argument");
+    H2_REQUIRE(k <= ext_k && ext_k <= 28, "need k <= ext_k <= 28");
+    H2_REQUIRE(coeffs_dev != out_dev || k == ext_k, "coeffs and out must not alias");
+    Fr z = ld_fr(zeta);
+    Fr in3[3] = {Fr::one(), z, fe_mul(z, z)};
+    return ntt_run(ctx, (Fr *)out_dev, ext_k, ld_fr(ext_omega), (const Fr *)coeffs_dev, (uint64_t)1 << k, in3, nullptr);
+}
+// the same two transforms over `count` columns at once (host arrays of device pointers): 32 columns per launch
+int h2hip_ifft_batch_dev(h2hip_ctx *ctx, void *const *cols_dev, size_t count, const void *omega_inv, uint32_t log_n, const void *divisor) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && omega_inv && divisor && (count == 0 || cols_dev), "NULL argument");
+    Fr d = ld_fr(divisor);
+    Fr out3[3] = {d, d, d};
+    return ntt_run_batch(ctx, (Fr *const *)cols_dev, nullptr, count, log_n, ld_fr(omega_inv), 0, nullptr, out3);
+}
+int h2hip_coeff_to_extended_batch_dev(h2hip_ctx *ctx, const void *const *coeffs_dev, uint32_t k, void *const *outs_dev, uint32_t ext_k, size_t count,
+                                      const void *ext_omega, const void *zeta) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && ext_omega && zeta && (count == 0 || (coeffs_dev && outs_dev)), "NULL argument");
+    H2_REQUIRE(k <= ext_k && ext_k <= 28, "need k <= ext_k <= 28");
+    for (size_t j = 0; j < count; ++j) H2_REQUIRE(coeffs_dev[j] && outs_dev[j] && (coeffs_dev[j] != outs_dev[j] || k == ext_k), "NULL column, or coeffs and out alias");
+    Fr z = ld_fr(zeta);
+    Fr in3[3] = {Fr::one(), z, fe_mul(z, z)};
+    return ntt_run_batch(ctx, (Fr *const *)outs_dev, (const Fr *const *)coeffs_dev, count, ext_k, ld_fr(ext_omega), (uint64_t)1 << k, in3, nullptr);
+}
+int h2hip_coeff_to_extended(h2hip_ctx *ctx, const void *coeffs_host, uint32_t k, void *out_host, uint32_t ext_k, const void *ext_omega,
+                            const void *zeta) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && coeffs_host && out_host && ext_omega && zeta, "NULL argument");
+    H2_REQUIRE(k <= ext_k && ext_k <= 28, "need k <= ext_k <= 28");
+    Fr *d = nullptr;
+    const size_t n = (size_t)1 << k, ne = (size_t)1 << ext_k;
+    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_STAGE, sizeof(Fr) * (n + ne), (void **)&d));
+    H2_HIPCHK(hipMemcpyAsync(d, coeffs_host, sizeof(Fr) * n, hipMemcpyHostToDevice, ctx->stream));
+    H2_CHK(h2hip_coeff_to_extended_dev(ctx, d, k, d + n, ext_k, ext_omega, zeta));
+    return stage_out(ctx, out_host, d + n, ne);
+}
+int h2hip_extended_to_coeff_dev(h2hip_ctx *ctx, void *a_dev, uint32_t ext_k, const void *ext_omega_inv, const void *ext_divisor,
+                                const void *zeta_inv) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && a_dev && ext_omega_inv && ext_divisor && zeta_inv, "NULL argument");
+    Fr d = ld_fr(ext_divisor), zi = ld_fr(zeta_inv);
+    Fr out3[3] = {d, fe_mul(d, zi), fe_mul(d, fe_mul(zi, zi))};
+    return ntt_run(ctx, (Fr *)a_dev, ext_k, ld_fr(ext_omega_inv), nullptr, 0, nullptr, out3);
+}
+int h2hip_extended_to_coeff(h2hip_ctx *ctx, void *a_host, uint32_t ext_k, const void *ext_omega_inv, const void *ext_divisor,
+                            const void *zeta_inv) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && a_host && ext_omega_inv && ext_divisor && zeta_inv && ext_k <= 28, "bad argument");
+    Fr *d = nullptr;
+    H2_CHK(stage_in(ctx, a_host, (size_t)1 << ext_k, &d));
+    H2_CHK(h2hip_extended_to_coeff_dev(ctx, d, ext_k, ext_omega_inv, ext_divisor, zeta_inv));
+    return stage_out(ctx, a_host, d, (size_t)1 << ext_k);
+}
+
+}  // extern "C"

@@ -290,6 +290,45 @@ def test_division_step_inversion_matches_fermat(tmp_path):
     assert out.returncode == 0 and "modinv selftest OK" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
 
 
+def test_msm_plans_match_recorded_decisions(tmp_path):
+    """msm_plan / msm_batch_plan (csrc/msm_plan.h: window, sort chunks, entries per lane, lanes, fused groups, deferral, staggered sorts and
+    what they refuse) on both sides of every threshold, against what the drivers decided before the planners were split out of them
+    (tests/golden/msm_plan_cases.json).  Host code only: tests/emu/msm_plan_selftest.cpp on a hand-filled context."""
+    import json
+    import os
+    import subprocess
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "tests", "golden", "msm_plan_cases.json")) as f:
+        golden = json.load(f)
+    cases = golden["cases"]
+    assert len(cases) >= 560
+    case_file = tmp_path / "cases.txt"
+    case_file.write_text("".join(case + "\n" for case, _ in cases))
+    exe = str(tmp_path / "msm_plan_selftest")
+    subprocess.check_call(["/opt/rocm/lib/llvm/bin/clang++", "-x", "c++", "-std=c++17", "-O2", "-I", os.path.join(root, "tests", "emu"),
+                           "-Wno-unused-value", "-o", exe, os.path.join(root, "tests", "emu", "msm_plan_selftest.cpp"), "-lpthread"])
+    out = subprocess.run([exe, str(case_file)], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = out.stdout.splitlines()
+    assert len(lines) == len(cases)
+
+    def values(case, line):   # a plan is printed as "rc=0 field=value ...", recorded as the values of golden["fields"] in that order
+        if not line.startswith("rc=0 ") or "=" not in line[5:]:
+            return line
+        pairs = [t.split("=", 1) for t in line.split()[1:]]
+        assert " ".join(k for k, _ in pairs) == golden["fields"][case.split()[0]]
+        return " ".join(v for _, v in pairs)
+
+    wrong = [(case, want, got) for (case, want), got in zip(cases, lines) if values(case, got) != want]
+    assert not wrong, "%d of %d plans differ, the first:\n%s\nexpected: %s\ngot:      %s" % ((len(wrong), len(cases)) + wrong[0])
+    refused = {want.split("err=", 1)[1] for _, want in cases if "err=" in want}
+    for message in ("msm_run_cols: invalid argument: n too large for 32-bit entry indices", "msm_run_cols: invalid argument: n*W overflows 32 bits",
+                    "msm_run_cols: invalid argument: a fused multi-column MSM needs precomputed bases",
+                    "msm_batch: invalid argument: the base sets of one batch must share their table layout (plain, or precomputed with the same window)"):
+        assert message in refused   # (the case list holds the rejections; the comparison above checked their messages)
+
+
 def _quotient_identity_checks(ctx, k, ek, edge_patterns=False):
     ne, step = 1 << ek, 1 << (ek - k)
     rs = lambda seed: O.random_scalars(ne, seed)
