@@ -202,6 +202,9 @@ extern "C" {
     pub fn h2hip_fr_mul_add_batch_dev(ctx: *mut h2hip_ctx, out_dev: *mut c_void, a_dev: *const c_void, b_dev: *const c_void, c_dev: *const c_void, n: usize) -> c_int;
     pub fn h2hip_poseidon_set_spec(ctx: *mut h2hip_ctx, t: u32, r_f: u32, r_p: u32, round_constants: *const c_void, mds: *const c_void) -> c_int;
     pub fn h2hip_poseidon_permute_batch_dev(ctx: *mut h2hip_ctx, states_dev: *mut c_void, inputs_dev: *const c_void, num_inputs: u32, n: usize) -> c_int;
+    pub fn h2hip_poseidon_hash_batch_dev(ctx: *mut h2hip_ctx, digests_dev: *mut c_void, inputs_dev: *const c_void, max_len: usize, lens_dev: *const u32, n: usize) -> c_int;
+    pub fn h2hip_poseidon_merkle_tree_dev(ctx: *mut h2hip_ctx, nodes_dev: *mut c_void, leaves_dev: *const c_void, log_leaves: u32) -> c_int;
+    pub fn h2hip_poseidon_spec_generate(t: u32, r_f: u32, r_p: u32, round_constants_out: *mut c_void, mds_out: *mut c_void) -> c_int;
     // polynomial linear combinations (multiopen), h(X) = numerator / (X^n - 1)
     pub fn h2hip_fr_axpy_dev(ctx: *mut h2hip_ctx, y_dev: *mut c_void, a: *const c_void, x_dev: *const c_void, n: usize) -> c_int;
     pub fn h2hip_fr_scale_dev(ctx: *mut h2hip_ctx, y_dev: *mut c_void, s: *const c_void, n: usize) -> c_int;

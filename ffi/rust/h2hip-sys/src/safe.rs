@@ -251,6 +251,51 @@ pub fn kate_division<'b>(be: &'b Backend, f: &DeviceVec<'b>, b: Fr) -> Result<De
     check(unsafe { h2hip_fr_kate_division_dev(be.ctx, q.ptr, f.ptr, f.len, fr_ptr(&b)) })?;
     Ok(q)
 }
+/// halo2-base's `PoseidonHasher`, batched over messages; the constants come from the library (`h2hip_poseidon_spec_generate`)
+pub struct PoseidonHasher<'b> {
+    be: &'b Backend,
+    t: u32,
+    r_f: u32,
+    r_p: u32,
+    round_constants: Vec<Fr>,
+    mds: Vec<Fr>,
+}
+impl<'b> PoseidonHasher<'b> {
+    pub fn new(be: &'b Backend, t: u32, r_f: u32, r_p: u32) -> Result<Self, HipError> {
+        let mut round_constants = vec![Fr::zero(); ((r_f + r_p) * t) as usize];
+        let mut mds = vec![Fr::zero(); (t * t) as usize];
+        check(unsafe { h2hip_poseidon_spec_generate(t, r_f, r_p, round_constants.as_mut_ptr().cast(), mds.as_mut_ptr().cast()) })?;
+        Ok(Self { be, t, r_f, r_p, round_constants, mds })
+    }
+    fn select(&self) -> Result<(), HipError> {
+        check(unsafe { h2hip_poseidon_set_spec(self.be.ctx, self.t, self.r_f, self.r_p, self.round_constants.as_ptr().cast(), self.mds.as_ptr().cast()) })
+    }
+    /// `hash_fix_len_array` of `inputs.len() / len` messages of `len` elements each (row-major)
+    pub fn hash_fix_len_array(&self, inputs: &DeviceVec<'b>, len: usize) -> Result<DeviceVec<'b>, HipError> {
+        let n = if len == 0 { inputs.len } else { inputs.len / len };
+        assert!(len == 0 || inputs.len % len == 0);
+        self.select()?;
+        let out = DeviceVec::zeroed(self.be, n)?;
+        check(unsafe { h2hip_poseidon_hash_batch_dev(self.be.ctx, out.ptr, inputs.ptr, len, ptr::null(), n) })?;
+        Ok(out)
+    }
+    /// `hash_var_len_array`: message i = the first `lens_dev[i]` elements of row i of `inputs` (`n` rows of `max_len`); `lens_dev`: n u32 on the device
+    pub fn hash_var_len_array(&self, inputs: &DeviceVec<'b>, max_len: usize, lens_dev: *const u32, n: usize) -> Result<DeviceVec<'b>, HipError> {
+        assert!(inputs.len >= max_len * n);
+        self.select()?;
+        let out = DeviceVec::zeroed(self.be, n)?;
+        check(unsafe { h2hip_poseidon_hash_batch_dev(self.be.ctx, out.ptr, inputs.ptr, max_len, lens_dev, n) })?;
+        Ok(out)
+    }
+    /// the heap-layout Merkle tree over 2^log_leaves leaves: node j = H([node 2j, node 2j+1]), node 1 the root
+    pub fn merkle_tree(&self, leaves: &DeviceVec<'b>, log_leaves: u32) -> Result<DeviceVec<'b>, HipError> {
+        assert_eq!(leaves.len, 1usize << log_leaves);
+        self.select()?;
+        let nodes = DeviceVec::zeroed(self.be, 2usize << log_leaves)?;
+        check(unsafe { h2hip_poseidon_merkle_tree_dev(self.be.ctx, nodes.ptr, leaves.ptr, log_leaves) })?;
+        Ok(nodes)
+    }
+}
 /// `poly * scalar` / `poly += other * scalar` of the multiopen argument
 pub fn axpy(be: &Backend, y: &mut DeviceVec, a: Fr, x: &DeviceVec) -> Result<(), HipError> {
     check(unsafe { h2hip_fr_axpy_dev(be.ctx, y.ptr, fr_ptr(&a), x.ptr, x.len.min(y.len)) })

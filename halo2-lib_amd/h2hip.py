@@ -145,6 +145,9 @@ _PROTOS = {
     "h2hip_lookup_permute_presorted_dev": (_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "h2hip_poseidon_set_spec": (_int, [_vp, _u32, _u32, _u32, _vp, _vp]),
     "h2hip_poseidon_permute_batch_dev": (_int, [_vp, _vp, _vp, _u32, _sz]),
+    "h2hip_poseidon_hash_batch_dev": (_int, [_vp, _vp, _vp, _sz, C.POINTER(_u32), _sz]),
+    "h2hip_poseidon_merkle_tree_dev": (_int, [_vp, _vp, _vp, _u32]),
+    "h2hip_poseidon_spec_generate": (_int, [_u32, _u32, _u32, _vp, _vp]),
     "h2hip_plonk_check_witness": (_int, [_vp, _vp, C.POINTER(_vp), _int, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_sz)]),
     "h2hip_plonk_verify_proof": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_int)]),
     "h2hip_plonk_verify_proof_dyn": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_int)]),
@@ -233,6 +236,16 @@ def _fe(a) -> np.ndarray:
 
 def _ptr(a: np.ndarray):
     return a.ctypes.data_as(_vp)
+
+
+def poseidon_spec_generate(t: int, r_f: int, r_p: int, lib=None):
+    """(round constants ((r_f + r_p) * t, 4), mds (t * t, 4)) of the Poseidon instance (t, r_f, r_p) as PoseidonHasher derives them"""
+    lib = lib or load_library()
+    rc, mds = np.zeros(((r_f + r_p) * t, 4), dtype=np.uint64), np.zeros((t * t, 4), dtype=np.uint64)
+    code = lib.h2hip_poseidon_spec_generate(t, r_f, r_p, _ptr(rc), _ptr(mds))
+    if code != 0:
+        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    return rc, mds
 
 
 class Bases:
@@ -818,6 +831,43 @@ class Context:
             self.free(ds)
             if di:
                 self.free(di)
+
+    def poseidon_hash(self, inputs: np.ndarray, lens: Optional[np.ndarray] = None) -> np.ndarray:
+        """digests (n, 4) of the messages inputs (n, max_len, 4): whole rows (hash_fix_len_array), or with lens (n,) the first lens[i]
+        elements of row i (hash_var_len_array)"""
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64)
+        assert inp.ndim == 3 and inp.shape[2] == 4, "inputs: (n, max_len, 4)"
+        n, max_len = inp.shape[0], inp.shape[1]
+        if lens is not None:
+            lens = np.ascontiguousarray(lens, dtype=np.uint32)
+            assert lens.shape == (n,)
+        if n == 0:
+            self._chk(self.lib.h2hip_poseidon_hash_batch_dev(self.handle, None, None, max_len, None, 0))
+            return np.empty((0, 4), dtype=np.uint64)
+        dd = self.malloc(32 * n)
+        di = self.to_device(inp) if max_len else None
+        dl = self.to_device(lens) if lens is not None else None
+        try:
+            self._chk(self.lib.h2hip_poseidon_hash_batch_dev(self.handle, _vp(dd), _vp(di) if di else None, max_len,
+                                                             C.cast(_vp(dl), C.POINTER(_u32)) if dl else None, n))
+            return self.download(dd, (n, 4))
+        finally:
+            for d in (dd, di, dl):
+                if d:
+                    self.free(d)
+
+    def poseidon_merkle_tree(self, leaves: np.ndarray) -> np.ndarray:
+        """the heap-layout tree (2 * 2^d, 4) over leaves (2^d, 4): node j = H([node 2j, node 2j+1]), node 1 the root, node 0 zero"""
+        lv = _fe(leaves)
+        d = len(lv).bit_length() - 1
+        assert len(lv) == 1 << d, "the number of leaves must be a power of two"
+        dn, dl = self.malloc(32 * 2 * len(lv)), self.to_device(lv)
+        try:
+            self._chk(self.lib.h2hip_poseidon_merkle_tree_dev(self.handle, _vp(dn), _vp(dl), d))
+            return self.download(dn, (2 * len(lv), 4))
+        finally:
+            self.free(dn)
+            self.free(dl)
 
     # -- K6 lookup / permutation identities (host-array conveniences for tests)
     def quotient_lookup(self, acc, z, a, s, a_perm, s_perm, l0, l_last, l_blind, ext_k, k, beta, gamma, y) -> np.ndarray:

@@ -524,4 +524,44 @@ inline std::pair<std::vector<Fr>, std::vector<Fr>> permute_expression_pair(Backe
 }
 }  // namespace lookup
 }  // namespace plonk
+
+// ---- halo2-base's PoseidonHasher (poseidon/hasher/mod.rs), batched over messages ------------------------------------
+namespace poseidon {
+class PoseidonHasher {
+  public:
+    // PoseidonHasher::new(OptimizedPoseidonSpec::new::<R_F, R_P, 0>()): the constants come from the library, not from the caller
+    PoseidonHasher(Backend &b, uint32_t t, uint32_t r_f, uint32_t r_p) : be_(&b), t_(t), r_f_(r_f), r_p_(r_p), rc_((size_t)(r_f + r_p) * t), mds_((size_t)t * t) {
+        check(h2hip_poseidon_spec_generate(t, r_f, r_p, rc_.data(), mds_.data()));
+    }
+    // hash_fix_len_array over n messages of len elements each (row-major); len = 0: n empty messages
+    std::vector<Fr> hash_fix_len_array(const std::vector<Fr> &inputs, size_t len, size_t n) const { return run(inputs, len, nullptr, n); }
+    std::vector<Fr> hash_fix_len_array(const std::vector<Fr> &message) const { return run(message, message.size(), nullptr, 1); }
+    // hash_var_len_array over n rows of max_len elements: message i = the first lens[i] elements of row i
+    std::vector<Fr> hash_var_len_array(const std::vector<Fr> &inputs, size_t max_len, const std::vector<uint32_t> &lens) const {
+        return run(inputs, max_len, &lens, lens.size());
+    }
+
+  private:
+    std::vector<Fr> run(const std::vector<Fr> &inputs, size_t max_len, const std::vector<uint32_t> *lens, size_t n) const {
+        if (inputs.size() != max_len * n) throw Error(H2HIP_ERR_INVALID, "PoseidonHasher: inputs.len() != n * len");
+        // the spec is resident per context: select this hasher's before each batch
+        check(h2hip_poseidon_set_spec(be_->raw(), t_, r_f_, r_p_, rc_.data(), mds_.data()));
+        DeviceVec in(*be_, inputs), out(*be_, n);
+        void *dl = nullptr;
+        if (lens && n) {
+            check(h2hip_malloc(be_->raw(), sizeof(uint32_t) * n, &dl));
+            int rc = h2hip_upload(be_->raw(), dl, lens->data(), sizeof(uint32_t) * n);
+            if (rc == H2HIP_OK) rc = h2hip_poseidon_hash_batch_dev(be_->raw(), out.ptr(), in.ptr(), max_len, (const uint32_t *)dl, n);
+            h2hip_free(be_->raw(), dl);
+            check(rc);
+        } else {
+            check(h2hip_poseidon_hash_batch_dev(be_->raw(), out.ptr(), in.ptr(), max_len, nullptr, n));
+        }
+        return out.to_host();
+    }
+    Backend *be_;
+    uint32_t t_, r_f_, r_p_;
+    std::vector<Fr> rc_, mds_;
+};
+}  // namespace poseidon
 }  // namespace halo2_proofs

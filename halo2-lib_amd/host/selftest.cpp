@@ -136,10 +136,34 @@ static void layout_selftest(Backend &be) {
     if (plonk::verify_proof(pk, bp, repr, g[0], g2, s_g2, {}, forged)) throw Error(-1, "layout: a broken break-cell copy was accepted");
 }
 
+// PoseidonHasher::new(3, 8, 57).hash_fix_len_array([1, 2]) against the digest of the textbook sponge, and the fixed / variable forms against each other
+static void poseidon_selftest(Backend &be) {
+    poseidon::PoseidonHasher h(be, 3, 8, 57);
+    const uint64_t want[4] = {0xa066cb6a69deff53ULL, 0xb8ad8a16953065fcULL, 0x91427aa9fd8ff8b8ULL, 0x305df2f9f9f1c0b5ULL};
+    std::vector<Fr> d = h.hash_fix_len_array({host_fr::from_u64(1), host_fr::from_u64(2)});
+    if (d.size() != 1 || !(d[0] == host_fr::from_canonical(want))) throw Error(-1, "poseidon: H([1, 2]) differs from the known digest");
+    std::vector<Fr> rows;
+    for (uint64_t i = 0; i < 6; ++i) rows.push_back(host_fr::from_u64(i < 2 ? i + 1 : 77 + i));
+    std::vector<Fr> v = h.hash_var_len_array(rows, 3, {2, 3});
+    if (v.size() != 2 || !(v[0] == d[0]) || v[1] == d[0]) throw Error(-1, "poseidon: hash_var_len_array");
+    bool refused = false;
+    try {
+        h.hash_var_len_array(rows, 3, {2, 4});
+    } catch (const Error &e) {
+        refused = e.code == H2HIP_ERR_INVALID;
+    }
+    if (!refused) throw Error(-1, "poseidon: a length above max_len was accepted");
+}
+
 int main(int argc, char **argv) {
     uint32_t k = argc > 1 ? (uint32_t)atoi(argv[1]) : 10;
     try {
         Backend be(0);
+        if (argc > 2 && std::string(argv[2]) == "--poseidon") {
+            poseidon_selftest(be);
+            printf("poseidon selftest OK\n");
+            return 0;
+        }
         if (argc > 2 && std::string(argv[2]) == "--dump-proof") {
             std::vector<uint8_t> proof = prove_small_circuit(be, k, 7, 99);
             for (uint8_t c : proof) printf("%02x", c);
@@ -151,6 +175,7 @@ int main(int argc, char **argv) {
             if (p1.empty() || p1 != p2) throw Error(-1, "create_proof is not deterministic for a fixed RNG stream");
             if (p1 == p3) throw Error(-1, "create_proof ignores the RNG");
         }
+        poseidon_selftest(be);
         poly::EvaluationDomain dom(be, 5, k);
         if (dom.extended_k() != k + 2) throw Error(-1, "extended_k");
         uint64_t seed = 42;

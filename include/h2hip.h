@@ -377,6 +377,24 @@ int h2hip_lookup_permute_presorted_batch_dev(h2hip_ctx *ctx, const void *const *
  *      after the last input when num_inputs < t-1. -------------------------------------------------------- */
 int h2hip_poseidon_set_spec(h2hip_ctx *ctx, uint32_t t, uint32_t r_f, uint32_t r_p, const void *round_constants, const void *mds);
 int h2hip_poseidon_permute_batch_dev(h2hip_ctx *ctx, void *states_dev, const void *inputs_dev, uint32_t num_inputs, size_t n);
+/* The sponge PoseidonHasher computes (halo2-base/src/poseidon/hasher/mod.rs, hash_fix_len_array / hash_var_len_array), one function H: start with
+ * s = [2^64, 0, ..], split the message into chunks of RATE = t - 1, add each chunk to s[1..] (a chunk shorter than RATE gets 1 added to the first
+ * lane after it) and permute; when the length is a multiple of RATE (0 included) permute the empty chunk once more; H = s[1].
+ *
+ * digests[i] = H(message i).  inputs_dev: n rows of max_len Fr (row stride max_len).  lens_dev == NULL: every message has
+ * max_len elements (hash_fix_len_array); otherwise n u32 on the device, message i = the first lens[i] elements of row i
+ * (hash_var_len_array / the compact-input forms).  max_len == 0 is legal (inputs_dev may be NULL): the empty hash.
+ * A lens[i] > max_len makes the call return H2HIP_ERR_INVALID (h2hip_last_error says how many messages; nothing is read out of bounds, the
+ * digests are then unspecified).  With lens_dev the call waits for that check; without, it is asynchronous on the context's stream. */
+int h2hip_poseidon_hash_batch_dev(h2hip_ctx *ctx, void *digests_dev, const void *inputs_dev, size_t max_len,
+                                  const uint32_t *lens_dev, size_t n);
+/* Binary Merkle tree, heap layout: nodes_dev holds 2^(log_leaves+1) Fr; nodes[2^log_leaves + i] = leaf i (taken as given, not
+ * hashed), nodes[j] = H([nodes[2j], nodes[2j+1]]) for 1 <= j < 2^log_leaves, nodes[1] = the root, nodes[0] = 0.
+ * leaves_dev == NULL: the leaves are already in place in nodes_dev.  log_leaves <= 30.  Asynchronous on the context's stream. */
+int h2hip_poseidon_merkle_tree_dev(h2hip_ctx *ctx, void *nodes_dev, const void *leaves_dev, uint32_t log_leaves);
+/* The spec PoseidonHasher / pse-poseidon derive from (T, R_F, R_P) alone, secure-MDS index 0: Grain-LFSR round constants
+ * [(r_f + r_p)][t] and the Cauchy MDS [t][t], Montgomery Fr, in the textbook (unoptimised) form set_spec takes.  Host only. */
+int h2hip_poseidon_spec_generate(uint32_t t, uint32_t r_f, uint32_t r_p, void *round_constants_out, void *mds_out);
 
 /* ---- a1: plonk::create_proof for halo2-base circuits, resident on the GPU -------------------------------------------------
  * Replaces create_proof::<KZGCommitmentScheme<Bn256>, ProverSHPLONK<_>, Challenge255<_>, _, Blake2bWrite<_, _, _>, _> as the
