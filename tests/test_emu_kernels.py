@@ -887,3 +887,26 @@ def test_sharded_step_argument_errors_emulated(ctx):
     from tests import sharded_step_checks as S
 
     S.check_argument_errors(ctx)
+
+
+def test_quotient_scale_references_emulated(ctx):
+    """the vectorised one-job reference of tests/quotient_scale_checks.py against big-int arithmetic for every mask it is used with, and the
+    divide / extended_to_coeff checks at emulated sizes: the table path of divide_by_vanishing_poly with 1024 inverses and the one-value form,
+    extended_to_coeff on full-degree data, the in-place k == ext_k transform"""
+    from tests import quotient_scale_checks as K
+
+    K.check_set_reference_against_bigint(4, 6)
+    K.check_permutation_set_jobs(ctx, 4, 6)
+    K.check_divide(ctx, 2, 12)
+    K.check_divide(ctx, 3, 3)
+    for ek in (5, 11):
+        K.check_extended_to_coeff_full_degree(ctx, ek)
+    K.check_coeff_to_extended_in_place(ctx, 5)
+    assert ctx.get_param("quotient_29") == 1
+
+
+def test_quotient_permutation_sets_two_points_per_lane_emulated(ctx):
+    """the batched permutation kernel on 2^19 extended points: every lane takes a second point, w_ext^i carried forward by xstep"""
+    from tests import quotient_scale_checks as K
+
+    K.check_permutation_sets(ctx, 17, 19, forms=(1,), expect_per_lane=2)
