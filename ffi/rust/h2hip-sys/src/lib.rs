@@ -114,6 +114,9 @@ pub struct h2hip_plonk_shape {
 pub type h2hip_rng_fill_fn = Option<unsafe extern "C" fn(user: *mut c_void, out_fr: *mut c_void, n: usize)>;
 pub type h2hip_allgather_fn = Option<unsafe extern "C" fn(user: *mut c_void, local: *const c_void, bytes: usize, all: *mut c_void) -> c_int>;
 pub const H2HIP_PLONK_STAGES: usize = 12;
+pub const H2HIP_CIRCUIT_BASE: c_int = 0;
+pub const H2HIP_CIRCUIT_DYN: c_int = 1;
+pub const H2HIP_CIRCUIT_PHASED: c_int = 2;
 
 #[repr(C)]
 pub struct h2hip_comm {
@@ -174,6 +177,8 @@ extern "C" {
     pub fn h2hip_g1_fixed_base_mul_batch_dev(ctx: *mut h2hip_ctx, base_affine: *const c_void, scalars_dev: *const c_void, n: usize, out_affine_dev: *mut c_void) -> c_int;
     pub fn h2hip_g1_validate_dev(ctx: *mut h2hip_ctx, points_dev: *const c_void, n: usize, invalid: *mut usize) -> c_int;
     pub fn h2hip_g1_decompress_batch_dev(ctx: *mut h2hip_ctx, compressed_dev: *const c_void, n: usize, out_affine_dev: *mut c_void, sign_bit: u32, inf_bit: u32) -> c_int;
+    pub fn h2hip_g1_decompress_checked_dev(ctx: *mut h2hip_ctx, words_dev: *const c_void, slots_dev: *const u32, n: usize, out_affine_dev: *mut c_void,
+                                           status_dev: *mut u32) -> c_int;
     // K2/K3 — arithmetic::best_fft, EvaluationDomain::*
     pub fn h2hip_best_fft(ctx: *mut h2hip_ctx, a_host: *mut c_void, omega: *const c_void, log_n: u32) -> c_int;
     pub fn h2hip_best_fft_dev(ctx: *mut h2hip_ctx, a_dev: *mut c_void, omega: *const c_void, log_n: u32) -> c_int;
@@ -320,6 +325,12 @@ extern "C" {
                                            transcript_repr: *const c_void, g1: *const c_void, g2: *const c_void, s_g2: *const c_void,
                                            instances_host: *const *const c_void, instance_lens: *const usize, proof: *const u8, proof_len: usize,
                                            accepted: *mut c_int) -> c_int;
+    /// verify_proof for `num_proofs` proofs under one verifying key with one pairing (`kind`: `H2HIP_CIRCUIT_*`, `params`: the matching struct)
+    pub fn h2hip_plonk_verify_batch(ctx: *mut h2hip_ctx, kind: c_int, params: *const c_void, fixed_commitments: *const c_void,
+                                    permutation_commitments: *const c_void, transcript_repr: *const c_void, g1: *const c_void, g2: *const c_void,
+                                    s_g2: *const c_void, num_proofs: usize, instances_host: *const *const c_void, instance_lens: *const usize,
+                                    proofs: *const *const u8, proof_lens: *const usize, rng: h2hip_rng_fill_fn, rng_user: *mut c_void,
+                                    accepted: *mut c_int, rejected_out: *mut u8, acc_out: *mut c_void) -> c_int;
     pub fn h2hip_pairing_check(g1_points: *const c_void, g2_points: *const c_void, n: usize, is_one: *mut c_int) -> c_int;
     pub fn h2hip_blake2b(personal16: *const c_void, digest_len: c_uint, msg: *const c_void, len: usize, out: *mut c_void) -> c_int;
     // timing / diagnostics

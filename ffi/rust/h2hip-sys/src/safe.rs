@@ -596,6 +596,41 @@ pub fn verify_proof(params: h2hip_base_circuit_params, phases: &PhaseCounts, fix
     Ok(ok != 0)
 }
 
+/// `BatchVerifier::finalize`: every proof of `proofs` under one (first-phase-only BaseConfig) verifying key with ONE pairing; the proofs' points are
+/// decompressed and all scalar multiplications run on the GPU (h2hip_plonk_verify_batch).  `instances[i]`: the instance columns of proof i.
+/// `rng_fill` draws one combiner per proof, in one call.  -> (accepted, per-proof rejections).
+pub fn verify_proofs<R: FnMut(&mut [Fr])>(be: &Backend, params: h2hip_base_circuit_params, fixed_commitments: &[G1Affine],
+                                         permutation_commitments: &[G1Affine], transcript_repr: Fr, g1: G1Affine, g2: &[u8; 128], s_g2: &[u8; 128],
+                                         instances: &[&[&[Fr]]], proofs: &[&[u8]], mut rng_fill: R) -> Result<(bool, Vec<bool>), HipError> {
+    unsafe extern "C" fn trampoline<R: FnMut(&mut [Fr])>(user: *mut c_void, out: *mut c_void, n: usize) {
+        let f = &mut *(user as *mut R);
+        f(std::slice::from_raw_parts_mut(out as *mut Fr, n));
+    }
+    let mut shape = h2hip_plonk_shape::default();
+    check(unsafe { h2hip_plonk_shape_of(&params, &mut shape) })?;
+    if fixed_commitments.len() != shape.num_fixed_total as usize || permutation_commitments.len() != shape.num_perm_columns as usize {
+        return Err(invalid(format!("verify_proofs: {} fixed / {} permutation commitments, the shape has {} / {}", fixed_commitments.len(),
+                                   permutation_commitments.len(), shape.num_fixed_total, shape.num_perm_columns)));
+    }
+    if instances.len() != proofs.len() || instances.iter().any(|cols| cols.len() != params.num_instance as usize) {
+        return Err(invalid(format!("verify_proofs: {} instance columns per proof, one list per proof", params.num_instance)));
+    }
+    let ins: Vec<*const c_void> = instances.iter().flat_map(|cols| cols.iter().map(|c| c.as_ptr().cast())).collect();
+    let lens: Vec<usize> = instances.iter().flat_map(|cols| cols.iter().map(|c| c.len())).collect();
+    let ptrs: Vec<*const u8> = proofs.iter().map(|p| p.as_ptr()).collect();
+    let plens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+    let mut rejected = vec![0u8; proofs.len().max(1)];
+    let mut ok: c_int = 0;
+    check(unsafe {
+        h2hip_plonk_verify_batch(be.ctx, H2HIP_CIRCUIT_BASE, (&params as *const h2hip_base_circuit_params).cast(), fixed_commitments.as_ptr().cast(),
+                                 permutation_commitments.as_ptr().cast(), fr_ptr(&transcript_repr), (&g1 as *const G1Affine).cast(), g2.as_ptr().cast(),
+                                 s_g2.as_ptr().cast(), proofs.len(), ins.as_ptr(), lens.as_ptr(), ptrs.as_ptr(), plens.as_ptr(), Some(trampoline::<R>),
+                                 (&mut rng_fill as *mut R).cast(), &mut ok, rejected.as_mut_ptr(), ptr::null_mut())
+    })?;
+    rejected.truncate(proofs.len());
+    Ok((ok != 0, rejected.iter().map(|&b| b != 0).collect()))
+}
+
 impl Drop for ProvingKeyHip<'_, '_> {
     fn drop(&mut self) {
         unsafe { h2hip_plonk_pk_free(self.be.ctx, self.pk) }

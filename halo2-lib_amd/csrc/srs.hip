@@ -180,43 +180,61 @@ __global__ __launch_bounds__(256) void g1_validate_kernel(const G1Affine *__rest
     bool ok = fq_is_canonical(a.x) && fq_is_canonical(a.y) && (a.is_identity() || g1_on_curve_mont(a.x, a.y));
     if (!ok) atomicAdd(bad, 1u);
 }
-// SerdeFormat::Processed points: 32 bytes, x little-endian canonical, sign(y) = y mod 2 and the identity flag in the top byte
-__global__ __launch_bounds__(256) void g1_decompress_kernel(const uint32_t *__restrict__ in, size_t n, G1Affine *__restrict__ out, uint32_t sign_bit,
-                                                            uint32_t inf_bit, Exp256 sqrt_exp, uint32_t *__restrict__ bad) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+// SerdeFormat::Processed points: 32 bytes, x little-endian canonical, sign(y) = y mod 2 and the identity flag in the top byte.
+// One point of either decompressor: r = the Montgomery affine point, or (0, 0); returns 0 ok, 1 the identity encoding, 2 malformed
+// (non-canonical x, not on the curve, or the identity flag with other bits set).
+enum : uint32_t { G1_POINT_OK = 0, G1_POINT_IDENTITY = 1, G1_POINT_MALFORMED = 2 };
+__device__ __forceinline__ uint32_t g1_decompress_one(const uint32_t *__restrict__ word, uint32_t sign_bit, uint32_t inf_bit, const Exp256 &sqrt_exp,
+                                                      G1Affine &r) {
     Fq x;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) x.l[j] = in[i * 8 + j];
+    for (int j = 0; j < 8; ++j) x.l[j] = word[j];
     const uint32_t top = x.l[7] >> 24;
     const bool inf = (top >> inf_bit) & 1u, sign = (top >> sign_bit) & 1u;
     x.l[7] &= ~(((1u << sign_bit) | (1u << inf_bit)) << 24);
-    G1Affine r;
     r.x = Fq::zero();
     r.y = Fq::zero();
-    if (inf) {
-        if (!x.is_zero() || sign) atomicAdd(bad, 1u);   // non-canonical identity encoding
-        out[i] = r;
-        return;
-    }
-    if (!fq_is_canonical(x)) {
-        atomicAdd(bad, 1u);
-        out[i] = r;
-        return;
-    }
+    if (inf) return (!x.is_zero() || sign) ? G1_POINT_MALFORMED : G1_POINT_IDENTITY;   // non-canonical identity encoding
+    if (!fq_is_canonical(x)) return G1_POINT_MALFORMED;
     const Fq xm = fe_to_mont(x);
     const Fq b3 = fe_add(fe_add(Fq::one(), Fq::one()), Fq::one());
     const Fq y2 = fe_add(fe_mul(fe_sqr(xm), xm), b3);
     Fq y = fe_pow(y2, sqrt_exp.e);   // q = 3 mod 4: a square root of y2, if one exists, is y2^((q+1)/4)
-    if (!(fe_sqr(y) == y2)) {
-        atomicAdd(bad, 1u);
-        out[i] = r;
-        return;
-    }
+    if (!(fe_sqr(y) == y2)) return G1_POINT_MALFORMED;
     if ((fe_from_mont(y).l[0] & 1u) != (sign ? 1u : 0u)) y = fe_neg(y);
     r.x = xm;
     r.y = y;
+    return G1_POINT_OK;
+}
+__global__ __launch_bounds__(256) void g1_decompress_kernel(const uint32_t *__restrict__ in, size_t n, G1Affine *__restrict__ out, uint32_t sign_bit,
+                                                            uint32_t inf_bit, Exp256 sqrt_exp, uint32_t *__restrict__ bad) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    G1Affine r;
+    if (g1_decompress_one(in + i * 8, sign_bit, inf_bit, sqrt_exp, r) == G1_POINT_MALFORMED) atomicAdd(bad, 1u);
     out[i] = r;
+}
+// The verifier's decompressor: lane i takes word slots[i] (or i) and reports its own verdict; a bad encoding is data, not an error
+__global__ __launch_bounds__(256) void g1_decompress_checked_kernel(const uint32_t *__restrict__ words, const uint32_t *__restrict__ slots, size_t n,
+                                                                    G1Affine *__restrict__ out, uint32_t *__restrict__ status, Exp256 sqrt_exp) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t w = slots ? slots[i] : i;
+    G1Affine r;
+    status[i] = g1_decompress_one(words + w * 8, 6, 7, sqrt_exp, r);
+    out[i] = r;
+}
+static Exp256 fq_sqrt_exponent() {   // (q + 1) / 4
+    Exp256 e;
+    uint64_t carry = 1;
+    uint32_t t[8];
+    for (int j = 0; j < 8; ++j) {
+        uint64_t v = (uint64_t)FqP::m(j) + carry;
+        t[j] = (uint32_t)v;
+        carry = v >> 32;
+    }
+    for (int j = 0; j < 8; ++j) e.e[j] = (t[j] >> 2) | (j < 7 ? t[j + 1] << 30 : 0u);
+    return e;
 }
 
 extern "C" {
@@ -354,17 +372,7 @@ int h2hip_g1_decompress_batch_dev(h2hip_ctx *ctx, const void *compressed_dev, si
     H2_REQUIRE(ctx && (n == 0 || (compressed_dev && out_affine_dev)), "NULL argument");
     H2_REQUIRE(sign_bit < 8 && inf_bit < 8 && sign_bit != inf_bit && sign_bit >= 6 && inf_bit >= 6, "flag bits must be the two spare bits (6, 7) of the top byte");
     if (!n) return H2HIP_OK;
-    Exp256 e;   // (q + 1) / 4
-    {
-        uint64_t carry = 1;
-        uint32_t t[8];
-        for (int j = 0; j < 8; ++j) {
-            uint64_t v = (uint64_t)FqP::m(j) + carry;
-            t[j] = (uint32_t)v;
-            carry = v >> 32;
-        }
-        for (int j = 0; j < 8; ++j) e.e[j] = (t[j] >> 2) | (j < 7 ? t[j + 1] << 30 : 0u);
-    }
+    const Exp256 e = fq_sqrt_exponent();
     uint32_t *bad = nullptr, host_bad = 0;
     H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_OUT, 1024, (void **)&bad));
     H2_HIPCHK(hipMemsetAsync(bad, 0, sizeof(uint32_t), ctx->stream));
@@ -379,6 +387,21 @@ int h2hip_g1_decompress_batch_dev(h2hip_ctx *ctx, const void *compressed_dev, si
         set_error("h2hip_g1_decompress_batch_dev: %u of %zu point encodings are invalid (non-canonical x, not on the curve, or a malformed identity)", host_bad, n);
         return H2HIP_ERR_INVALID;
     }
+    return H2HIP_OK;
+}
+// The verifier's point reader for many proofs at once: point i is the 32-byte word slots_dev[i] (or i) of words_dev in halo2curves' compressed
+// encoding; out_affine_dev[i] = the Montgomery point and status_dev[i] = 0 ok, 1 the identity encoding, 2 malformed, with (0, 0) for every
+// status != 0.  A malformed proof is a rejection, so the data never fails the call.  The caller keeps every slot inside words_dev.
+int h2hip_g1_decompress_checked_dev(h2hip_ctx *ctx, const void *words_dev, const uint32_t *slots_dev, size_t n, void *out_affine_dev, uint32_t *status_dev) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && (n == 0 || (words_dev && out_affine_dev && status_dev)), "NULL argument");
+    H2_REQUIRE(n < ((size_t)1 << 31), "n too large");
+    if (!n) return H2HIP_OK;
+    prof_begin(ctx, "g1_decompress_checked_kernel");
+    hipLaunchKernelGGL(g1_decompress_checked_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t *)words_dev, slots_dev, n,
+                       (G1Affine *)out_affine_dev, status_dev, fq_sqrt_exponent());
+    prof_end(ctx);
+    H2_HIPCHK(hipGetLastError());
     return H2HIP_OK;
 }
 

@@ -10,8 +10,7 @@
 #include <vector>
 
 #include "blake2b.h"
-#include "host_field.h"
-#include "internal.h"
+#include "verifier_internal.h"
 
 namespace h2 {
 namespace verifier {
@@ -254,18 +253,22 @@ static G1Affine g1_neg(const G1Affine &p) {
 
 // ---------------------------------------------------------------------------------------------- transcript (Blake2bRead)
 static const unsigned SIGN_BIT = 6, INF_BIT = 7;
-template <class P>
-static bool canonical(const Fe<P> &a) {
-    unsigned br = 0;
-    for (int j = 0; j < 8; ++j) subb32(a.l[j], P::m(j), br);
-    return br != 0;
-}
 struct Reader {
     Blake2b st;
     const uint8_t *p;
     size_t len, pos = 0;
     bool ok = true;
-    Reader(const uint8_t *proof, size_t n) : st(64, "Halo2-Transcript"), p(proof), len(n) {}
+    const DecodedPoints *pre;   // the points already decompressed, in reading order (the batch verifier), or nullptr
+    size_t pre_pos = 0;
+    Reader(const uint8_t *proof, size_t n, const DecodedPoints *decoded = nullptr) : st(64, "Halo2-Transcript"), p(proof), len(n), pre(decoded) {}
+    void common_point(const G1Affine &r) {
+        uint8_t b[65];
+        b[0] = 0x01;
+        Fq cx = fe_from_mont(r.x), cy = fe_from_mont(r.y);
+        memcpy(b + 1, cx.l, 32);
+        memcpy(b + 33, cy.l, 32);
+        st.update(b, 65);
+    }
     void common_scalar(const Fr &s) {
         uint8_t b[33];
         b[0] = 0x02;
@@ -294,6 +297,17 @@ struct Reader {
         r.y = Fq::zero();
         if (pos + 32 > len) {
             ok = false;
+            return r;
+        }
+        if (pre) {   // status 1 is the identity, which a prover cannot have written; 2 is what the host path below rejects
+            pos += 32;
+            if (pre_pos >= pre->n || pre->status[pre_pos] != 0) {
+                ok = false;
+                ++pre_pos;
+                return r;
+            }
+            r = pre->pts[pre_pos++];
+            common_point(r);
             return r;
         }
         Fq x;
@@ -327,12 +341,7 @@ struct Reader {
         if ((fe_from_mont(y).l[0] & 1u) != (sign ? 1u : 0u)) y = fe_neg(y);
         r.x = xm;
         r.y = y;
-        uint8_t b[65];
-        b[0] = 0x01;
-        Fq cx = fe_from_mont(r.x), cy = fe_from_mont(r.y);
-        memcpy(b + 1, cx.l, 32);
-        memcpy(b + 33, cy.l, 32);
-        st.update(b, 65);
+        common_point(r);
         return r;
     }
     Fr squeeze_challenge() {
@@ -437,44 +446,49 @@ F2 load_f2(const uint8_t *p) {
 
 }  // namespace
 
-namespace {
-// What the verifier needs of a constraint system: the query lists in the prover's order, the permutation columns, the gates, and every lookup
-// as (input, table) lists of expressions, each expression a product of columns queried at the current row; a lookup's expressions are
-// compressed by Horner in theta (upstream's compress_expressions) — BaseConfig's lookups have one expression each, so theta drops out there.
-struct VCol {
-    int kind;   // 0 = fixed, 1 = advice, 2 = instance
-    int index;
-};
-using VExpr = std::vector<VCol>;   // product of columns at Rotation::cur()
-struct VShape {
-    h2hip_plonk_shape sh;
-    uint32_t k, num_instance;
-    std::vector<std::pair<int, int>> adv_q;   // (advice column, rotation)
-    std::vector<int> fixed_q;                 // fixed columns, queried at the current row
-    std::vector<VCol> perm;
-    std::vector<std::pair<int, int>> gates;   // (q_enable fixed column, advice column): q * (a + b*c - d) at rotations 0..3
-    std::vector<std::vector<VExpr>> lk_in, lk_tab;
-    std::vector<std::vector<int>> phase_cols;   // multi-phase: the advice columns of each phase, whose commitments come phase by phase
-    uint32_t phase_challenges[H2HIP_MAX_PHASE] = {0, 0, 0};
-};
+namespace h2 {
+namespace verifier {
 
-int verify_impl(const VShape &vs, const void *fixed_commitments, const void *permutation_commitments, const void *transcript_repr, const void *g1,
-                const void *g2, const void *s_g2, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
-                int *accepted) {
-    const h2hip_plonk_shape &sh = vs.sh;
-    H2_REQUIRE(sh.num_perm_columns == 0 || permutation_commitments, "NULL argument");
+int check_key(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens) {
+    H2_REQUIRE(vs.sh.num_perm_columns == 0 || vk.permutation_commitments, "NULL argument");
     H2_REQUIRE(vs.num_instance == 0 || (instances_host && instance_lens), "NULL argument");
+    G2A Q2 = {load_f2((const uint8_t *)vk.g2), load_f2((const uint8_t *)vk.g2 + 64), false},
+        SQ2 = {load_f2((const uint8_t *)vk.s_g2), load_f2((const uint8_t *)vk.s_g2 + 64), false};
+    H2_REQUIRE(g2_on_curve(Q2) && g2_on_curve(SQ2), "g2 / s_g2 are not points of the twist");
+    return H2HIP_OK;
+}
+
+size_t proof_words(const VShape &vs, std::vector<uint32_t> *point_words) {
+    const h2hip_plonk_shape &sh = vs.sh;
+    size_t advice = sh.num_advice_total;
+    if (!vs.phase_cols.empty()) {
+        advice = 0;
+        for (const auto &cols : vs.phase_cols) advice += cols.size();
+    }
+    const size_t head = advice + 3 * (size_t)sh.num_lookups + sh.num_perm_sets + 1 + sh.quotient_pieces;   // ... the random polynomial, the h pieces
+    size_t evals = vs.adv_q.size() + vs.fixed_q.size() + 1 + sh.num_perm_columns + 5 * (size_t)sh.num_lookups;
+    if (sh.num_perm_sets) evals += 3 * (size_t)sh.num_perm_sets - 1;
+    if (point_words) {
+        point_words->clear();
+        for (size_t i = 0; i < head; ++i) point_words->push_back((uint32_t)i);
+        point_words->push_back((uint32_t)(head + evals));       // h1
+        point_words->push_back((uint32_t)(head + evals + 1));   // h2
+    }
+    return head + evals + 2;
+}
+
+// derive: the transcript replay, the quotient identity rebuilt from the openings, SHPLONK's folded opening as a list of (commitment, scalar)
+int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
+           const DecodedPoints *pre, Derived *out, int *well_formed) {
+    const h2hip_plonk_shape &sh = vs.sh;
+    *well_formed = 0;
     const uint32_t k = vs.k, n = 1u << k, bf = sh.blinding_factors;
     const uint32_t chunk = sh.degree - 2;
     std::vector<G1Affine> fixed_comm(sh.num_fixed_total), perm_comm(sh.num_perm_columns);
-    memcpy(fixed_comm.data(), fixed_commitments, sizeof(G1Affine) * fixed_comm.size());
-    if (!perm_comm.empty()) memcpy(perm_comm.data(), permutation_commitments, sizeof(G1Affine) * perm_comm.size());
+    memcpy(fixed_comm.data(), vk.fixed_commitments, sizeof(G1Affine) * fixed_comm.size());
+    if (!perm_comm.empty()) memcpy(perm_comm.data(), vk.permutation_commitments, sizeof(G1Affine) * perm_comm.size());
     Fr repr;
-    memcpy(&repr, transcript_repr, sizeof(Fr));
-    G1Affine g0;
-    memcpy(&g0, g1, sizeof(G1Affine));
-    G2A Q2 = {load_f2((const uint8_t *)g2), load_f2((const uint8_t *)g2 + 64), false}, SQ2 = {load_f2((const uint8_t *)s_g2), load_f2((const uint8_t *)s_g2 + 64), false};
-    H2_REQUIRE(g2_on_curve(Q2) && g2_on_curve(SQ2), "g2 / s_g2 are not points of the twist");
+    memcpy(&repr, vk.transcript_repr, sizeof(Fr));
     // domain constants
     static const uint64_t ROOT[4] = {0xd34f1ed960c37c9cULL, 0x3215cf6dd39329c8ULL, 0x98865ea93dd31f74ULL, 0x03ddb9f5166d18b7ULL};
     static const uint64_t DELTA[4] = {0x870e56bbe533e9a2ULL, 0x5b5f898e5e963f25ULL, 0x64ec26aad4c86e71ULL, 0x09226b6e22c6f0caULL};
@@ -486,7 +500,7 @@ int verify_impl(const VShape &vs, const void *fixed_commitments, const void *per
     delta = fe_to_mont(delta);
     const Fr one = Fr::one();
 
-    Reader tr(proof, proof_len);
+    Reader tr(proof, proof_len, pre);
     tr.common_scalar(repr);
     std::vector<std::vector<Fr>> inst(vs.num_instance);
     for (uint32_t i = 0; i < vs.num_instance; ++i) {
@@ -562,8 +576,26 @@ int verify_impl(const VShape &vs, const void *fixed_commitments, const void *per
     };
     if (fe_sub(xn, one).is_zero()) return H2HIP_OK;   // x on the domain: negligible; reject rather than divide by zero
     std::vector<Fr> inst_ev(vs.num_instance, Fr::zero());
-    for (uint32_t c = 0; c < vs.num_instance; ++c)
-        for (size_t j = 0; j < inst[c].size(); ++j) inst_ev[c] = fe_add(inst_ev[c], fe_mul(inst[c][j], l_i((int)j)));
+    {   // l_j(x) for every instance row j, with ONE inversion (Montgomery's trick) for all the denominators n * (x - omega^j)
+        size_t rows = 0;
+        for (const auto &col : inst) rows = std::max(rows, col.size());
+        std::vector<Fr> lj(rows), den(rows), pre_prod(rows);
+        Fr wi = one, run = one;
+        for (size_t j = 0; j < rows; ++j) {
+            lj[j] = fe_mul(fe_sub(xn, one), wi);
+            den[j] = fe_mul(fr_u64(n), fe_sub(x, wi));
+            pre_prod[j] = run;
+            run = fe_mul(run, den[j]);
+            wi = fe_mul(wi, omega);
+        }
+        Fr inv = rows ? fe_inv(run) : one;
+        for (size_t j = rows; j-- > 0;) {
+            lj[j] = fe_mul(lj[j], fe_mul(inv, pre_prod[j]));
+            inv = fe_mul(inv, den[j]);
+        }
+        for (uint32_t c = 0; c < vs.num_instance; ++c)
+            for (size_t j = 0; j < inst[c].size(); ++j) inst_ev[c] = fe_add(inst_ev[c], fe_mul(inst[c][j], lj[j]));
+    }
     const Fr l_last = l_i(-(int)(bf + 1)), l_0 = l_i(0);
     Fr l_blind = Fr::zero();
     for (uint32_t r = 1; r <= bf; ++r) l_blind = fe_add(l_blind, l_i(-(int)(bf + 1) + (int)r));
@@ -613,9 +645,13 @@ int verify_impl(const VShape &vs, const void *fixed_commitments, const void *per
     }
     const Fr expected_h = fe_mul(expected, fe_inv(fe_sub(xn, one)));
     // ---- commitments and queries in the prover's order
-    std::vector<G1Affine> comm;
-    auto add_comm = [&](const G1Affine &c) -> int {
-        comm.push_back(c);
+    struct CommRef {
+        int vk_slot;   // as Term::vk_slot; -2: the h commitment, which enters the list piece by piece
+        G1Affine p;
+    };
+    std::vector<CommRef> comm;
+    auto add_comm = [&](const G1Affine &c, int vk_slot = -1) -> int {
+        comm.push_back({vk_slot, c});
         return (int)comm.size() - 1;
     };
     std::vector<VQuery> queries;
@@ -642,18 +678,14 @@ int verify_impl(const VShape &vs, const void *fixed_commitments, const void *per
         queries.push_back({ka, x_inv, l.aie});
         queries.push_back({kz, x_next, l.pne});
     }
-    for (int c : vs.fixed_q) queries.push_back({add_comm(fixed_comm[c]), x, fixed_ev[c]});
-    for (uint32_t j = 0; j < sh.num_perm_columns; ++j) queries.push_back({add_comm(perm_comm[j]), x, sigma_ev[j]});
-    {   // h commitment = sum_i xn^i H_i
-        XYZZ hc = XYZZ::identity();
-        for (size_t i = h_comm.size(); i-- > 0;) {
-            G1Affine cur = xyzz_to_affine(hc);
-            hc = g1_scalar_mul(cur, xn);
-            xyzz_add_affine(hc, h_comm[i].x, h_comm[i].y);
-        }
-        queries.push_back({add_comm(xyzz_to_affine(hc)), x, expected_h});
-        queries.push_back({add_comm(random_comm), x, random_eval});
-    }
+    for (int c : vs.fixed_q) queries.push_back({add_comm(fixed_comm[c], c), x, fixed_ev[c]});
+    for (uint32_t j = 0; j < sh.num_perm_columns; ++j) queries.push_back({add_comm(perm_comm[j], (int)(sh.num_fixed_total + j)), x, sigma_ev[j]});
+    // h commitment = sum_i xn^i H_i: no point arithmetic here, the pieces enter the list with scalar * xn^i
+    G1Affine h_placeholder;
+    h_placeholder.x = Fq::zero();
+    h_placeholder.y = Fq::zero();
+    queries.push_back({add_comm(h_placeholder, -2), x, expected_h});
+    queries.push_back({add_comm(random_comm), x, random_eval});
     // ---- VerifierSHPLONK
     std::vector<VSet> sets;
     std::vector<Fr> super_points;
@@ -663,7 +695,7 @@ int verify_impl(const VShape &vs, const void *fixed_commitments, const void *per
     const Fr u = tr.squeeze_challenge();
     const G1Affine h2 = tr.read_point();
     if (!tr.ok || tr.pos != proof_len) return H2HIP_OK;   // malformed or trailing bytes
-    XYZZ outer = XYZZ::identity();
+    out->terms.clear();
     Fr r_outer = Fr::zero(), z_0 = Fr::zero(), z_0_diff_inv = Fr::zero(), vpow = one;
     for (size_t i = 0; i < sets.size(); ++i) {
         Fr z_diff = one;
@@ -681,37 +713,66 @@ int verify_impl(const VShape &vs, const void *fixed_commitments, const void *per
         } else {
             z_diff = fe_mul(z_diff, z_0_diff_inv);
         }
-        XYZZ inner = XYZZ::identity();
+        const Fr scale = fe_mul(vpow, z_diff);
         Fr r_inner = Fr::zero(), ypow = one;
         for (size_t j = 0; j < sets[i].keys.size(); ++j) {
             r_inner = fe_add(r_inner, fe_mul(ypow, interpolate_at(sets[i].points, sets[i].evals[j], u)));
-            XYZZ t = g1_scalar_mul(comm[sets[i].keys[j]], ypow);
-            xyzz_add(inner, t);
+            const CommRef &c = comm[sets[i].keys[j]];
+            Fr s = fe_mul(scale, ypow);
+            if (c.vk_slot == -2) {
+                for (const G1Affine &piece : h_comm) {
+                    out->terms.push_back({-1, piece, s});
+                    s = fe_mul(s, xn);
+                }
+            } else {
+                out->terms.push_back({c.vk_slot, c.p, s});
+            }
             ypow = fe_mul(ypow, y2);
         }
-        const Fr scale = fe_mul(vpow, z_diff);
-        XYZZ t = g1_scalar_mul(xyzz_to_affine(inner), scale);
-        xyzz_add(outer, t);
         r_outer = fe_add(r_outer, fe_mul(scale, r_inner));
         vpow = fe_mul(vpow, v);
     }
-    {
-        XYZZ t = g1_scalar_mul(g0, fe_neg(r_outer));
-        xyzz_add(outer, t);
-        t = g1_scalar_mul(h1, fe_neg(z_0));
-        xyzz_add(outer, t);
-        t = g1_scalar_mul(h2, u);
-        xyzz_add(outer, t);
+    out->g0_scalar = fe_neg(r_outer);
+    out->terms.push_back({-1, h1, fe_neg(z_0)});
+    out->terms.push_back({-1, h2, u});
+    out->w = h2;
+    *well_formed = 1;
+    return H2HIP_OK;
+}
+
+// finish, one proof: the scalar multiplications by double-and-add on the host ...
+G1Affine outer_on_host(const VKey &vk, const Derived &d) {
+    G1Affine g0;
+    memcpy(&g0, vk.g1, sizeof(G1Affine));
+    XYZZ outer = g1_scalar_mul(g0, d.g0_scalar);
+    for (const Term &t : d.terms) {
+        XYZZ m = g1_scalar_mul(t.p, t.s);
+        xyzz_add(outer, m);
     }
-    // DualMSM::check: e(h2, s*g2) * e(-outer, g2) == 1
-    const G1Affine right = g1_neg(xyzz_to_affine(outer));
-    F12 f = f12_mul(miller_loop(h2, SQ2), miller_loop(right, Q2));
+    return xyzz_to_affine(outer);
+}
+// ... and DualMSM::check: e(left, s*g2) * e(-outer, g2) == 1
+int pairing_verdict(const VKey &vk, const G1Affine &left, const G1Affine &outer, int *accepted) {
+    G2A Q2 = {load_f2((const uint8_t *)vk.g2), load_f2((const uint8_t *)vk.g2 + 64), false},
+        SQ2 = {load_f2((const uint8_t *)vk.s_g2), load_f2((const uint8_t *)vk.s_g2 + 64), false};
+    F12 f = f12_mul(miller_loop(left, SQ2), miller_loop(g1_neg(outer), Q2));
     *accepted = f12_is_one(final_exponentiation(f)) ? 1 : 0;
     return H2HIP_OK;
 }
 
+int verify_one(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
+               int *accepted) {
+    *accepted = 0;
+    H2_CHK(check_key(vs, vk, instances_host, instance_lens));
+    Derived d;
+    int well_formed = 0;
+    H2_CHK(derive(vs, vk, instances_host, instance_lens, proof, proof_len, nullptr, &d, &well_formed));
+    if (!well_formed) return H2HIP_OK;   // a malformed proof is a rejection
+    return pairing_verdict(vk, d.w, outer_on_host(vk, d), accepted);
+}
+
 // FlexGateConfig + RangeConfig: num_advice gate columns, then the dedicated lookup-advice columns; the q_lookup lookup (if any) reads gate column 0
-void base_vshape(VShape &vs, uint32_t k, uint32_t num_advice, uint32_t num_fixed, uint32_t num_instance) {
+static void base_vshape(VShape &vs, uint32_t k, uint32_t num_advice, uint32_t num_fixed, uint32_t num_instance) {
     const h2hip_plonk_shape &sh = vs.sh;
     vs.k = k;
     vs.num_instance = num_instance;
@@ -737,34 +798,14 @@ void base_vshape(VShape &vs, uint32_t k, uint32_t num_advice, uint32_t num_fixed
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-// verify_proof + VerifierSHPLONK + SingleStrategy for a BaseConfig circuit.  fixed_commitments / permutation_commitments: the verifying key
-// (h2hip_plonk_pk_commitments), transcript_repr: the key's hash into the transcript, g1: params.g[0] (the G1 generator of the SRS), g2 / s_g2:
-// 128 bytes each as SerdeFormat::RawBytes stores them (x.c0, x.c1, y.c0, y.c1 Montgomery limbs).  *accepted = 1 iff the proof verifies; a
-// malformed proof is a rejection (accepted = 0, return H2HIP_OK); H2HIP_ERR_INVALID is reserved for bad arguments.
-int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
-                             const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
-                             const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted) {
-    H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
-    *accepted = 0;
-    VShape vs;
+int vshape_base(const h2hip_base_circuit_params *params, VShape &vs) {
     H2_CHK(h2hip_plonk_shape_of(params, &vs.sh));
     base_vshape(vs, params->k, params->num_advice, params->num_fixed, params->num_instance);
-    return verify_impl(vs, fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2, instances_host, instance_lens, proof, proof_len,
-                       accepted);
+    return H2HIP_OK;
 }
-
-// the same for the dynamic-lookup configuration (include/h2hip.h states its layout): the lookups' compressed input and table evaluations are
-// Horner sums in theta of the advice / fixed openings at x
-int h2hip_plonk_verify_proof_dyn(const h2hip_dyn_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
-                                 const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const uint8_t *proof, size_t proof_len,
-                                 int *accepted) {
-    H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
-    *accepted = 0;
-    VShape vs;
+// the dynamic-lookup configuration (include/h2hip.h states its layout): the lookups' compressed input and table evaluations are Horner sums in
+// theta of the advice / fixed openings at x
+int vshape_dyn(const h2hip_dyn_circuit_params *params, VShape &vs) {
     H2_CHK(h2hip_plonk_shape_of_dyn(params, &vs.sh));
     const h2hip_plonk_shape &sh = vs.sh;
     vs.k = params->k;
@@ -789,7 +830,52 @@ int h2hip_plonk_verify_proof_dyn(const h2hip_dyn_circuit_params *params, const v
         vs.lk_in.push_back(in);
         vs.lk_tab.push_back(tab);
     }
-    return verify_impl(vs, fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2, nullptr, nullptr, proof, proof_len, accepted);
+    return H2HIP_OK;
+}
+// the multi-phase configuration (include/h2hip.h states its layout): the advice commitments are read phase by phase, each phase's challenges
+// squeezed after them; one used phase without challenges is the BaseConfig of that phase's BaseCircuitParams
+int vshape_phased(const h2hip_phased_circuit_params *params, VShape &vs) {
+    h2hip_base_circuit_params bp;
+    bool phased = false;
+    H2_CHK(plonk_phased_layout(*params, &vs.sh, &vs.phase_cols, vs.phase_challenges, &phased, &bp));
+    if (!phased) {
+        vs = VShape();
+        return vshape_base(&bp, vs);
+    }
+    base_vshape(vs, bp.k, bp.num_advice, bp.num_fixed, bp.num_instance);
+    return H2HIP_OK;
+}
+
+}  // namespace verifier
+}  // namespace h2
+
+extern "C" {
+
+// verify_proof + VerifierSHPLONK + SingleStrategy for a BaseConfig circuit.  fixed_commitments / permutation_commitments: the verifying key
+// (h2hip_plonk_pk_commitments), transcript_repr: the key's hash into the transcript, g1: params.g[0] (the G1 generator of the SRS), g2 / s_g2:
+// 128 bytes each as SerdeFormat::RawBytes stores them (x.c0, x.c1, y.c0, y.c1 Montgomery limbs).  *accepted = 1 iff the proof verifies; a
+// malformed proof is a rejection (accepted = 0, return H2HIP_OK); H2HIP_ERR_INVALID is reserved for bad arguments.
+int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
+                             const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
+                             const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted) {
+    H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
+    *accepted = 0;
+    VShape vs;
+    H2_CHK(vshape_base(params, vs));
+    return verify_one(vs, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, instances_host, instance_lens, proof, proof_len,
+                      accepted);
+}
+
+// the same for the dynamic-lookup configuration (include/h2hip.h states its layout): the lookups' compressed input and table evaluations are
+// Horner sums in theta of the advice / fixed openings at x
+int h2hip_plonk_verify_proof_dyn(const h2hip_dyn_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
+                                 const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const uint8_t *proof, size_t proof_len,
+                                 int *accepted) {
+    H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
+    *accepted = 0;
+    VShape vs;
+    H2_CHK(vshape_dyn(params, vs));
+    return verify_one(vs, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, nullptr, nullptr, proof, proof_len, accepted);
 }
 
 // the same for the multi-phase configuration (include/h2hip.h states its layout): the advice commitments are read phase by phase, each phase's
@@ -800,15 +886,9 @@ int h2hip_plonk_verify_proof_phased(const h2hip_phased_circuit_params *params, c
     H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
     *accepted = 0;
     VShape vs;
-    h2hip_base_circuit_params bp;
-    bool phased = false;
-    H2_CHK(plonk_phased_layout(*params, &vs.sh, &vs.phase_cols, vs.phase_challenges, &phased, &bp));
-    if (!phased)
-        return h2hip_plonk_verify_proof(&bp, fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2, instances_host, instance_lens, proof,
-                                        proof_len, accepted);
-    base_vshape(vs, bp.k, bp.num_advice, bp.num_fixed, bp.num_instance);
-    return verify_impl(vs, fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2, instances_host, instance_lens, proof, proof_len,
-                       accepted);
+    H2_CHK(vshape_phased(params, vs));
+    return verify_one(vs, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, instances_host, instance_lens, proof, proof_len,
+                      accepted);
 }
 
 // e(P_0, Q_0) * ... * e(P_{n-1}, Q_{n-1}) == 1 — the "final CPU-side pairing" of the north star as an entry of its own (the verifier above ends in

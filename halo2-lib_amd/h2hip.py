@@ -59,6 +59,7 @@ _PROTOS = {
     "h2hip_bases_download": (_int, [_vp, _vp, _vp]),
     "h2hip_g1_validate_dev": (_int, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "h2hip_g1_decompress_batch_dev": (_int, [_vp, _vp, _sz, _vp, _u32, _u32]),
+    "h2hip_g1_decompress_checked_dev": (_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "h2hip_g1_sum_jacobian_dev": (_int, [_vp, _vp, _sz, _int, _vp]),
     "h2hip_g1_sum_partials_host": (_int, [_vp, _sz, _sz, _int, _vp]),
     "h2hip_best_fft": (_int, [_vp, _vp, _vp, _u32]),
@@ -152,6 +153,8 @@ _PROTOS = {
     "h2hip_plonk_verify_proof": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_int)]),
     "h2hip_plonk_verify_proof_dyn": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_int)]),
     "h2hip_plonk_verify_proof_phased": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_int)]),
+    "h2hip_plonk_verify_batch": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_sz),
+                                        _vp, _vp, C.POINTER(_int), _vp, _vp]),
     "h2hip_pairing_check": (_int, [_vp, _vp, _sz, C.POINTER(_int)]),
     "h2hip_blake2b": (_int, [_vp, C.c_uint, _vp, _sz, _vp]),
     "h2hip_bench_gather": (_int, [_vp, _u32, _sz, _u32, _u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -509,6 +509,40 @@ inline bool verify_proof(const ProvingKey &pk, const h2hip_base_circuit_params &
     return ok != 0;
 }
 
+// BatchVerifier: every proof of `proofs` under pk's verifying key with ONE pairing, the points decompressed and the scalar multiplications
+// run on the GPU (h2hip_plonk_verify_batch).  instances_per_proof[i]: the instance columns of proof i.  Rng: as for create_proof; it is asked
+// once, for one combiner per proof.  rejected (optional): resized to proofs.size(), 1 for every proof that does not verify.
+template <class Rng>
+inline bool verify_proofs(Backend &b, const ProvingKey &pk, const h2hip_base_circuit_params &params, const Fr &transcript_repr, const G1Affine &g1,
+                          const uint8_t g2[128], const uint8_t s_g2[128], const std::vector<std::vector<std::vector<Fr>>> &instances_per_proof,
+                          const std::vector<std::vector<uint8_t>> &proofs, Rng &rng, std::vector<uint8_t> *rejected = nullptr) {
+    if (instances_per_proof.size() != proofs.size()) throw Error(H2HIP_ERR_INVALID, "verify_proofs: one list of instance columns per proof");
+    std::vector<const void *> ins;
+    std::vector<size_t> lens, plens;
+    std::vector<const uint8_t *> ptrs;
+    for (auto &cols : instances_per_proof) {
+        if (cols.size() != params.num_instance) throw Error(H2HIP_ERR_INVALID, "verify_proofs: wrong number of instance columns");
+        for (auto &c : cols) {
+            ins.push_back(c.data());
+            lens.push_back(c.size());
+        }
+    }
+    static const uint8_t none = 0;
+    for (auto &p : proofs) {
+        ptrs.push_back(p.empty() ? &none : p.data());
+        plens.push_back(p.size());
+    }
+    if (rejected) rejected->assign(proofs.size(), 0);
+    int ok = 0;
+    G1Affine dummy{};
+    auto tramp = [](void *user, void *out, size_t n) { (*static_cast<Rng *>(user))(static_cast<Fr *>(out), n); };
+    check(h2hip_plonk_verify_batch(b.raw(), H2HIP_CIRCUIT_BASE, &params, pk.fixed_commitments().data(),
+                                   pk.permutation_commitments().empty() ? &dummy : pk.permutation_commitments().data(), &transcript_repr, &g1, g2, s_g2,
+                                   proofs.size(), ins.empty() ? nullptr : ins.data(), lens.empty() ? nullptr : lens.data(), ptrs.data(), plens.data(), +tramp,
+                                   &rng, &ok, rejected && !proofs.empty() ? rejected->data() : nullptr, nullptr));
+    return ok != 0;
+}
+
 namespace lookup {
 // permute_expression_pair over the usable rows: (permuted_input, permuted_table); throws where upstream returns
 // Err(ConstraintSystemFailure) (an input value that the table does not contain)

@@ -155,10 +155,61 @@ static void poseidon_selftest(Backend &be) {
     if (!refused) throw Error(-1, "poseidon: a length above max_len was accepted");
 }
 
+// plonk::verify_proofs: proofs of three witnesses of one small key (one gate column, no table) are accepted together; with a proof of a
+// witness that violates the gate among them the batch is rejected and exactly that proof is named
+static void verify_batch_selftest(Backend &be, uint32_t k) {
+    h2hip_base_circuit_params bp = {k, 1, 0, 1, 0, -1};
+    h2hip_plonk_shape sh;
+    check(h2hip_plonk_shape_of(&bp, &sh));
+    const size_t n = (size_t)1 << k, m = sh.usable_rows / 4;
+    const Fr zero = {{0, 0, 0, 0}}, one = host_fr::R1;
+    std::vector<std::vector<Fr>> fixed(sh.num_fixed_total, std::vector<Fr>(n, zero));
+    for (size_t j = 0; j < m; ++j) fixed[sh.first_q_enable_col][4 * j] = one;
+    Fr toxic = host_fr::from_u64(0x7e57ab1e5ULL);
+    poly::kzg::ParamsKZG params = poly::kzg::ParamsKZG::setup(be, k, toxic, false);
+    plonk::ProvingKey pk(be, bp, params, fixed, {});
+    const Fr repr = host_fr::from_u64(99);
+    pk.set_transcript_repr(repr);
+    std::vector<std::vector<uint8_t>> proofs;
+    for (uint64_t w = 0; w < 4; ++w) {   // the fourth witness breaks gate 0
+        uint64_t s = 300 + w;
+        std::vector<std::vector<Fr>> advice(1, std::vector<Fr>(n, zero));
+        for (size_t j = 0; j < m; ++j) {
+            Fr a = draw_fr(s), b = draw_fr(s), c = draw_fr(s);
+            advice[0][4 * j] = a;
+            advice[0][4 * j + 1] = b;
+            advice[0][4 * j + 2] = c;
+            advice[0][4 * j + 3] = host_fr::add(a, host_fr::mul(b, c));
+        }
+        if (w == 3) advice[0][3] = host_fr::add(advice[0][3], one);
+        StreamRng rng{40 + w};
+        proofs.push_back(plonk::create_proof(be, pk, advice, {}, rng));
+    }
+    std::vector<G1Affine> g = params.get_g().download();
+    uint8_t g2[128], s_g2[128];
+    poly::kzg::ParamsKZG::g2_pair(be, toxic, g2, s_g2);
+    std::vector<std::vector<uint8_t>> good(proofs.begin(), proofs.begin() + 3), mixed = {proofs[0], proofs[3], proofs[2]};
+    std::vector<std::vector<std::vector<Fr>>> no_instances(3);
+    StreamRng rho{9};
+    std::vector<uint8_t> rejected;
+    if (!plonk::verify_proofs(be, pk, bp, repr, g[0], g2, s_g2, no_instances, good, rho, &rejected)) throw Error(-1, "verify_proofs: three good proofs were rejected");
+    if (rejected != std::vector<uint8_t>{0, 0, 0}) throw Error(-1, "verify_proofs: a good proof was flagged");
+    if (plonk::verify_proofs(be, pk, bp, repr, g[0], g2, s_g2, no_instances, mixed, rho, &rejected)) throw Error(-1, "verify_proofs: a forged proof was accepted");
+    if (rejected != std::vector<uint8_t>{0, 1, 0}) throw Error(-1, "verify_proofs: the wrong proof was flagged");
+    if (plonk::verify_proofs(be, pk, bp, repr, g[0], g2, s_g2, no_instances, mixed, rho)) throw Error(-1, "verify_proofs: a forged proof was accepted");
+    for (size_t i = 0; i < 3; ++i)
+        if (plonk::verify_proof(pk, bp, repr, g[0], g2, s_g2, {}, mixed[i]) != (i != 1)) throw Error(-1, "verify_proofs: the single verifier disagrees");
+}
+
 int main(int argc, char **argv) {
     uint32_t k = argc > 1 ? (uint32_t)atoi(argv[1]) : 10;
     try {
         Backend be(0);
+        if (argc > 2 && std::string(argv[2]) == "--verify-batch") {
+            verify_batch_selftest(be, k);
+            printf("verify_batch selftest OK\n");
+            return 0;
+        }
         if (argc > 2 && std::string(argv[2]) == "--poseidon") {
             poseidon_selftest(be);
             printf("poseidon selftest OK\n");

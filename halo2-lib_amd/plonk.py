@@ -404,6 +404,82 @@ def verify_proof(pk: ProvingKey, instances: Sequence[np.ndarray], proof: bytes) 
     return bool(ok.value)
 
 
+_CIRCUIT_KINDS = {BaseCircuitParams: 0, DynLookupCircuitParams: 1, PhasedCircuitParams: 2}   # H2HIP_CIRCUIT_BASE / _DYN / _PHASED
+
+
+def verify_batch(pk: ProvingKey, instances_per_proof: Sequence, proofs: Sequence[bytes], rng=None, want_rejected: bool = False,
+                 want_acc: bool = False, kind: Optional[int] = None):
+    """h2hip_plonk_verify_batch: every proof of `proofs` under pk's verifying key with one pairing; the points are decompressed and the scalar
+    multiplications run on the GPU.  -> (accepted, rejected: list[bool] or None, acc: (2, 8) uint64 array (L, R) or None).  rng draws one
+    combiner per proof in one call: ArrayRng / ChaChaRng / any object with fill_into(dst, n); None = a ChaChaRng seeded from os.urandom, host
+    draws."""
+    ctx, kzg = pk.ctx, pk.kzg
+    if len(kzg.g2_raw) != 256:
+        raise ValueError("verify_batch: the ParamsKZG carries no G2 elements (g2_raw)")
+    if len(instances_per_proof) != len(proofs):
+        raise ValueError("verify_batch: need one list of instance columns per proof")
+    ni, count = pk.params.num_instance, len(proofs)
+    inst = [[_fe(c) for c in cols] for cols in instances_per_proof]
+    if any(len(cols) != ni for cols in inst):
+        raise ValueError("verify_batch: need %d instance columns per proof" % ni)
+    flat = [c for cols in inst for c in cols]
+    ip = (_vp * max(len(flat), 1))(*[_vp(c.ctypes.data) for c in flat])
+    il = (C.c_size_t * max(len(flat), 1))(*[len(c) for c in flat])
+    bufs = [np.frombuffer(bytes(p), dtype=np.uint8).copy() if len(p) else np.zeros(1, dtype=np.uint8) for p in proofs]
+    pp = (_vp * max(count, 1))(*[_vp(b.ctypes.data) for b in bufs])
+    pl = (C.c_size_t * max(count, 1))(*[len(p) for p in proofs])
+    g0 = ctx.bases_download(kzg.g)[:1].copy() if not hasattr(kzg, "_g0") else kzg._g0
+    kzg._g0 = g0
+    g2 = np.frombuffer(kzg.g2_raw, dtype=np.uint8).copy()
+    pc = pk.permutation_commitments if len(pk.permutation_commitments) else np.zeros((1, 8), dtype=np.uint64)
+    if rng is None:
+        import os
+
+        rng = ChaChaRng(ctx.lib, os.urandom(32), device=False)
+    err = []
+
+    def _fill(_user, out, n):
+        try:
+            rng.fill_into(out, n)
+        except BaseException as e:   # never unwind through the C frames
+            err.append(e)
+            C.memset(out, 0, 32 * n)
+
+    cb = _RNG_FN(_fill)
+    ok = C.c_int(0)
+    rejected = np.zeros(max(count, 1), dtype=np.uint8) if want_rejected else None
+    acc = np.zeros((2, 8), dtype=np.uint64) if want_acc else None
+    rc = ctx.lib.h2hip_plonk_verify_batch(ctx.handle, _CIRCUIT_KINDS[type(pk.params)] if kind is None else kind, C.cast(C.byref(pk.params), _vp),
+                                          _ptr(np.ascontiguousarray(pk.fixed_commitments)), _ptr(np.ascontiguousarray(pc)),
+                                          _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128), count,
+                                          ip if ni else None, il if ni else None, pp, pl, C.cast(cb, _vp), None, C.byref(ok),
+                                          _ptr(rejected) if want_rejected else None, _ptr(acc) if want_acc else None)
+    if err:
+        raise err[0]
+    ctx._chk(rc)
+    return bool(ok.value), ([bool(v) for v in rejected[:count]] if want_rejected else None), acc
+
+
+def verify_proofs(pk: ProvingKey, instances_per_proof: Sequence, proofs: Sequence[bytes], rng=None, want_rejected: bool = False):
+    """verify_proof for a batch of proofs of one key (upstream's BatchVerifier): True iff every proof verifies; with want_rejected also the
+    list of per-proof rejections.  instances_per_proof[i]: the instance columns of proof i."""
+    ok, rejected, _ = verify_batch(pk, instances_per_proof, proofs, rng, want_rejected)
+    return (ok, rejected) if want_rejected else ok
+
+
+class BatchVerifier:
+    """halo2_proofs::plonk::BatchVerifier: collect proofs with add_proof, decide them together with finalize"""
+
+    def __init__(self):
+        self.items = []
+
+    def add_proof(self, instances: Sequence[np.ndarray], proof: bytes):
+        self.items.append((list(instances), bytes(proof)))
+
+    def finalize(self, pk: ProvingKey, rng=None) -> bool:
+        return verify_proofs(pk, [i for i, _ in self.items], [p for _, p in self.items], rng)
+
+
 class WitnessFailure(NamedTuple):
     """one failure of check_witness (h2hip_witness_failure): kind = "gate" (column = advice index of the gate column), "lookup" (column = lookup
     index in the key's order) or "copy" (column, row = permutation column and row; peer_* = sigma of that cell); row = the gate's / input's row"""

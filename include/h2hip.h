@@ -178,6 +178,11 @@ int h2hip_bases_download(h2hip_ctx *ctx, const h2hip_bases *bases, void *out_hos
  * identity flags in the top byte (6 / 7 in halo2curves' encoding). */
 int h2hip_g1_validate_dev(h2hip_ctx *ctx, const void *points_dev, size_t n, size_t *invalid);
 int h2hip_g1_decompress_batch_dev(h2hip_ctx *ctx, const void *compressed_dev, size_t n, void *out_affine_dev, uint32_t sign_bit, uint32_t inf_bit);
+/* The verifier's decompressor: one verdict per point, because a malformed proof is a rejection and not an error.
+ * words_dev: 32-byte words; point i is words_dev[slots_dev ? slots_dev[i] : i] in halo2curves' compressed encoding (sign bit 6, identity bit 7).
+ * out_affine_dev[i] = the Montgomery G1Affine, status_dev[i] (uint32) = 0 ok, 1 the identity encoding, 2 malformed (non-canonical x, not on the
+ * curve, flag bits inconsistent); out is (0,0) for status != 0.  Never fails on account of the data.  Every slot must lie inside words_dev. */
+int h2hip_g1_decompress_checked_dev(h2hip_ctx *ctx, const void *words_dev, const uint32_t *slots_dev, size_t n, void *out_affine_dev, uint32_t *status_dev);
 
 /* Sum of n Jacobian points resident on the device (multi-GPU: the all-gathered per-GPU partial MSM results;
  * RCCL has no group-law reduction). */
@@ -675,6 +680,23 @@ int h2hip_plonk_verify_proof_dyn(const h2hip_dyn_circuit_params *params, const v
 int h2hip_plonk_verify_proof_phased(const h2hip_phased_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
                                     const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
                                     const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted);
+
+/* verify_proof for num_proofs proofs under ONE verifying key, with one pairing: accepted = 1 iff every proof verifies.  The proofs' points are
+ * decompressed in one launch, the transcripts replayed on the host, and every scalar multiplication of every proof goes into one MSM on the
+ * GPU.  kind / params: one of the three params structs.  vk and SRS arguments as for the single verifier above.
+ * instances_host / instance_lens: num_proofs * num_instance entries, proof-major (NULL when the configuration has no instance columns).  rng
+ * draws the num_proofs combiners rho_i in ONE call; a zero rho_i is H2HIP_ERR_INVALID, because that proof would go unchecked.  rejected_out
+ * (optional, num_proofs bytes): 1 for every proof that does not verify; when the pairing fails the well-formed proofs are re-verified one by
+ * one to find out which (without rejected_out only *accepted = 0 is reported).  acc_out (optional, 2 x 64 B affine, identity all-zero):
+ * L = sum rho_i * W'_i and R = sum rho_i * outer_i over the well-formed proofs, i.e. accepted <=> no proof malformed and
+ * e(L, s_g2) * e(-R, g2) = 1.  num_proofs = 0 is accepted without device work. */
+#define H2HIP_CIRCUIT_BASE 0
+#define H2HIP_CIRCUIT_DYN 1
+#define H2HIP_CIRCUIT_PHASED 2
+int h2hip_plonk_verify_batch(h2hip_ctx *ctx, int kind, const void *params, const void *fixed_commitments, const void *permutation_commitments,
+                             const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, size_t num_proofs,
+                             const void *const *instances_host, const size_t *instance_lens, const uint8_t *const *proofs, const size_t *proof_lens,
+                             h2hip_rng_fill_fn rng, void *rng_user, int *accepted, uint8_t *rejected_out, void *acc_out);
 
 /* The final CPU-side pairing check of the north star as an entry of its own: *is_one = 1 iff prod_i e(P_i, Q_i) == 1 in Fq12 (what
  * DualMSM::check / halo2curves' multi_miller_loop + final_exponentiation decide for KZG's two pairs).  g1_points: n x 64 B G1Affine

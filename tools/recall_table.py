@@ -16,6 +16,7 @@ OP, OT, OB = "oracle/plonk.py", "oracle/transcript.py", "oracle/bn254.py"
 HP, VR, PL = "halo2-lib_amd/halo2_proofs.py", "halo2-lib_amd/virtual_region.py", "halo2-lib_amd/plonk.py"
 RG, OC = "halo2-lib_amd/csrc/rng.hip", "oracle/chacha.py"
 PO = "tests/phased_oracle.py"
+VB = "halo2-lib_amd/csrc/verify_batch.hip"
 
 # (item, what is assumed about upstream, [(file, anchor)] product, [(file, anchor)] oracle, how to flip)
 ITEMS = [
@@ -70,7 +71,10 @@ ITEMS = [
      "`virtual_region.py` (and `host/halo2_proofs.hpp`); affects the sigma polynomials (verifying key), not validity"),
     ("multi-phase advice order", "after the instances, per phase in order: the blinding rows of the phase's advice columns (column by column, index order), one blind per column, the phase's commitments in index order, then the challenges `challenge_usable_after(phase)` squeezed (Challenge255); the next phase's witness is synthesised with them; theta follows the last phase.  The advice commitments in the proof are grouped by phase, not in column order; the RNG draws the same number of values before the random polynomial",
      [(PP, "// Multi-phase keys [UPSTREAM-RECALL: create_proof's per-phase loop]")], [(PO, "# ---- advice, phase by phase [UPSTREAM-RECALL")],
-     "`ProofRun::round1_phased` (and `blind_phase`), the verifier's phase loop in `verify_impl`, and the oracle's block"),
+     "`ProofRun::round1_phased` (and `blind_phase`), the verifier's phase loop in `derive` (verifier.hip), and the oracle's block"),
+    ("batch verification", "`BatchVerifier::finalize` / `AccumulatorStrategy` combine the proofs' final pairing inputs with random scalars into ONE `DualMSM` check; only the verdict is shared with upstream (no bytes), and which random scalars upstream draws, and from what, is not relied on",
+     [(VB, "upstream's BatchVerifier / AccumulatorStrategy seam [UPSTREAM-RECALL")], [],
+     "nothing to flip for correctness: any non-zero combiners decide the same batches except with probability ~ N/r; the combiners come through the caller's `h2hip_rng_fill_fn`"),
 ]
 
 
