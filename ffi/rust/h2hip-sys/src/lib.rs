@@ -50,6 +50,40 @@ pub struct h2hip_phased_circuit_params {
     pub lookup_bits: i32,
     pub num_challenges_per_phase: [u32; 3],
 }
+/// BaseConfig::configure(base) followed by num_rlc_advice RLC columns: phase-1 advice columns with the gate q_rlc * (a * gamma + a(wX) - a(w^2 X)),
+/// gamma = challenge 0 (include/h2hip.h states the layout)
+/// The C struct nests `h2hip_phased_circuit_params base`; here its fields stand in place (repr(C) lays a nested struct of 4-byte fields out
+/// exactly like the fields themselves), so that every field of the ABI's structs is a scalar or an array of scalars.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct h2hip_rlc_circuit_params {
+    pub k: u32,
+    pub num_advice_per_phase: [u32; 3],
+    pub num_lookup_advice_per_phase: [u32; 3],
+    pub num_fixed: u32,
+    pub num_instance: u32,
+    pub lookup_bits: i32,
+    pub num_challenges_per_phase: [u32; 3],
+    pub num_rlc_advice: u32,
+}
+impl h2hip_rlc_circuit_params {
+    pub fn new(base: &h2hip_phased_circuit_params, num_rlc_advice: u32) -> Self {
+        Self { k: base.k, num_advice_per_phase: base.num_advice_per_phase, num_lookup_advice_per_phase: base.num_lookup_advice_per_phase,
+               num_fixed: base.num_fixed, num_instance: base.num_instance, lookup_bits: base.lookup_bits,
+               num_challenges_per_phase: base.num_challenges_per_phase, num_rlc_advice }
+    }
+}
+/// one piece of h2hip_rlc_fill_chains_dev: a head piece (flags 0) or the continuation of the piece before it after a column break (H2HIP_RLC_CARRY)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct h2hip_rlc_chain {
+    pub column: u32,
+    pub row: u32,
+    pub len: u32,
+    pub flags: u32,
+    pub value_offset: u64,
+}
+pub const H2HIP_RLC_CARRY: u32 = 1;
 /// a later phase's witness: `fill(user, phase, challenges, num_challenges, columns_dev, num_columns)` (include/h2hip.h states the contract)
 pub type h2hip_phase_witness_fn = Option<unsafe extern "C" fn(user: *mut c_void, phase: u32, challenges_fr: *const c_void, num_challenges: usize,
                                                               columns_dev: *const *mut c_void, num_columns: usize) -> c_int>;
@@ -273,6 +307,13 @@ extern "C" {
     pub fn h2hip_plonk_shape_of_phased(params: *const h2hip_phased_circuit_params, out: *mut h2hip_plonk_shape) -> c_int;
     pub fn h2hip_plonk_keygen_phased(ctx: *mut h2hip_ctx, params: *const h2hip_phased_circuit_params, g: *const h2hip_bases, g_lagrange: *const h2hip_bases,
                                      fixed_host: *const *const c_void, copies: *const u32, ncopies: usize, out: *mut *mut h2hip_plonk_pk) -> c_int;
+    pub fn h2hip_plonk_shape_of_rlc(params: *const h2hip_rlc_circuit_params, out: *mut h2hip_plonk_shape) -> c_int;
+    pub fn h2hip_plonk_keygen_rlc(ctx: *mut h2hip_ctx, params: *const h2hip_rlc_circuit_params, g: *const h2hip_bases, g_lagrange: *const h2hip_bases,
+                                  fixed_host: *const *const c_void, copies: *const u32, ncopies: usize, out: *mut *mut h2hip_plonk_pk) -> c_int;
+    pub fn h2hip_rlc_fill_chains_dev(ctx: *mut h2hip_ctx, columns_dev: *const *mut c_void, num_columns: usize, usable_rows: usize, values_dev: *const c_void,
+                                     num_values: usize, chains_host: *const h2hip_rlc_chain, count: usize, gamma: *const c_void) -> c_int;
+    pub fn h2hip_quotient_rlc_gate_batch_dev(ctx: *mut h2hip_ctx, acc_dev: *mut c_void, q_dev: *const *const c_void, a_dev: *const *const c_void,
+                                             count: usize, ext_k: u32, k: u32, gamma: *const c_void, y: *const c_void) -> c_int;
     pub fn h2hip_plonk_pk_free(ctx: *mut h2hip_ctx, pk: *mut h2hip_plonk_pk);
     pub fn h2hip_plonk_pk_commitments(pk: *const h2hip_plonk_pk, fixed_out: *mut c_void, permutation_out: *mut c_void) -> c_int;
     pub fn h2hip_plonk_pk_set_transcript_repr(pk: *mut h2hip_plonk_pk, fr: *const c_void) -> c_int;
@@ -310,6 +351,14 @@ extern "C" {
     pub fn h2hip_plonk_check_witness(ctx: *mut h2hip_ctx, pk: *const h2hip_plonk_pk, advice: *const *const c_void, advice_on_device: c_int,
                                      instances_host: *const *const c_void, instance_lens: *const usize, failures_out: *mut h2hip_witness_failure,
                                      max_failures: usize, num_failures: *mut usize) -> c_int;
+    pub fn h2hip_plonk_check_witness_challenges(ctx: *mut h2hip_ctx, pk: *const h2hip_plonk_pk, advice: *const *const c_void, advice_on_device: c_int,
+                                                instances_host: *const *const c_void, instance_lens: *const usize, challenges_fr: *const c_void,
+                                                num_challenges: usize, failures_out: *mut h2hip_witness_failure, max_failures: usize,
+                                                num_failures: *mut usize) -> c_int;
+    pub fn h2hip_plonk_verify_proof_rlc(params: *const h2hip_rlc_circuit_params, fixed_commitments: *const c_void, permutation_commitments: *const c_void,
+                                        transcript_repr: *const c_void, g1: *const c_void, g2: *const c_void, s_g2: *const c_void,
+                                        instances_host: *const *const c_void, instance_lens: *const usize, proof: *const u8, proof_len: usize,
+                                        accepted: *mut c_int) -> c_int;
     pub fn h2hip_lookup_sorted_table_bytes(usable_rows: usize) -> usize;
     pub fn h2hip_lookup_table_sort_dev(ctx: *mut h2hip_ctx, s_dev: *const c_void, usable_rows: usize, sorted_out_dev: *mut c_void) -> c_int;
     pub fn h2hip_lookup_permute_presorted_dev(ctx: *mut h2hip_ctx, a_dev: *const c_void, sorted_table_dev: *const c_void, usable_rows: usize,

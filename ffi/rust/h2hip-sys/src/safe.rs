@@ -348,6 +348,8 @@ pub struct ProvingKeyHip<'b, 'g> {
     pub params: h2hip_base_circuit_params,
     /// Some for a circuit with more than one phase or with challenges (h2hip_plonk_keygen_phased)
     pub phased: Option<h2hip_phased_circuit_params>,
+    /// Some for a circuit with RLC columns (h2hip_plonk_keygen_rlc); `phased` is then its base
+    pub rlc: Option<h2hip_rlc_circuit_params>,
     pub shape: h2hip_plonk_shape,
     _g: &'g ResidentBases<'b>,
     _g_lagrange: &'g ResidentBases<'b>,
@@ -362,10 +364,19 @@ pub struct PhaseCounts {
     pub num_advice_per_phase: Vec<u32>,
     pub num_lookup_advice_per_phase: Vec<u32>,
     pub num_challenges_per_phase: Vec<u32>,
+    /// RLC columns configured next to BaseConfig (downstream's RlcConfig): non-zero routes to the h2hip_*_rlc entries
+    pub num_rlc_advice: u32,
 }
 impl PhaseCounts {
     fn is_first_phase_only(&self) -> bool {
-        self.num_advice_per_phase.len() <= 1 && self.num_lookup_advice_per_phase.len() <= 1 && self.num_challenges_per_phase.iter().all(|&c| c == 0)
+        self.num_rlc_advice == 0 && self.num_advice_per_phase.len() <= 1 && self.num_lookup_advice_per_phase.len() <= 1
+            && self.num_challenges_per_phase.iter().all(|&c| c == 0)
+    }
+    fn to_c_rlc(&self, params: &h2hip_base_circuit_params) -> Result<Option<h2hip_rlc_circuit_params>, HipError> {
+        if self.num_rlc_advice == 0 {
+            return Ok(None);
+        }
+        Ok(Some(h2hip_rlc_circuit_params::new(&self.to_c(params)?, self.num_rlc_advice)))
     }
     fn to_c(&self, params: &h2hip_base_circuit_params) -> Result<h2hip_phased_circuit_params, HipError> {
         let arr = |v: &[u32], what: &str| -> Result<[u32; 3], HipError> {
@@ -398,14 +409,17 @@ impl<'b, 'g> ProvingKeyHip<'b, 'g> {
     /// `keygen_vk` + `keygen_pk`: `fixed` = the fixed columns after synthesis (table, constants, selector columns), `copies` = the copy
     /// constraints as (permutation column, row, permutation column, row) in emission order.
     /// `params` carries phase 0's counts; `phases` all of them: a circuit with more than one phase or with challenges goes through
-    /// `h2hip_plonk_keygen_phased` (include/h2hip.h states the layout and the limits).
+    /// `h2hip_plonk_keygen_phased`, one with RLC columns (`phases.num_rlc_advice != 0`) through `h2hip_plonk_keygen_rlc` (include/h2hip.h states
+    /// the layouts and the limits).
     pub fn keygen(be: &'b Backend, params: h2hip_base_circuit_params, phases: &PhaseCounts, g: &'g ResidentBases<'b>, g_lagrange: &'g ResidentBases<'b>,
                   fixed: &[Vec<Fr>], copies: &[[u32; 4]], transcript_repr: impl FnOnce(&[G1Affine], &[G1Affine]) -> Fr) -> Result<Self, HipError> {
         let phased = if phases.is_first_phase_only() { None } else { Some(phases.to_c(&params)?) };
+        let rlc = phases.to_c_rlc(&params)?;
         let mut shape = h2hip_plonk_shape::default();
-        match &phased {
-            Some(pp) => check(unsafe { h2hip_plonk_shape_of_phased(pp, &mut shape) })?,
-            None => check(unsafe { h2hip_plonk_shape_of(&params, &mut shape) })?,
+        match (&rlc, &phased) {
+            (Some(rp), _) => check(unsafe { h2hip_plonk_shape_of_rlc(rp, &mut shape) })?,
+            (None, Some(pp)) => check(unsafe { h2hip_plonk_shape_of_phased(pp, &mut shape) })?,
+            (None, None) => check(unsafe { h2hip_plonk_shape_of(&params, &mut shape) })?,
         }
         // the C side reads num_fixed_total pointers and 2^k elements behind each: check the shapes here, in safe code
         let n = 1usize << params.k;
@@ -421,13 +435,14 @@ impl<'b, 'g> ProvingKeyHip<'b, 'g> {
         let cols: Vec<*const c_void> = fixed.iter().map(|c| c.as_ptr().cast()).collect();
         let mut pk = ptr::null_mut();
         check(unsafe {
-            match &phased {
-                Some(pp) => h2hip_plonk_keygen_phased(be.ctx, pp, g.h, g_lagrange.h, cols.as_ptr(), copies.as_ptr().cast(), copies.len(), &mut pk),
-                None => h2hip_plonk_keygen(be.ctx, &params, g.h, g_lagrange.h, cols.as_ptr(), copies.as_ptr().cast(), copies.len(), &mut pk),
+            match (&rlc, &phased) {
+                (Some(rp), _) => h2hip_plonk_keygen_rlc(be.ctx, rp, g.h, g_lagrange.h, cols.as_ptr(), copies.as_ptr().cast(), copies.len(), &mut pk),
+                (None, Some(pp)) => h2hip_plonk_keygen_phased(be.ctx, pp, g.h, g_lagrange.h, cols.as_ptr(), copies.as_ptr().cast(), copies.len(), &mut pk),
+                (None, None) => h2hip_plonk_keygen(be.ctx, &params, g.h, g_lagrange.h, cols.as_ptr(), copies.as_ptr().cast(), copies.len(), &mut pk),
             }
         })?;
         // from here on `key`'s Drop frees the handle on every early return and on a panic inside the caller's `transcript_repr`
-        let key = Self { be, pk, params, phased, shape, _g: g, _g_lagrange: g_lagrange };
+        let key = Self { be, pk, params, phased, rlc, shape, _g: g, _g_lagrange: g_lagrange };
         let mut fc = vec![G1Affine::default(); shape.num_fixed_total as usize];
         let mut pc = vec![G1Affine::default(); (shape.num_perm_columns as usize).max(1)];
         check(unsafe { h2hip_plonk_pk_commitments(key.pk, fc.as_mut_ptr().cast(), pc.as_mut_ptr().cast()) })?;
@@ -441,6 +456,12 @@ impl<'b, 'g> ProvingKeyHip<'b, 'g> {
     /// first `max_failures` of them in canonical order (gate, lookup, copy; by column, then row).
     pub fn check_witness(&self, advice: &[Vec<Fr>], instances: &[&[Fr]], max_failures: usize)
                          -> Result<(usize, Vec<h2hip_witness_failure>), HipError> {
+        self.check_witness_challenges(advice, instances, &[], max_failures)
+    }
+    /// the same with the phases' challenges (squeeze order): a key with RLC columns needs challenge 0, with which its RLC gates are checked
+    /// (h2hip_plonk_check_witness_challenges); without challenges this is h2hip_plonk_check_witness.
+    pub fn check_witness_challenges(&self, advice: &[Vec<Fr>], instances: &[&[Fr]], challenges: &[Fr], max_failures: usize)
+                                    -> Result<(usize, Vec<h2hip_witness_failure>), HipError> {
         if advice.len() != self.shape.num_advice_total as usize {
             return Err(invalid(format!("check_witness: {} advice columns, the key has {}", advice.len(), self.shape.num_advice_total)));
         }
@@ -455,9 +476,14 @@ impl<'b, 'g> ProvingKeyHip<'b, 'g> {
         let lens: Vec<usize> = instances.iter().map(|c| c.len()).collect();
         let mut out = vec![h2hip_witness_failure::default(); max_failures];
         let mut total = 0usize;
+        let out_ptr = if max_failures == 0 { ptr::null_mut() } else { out.as_mut_ptr() };
         check(unsafe {
-            h2hip_plonk_check_witness(self.be.ctx, self.pk, adv.as_ptr(), 0, ins.as_ptr(), lens.as_ptr(),
-                                      if max_failures == 0 { ptr::null_mut() } else { out.as_mut_ptr() }, max_failures, &mut total)
+            if challenges.is_empty() {
+                h2hip_plonk_check_witness(self.be.ctx, self.pk, adv.as_ptr(), 0, ins.as_ptr(), lens.as_ptr(), out_ptr, max_failures, &mut total)
+            } else {
+                h2hip_plonk_check_witness_challenges(self.be.ctx, self.pk, adv.as_ptr(), 0, ins.as_ptr(), lens.as_ptr(), challenges.as_ptr().cast(),
+                                                     challenges.len(), out_ptr, max_failures, &mut total)
+            }
         })?;
         out.truncate(total.min(max_failures));
         Ok((total, out))
@@ -477,7 +503,8 @@ impl<'b, 'g> ProvingKeyHip<'b, 'g> {
     /// `create_proof(params, pk, &[circuit], &[instances], rng, &mut transcript)` after synthesis: returns what
     /// `transcript.finalize()` would.  `rng_fill` is called for every batch of `Fr::random(rng)` draws, in upstream's order.
     /// `advice` holds phase 0's columns; `later_phases(phase, challenges)` synthesises every later phase's columns (gate columns, then
-    /// lookup-advice columns, index order) from the challenges squeezed so far — where halo2-axiom's create_proof runs the next phase's synthesis.
+    /// lookup-advice columns, index order; a key with RLC columns: phase 1's list ends with them) from the challenges squeezed so far — where
+    /// halo2-axiom's create_proof runs the next phase's synthesis.
     pub fn create_proof<R: FnMut(&mut [Fr]), W: FnMut(u32, &[Fr]) -> Result<Vec<Vec<Fr>>, E>, E: std::fmt::Display>(
         &self, advice: &[Vec<Fr>], instances: &[&[Fr]], mut rng_fill: R, later_phases: W) -> Result<Vec<u8>, HipError> {
         unsafe extern "C" fn trampoline<R: FnMut(&mut [Fr])>(user: *mut c_void, out: *mut c_void, n: usize) {
@@ -563,15 +590,18 @@ impl<'b, 'g> ProvingKeyHip<'b, 'g> {
 }
 /// `verify_proof(params, vk, SingleStrategy::new(params), &[instances], &mut Blake2bRead::init(proof))` (check_proof,
 /// halo2-base/src/utils/testing.rs:64-88): `g1` = params.get_g()[0], `g2` / `s_g2` = the verifier half of the SRS in RawBytes form.
-/// `phases`: as for `ProvingKeyHip::keygen` (a circuit with more than one phase or with challenges goes through h2hip_plonk_verify_proof_phased).
+/// `phases`: as for `ProvingKeyHip::keygen` (a circuit with more than one phase or with challenges goes through h2hip_plonk_verify_proof_phased,
+/// one with RLC columns through h2hip_plonk_verify_proof_rlc).
 pub fn verify_proof(params: h2hip_base_circuit_params, phases: &PhaseCounts, fixed_commitments: &[G1Affine], permutation_commitments: &[G1Affine],
                     transcript_repr: Fr, g1: G1Affine, g2: &[u8; 128], s_g2: &[u8; 128], instances: &[&[Fr]], proof: &[u8]) -> Result<bool, HipError> {
     let phased = if phases.is_first_phase_only() { None } else { Some(phases.to_c(&params)?) };
+    let rlc = phases.to_c_rlc(&params)?;
     // the C side reads num_fixed_total / num_perm_columns commitments and num_instance instance arrays: check the slices first
     let mut shape = h2hip_plonk_shape::default();
-    match &phased {
-        Some(pp) => check(unsafe { h2hip_plonk_shape_of_phased(pp, &mut shape) })?,
-        None => check(unsafe { h2hip_plonk_shape_of(&params, &mut shape) })?,
+    match (&rlc, &phased) {
+        (Some(rp), _) => check(unsafe { h2hip_plonk_shape_of_rlc(rp, &mut shape) })?,
+        (None, Some(pp)) => check(unsafe { h2hip_plonk_shape_of_phased(pp, &mut shape) })?,
+        (None, None) => check(unsafe { h2hip_plonk_shape_of(&params, &mut shape) })?,
     }
     if fixed_commitments.len() != shape.num_fixed_total as usize || permutation_commitments.len() != shape.num_perm_columns as usize {
         return Err(invalid(format!("verify_proof: {} fixed / {} permutation commitments, the shape has {} / {}", fixed_commitments.len(),
@@ -584,11 +614,14 @@ pub fn verify_proof(params: h2hip_base_circuit_params, phases: &PhaseCounts, fix
     let lens: Vec<usize> = instances.iter().map(|c| c.len()).collect();
     let mut ok: c_int = 0;
     check(unsafe {
-        match &phased {
-            Some(pp) => h2hip_plonk_verify_proof_phased(pp, fixed_commitments.as_ptr().cast(), permutation_commitments.as_ptr().cast(),
+        match (&rlc, &phased) {
+            (Some(rp), _) => h2hip_plonk_verify_proof_rlc(rp, fixed_commitments.as_ptr().cast(), permutation_commitments.as_ptr().cast(),
+                                                          fr_ptr(&transcript_repr), (&g1 as *const G1Affine).cast(), g2.as_ptr().cast(), s_g2.as_ptr().cast(),
+                                                          ins.as_ptr(), lens.as_ptr(), proof.as_ptr(), proof.len(), &mut ok),
+            (None, Some(pp)) => h2hip_plonk_verify_proof_phased(pp, fixed_commitments.as_ptr().cast(), permutation_commitments.as_ptr().cast(),
                                                         fr_ptr(&transcript_repr), (&g1 as *const G1Affine).cast(), g2.as_ptr().cast(), s_g2.as_ptr().cast(),
                                                         ins.as_ptr(), lens.as_ptr(), proof.as_ptr(), proof.len(), &mut ok),
-            None => h2hip_plonk_verify_proof(&params, fixed_commitments.as_ptr().cast(), permutation_commitments.as_ptr().cast(), fr_ptr(&transcript_repr),
+            (None, None) => h2hip_plonk_verify_proof(&params, fixed_commitments.as_ptr().cast(), permutation_commitments.as_ptr().cast(), fr_ptr(&transcript_repr),
                                              (&g1 as *const G1Affine).cast(), g2.as_ptr().cast(), s_g2.as_ptr().cast(), ins.as_ptr(), lens.as_ptr(),
                                              proof.as_ptr(), proof.len(), &mut ok),
         }

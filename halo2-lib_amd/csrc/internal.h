@@ -340,7 +340,7 @@ int comm_reserve_alltoall_dev(h2hip_comm *c, size_t bytes);
 // plonk.hip: the multi-phase layout (Shape::init_phased, plonk_internal.h) for the verifier: the shape, each used phase's advice columns and challenges, whether
 // the key is multi-phase at all (otherwise it proves as the BaseConfig of `bp`), and the BaseCircuitParams of the gate / lookup-advice totals
 int plonk_phased_layout(const h2hip_phased_circuit_params &pp, h2hip_plonk_shape *shape, std::vector<std::vector<int>> *phase_cols,
-                        uint32_t challenges[H2HIP_MAX_PHASE], bool *phased, h2hip_base_circuit_params *bp);
+                        uint32_t challenges[H2HIP_MAX_PHASE], bool *phased, h2hip_base_circuit_params *bp, const h2hip_rlc_circuit_params *rlc = nullptr);   // rlc: the RLC configuration's layout instead (pp unused)
 int msm_reduce_cols(h2hip_ctx *ctx, const h2hip_bases *bases, uint32_t window_bits, const XYZZ29 *buckets, uint32_t ncols, XYZZ *out_dev);
 // lookup.hip: the key count a sort of u keys pads to (a power of two, at least one tile), and the bitonic network over N = lookup_padded_keys(u)
 // caller-made 32-byte keys (ascending by limb 7 .. 0; the caller pads with all-ones)
@@ -353,6 +353,8 @@ struct WitnessCheckJob {
     std::vector<const Fr *> cols;               // every column's values on the device
     std::vector<uint32_t> gate_adv, gate_q;     // per gate column: its advice column, its q_enable (flat indices)
     std::vector<uint32_t> gate_report;          // per gate column: the advice index a failure names
+    uint32_t num_rlc_gates = 0;                 // the LAST num_rlc_gates entries of the gate lists are RLC gates: q * (a[r] * rlc_gamma + a[r+1] - a[r+2])
+    Fr rlc_gamma;
     std::vector<uint32_t> lk_in, lk_q;          // range lookups: the input column, the complex selector (WC_NONE: none) per lookup
     const void *table_sorted = nullptr;         // range lookups: the table's sorted canonical keys (h2hip_lookup_table_sort_dev)
     uint32_t dyn_width = 0;                     // dynamic lookups: columns per tuple (0: range lookups)

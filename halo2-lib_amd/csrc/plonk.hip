@@ -207,17 +207,37 @@ int h2hip_plonk_shape_of_phased(const h2hip_phased_circuit_params *params, h2hip
     return H2HIP_OK;
 }
 
+int h2hip_plonk_shape_of_rlc(const h2hip_rlc_circuit_params *params, h2hip_plonk_shape *out) {
+    H2_REQUIRE(params && out, "NULL argument");
+    Shape sh;
+    H2_CHK(sh.init_rlc(*params));
+    fill_shape(sh, out);
+    return H2HIP_OK;
+}
+
 // Shape::init gives every gate column's q_enable selector a fixed column of its own.  Upstream's compress_selectors [UPSTREAM-RECALL] would
 // instead COMBINE simple selectors that are never enabled on a common row (as far as the degree bound allows) — e.g. a gate column that the
 // circuit left empty — which changes the number of fixed columns, the verifying key and the proof size.  Such circuits are rejected here
 // rather than proven against a key halo2 would not derive: every pair of q_enable columns must share an enabled row.
+// The rule covers the union of the q_enable and the q_rlc columns (simple selectors alike); a = 0 .. num_advice - 1 names a gate column, the
+// indices behind them the RLC columns.  A q_rlc enabled where the gate would read blinding rows is rejected here too.
 static int check_selectors_stay_apart(const Shape &sh, const void *const *fixed_host) {
-    const uint32_t na = sh.p.num_advice;
-    if (na < 2) return H2HIP_OK;
+    const uint32_t ng = sh.p.num_advice, na = ng + sh.num_rlc;
     const size_t words = (sh.n + 63) / 64;
+    for (uint32_t j = 0; j < sh.num_rlc; ++j) {
+        const Fr *col = (const Fr *)fixed_host[sh.first_q_rlc_col + (int)j];
+        H2_REQUIRE(col, "NULL fixed column");
+        for (size_t r = sh.usable_rows >= 2 ? sh.usable_rows - 2 : 0; r < sh.usable_rows; ++r)
+            if (!col[r].is_zero()) {
+                set_error("h2hip_plonk_keygen_rlc: q_rlc of RLC column %u is enabled on row %zu, but the gate reads rows r .. r + 2 and only %u rows are usable", j, r,
+                          sh.usable_rows);
+                return H2HIP_ERR_INVALID;
+            }
+    }
+    if (na < 2) return H2HIP_OK;
     std::vector<uint64_t> bits((size_t)na * words, 0);
     for (uint32_t a = 0; a < na; ++a) {
-        const Fr *col = (const Fr *)fixed_host[sh.first_q_enable_col + (int)a];
+        const Fr *col = (const Fr *)fixed_host[a < ng ? sh.first_q_enable_col + (int)a : sh.first_q_rlc_col + (int)(a - ng)];
         H2_REQUIRE(col, "NULL fixed column");
         for (size_t r = 0; r < sh.usable_rows; ++r)
             if (!col[r].is_zero()) bits[a * words + (r >> 6)] |= 1ull << (r & 63);
@@ -234,7 +254,8 @@ static int check_selectors_stay_apart(const Shape &sh, const void *const *fixed_
             for (size_t w = 0; w < words && !share; ++w) share = (bits[a * words + w] & bits[b * words + w]) != 0;
             if (!share) {
                 set_error("h2hip_plonk_keygen: the selectors of gate columns %u and %u are never enabled on a common row (an empty gate column?): "
-                          "halo2's selector compression would merge them into one fixed column, which this backend's fixed-column layout does not model", a, b);
+                          "halo2's selector compression would merge them into one fixed column, which this backend's fixed-column layout does not model%s", a, b,
+                          sh.num_rlc ? " (indices from the number of gate columns on name RLC columns)" : "");
                 return H2HIP_ERR_INVALID;
             }
         }
@@ -273,6 +294,14 @@ int h2hip_plonk_keygen_phased(h2hip_ctx *ctx, const h2hip_phased_circuit_params 
     H2_REQUIRE(ctx && params && g && g_lagrange && fixed_host && out && (ncopies == 0 || copies), "NULL argument");
     h2hip_plonk_pk *pk = new h2hip_plonk_pk();
     return keygen_common(ctx, pk, g, g_lagrange, fixed_host, copies, ncopies, pk->sh.init_phased(*params), out);
+}
+
+int h2hip_plonk_keygen_rlc(h2hip_ctx *ctx, const h2hip_rlc_circuit_params *params, const h2hip_bases *g, const h2hip_bases *g_lagrange,
+                           const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && params && g && g_lagrange && fixed_host && out && (ncopies == 0 || copies), "NULL argument");
+    h2hip_plonk_pk *pk = new h2hip_plonk_pk();
+    return keygen_common(ctx, pk, g, g_lagrange, fixed_host, copies, ncopies, pk->sh.init_rlc(*params), out);
 }
 
 static int keygen_common(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const h2hip_bases *g, const h2hip_bases *g_lagrange, const void *const *fixed_host,
@@ -514,21 +543,40 @@ int h2hip_plonk_create_proof_phased(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const vo
 }
 
 // MockProver's verdict on the GPU (include/h2hip.h): the key's layout as a WitnessCheckJob for witness_check.hip
+static int check_witness_entry(h2hip_ctx *ctx, const h2hip_plonk_pk *pk_in, const void *const *advice, int advice_on_device,
+                               const void *const *instances_host, const size_t *instance_lens, const Fr *challenge0, h2hip_witness_failure *failures_out,
+                               size_t max_failures, size_t *num_failures);
 int h2hip_plonk_check_witness(h2hip_ctx *ctx, const h2hip_plonk_pk *pk_in, const void *const *advice, int advice_on_device,
                               const void *const *instances_host, const size_t *instance_lens, h2hip_witness_failure *failures_out,
                               size_t max_failures, size_t *num_failures) {
+    H2_REQUIRE(!pk_in || !pk_in->sh.num_rlc, "the key has RLC gates, which query a challenge (use h2hip_plonk_check_witness_challenges)");
+    return check_witness_entry(ctx, pk_in, advice, advice_on_device, instances_host, instance_lens, nullptr, failures_out, max_failures, num_failures);
+}
+int h2hip_plonk_check_witness_challenges(h2hip_ctx *ctx, const h2hip_plonk_pk *pk_in, const void *const *advice, int advice_on_device,
+                                         const void *const *instances_host, const size_t *instance_lens, const void *challenges_fr,
+                                         size_t num_challenges, h2hip_witness_failure *failures_out, size_t max_failures, size_t *num_failures) {
+    H2_REQUIRE(num_challenges == 0 || challenges_fr, "NULL argument");
+    H2_REQUIRE(!pk_in || !pk_in->sh.num_rlc || num_challenges >= 1, "the key's RLC gates need challenge 0");
+    Fr c0 = Fr::zero();
+    if (num_challenges) c0 = ld_fr(challenges_fr);
+    return check_witness_entry(ctx, pk_in, advice, advice_on_device, instances_host, instance_lens, num_challenges ? &c0 : nullptr, failures_out, max_failures,
+                               num_failures);
+}
+static int check_witness_entry(h2hip_ctx *ctx, const h2hip_plonk_pk *pk_in, const void *const *advice, int advice_on_device,
+                               const void *const *instances_host, const size_t *instance_lens, const Fr *challenge0, h2hip_witness_failure *failures_out,
+                               size_t max_failures, size_t *num_failures) {
     H2_DEVICE_GUARD(ctx);
-    H2_REQUIRE(ctx && pk_in && advice && num_failures, "NULL argument");
-    H2_REQUIRE(failures_out || max_failures == 0, "failures_out is NULL and max_failures > 0");
+    H2_REQUIRE_AS("h2hip_plonk_check_witness", ctx && pk_in && advice && num_failures, "NULL argument");
+    H2_REQUIRE_AS("h2hip_plonk_check_witness", failures_out || max_failures == 0, "failures_out is NULL and max_failures > 0");
     h2hip_plonk_pk *pk = const_cast<h2hip_plonk_pk *>(pk_in);   // (its buffer pool and the one-time upload of the cycles)
-    H2_REQUIRE(pk->ctx == ctx, "the proving key belongs to another context");
+    H2_REQUIRE_AS("h2hip_plonk_check_witness", pk->ctx == ctx, "the proving key belongs to another context");
     const Shape &sh = pk->sh;
     const uint32_t n = sh.n, u = sh.usable_rows, F = sh.num_fixed_total, A = sh.num_advice_total, I = sh.p.num_instance;
-    H2_REQUIRE(I == 0 || instance_lens, "instance_lens is required");
-    for (uint32_t c = 0; c < A; ++c) H2_REQUIRE(advice[c], "NULL advice column");
+    H2_REQUIRE_AS("h2hip_plonk_check_witness", I == 0 || instance_lens, "instance_lens is required");
+    for (uint32_t c = 0; c < A; ++c) H2_REQUIRE_AS("h2hip_plonk_check_witness", advice[c], "NULL advice column");
     for (uint32_t i = 0; i < I; ++i) {
-        H2_REQUIRE(instance_lens[i] <= u, "InstanceTooLarge");
-        H2_REQUIRE(instance_lens[i] == 0 || (instances_host && instances_host[i]), "NULL instance column");
+        H2_REQUIRE_AS("h2hip_plonk_check_witness", instance_lens[i] <= u, "InstanceTooLarge");
+        H2_REQUIRE_AS("h2hip_plonk_check_witness", instance_lens[i] == 0 || (instances_host && instances_host[i]), "NULL instance column");
     }
     *num_failures = 0;
     hipStream_t st = ctx->stream;
@@ -580,6 +628,13 @@ int h2hip_plonk_check_witness(h2hip_ctx *ctx, const h2hip_plonk_pk *pk_in, const
             job.gate_adv.push_back(F + sh.first_gate_advice + g);
             job.gate_q.push_back((uint32_t)sh.first_q_enable_col + g);
         }
+        for (uint32_t j = 0; j < sh.num_rlc; ++j) {   // behind the flex gates, as the prover folds them
+            job.gate_report.push_back(sh.first_rlc_advice + j);
+            job.gate_adv.push_back(F + sh.first_rlc_advice + j);
+            job.gate_q.push_back((uint32_t)sh.first_q_rlc_col + j);
+        }
+        job.num_rlc_gates = sh.num_rlc;
+        if (sh.num_rlc) job.rlc_gamma = *challenge0;
         job.num_lookups = (uint32_t)sh.lookups.size();
         if (sh.dyn) {
             job.dyn_width = sh.key_cols + 1;
@@ -608,9 +663,9 @@ int h2hip_plonk_check_witness(h2hip_ctx *ctx, const h2hip_plonk_pk *pk_in, const
 
 // (declared in internal.h: the verifier reads the multi-phase layout from here)
 int h2::plonk_phased_layout(const h2hip_phased_circuit_params &pp, h2hip_plonk_shape *shape, std::vector<std::vector<int>> *phase_cols,
-                        uint32_t challenges[H2HIP_MAX_PHASE], bool *phased, h2hip_base_circuit_params *bp) {
+                        uint32_t challenges[H2HIP_MAX_PHASE], bool *phased, h2hip_base_circuit_params *bp, const h2hip_rlc_circuit_params *rlc) {
     Shape sh;
-    H2_CHK(sh.init_phased(pp));
+    H2_CHK(rlc ? sh.init_rlc(*rlc) : sh.init_phased(pp));
     fill_shape(sh, shape);
     *phased = sh.phased;
     *bp = sh.p;

@@ -39,6 +39,9 @@ struct Shape {
     bool phased = false;           // multi-phase BaseConfig (init_phased) with more than one used phase or a challenge
     std::vector<std::vector<int>> phase_cols;   // phased: the advice columns of every used phase, index order (gate, then lookup advice)
     uint32_t phase_challenges[H2HIP_MAX_PHASE] = {0, 0, 0};   // phased: challenges squeezed after each phase's commitments
+    uint32_t num_rlc = 0;          // RLC columns (init_rlc): phase-1 advice columns behind every BaseConfig column, gate q_rlc * (a0 * gamma + a1 - a2)
+    uint32_t first_rlc_advice = 0; // advice index of RLC column 0
+    int first_q_rlc_col = -1;      // fixed column of RLC column 0's selector
     int table_col = -1, q_lookup_col = -1, first_constant_col = -1, first_q_enable_col = -1;
     uint32_t num_advice_total, num_fixed_total;
     std::vector<Lookup> lookups;
@@ -73,24 +76,31 @@ struct Shape {
         if (single) q_lookup_col = nf++;
         first_q_enable_col = nf;
         nf += (int)bp.num_advice;
+        if (num_rlc) first_q_rlc_col = nf;   // the RLC selectors are created after BaseConfig's
+        nf += (int)num_rlc;
         num_fixed_total = (uint32_t)nf;
-        num_advice_total = bp.num_advice + nla;
+        first_rlc_advice = bp.num_advice + nla;
+        num_advice_total = bp.num_advice + nla + num_rlc;
         if (single) lookups.push_back({q_lookup_col, 0, table_col});
         for (uint32_t i = 0; i < nla; ++i) lookups.push_back({-1, (int)(bp.num_advice + i), table_col});
         // enable_equality order: constants, gate advice, lookup advice, instance
         for (uint32_t i = 0; i < bp.num_fixed; ++i) perm_columns.push_back({0, first_constant_col + (int)i});
-        for (uint32_t i = 0; i < num_advice_total; ++i) perm_columns.push_back({1, (int)i});
+        for (uint32_t i = 0; i < first_rlc_advice; ++i) perm_columns.push_back({1, (int)i});
         for (uint32_t i = 0; i < bp.num_instance; ++i) perm_columns.push_back({2, (int)i});
+        for (uint32_t i = 0; i < num_rlc; ++i) perm_columns.push_back({1, (int)(first_rlc_advice + i)});   // enable_equality is called on them last
         for (uint32_t a = 0; a < bp.num_advice; ++a)
             for (int r = 0; r < 4; ++r) advice_queries.push_back({(int)a, r});
         for (uint32_t i = 0; i < nla; ++i) advice_queries.push_back({(int)(bp.num_advice + i), 0});
+        for (uint32_t i = 0; i < num_rlc; ++i)
+            for (int r = 0; r < 3; ++r) advice_queries.push_back({(int)(first_rlc_advice + i), r});
         for (uint32_t i = 0; i < bp.num_fixed; ++i) fixed_queries.push_back({first_constant_col + (int)i, 0});
         if (with_range) fixed_queries.push_back({table_col, 0});
         if (single) fixed_queries.push_back({q_lookup_col, 0});
         for (uint32_t i = 0; i < bp.num_advice; ++i) fixed_queries.push_back({first_q_enable_col + (int)i, 0});
-        degree = 3;   // gate and permutation argument
+        for (uint32_t i = 0; i < num_rlc; ++i) fixed_queries.push_back({first_q_rlc_col + (int)i, 0});
+        degree = 3;   // gate and permutation argument; the RLC gate is selector * degree 2 as well
         for (const Lookup &l : lookups) degree = std::max<uint32_t>(degree, std::max<uint32_t>(4, 2 + (l.q_col >= 0 ? 2 : 1) + 1));
-        blinding_factors = std::max<uint32_t>(3, 4) + 2;   // a gate column is queried at four rotations
+        blinding_factors = std::max<uint32_t>(3, 4) + 2;   // a gate column is queried at four rotations (an RLC column at three)
         H2_REQUIRE(n > blinding_factors + 8, "k too small for the blinding rows");
         usable_rows = n - (blinding_factors + 1);
         chunk_len = degree - 2;
@@ -151,8 +161,10 @@ struct Shape {
     }
     // FlexGateConfig / RangeConfig::configure with num_advice_per_phase / num_lookup_advice_per_phase (flex_gate/mod.rs:121-137,
     // range/mod.rs:87-108); include/h2hip.h states the layout.  One used phase and no challenge is init() of that phase's BaseCircuitParams.
-    int init_phased(const h2hip_phased_circuit_params &pp) {
+    // rlc != 0 (init_rlc): `rlc` RLC columns join phase 1 behind every column of this layout
+    int init_phased(const h2hip_phased_circuit_params &pp, uint32_t rlc = 0) {
         from_phased = true;
+        num_rlc = rlc;
         const uint32_t *g = pp.num_advice_per_phase, *la = pp.num_lookup_advice_per_phase;
         uint64_t G = 0, LA = 0, CH = 0;
         for (int ph = 0; ph < H2HIP_MAX_PHASE; ++ph) {
@@ -167,7 +179,7 @@ struct Shape {
         uint32_t ded[H2HIP_MAX_PHASE], cols[H2HIP_MAX_PHASE];
         for (int ph = 0; ph < H2HIP_MAX_PHASE; ++ph) {
             ded[ph] = !range || (ph == 0 && q_lookup) ? 0 : la[ph];   // range/mod.rs:93-95: later phases always get dedicated columns
-            cols[ph] = g[ph] + ded[ph];
+            cols[ph] = g[ph] + ded[ph] + (ph == 1 ? rlc : 0);
         }
         uint32_t used = 0;
         for (int ph = 0; ph < H2HIP_MAX_PHASE; ++ph) {
@@ -177,7 +189,7 @@ struct Shape {
             }
             H2_REQUIRE(!pp.num_challenges_per_phase[ph] || cols[ph], "a challenge follows a phase that has no advice column");
         }
-        if (used == 1 && CH == 0) {
+        if (used == 1 && CH == 0 && !rlc) {
             H2_CHK(init(h2hip_base_circuit_params{pp.k, g[0], la[0], pp.num_fixed, pp.num_instance, pp.lookup_bits}));
             phase_cols.push_back({});
             for (uint32_t c = 0; c < num_advice_total; ++c) phase_cols[0].push_back((int)c);
@@ -196,11 +208,28 @@ struct Shape {
             std::vector<int> c;
             for (uint32_t i = 0; i < g[ph]; ++i) c.push_back((int)(go + i));
             for (uint32_t i = 0; i < ded[ph]; ++i) c.push_back((int)(lo + i));
+            if (ph == 1)
+                for (uint32_t i = 0; i < rlc; ++i) c.push_back((int)(first_rlc_advice + i));
             go += g[ph];
             lo += ded[ph];
             phase_cols.push_back(c);
             phase_challenges[ph] = pp.num_challenges_per_phase[ph];
         }
+        return H2HIP_OK;
+    }
+    // BaseConfig::configure(base) followed by num_rlc_advice RLC columns (downstream's RlcConfig); include/h2hip.h states the layout
+    int init_rlc(const h2hip_rlc_circuit_params &rp) {
+        H2_REQUIRE(rp.num_rlc_advice >= 1 && rp.num_rlc_advice <= 64, "num_rlc_advice out of range (1..64; a circuit without RLC columns uses h2hip_phased_circuit_params)");
+        H2_REQUIRE(rp.base.num_challenges_per_phase[0] >= 1, "the RLC gate needs a challenge usable after phase 0 (num_challenges_per_phase[0] >= 1)");
+        H2_CHK(init_phased(rp.base, rp.num_rlc_advice));
+        // the gate has degree 2 + selector and three rotations: degree, extended_k and the blinding factors stay the base layout's
+        H2_REQUIRE(blinding_factors == 6, "internal: the RLC columns changed the blinding factors");
+        Shape base;
+        if (base.init_phased(rp.base) == H2HIP_OK)   // (a base that is only legal with phase 1's RLC columns has nothing to compare with)
+            H2_REQUIRE(degree == base.degree && extended_k == base.extended_k && blinding_factors == base.blinding_factors && usable_rows == base.usable_rows,
+                       "internal: the RLC gate changed the degree, the extended domain or the blinding factors of the base layout");
+        else
+            set_error("");
         return H2HIP_OK;
     }
     uint32_t num_commitments() const {

@@ -498,6 +498,7 @@ struct ProofRun {
     Fr *acc_loc = nullptr;                  // = acc, or (sharded quotient) [coset][n] numerators of this rank's cosets (max_cosets slots: the all-gather's send buffer)
     // ---- challenges
     Fr theta = Fr::zero(), beta, gamma, y, x;
+    std::vector<Fr> challenges;             // multi-phase keys: the phases' challenges in squeeze order ([0] is the RLC gates' gamma)
     // ---- evaluations -> SHPLONK
     std::vector<const Fr *> polys;          // SHPLONK's polynomial list; Query.poly indexes it
     std::vector<Query> queries;             // the multiopen's queries in upstream's order
@@ -806,7 +807,6 @@ struct ProofRun {
     // the phase's challenges, then the next phase's witness from the caller (at a quiescent point: only the points made the round
     // trip) and its blinding rows.  The range lookups' permuted columns wait for the last phase and go out after theta, as upstream's.
     int round1_phased(const std::vector<const void *> &lookup_cols) {
-        std::vector<Fr> challenges;
         for (size_t ph = 0; ph < sh.phase_cols.size(); ++ph) {
             const std::vector<int> &pcols = sh.phase_cols[ph];
             if (ph > 0) {
@@ -1223,6 +1223,15 @@ struct ProofRun {
                 ga[a] = adv[sh.first_gate_advice + a].coset + off;
             }
             H2_CHK(h2hip_quotient_flex_gate_batch_dev(ctx, acc_loc + off, gq.data(), ga.data(), gq.size(), ek_, k, &y));
+        }
+        if (sh.num_rlc) {   // the RLC gates follow the flex gates in the constraint system's gate list
+            H2_REQUIRE(!challenges.empty(), "internal: an RLC key without a challenge");
+            std::vector<const void *> gq(sh.num_rlc), ga(sh.num_rlc);
+            for (uint32_t j = 0; j < sh.num_rlc; ++j) {
+                gq[j] = fixed_cos(sh.first_q_rlc_col + (int)j) + off;
+                ga[j] = adv[sh.first_rlc_advice + j].coset + off;
+            }
+            H2_CHK(h2hip_quotient_rlc_gate_batch_dev(ctx, acc_loc + off, gq.data(), ga.data(), gq.size(), ek_, k, &challenges[0], &y));
         }
         if (products_join_late) {
             products_join_late = false;

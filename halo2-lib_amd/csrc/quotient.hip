@@ -91,6 +91,25 @@ __global__ __launch_bounds__(256) void quotient_flex_gate_batch_kernel(Fr *__res
         acc[i] = v;
     }
 }
+// the RLC gate, q * (a * gamma + a(wX) - a(w^2 X)): one product by a constant and one by the selector per column, the same grid policy
+struct RlcGateBatchArgs {
+    const Fr *q[GATE_BATCH], *a[GATE_BATCH];
+    uint32_t count;
+    Fr gamma, y;
+};
+__global__ __launch_bounds__(256) void quotient_rlc_gate_batch_kernel(Fr *__restrict__ acc, RlcGateBatchArgs g, size_t n_ext, uint32_t rot_step) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x, mask = n_ext - 1;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_ext; i += stride) {
+        const size_t i1 = (i + rot_step) & mask, i2 = (i + 2 * (size_t)rot_step) & mask;
+        Fr v = acc[i];
+        for (uint32_t j = 0; j < g.count; ++j) {
+            const Fr *__restrict__ a = g.a[j];
+            Fr t = fe_mul(g.q[j][i], fe_sub(fe_add(fe_mul(a[i], g.gamma), a[i1]), a[i2]));
+            v = fe_add(fe_mul(v, g.y), t);
+        }
+        acc[i] = v;
+    }
+}
 struct LookupJob {
     const Fr *z, *a, *s, *ap, *sp;
 };
@@ -274,6 +293,26 @@ static int quotient_gates_run(h2hip_ctx *ctx, Fr *acc, const void *const *q, con
                                1u << (ext_k - k));
         else
             hipLaunchKernelGGL(quotient_flex_gate_batch_kernel, dim3(grid_for(ctx, n_ext)), dim3(256), 0, ctx->stream, acc, g, n_ext, 1u << (ext_k - k));
+        prof_end(ctx);
+    }
+    H2_HIPCHK(hipGetLastError());
+    return H2HIP_OK;
+}
+static int quotient_rlc_gates_run(h2hip_ctx *ctx, Fr *acc, const void *const *q, const void *const *a, size_t count, uint32_t ext_k, uint32_t k, const Fr &gamma,
+                                  const Fr &y) {
+    const size_t n_ext = (size_t)1 << ext_k;
+    for (size_t j0 = 0; j0 < count; j0 += GATE_BATCH) {
+        RlcGateBatchArgs g;
+        memset(&g, 0, sizeof(g));
+        g.count = (uint32_t)(count - j0 < GATE_BATCH ? count - j0 : GATE_BATCH);
+        g.gamma = gamma;
+        g.y = y;
+        for (uint32_t j = 0; j < g.count; ++j) {
+            g.q[j] = (const Fr *)q[j0 + j];
+            g.a[j] = (const Fr *)a[j0 + j];
+        }
+        prof_begin(ctx, "quotient_rlc_gate_batch_kernel");
+        hipLaunchKernelGGL(quotient_rlc_gate_batch_kernel, dim3(grid_for(ctx, n_ext)), dim3(256), 0, ctx->stream, acc, g, n_ext, 1u << (ext_k - k));
         prof_end(ctx);
     }
     H2_HIPCHK(hipGetLastError());
@@ -488,6 +527,14 @@ int h2hip_quotient_flex_gate_batch_dev(h2hip_ctx *ctx, void *acc, const void *co
     H2_REQUIRE(k <= ext_k && ext_k <= 28, "need k <= ext_k <= 28");
     for (size_t j = 0; j < count; ++j) H2_REQUIRE(q[j] && a[j], "NULL column");
     return quotient_gates_run(ctx, (Fr *)acc, q, a, count, ext_k, k, ld_fr(y));
+}
+int h2hip_quotient_rlc_gate_batch_dev(h2hip_ctx *ctx, void *acc, const void *const *q, const void *const *a, size_t count, uint32_t ext_k, uint32_t k,
+                                      const void *gamma, const void *y) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && acc && gamma && y && (count == 0 || (q && a)), "NULL argument");
+    H2_REQUIRE(k <= ext_k && ext_k <= 28, "need k <= ext_k <= 28");
+    for (size_t j = 0; j < count; ++j) H2_REQUIRE(q[j] && a[j] && q[j] != acc && a[j] != acc, "NULL column, or a column that aliases acc");
+    return quotient_rlc_gates_run(ctx, (Fr *)acc, q, a, count, ext_k, k, ld_fr(gamma), ld_fr(y));
 }
 int h2hip_quotient_lookups_dev(h2hip_ctx *ctx, void *acc, const void *const *z, const void *const *a, const void *const *s, const void *const *a_perm,
                                const void *const *s_perm, size_t count, const void *l0, const void *l_last, const void *l_blind, uint32_t ext_k, uint32_t k,

@@ -510,14 +510,16 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
         for (const Fr &v : inst[i]) tr.common_scalar(v);
     }
     std::vector<G1Affine> advice_comm(sh.num_advice_total);
+    std::vector<Fr> challenges;
     if (vs.phase_cols.empty()) {
         for (auto &c : advice_comm) c = tr.read_point();
-    } else {   // phase by phase, each followed by its challenges (gates and lookups query none: squeezed for the transcript only)
+    } else {   // phase by phase, each followed by its challenges (only the RLC gates query one, challenge 0)
         for (size_t ph = 0; ph < vs.phase_cols.size(); ++ph) {
             for (int c : vs.phase_cols[ph]) advice_comm[c] = tr.read_point();
-            for (uint32_t i = 0; i < vs.phase_challenges[ph]; ++i) (void)tr.squeeze_challenge();
+            for (uint32_t i = 0; i < vs.phase_challenges[ph]; ++i) challenges.push_back(tr.squeeze_challenge());
         }
     }
+    if (!vs.rlc_gates.empty() && challenges.empty()) return H2HIP_OK;   // (vshape_rlc requires the challenge)
     const Fr theta = tr.squeeze_challenge();
     std::vector<G1Affine> lk_a_comm(sh.num_lookups), lk_s_comm(sh.num_lookups), lk_z_comm(sh.num_lookups), permz_comm(sh.num_perm_sets);
     for (uint32_t i = 0; i < sh.num_lookups; ++i) {
@@ -616,6 +618,10 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
     for (const auto &g : vs.gates) {
         const int a = g.second;
         fold(fe_mul(fixed_ev[g.first], fe_sub(fe_add(adv_at(a, 0), fe_mul(adv_at(a, 1), adv_at(a, 2))), adv_at(a, 3))));
+    }
+    for (const auto &g : vs.rlc_gates) {
+        const int a = g.second;
+        fold(fe_mul(fixed_ev[g.first], fe_sub(fe_add(fe_mul(adv_at(a, 0), challenges[0]), adv_at(a, 1)), adv_at(a, 2))));
     }
     if (sh.num_perm_sets) {
         fold(fe_mul(l_0, fe_sub(one, perm_ev[0].e0)));
@@ -845,6 +851,27 @@ int vshape_phased(const h2hip_phased_circuit_params *params, VShape &vs) {
     base_vshape(vs, bp.k, bp.num_advice, bp.num_fixed, bp.num_instance);
     return H2HIP_OK;
 }
+// the RLC configuration (include/h2hip.h states its layout): the multi-phase layout of `base` with the RLC columns' queries, selectors, gates
+// and permutation columns behind it
+int vshape_rlc(const h2hip_rlc_circuit_params *params, VShape &vs) {
+    h2hip_base_circuit_params bp;
+    bool phased = false;
+    H2_CHK(plonk_phased_layout(params->base, &vs.sh, &vs.phase_cols, vs.phase_challenges, &phased, &bp, params));
+    const uint32_t R = params->num_rlc_advice;
+    h2hip_plonk_shape base_sh = vs.sh;   // base_vshape reads the column counts: what the layout has without the RLC columns
+    base_sh.num_advice_total -= R;
+    std::swap(vs.sh, base_sh);
+    base_vshape(vs, bp.k, bp.num_advice, bp.num_fixed, bp.num_instance);
+    std::swap(vs.sh, base_sh);
+    const int first_adv = (int)(vs.sh.num_advice_total - R), first_q = (int)(vs.sh.num_fixed_total - R);
+    for (uint32_t j = 0; j < R; ++j) {
+        for (int r = 0; r < 3; ++r) vs.adv_q.push_back({first_adv + (int)j, r});
+        vs.fixed_q.push_back(first_q + (int)j);
+        vs.perm.push_back({1, first_adv + (int)j});
+        vs.rlc_gates.push_back({first_q + (int)j, first_adv + (int)j});
+    }
+    return H2HIP_OK;
+}
 
 }  // namespace verifier
 }  // namespace h2
@@ -887,6 +914,19 @@ int h2hip_plonk_verify_proof_phased(const h2hip_phased_circuit_params *params, c
     *accepted = 0;
     VShape vs;
     H2_CHK(vshape_phased(params, vs));
+    return verify_one(vs, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, instances_host, instance_lens, proof, proof_len,
+                      accepted);
+}
+
+// the same for the RLC configuration (include/h2hip.h states its layout): as the multi-phase verifier, with challenge 0 of the replay in the
+// RLC gates' terms of the quotient identity
+int h2hip_plonk_verify_proof_rlc(const h2hip_rlc_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
+                                 const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
+                                 const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted) {
+    H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
+    *accepted = 0;
+    VShape vs;
+    H2_CHK(vshape_rlc(params, vs));
     return verify_one(vs, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, instances_host, instance_lens, proof, proof_len,
                       accepted);
 }

@@ -28,6 +28,7 @@ struct VShape {
     std::vector<int> fixed_q;                 // fixed columns, queried at the current row
     std::vector<VCol> perm;
     std::vector<std::pair<int, int>> gates;   // (q_enable fixed column, advice column): q * (a + b*c - d) at rotations 0..3
+    std::vector<std::pair<int, int>> rlc_gates;   // (q_rlc fixed column, advice column): q * (a * challenge 0 + a(wX) - a(w^2 X)), folded behind `gates`
     std::vector<std::vector<VExpr>> lk_in, lk_tab;
     std::vector<std::vector<int>> phase_cols;   // multi-phase: the advice columns of each phase, whose commitments come phase by phase
     uint32_t phase_challenges[H2HIP_MAX_PHASE] = {0, 0, 0};
@@ -36,6 +37,7 @@ struct VShape {
 int vshape_base(const h2hip_base_circuit_params *params, VShape &vs);
 int vshape_dyn(const h2hip_dyn_circuit_params *params, VShape &vs);
 int vshape_phased(const h2hip_phased_circuit_params *params, VShape &vs);
+int vshape_rlc(const h2hip_rlc_circuit_params *params, VShape &vs);
 
 // the verifying key and the SRS elements, as the entry points receive them
 struct VKey {

@@ -23,17 +23,21 @@ struct alignas(16) WcKey {   // a 32-byte sort key, compared from limb 7 down (l
 
 __device__ __forceinline__ void wc_flag(uint32_t *mask, size_t unit) { atomicAdd(&mask[unit >> 5], 1u << (unit & 31)); }
 
-// GATE: q * (a[r] + b[r+1] * c[r+2] - d[r+3]) on gate column blockIdx.y (flex_gate/mod.rs:80-91, the prover's quotient term)
+// GATE: q * (a[r] + b[r+1] * c[r+2] - d[r+3]) on gate column blockIdx.y (flex_gate/mod.rs:80-91, the prover's quotient term); the gates from
+// first_rlc on are RLC gates, q * (a[r] * gamma + a[r+1] - a[r+2])
 __global__ __launch_bounds__(WC_THREADS) void wc_gate_kernel(const Fr *const *__restrict__ cols, const uint32_t *__restrict__ gate_adv,
-                                                            const uint32_t *__restrict__ gate_q, uint32_t u, uint32_t stride, uint32_t *mask) {
+                                                            const uint32_t *__restrict__ gate_q, uint32_t u, uint32_t stride, uint32_t *mask,
+                                                            uint32_t first_rlc, Fr gamma) {
     const uint32_t g = blockIdx.y, r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= u) return;
     const Fr q = cols[gate_q[g]][r];
     if (q.is_zero()) return;
-    bool fail = true;   // rows r + 3 >= u reach the blinding rows
-    if (r + 3 < u) {
+    const uint32_t last = g >= first_rlc ? 2 : 3;
+    bool fail = true;   // rows r + last >= u reach the blinding rows
+    if (r + last < u) {
         const Fr *__restrict__ a = cols[gate_adv[g]];
-        const Fr e = fe_mul(q, fe_sub(fe_add(a[r], fe_mul(a[r + 1], a[r + 2])), a[r + 3]));
+        const Fr e = g >= first_rlc ? fe_mul(q, fe_sub(fe_add(fe_mul(a[r], gamma), a[r + 1]), a[r + 2]))
+                                    : fe_mul(q, fe_sub(fe_add(a[r], fe_mul(a[r + 1], a[r + 2])), a[r + 3]));
         fail = !e.is_zero();
     }
     if (fail) wc_flag(mask, (size_t)g * stride + r);
@@ -231,7 +235,8 @@ int witness_check_run(h2hip_ctx *ctx, const WitnessCheckJob &job, h2hip_witness_
     const uint32_t gx = (u + WC_THREADS - 1) / WC_THREADS;
     if (G) {
         prof_begin(ctx, "wc_gate_kernel");
-        hipLaunchKernelGGL(wc_gate_kernel, dim3(gx, G), dim3(WC_THREADS), 0, st, cols, ix + o_gadv, ix + o_gq, u, stride, mask);
+        hipLaunchKernelGGL(wc_gate_kernel, dim3(gx, G), dim3(WC_THREADS), 0, st, cols, ix + o_gadv, ix + o_gq, u, stride, mask, G - job.num_rlc_gates,
+                           job.num_rlc_gates ? job.rlc_gamma : Fr::zero());
         prof_end(ctx);
     }
     uint32_t *lmask = mask + (size_t)G * stride / 32, *cmask = mask + (size_t)(G + L) * stride / 32;

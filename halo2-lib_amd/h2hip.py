@@ -117,6 +117,10 @@ _PROTOS = {
     "h2hip_plonk_keygen_dyn": (_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, C.POINTER(_vp)]),
     "h2hip_plonk_shape_of_phased": (_int, [_vp, _vp]),
     "h2hip_plonk_keygen_phased": (_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, C.POINTER(_vp)]),
+    "h2hip_plonk_shape_of_rlc": (_int, [_vp, _vp]),
+    "h2hip_plonk_keygen_rlc": (_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, C.POINTER(_vp)]),
+    "h2hip_rlc_fill_chains_dev": (_int, [_vp, C.POINTER(_vp), _sz, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "h2hip_quotient_rlc_gate_batch_dev": (_int, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _sz, _u32, _u32, _vp, _vp]),
     "h2hip_plonk_pk_free": (None, [_vp, _vp]),
     "h2hip_plonk_pk_commitments": (_int, [_vp, _vp, _vp]),
     "h2hip_plonk_pk_set_transcript_repr": (_int, [_vp, _vp]),
@@ -150,6 +154,8 @@ _PROTOS = {
     "h2hip_poseidon_merkle_tree_dev": (_int, [_vp, _vp, _vp, _u32]),
     "h2hip_poseidon_spec_generate": (_int, [_u32, _u32, _u32, _vp, _vp]),
     "h2hip_plonk_check_witness": (_int, [_vp, _vp, C.POINTER(_vp), _int, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_sz)]),
+    "h2hip_plonk_check_witness_challenges": (_int, [_vp, _vp, C.POINTER(_vp), _int, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "h2hip_plonk_verify_proof_rlc": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_int)]),
     "h2hip_plonk_verify_proof": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_int)]),
     "h2hip_plonk_verify_proof_dyn": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_int)]),
     "h2hip_plonk_verify_proof_phased": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_int)]),

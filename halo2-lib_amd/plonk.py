@@ -84,6 +84,37 @@ class PhasedCircuitParams(C.Structure):
                                  self.lookup_bits)
 
 
+class RlcCircuitParams(C.Structure):
+    """h2hip_rlc_circuit_params: BaseConfig::configure(base) followed by num_rlc_advice RLC columns (downstream's RlcConfig): phase-1 advice
+    columns behind every column of `base`, one selector q_rlc each, the gate q_rlc * (a[r] * gamma + a[r+1] - a[r+2]) with gamma = challenge 0.
+    include/h2hip.h states the layout."""
+    _fields_ = [("base", PhasedCircuitParams), ("num_rlc_advice", C.c_uint32)]
+
+    @classmethod
+    def new(cls, k, num_advice_per_phase, num_lookup_advice_per_phase, num_fixed, num_instance=0, lookup_bits: Optional[int] = None,
+            num_challenges_per_phase=(1,), num_rlc_advice=1):
+        return cls(PhasedCircuitParams.new(k, num_advice_per_phase, num_lookup_advice_per_phase, num_fixed, num_instance, lookup_bits,
+                                           num_challenges_per_phase), num_rlc_advice)
+
+    k = property(lambda self: self.base.k)
+    num_fixed = property(lambda self: self.base.num_fixed)
+    num_instance = property(lambda self: self.base.num_instance)
+    lookup_bits = property(lambda self: self.base.lookup_bits)
+
+    def rlc_columns(self) -> list:
+        """the advice indices of the RLC columns (the last ones)"""
+        first = sum(len(c) for c in self.base.phase_columns())
+        return list(range(first, first + self.num_rlc_advice))
+
+    def phase_columns(self) -> list:
+        """base's phases with the RLC columns at the end of phase 1"""
+        out = self.base.phase_columns()
+        while len(out) < 2:
+            out.append([])
+        out[1] = out[1] + self.rlc_columns()
+        return out
+
+
 class ConstraintSystemShape(C.Structure):
     """what BaseConfig::configure derives from the params (h2hip_plonk_shape)"""
     _fields_ = [("num_advice_total", C.c_uint32), ("num_fixed_total", C.c_uint32), ("table_col", C.c_int32), ("first_constant_col", C.c_int32),
@@ -94,14 +125,19 @@ class ConstraintSystemShape(C.Structure):
 
 def shape_of(ctx: Context, params) -> ConstraintSystemShape:
     out = ConstraintSystemShape()
-    fn = {DynLookupCircuitParams: ctx.lib.h2hip_plonk_shape_of_dyn, PhasedCircuitParams: ctx.lib.h2hip_plonk_shape_of_phased}.get(
-        type(params), ctx.lib.h2hip_plonk_shape_of)
+    fn = {DynLookupCircuitParams: ctx.lib.h2hip_plonk_shape_of_dyn, PhasedCircuitParams: ctx.lib.h2hip_plonk_shape_of_phased,
+          RlcCircuitParams: ctx.lib.h2hip_plonk_shape_of_rlc}.get(type(params), ctx.lib.h2hip_plonk_shape_of)
     ctx._chk(fn(C.byref(params), C.byref(out)))
     return out
 
 
 def describe(params) -> str:
     """the key description transcript_repr hashes (one per configuration)"""
+    if isinstance(params, RlcCircuitParams):
+        b = params.base
+        return "halo2-lib_amd BaseConfig+RlcConfig k=%d advice=%s lookup_advice=%s fixed=%d instance=%d lookup_bits=%s challenges=%s rlc_advice=%d" % (
+            b.k, list(b.num_advice_per_phase), list(b.num_lookup_advice_per_phase), b.num_fixed, b.num_instance,
+            None if b.lookup_bits < 0 else b.lookup_bits, list(b.num_challenges_per_phase), params.num_rlc_advice)
     if isinstance(params, PhasedCircuitParams):
         if params.base_params() is not None:   # one phase, no challenge: the BaseConfig key, the same transcript_repr
             return describe(params.base_params())
@@ -241,6 +277,12 @@ def perm_column_index(params, shape: ConstraintSystemShape, kind: str, index: in
         if kind == "advice":
             return index if index < ndyn else ndyn + params.num_fixed + index - ndyn
         raise ValueError(kind)
+    if isinstance(params, RlcCircuitParams):   # constants, gate advice, lookup advice, instance, then the RLC columns
+        first_rlc = shape.num_advice_total - params.num_rlc_advice
+        if kind == "advice" and index >= first_rlc:
+            return params.num_fixed + index + params.num_instance
+        if kind == "instance":
+            return params.num_fixed + first_rlc + index
     if kind == "fixed":
         return index - shape.first_constant_col
     if kind == "advice":   # (PhasedCircuitParams: advice indices run over every phase's gate columns, then the lookup-advice columns)
@@ -265,22 +307,26 @@ def keygen(kzg: ParamsKZG, params, fixed: Sequence[np.ndarray], copies) -> Provi
     copies = np.ascontiguousarray(copies, dtype=np.uint32).reshape(-1, 4)
     arr = (_vp * len(cols))(*[_vp(c.ctypes.data) for c in cols])
     out = _vp()
-    fn = {DynLookupCircuitParams: ctx.lib.h2hip_plonk_keygen_dyn, PhasedCircuitParams: ctx.lib.h2hip_plonk_keygen_phased}.get(type(params),
-                                                                                                                       ctx.lib.h2hip_plonk_keygen)
+    fn = {DynLookupCircuitParams: ctx.lib.h2hip_plonk_keygen_dyn, PhasedCircuitParams: ctx.lib.h2hip_plonk_keygen_phased,
+          RlcCircuitParams: ctx.lib.h2hip_plonk_keygen_rlc}.get(type(params), ctx.lib.h2hip_plonk_keygen)
     ctx._chk(fn(ctx.handle, C.byref(params), kzg.g.handle, kzg.g_lagrange.handle, arr, _vp(copies.ctypes.data), len(copies),
                                         C.byref(out)))
     return ProvingKey(ctx, out, params, shape, kzg)
 
 
 def create_proof(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarray], rng, timings: Optional[dict] = None,
-                 advice_on_device: bool = False, phase_witness=None) -> bytes:
+                 advice_on_device: bool = False, phase_witness=None, phase_witness_dev=None) -> bytes:
     """create_proof for one circuit: advice columns (host (n,4) arrays, or device pointers with advice_on_device), instance columns
     ((m,4) arrays), rng = ArrayRng / ChaChaRng / CallbackRng.  Returns the proof bytes (Blake2bWrite::finalize).
     A PhasedCircuitParams key takes phase 0's columns in `advice`; phase_witness(phase, challenges: list[int]) -> list returns each later
-    phase's columns (host (n,4) arrays or device pointers to n Fr) given every challenge squeezed so far."""
+    phase's columns (host (n,4) arrays or device pointers to n Fr) given every challenge squeezed so far.  An RlcCircuitParams key likewise;
+    its phase-1 column list ends with the RLC columns.  phase_witness_dev(phase, challenges: list[int], column_ptrs: list[int]) instead writes
+    the phase's zeroed device columns in place (rlc_fill_chains, `_dev` functions on the key's context, completed device copies)."""
     ctx, sh = pk.ctx, pk.shape
     n = 1 << pk.params.k
-    phased = isinstance(pk.params, PhasedCircuitParams)
+    phased = isinstance(pk.params, (PhasedCircuitParams, RlcCircuitParams))
+    if phase_witness is not None and phase_witness_dev is not None:
+        raise ValueError("create_proof: give phase_witness or phase_witness_dev, not both")
     want = len(pk.params.phase_columns()[0]) if phased else sh.num_advice_total
     if len(advice) != want:
         raise ValueError("create_proof: need %d advice columns" % want)
@@ -310,7 +356,7 @@ def create_proof(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarra
     plen = C.c_size_t(0)
     stage = (C.c_double * PLONK_STAGES)() if timings is not None else None
     if phased:
-        wit = _phase_witness_trampoline(ctx, n, phase_witness, err)
+        wit = _phase_witness_trampoline(ctx, n, phase_witness, err, phase_witness_dev)
         entry = lambda *a: ctx.lib.h2hip_plonk_create_proof_phased(*a[:8], C.byref(wit[0]), *a[8:])
     else:
         entry = ctx.lib.h2hip_plonk_create_proof
@@ -341,15 +387,20 @@ def create_proof(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarra
     return proof[: plen.value].tobytes()
 
 
-def _phase_witness_trampoline(ctx: Context, n: int, phase_witness, err: list):
-    """(h2hip_phase_witness, the callback object to keep alive) over phase_witness(phase, challenges) -> list of columns"""
+def _phase_witness_trampoline(ctx: Context, n: int, phase_witness, err: list, phase_witness_dev=None):
+    """(h2hip_phase_witness, the callback object to keep alive) over phase_witness(phase, challenges) -> list of columns, or over
+    phase_witness_dev(phase, challenges, column_ptrs), which writes the device columns itself"""
     one = fr_limbs(1)
 
     def _fill(_user, phase, chal, nchal, cols, ncols):
         try:
-            if phase_witness is None:
+            if phase_witness is None and phase_witness_dev is None:
                 raise ValueError("create_proof: the key has a later phase and no phase_witness was given")
             ch = np.ctypeslib.as_array(C.cast(chal, C.POINTER(C.c_uint64)), shape=(nchal, 4)).copy() if nchal else np.zeros((0, 4), dtype=np.uint64)
+            if phase_witness_dev is not None:
+                phase_witness_dev(int(phase), [fr_int(r) for r in ch], [int(cols[j]) for j in range(ncols)])
+                ctx.sync()
+                return 0
             got = list(phase_witness(int(phase), [fr_int(r) for r in ch]))
             if len(got) != ncols:
                 raise ValueError("phase_witness: phase %d has %d columns, got %d" % (phase, ncols, len(got)))
@@ -388,6 +439,11 @@ def verify_proof(pk: ProvingKey, instances: Sequence[np.ndarray], proof: bytes) 
     buf = np.frombuffer(bytes(proof), dtype=np.uint8).copy()
     ok = C.c_int(0)
     pc = pk.permutation_commitments if len(pk.permutation_commitments) else np.zeros((1, 8), dtype=np.uint64)
+    if isinstance(pk.params, RlcCircuitParams):
+        ctx._chk(ctx.lib.h2hip_plonk_verify_proof_rlc(C.byref(pk.params), _ptr(np.ascontiguousarray(pk.fixed_commitments)), _ptr(np.ascontiguousarray(pc)),
+                                                      _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128), ip, il,
+                                                      _vp(buf.ctypes.data), len(buf), C.byref(ok)))
+        return bool(ok.value)
     if isinstance(pk.params, PhasedCircuitParams):
         ctx._chk(ctx.lib.h2hip_plonk_verify_proof_phased(C.byref(pk.params), _ptr(np.ascontiguousarray(pk.fixed_commitments)), _ptr(np.ascontiguousarray(pc)),
                                                          _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128), ip, il,
@@ -404,7 +460,7 @@ def verify_proof(pk: ProvingKey, instances: Sequence[np.ndarray], proof: bytes) 
     return bool(ok.value)
 
 
-_CIRCUIT_KINDS = {BaseCircuitParams: 0, DynLookupCircuitParams: 1, PhasedCircuitParams: 2}   # H2HIP_CIRCUIT_BASE / _DYN / _PHASED
+_CIRCUIT_KINDS = {BaseCircuitParams: 0, DynLookupCircuitParams: 1, PhasedCircuitParams: 2}   # H2HIP_CIRCUIT_BASE / _DYN / _PHASED (RLC keys: not batched)
 
 
 def verify_batch(pk: ProvingKey, instances_per_proof: Sequence, proofs: Sequence[bytes], rng=None, want_rejected: bool = False,
@@ -501,11 +557,12 @@ _KINDS = {WITNESS_GATE: "gate", WITNESS_LOOKUP: "lookup", WITNESS_COPY: "copy"}
 
 
 def check_witness(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarray] = (), max_failures: int = 64,
-                  advice_on_device: bool = False) -> tuple:
+                  advice_on_device: bool = False, challenges: Optional[Sequence[int]] = None) -> tuple:
     """MockProver::run(k, &circuit, instances).verify() for the key's configuration, on the GPU (h2hip_plonk_check_witness): every advice
     column of the key (all phases of a PhasedCircuitParams key, advice index order; host (n,4) arrays or device pointers with advice_on_device),
     the instance columns.  Returns (exact number of failures, the first max_failures of them in canonical order: gate, lookup, copy; by column,
-    then row)."""
+    then row).  challenges (the phases' challenges as ints, squeeze order): h2hip_plonk_check_witness_challenges, which also checks the RLC
+    gates of an RlcCircuitParams key with challenge 0 (their failures are gate failures naming the RLC column's advice index)."""
     ctx, sh = pk.ctx, pk.shape
     n = 1 << pk.params.k
     if len(advice) != sh.num_advice_total:
@@ -525,8 +582,15 @@ def check_witness(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarr
     il = (C.c_size_t * max(len(inst), 1))(*[len(c) for c in inst])
     out = (WitnessFailureStruct * max(max_failures, 1))()
     total = C.c_size_t(0)
-    ctx._chk(ctx.lib.h2hip_plonk_check_witness(ctx.handle, pk.handle, adv, 1 if advice_on_device else 0, ip, il,
-                                               C.cast(out, _vp) if max_failures else None, max_failures, C.byref(total)))
+    if challenges is not None:
+        ch = np.ascontiguousarray(np.concatenate([fr_limbs(int(c) % R_MOD).reshape(1, 4) for c in challenges]) if len(challenges) else
+                                  np.zeros((0, 4), dtype=np.uint64))
+        ctx._chk(ctx.lib.h2hip_plonk_check_witness_challenges(ctx.handle, pk.handle, adv, 1 if advice_on_device else 0, ip, il,
+                                                              _ptr(ch) if len(ch) else None, len(ch),
+                                                              C.cast(out, _vp) if max_failures else None, max_failures, C.byref(total)))
+    else:
+        ctx._chk(ctx.lib.h2hip_plonk_check_witness(ctx.handle, pk.handle, adv, 1 if advice_on_device else 0, ip, il,
+                                                   C.cast(out, _vp) if max_failures else None, max_failures, C.byref(total)))
     del keep
     got = [WitnessFailure(_KINDS[f.kind], f.column, f.row, f.peer_column, f.peer_row) for f in out[: min(total.value, max_failures)]]
     return total.value, got
@@ -540,3 +604,24 @@ def assert_satisfied(pk: ProvingKey, advice: Sequence, instances: Sequence[np.nd
     if total:
         more = "" if total <= len(fails) else "\n... and %d more" % (total - len(fails))
         raise AssertionError("witness not satisfied: %d failure%s\n" % (total, "" if total == 1 else "s") + "\n".join(map(str, fails)) + more)
+
+
+class RlcChainStruct(C.Structure):   # h2hip_rlc_chain
+    _fields_ = [("column", C.c_uint32), ("row", C.c_uint32), ("len", C.c_uint32), ("flags", C.c_uint32), ("value_offset", C.c_uint64)]
+
+
+RLC_CARRY = 1
+
+
+def rlc_fill_chains(ctx: Context, columns: Sequence[int], usable_rows: int, values_dev, chains: Sequence, gamma: int, num_values: Optional[int] = None) -> None:
+    """h2hip_rlc_fill_chains_dev: RlcChip::compute_rlc_fixed_len's cells for every piece of `chains`, written into the device columns
+    `columns` (pointers to Fr columns, e.g. the column_ptrs of phase_witness_dev).  chains: (column, row, len, flags, value_offset) tuples, flags 0
+    (head piece) or RLC_CARRY (continues the piece before it after a column break); values_dev: a device pointer (then num_values is required) or
+    an object with data_ptr() / nbytes (a torch tensor of Montgomery limbs).  gamma: an int.  Stream-ordered on the context's stream."""
+    if num_values is None:
+        num_values = int(values_dev.numel() * values_dev.element_size()) // 32
+    vptr = int(values_dev.data_ptr()) if hasattr(values_dev, "data_ptr") else int(values_dev)
+    arr = (RlcChainStruct * max(len(chains), 1))(*[RlcChainStruct(int(c[0]), int(c[1]), int(c[2]), int(c[3]), int(c[4])) for c in chains])
+    cols = (_vp * max(len(columns), 1))(*[_vp(int(p)) for p in columns])
+    ctx._chk(ctx.lib.h2hip_rlc_fill_chains_dev(ctx.handle, cols, len(columns), usable_rows, _vp(vptr), num_values, arr, len(chains),
+                                               _ptr(fr_limbs(int(gamma) % R_MOD))))

@@ -474,8 +474,8 @@ int h2hip_plonk_shape_of_dyn(const h2hip_dyn_circuit_params *params, h2hip_plonk
  * Protocol: after the instances, for each phase in order: the blinding rows of the phase's columns, one blind per column, the phase's
  * commitments (index order), then num_challenges_per_phase[p] challenges squeezed (Challenge255); theta and everything after as for BaseConfig.
  * LIMITS: the column counts summed over the phases are in h2hip_base_circuit_params' ranges; phases are contiguous (a phase with columns
- * follows a phase with columns); a challenge follows a phase with columns; at most 8 challenges; gates and lookups do not query a challenge
- * (halo2-base declares none: a challenge reaches the circuit through witness values); single-GPU only (h2hip_plonk_pk_set_sharding on a key
+ * follows a phase with columns); a challenge follows a phase with columns; at most 8 challenges; the gates and lookups of THIS
+ * configuration query no challenge (the one gate that does, the RLC gate, comes with h2hip_rlc_circuit_params below); single-GPU only (h2hip_plonk_pk_set_sharding on a key
  * with more than one used phase returns H2HIP_ERR_INVALID).  Anything else returns H2HIP_ERR_INVALID.  One used phase and no challenges IS a
  * BaseConfig: same shape, key and proof bytes as the h2hip_base_circuit_params of that phase. */
 #define H2HIP_MAX_PHASE 3
@@ -503,6 +503,53 @@ typedef struct h2hip_phase_witness {
     void *user;
 } h2hip_phase_witness;
 
+/* ---- RLC circuits [UPSTREAM-RECALL: downstream's RlcConfig, restated from memory — it is not part of the reference tree]:
+ * BaseConfig::configure(base) followed by num_rlc_advice RLC columns, each a SecondPhase advice column with a selector q_rlc and the vertical
+ * gate of ROTATIONS = 3 (threads/single_phase.rs:183-193 anticipates it)
+ *       q_rlc * (a[r] * gamma + a[r+1] - a[r+2]) = 0,   gamma = challenge 0, the first one squeezed after phase 0's commitments.
+ * Layout: everything not listed is the multi-phase layout of `base`.
+ *   advice columns       base's columns, then the RLC columns (last indices), all in phase 1: phase 1's commitment group is its gate columns,
+ *                        its lookup-advice columns, then the RLC columns (index order)
+ *   fixed columns        base's columns, then one q_rlc per RLC column (selectors follow the circuit's own columns in creation order)
+ *   permutation columns  constants, gate advice, lookup advice, instance, then the RLC columns (enable_equality is called on them last)
+ *   advice queries       base's, then per RLC column the rotations 0, 1, 2; fixed queries: base's, then the q_rlc columns
+ *   gates                folded by y in the order flex gates, RLC gates (column order), permutation argument, lookups
+ * The gate's degree is 2 + selector: degree, extended_k and the blinding factors (6) are base's.  LIMITS: base.num_challenges_per_phase[0] >= 1;
+ * 1 <= num_rlc_advice <= 64 (0 is H2HIP_ERR_INVALID: such a circuit uses h2hip_phased_circuit_params); phase 1 always has columns, which the
+ * contiguity rule counts; lookups query no challenge; RLC of variable length (a length cell) is the circuit's business.  Keygen: the selector
+ * rule covers the union of the q_enable and q_rlc columns (every pair shares an enabled row), and a q_rlc enabled on a row r with
+ * r + 2 >= usable_rows is H2HIP_ERR_INVALID.  Single-GPU only (h2hip_plonk_pk_set_sharding returns H2HIP_ERR_INVALID); not accepted by
+ * h2hip_plonk_verify_batch.  Proofs go through h2hip_plonk_create_proof_phased: `advice` is phase 0's columns, the callback's phase-1 column
+ * list ends with the RLC columns. */
+typedef struct h2hip_rlc_circuit_params {
+    h2hip_phased_circuit_params base;
+    uint32_t num_rlc_advice;
+} h2hip_rlc_circuit_params;
+int h2hip_plonk_shape_of_rlc(const h2hip_rlc_circuit_params *params, h2hip_plonk_shape *out);
+
+/* RlcChip::compute_rlc_fixed_len's cells, written on the device [UPSTREAM-RECALL].  A chain over values v_0 .. v_{len-1} is the Horner scan
+ * r_0 = v_0, r_i = r_{i-1} * gamma + v_i.  chains_host lists `count` pieces; piece j reads its len values at values_dev[value_offset ..]:
+ *   head piece  (flags == 0)              the cells v_0, v_1, r_1, v_2, r_2, ... (2 len - 1 cells) from (column, row) downwards
+ *   carry piece (flags & H2HIP_RLC_CARRY) continues the piece before it in the list after a column break: the break cell is duplicated at the
+ *               top of the next column, as assign_witnesses does — the cells r_prev, v_0, r_0', v_1, r_1', ... (2 len + 1 cells), with
+ *               r_0' = r_prev * gamma + v_0 and r_prev the last r of the piece before it
+ * H2HIP_ERR_INVALID before anything is launched: a column index >= num_columns, row + the cell count > usable_rows, len == 0, a value range
+ * outside num_values, a carry flag on piece 0.  Cells not addressed are not touched.  columns_dev: HOST array of device columns.  gamma: one
+ * Montgomery Fr on the host; 0 and 1 are ordinary values.  Stream-ordered on the context's stream: a segmented scan over the pieces' values
+ * (tile, tile sums, apply) and one placement kernel; the piece table is the only upload. */
+typedef struct h2hip_rlc_chain {
+    uint32_t column, row, len, flags;
+    uint64_t value_offset;
+} h2hip_rlc_chain;
+#define H2HIP_RLC_CARRY 1
+int h2hip_rlc_fill_chains_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const void *values_dev,
+                              size_t num_values, const h2hip_rlc_chain *chains_host, size_t count, const void *gamma);
+/* The RLC gates' terms of the quotient numerator on the extended domain, folded in order for j < count:
+ *      acc[i] = acc[i]*y + q_j[i]*(a_j[i]*gamma + a_j[i+s] - a_j[i+2s]),  s = 2^(ext_k-k), indices mod 2^ext_k.
+ * q_dev / a_dev: HOST arrays of device pointers; 64 columns per launch. */
+int h2hip_quotient_rlc_gate_batch_dev(h2hip_ctx *ctx, void *acc_dev, const void *const *q_dev, const void *const *a_dev, size_t count, uint32_t ext_k,
+                                      uint32_t k, const void *gamma, const void *y);
+
 typedef struct h2hip_plonk_pk h2hip_plonk_pk;
 /* keygen_vk + keygen_pk [UPSTREAM], reference halo2-base/src/utils/testing.rs:224-227.  fixed_host: num_fixed_total columns of 2^k
  * Montgomery Fr (Lagrange values, as the circuit's synthesize assigned them).  copies: ncopies x 4 u32 = (column, row, column, row)
@@ -518,6 +565,9 @@ int h2hip_plonk_keygen_dyn(h2hip_ctx *ctx, const h2hip_dyn_circuit_params *param
 /* the same for the multi-phase configuration above (fixed_host and copies in its layout) */
 int h2hip_plonk_keygen_phased(h2hip_ctx *ctx, const h2hip_phased_circuit_params *params, const h2hip_bases *g, const h2hip_bases *g_lagrange,
                               const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out);
+/* the same for the RLC configuration above (fixed_host and copies in its layout) */
+int h2hip_plonk_keygen_rlc(h2hip_ctx *ctx, const h2hip_rlc_circuit_params *params, const h2hip_bases *g, const h2hip_bases *g_lagrange,
+                           const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out);
 void h2hip_plonk_pk_free(h2hip_ctx *ctx, h2hip_plonk_pk *pk);
 /* VerifyingKey contents: fixed_commitments (num_fixed_total x 64 B affine) and permutation commitments (num_perm_columns x 64 B) */
 int h2hip_plonk_pk_commitments(const h2hip_plonk_pk *pk, void *fixed_out, void *permutation_out);
@@ -662,6 +712,15 @@ int h2hip_plonk_check_witness(h2hip_ctx *ctx, const h2hip_plonk_pk *pk, const vo
                               const void *const *instances_host, const size_t *instance_lens, h2hip_witness_failure *failures_out,
                               size_t max_failures, size_t *num_failures);
 
+/* h2hip_plonk_check_witness plus the gates that query a challenge: with challenges_fr (num_challenges Montgomery Fr on the host, squeeze
+ * order) every RLC column c, row r with q_rlc_c[r] != 0 must satisfy a[r] * challenge_0 + a[r+1] - a[r+2] == 0; a row with r + 2 >=
+ * usable_rows fails whatever the values.  Failures are H2HIP_WITNESS_GATE with column = the RLC column's advice index, behind the flex
+ * gates' in canonical order.  A key of the RLC configuration needs num_challenges >= 1 (H2HIP_ERR_INVALID otherwise) and is H2HIP_ERR_INVALID
+ * for h2hip_plonk_check_witness, whose error names this entry; every other key is checked exactly as h2hip_plonk_check_witness does. */
+int h2hip_plonk_check_witness_challenges(h2hip_ctx *ctx, const h2hip_plonk_pk *pk, const void *const *advice, int advice_on_device,
+                                         const void *const *instances_host, const size_t *instance_lens, const void *challenges_fr,
+                                         size_t num_challenges, h2hip_witness_failure *failures_out, size_t max_failures, size_t *num_failures);
+
 /* verify_proof::<KZGCommitmentScheme<Bn256>, VerifierSHPLONK<_>, Challenge255<_>, Blake2bRead<_, _, _>, SingleStrategy<_>> as the reference runs
  * it after every proof (check_proof, halo2-base/src/utils/testing.rs:64-88).  Host code (the reference verifies on the CPU too): transcript
  * replay, the quotient identity rebuilt from the openings, SHPLONK's folded opening and one pairing check.  fixed / permutation commitments:
@@ -680,6 +739,12 @@ int h2hip_plonk_verify_proof_dyn(const h2hip_dyn_circuit_params *params, const v
 int h2hip_plonk_verify_proof_phased(const h2hip_phased_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
                                     const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
                                     const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted);
+
+/* h2hip_plonk_verify_proof for the RLC configuration: the RLC gates' terms q * (a0 * gamma + a1 - a2) from the openings enter the quotient
+ * identity with gamma = challenge 0 of the transcript replay */
+int h2hip_plonk_verify_proof_rlc(const h2hip_rlc_circuit_params *params, const void *fixed_commitments, const void *permutation_commitments,
+                                 const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
+                                 const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted);
 
 /* verify_proof for num_proofs proofs under ONE verifying key, with one pairing: accepted = 1 iff every proof verifies.  The proofs' points are
  * decompressed in one launch, the transcripts replayed on the host, and every scalar multiplication of every proof goes into one MSM on the
