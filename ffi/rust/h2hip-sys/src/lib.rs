@@ -93,6 +93,25 @@ pub struct h2hip_phase_witness {
     pub fill: h2hip_phase_witness_fn,
     pub user: *mut c_void,
 }
+/// The caller's transcript (include/h2hip.h states the contract): a point crosses as 64 B (Montgomery x, y), a scalar or challenge as one
+/// Montgomery Fr; every callback returns 0, or non-zero for a failure of that operation.  `write_*` absorb and serialise into the caller's own
+/// buffer, `read_*` parse and absorb, `common_*` only absorb.
+pub type h2hip_transcript_point_fn = Option<unsafe extern "C" fn(user: *mut c_void, g1_affine: *const c_void) -> c_int>;
+pub type h2hip_transcript_scalar_fn = Option<unsafe extern "C" fn(user: *mut c_void, fr: *const c_void) -> c_int>;
+pub type h2hip_transcript_read_fn = Option<unsafe extern "C" fn(user: *mut c_void, out: *mut c_void) -> c_int>;
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct h2hip_transcript {
+    pub user: *mut c_void,
+    pub common_point: h2hip_transcript_point_fn,
+    pub write_point: h2hip_transcript_point_fn,
+    pub common_scalar: h2hip_transcript_scalar_fn,
+    pub write_scalar: h2hip_transcript_scalar_fn,
+    pub read_point: h2hip_transcript_read_fn,
+    pub read_scalar: h2hip_transcript_read_fn,
+    pub squeeze_challenge: h2hip_transcript_read_fn,
+}
+pub const H2HIP_CIRCUIT_RLC: c_int = 3;
 /// one failure of h2hip_plonk_check_witness: kind H2HIP_WITNESS_GATE (column = advice index of the gate column), _LOOKUP (column = lookup
 /// index) or _COPY (column, row = permutation column and row; peer_* = sigma of that cell)
 #[repr(C)]
@@ -348,6 +367,17 @@ extern "C" {
                                            instances_host: *const *const c_void, instance_lens: *const usize, rng: h2hip_rng_fill_fn, rng_user: *mut c_void,
                                            witness: *const h2hip_phase_witness, proof_out: *mut u8, proof_cap: usize, proof_len: *mut usize,
                                            stage_ms: *mut f64) -> c_int;
+    /// create_proof over the caller's transcript, for a key of any configuration; returns no bytes
+    pub fn h2hip_plonk_create_proof_transcript(ctx: *mut h2hip_ctx, pk: *mut h2hip_plonk_pk, advice: *const *const c_void, advice_on_device: c_int,
+                                               instances_host: *const *const c_void, instance_lens: *const usize, rng: h2hip_rng_fill_fn,
+                                               rng_user: *mut c_void, witness: *const h2hip_phase_witness, t: *const h2hip_transcript,
+                                               stage_ms: *mut f64) -> c_int;
+    /// verify_proof over the caller's transcript (`kind`: `H2HIP_CIRCUIT_*`, `_RLC` included); `acc_out`: optional 2 x 64 B (W', outer)
+    pub fn h2hip_plonk_verify_proof_transcript(kind: c_int, params: *const c_void, fixed_commitments: *const c_void,
+                                               permutation_commitments: *const c_void, transcript_repr: *const c_void, g1: *const c_void,
+                                               g2: *const c_void, s_g2: *const c_void, instances_host: *const *const c_void,
+                                               instance_lens: *const usize, t: *const h2hip_transcript, accepted: *mut c_int,
+                                               acc_out: *mut c_void) -> c_int;
     pub fn h2hip_plonk_check_witness(ctx: *mut h2hip_ctx, pk: *const h2hip_plonk_pk, advice: *const *const c_void, advice_on_device: c_int,
                                      instances_host: *const *const c_void, instance_lens: *const usize, failures_out: *mut h2hip_witness_failure,
                                      max_failures: usize, num_failures: *mut usize) -> c_int;

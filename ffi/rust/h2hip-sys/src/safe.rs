@@ -506,7 +506,37 @@ impl<'b, 'g> ProvingKeyHip<'b, 'g> {
     /// lookup-advice columns, index order; a key with RLC columns: phase 1's list ends with them) from the challenges squeezed so far — where
     /// halo2-axiom's create_proof runs the next phase's synthesis.
     pub fn create_proof<R: FnMut(&mut [Fr]), W: FnMut(u32, &[Fr]) -> Result<Vec<Vec<Fr>>, E>, E: std::fmt::Display>(
-        &self, advice: &[Vec<Fr>], instances: &[&[Fr]], mut rng_fill: R, later_phases: W) -> Result<Vec<u8>, HipError> {
+        &self, advice: &[Vec<Fr>], instances: &[&[Fr]], rng_fill: R, later_phases: W) -> Result<Vec<u8>, HipError> {
+        self.prove(advice, instances, rng_fill, later_phases, None).map(|p| p.unwrap_or_default())
+    }
+    /// `create_proof(params, pk, &[circuit], &[instances], rng, &mut transcript)` for ANY transcript (h2hip_plonk_create_proof_transcript):
+    /// every transcript operation of the proof goes to `transcript`, in upstream's order, and the proof's bytes are the transcript's — the
+    /// caller takes them with its own `finalize()`.  The other arguments are `create_proof`'s.  An `Err` from the transcript aborts the proof:
+    /// its message comes back with H2HIP_ERR_INVALID, and the key and the context serve the next proof.
+    pub fn create_proof_with_transcript<T: TranscriptWrite, R: FnMut(&mut [Fr]), W: FnMut(u32, &[Fr]) -> Result<Vec<Vec<Fr>>, E>, E: std::fmt::Display>(
+        &self, advice: &[Vec<Fr>], instances: &[&[Fr]], rng_fill: R, later_phases: W, transcript: &mut T) -> Result<(), HipError> {
+        let mut bridge = WriteBridge { t: transcript, err: None };
+        let cb = h2hip_transcript {
+            user: (&mut bridge as *mut WriteBridge<T>).cast(),
+            common_point: None,
+            write_point: Some(write_point_trampoline::<T>),
+            common_scalar: Some(common_scalar_trampoline::<T>),
+            write_scalar: Some(write_scalar_trampoline::<T>),
+            read_point: None,
+            read_scalar: None,
+            squeeze_challenge: Some(squeeze_trampoline::<T>),
+        };
+        let res = self.prove(advice, instances, rng_fill, later_phases, Some(&cb));
+        match (res, bridge.err.take()) {
+            (Err(e), Some(message)) => Err(HipError { code: e.code, message: format!("{message} ({})", e.message) }),
+            (Err(e), None) => Err(e),
+            (Ok(_), _) => Ok(()),
+        }
+    }
+    /// one proof: into the built-in Blake2b transcript (`transcript` = None, returns its bytes) or over the caller's callbacks (returns None)
+    fn prove<R: FnMut(&mut [Fr]), W: FnMut(u32, &[Fr]) -> Result<Vec<Vec<Fr>>, E>, E: std::fmt::Display>(
+        &self, advice: &[Vec<Fr>], instances: &[&[Fr]], mut rng_fill: R, later_phases: W, transcript: Option<&h2hip_transcript>)
+        -> Result<Option<Vec<u8>>, HipError> {
         unsafe extern "C" fn trampoline<R: FnMut(&mut [Fr])>(user: *mut c_void, out: *mut c_void, n: usize) {
             let f = &mut *(user as *mut R);
             f(std::slice::from_raw_parts_mut(out as *mut Fr, n));
@@ -565,18 +595,27 @@ impl<'b, 'g> ProvingKeyHip<'b, 'g> {
         let mut proof = vec![0u8; 32 * (self.shape.num_commitments + self.shape.num_evals) as usize];
         let mut len = 0usize;
         let mut err = None;
-        let rc = match &self.phased {
-            None => unsafe {
+        let rc = match (&self.phased, transcript) {
+            (None, Some(t)) => unsafe {
+                h2hip_plonk_create_proof_transcript(self.be.ctx, self.pk, adv.as_ptr(), 0, ins.as_ptr(), lens.as_ptr(), Some(trampoline::<R>),
+                                                    (&mut rng_fill as *mut R).cast(), ptr::null(), t, ptr::null_mut())
+            },
+            (None, None) => unsafe {
                 h2hip_plonk_create_proof(self.be.ctx, self.pk, adv.as_ptr(), 0, ins.as_ptr(), lens.as_ptr(), Some(trampoline::<R>),
                                          (&mut rng_fill as *mut R).cast(), proof.as_mut_ptr(), proof.len(), &mut len, ptr::null_mut())
             },
-            Some(_) => {
+            (Some(_), _) => {
                 let mut later = Later::<W, E> { f: later_phases, ctx: self.be.ctx, usable: self.shape.usable_rows as usize, n: 1usize << self.params.k,
                                                 err: &mut err, _e: std::marker::PhantomData };
                 let w = h2hip_phase_witness { fill: Some(witness::<W, E>), user: (&mut later as *mut Later<W, E>).cast() };
                 unsafe {
-                    h2hip_plonk_create_proof_phased(self.be.ctx, self.pk, adv.as_ptr(), 0, ins.as_ptr(), lens.as_ptr(), Some(trampoline::<R>),
-                                                    (&mut rng_fill as *mut R).cast(), &w, proof.as_mut_ptr(), proof.len(), &mut len, ptr::null_mut())
+                    match transcript {
+                        Some(t) => h2hip_plonk_create_proof_transcript(self.be.ctx, self.pk, adv.as_ptr(), 0, ins.as_ptr(), lens.as_ptr(),
+                                                                       Some(trampoline::<R>), (&mut rng_fill as *mut R).cast(), &w, t, ptr::null_mut()),
+                        None => h2hip_plonk_create_proof_phased(self.be.ctx, self.pk, adv.as_ptr(), 0, ins.as_ptr(), lens.as_ptr(), Some(trampoline::<R>),
+                                                                (&mut rng_fill as *mut R).cast(), &w, proof.as_mut_ptr(), proof.len(), &mut len,
+                                                                ptr::null_mut()),
+                    }
                 }
             }
         };
@@ -584,9 +623,153 @@ impl<'b, 'g> ProvingKeyHip<'b, 'g> {
             return Err(HipError { code: rc, message });
         }
         check(rc)?;
+        if transcript.is_some() {
+            return Ok(None);
+        }
         proof.truncate(len);
-        Ok(proof)
+        Ok(Some(proof))
     }
+}
+
+/// The writing half of a transcript as `create_proof_with_transcript` drives it: upstream's `TranscriptWrite<G1Affine, _>` with its
+/// `Transcript` supertrait, over the curve this library serves.  The fork implements it for every `T: halo2_proofs::transcript::TranscriptWrite`
+/// by forwarding (`squeeze_challenge` = `*squeeze_challenge_scalar::<()>()`); the proof's byte encoding belongs to the implementation.
+/// The methods run while the proof is in flight and must not use the proof's `Backend`.
+pub trait TranscriptWrite {
+    fn common_scalar(&mut self, scalar: Fr) -> std::io::Result<()>;
+    fn write_point(&mut self, point: G1Affine) -> std::io::Result<()>;
+    fn write_scalar(&mut self, scalar: Fr) -> std::io::Result<()>;
+    fn squeeze_challenge(&mut self) -> Fr;
+}
+/// The reading half (`TranscriptRead<G1Affine, _>`): `read_*` parse the next value (decompressing, if the encoding compresses) and absorb it.
+pub trait TranscriptRead {
+    fn common_scalar(&mut self, scalar: Fr) -> std::io::Result<()>;
+    fn read_point(&mut self) -> std::io::Result<G1Affine>;
+    fn read_scalar(&mut self) -> std::io::Result<Fr>;
+    fn squeeze_challenge(&mut self) -> Fr;
+}
+struct WriteBridge<'a, T> {
+    t: &'a mut T,
+    err: Option<String>,
+}
+struct ReadBridge<'a, T> {
+    t: &'a mut T,
+    err: Option<String>,
+}
+/// keeps the first error and turns it into the callback's non-zero return: nothing unwinds through the C frames
+fn io_status(err: &mut Option<String>, what: &str, r: std::io::Result<()>) -> c_int {
+    match r {
+        Ok(()) => 0,
+        Err(e) => {
+            err.get_or_insert_with(|| format!("transcript {what}: {e}"));
+            1
+        }
+    }
+}
+unsafe extern "C" fn common_scalar_trampoline<T: TranscriptWrite>(user: *mut c_void, fr: *const c_void) -> c_int {
+    let b = &mut *(user as *mut WriteBridge<T>);
+    let r = b.t.common_scalar(ptr::read_unaligned(fr as *const Fr));
+    io_status(&mut b.err, "common_scalar", r)
+}
+unsafe extern "C" fn write_scalar_trampoline<T: TranscriptWrite>(user: *mut c_void, fr: *const c_void) -> c_int {
+    let b = &mut *(user as *mut WriteBridge<T>);
+    let r = b.t.write_scalar(ptr::read_unaligned(fr as *const Fr));
+    io_status(&mut b.err, "write_scalar", r)
+}
+unsafe extern "C" fn write_point_trampoline<T: TranscriptWrite>(user: *mut c_void, g1_affine: *const c_void) -> c_int {
+    let b = &mut *(user as *mut WriteBridge<T>);
+    let r = b.t.write_point(ptr::read_unaligned(g1_affine as *const G1Affine));
+    io_status(&mut b.err, "write_point", r)
+}
+unsafe extern "C" fn squeeze_trampoline<T: TranscriptWrite>(user: *mut c_void, out: *mut c_void) -> c_int {
+    let b = &mut *(user as *mut WriteBridge<T>);
+    ptr::write_unaligned(out as *mut Fr, b.t.squeeze_challenge());
+    0
+}
+unsafe extern "C" fn read_common_scalar_trampoline<T: TranscriptRead>(user: *mut c_void, fr: *const c_void) -> c_int {
+    let b = &mut *(user as *mut ReadBridge<T>);
+    let r = b.t.common_scalar(ptr::read_unaligned(fr as *const Fr));
+    io_status(&mut b.err, "common_scalar", r)
+}
+unsafe extern "C" fn read_point_trampoline<T: TranscriptRead>(user: *mut c_void, out: *mut c_void) -> c_int {
+    let b = &mut *(user as *mut ReadBridge<T>);
+    match b.t.read_point() {
+        Ok(p) => {
+            ptr::write_unaligned(out as *mut G1Affine, p);
+            0
+        }
+        Err(_) => 1,   // a value that cannot be read is a rejection, not an error
+    }
+}
+unsafe extern "C" fn read_scalar_trampoline<T: TranscriptRead>(user: *mut c_void, out: *mut c_void) -> c_int {
+    let b = &mut *(user as *mut ReadBridge<T>);
+    match b.t.read_scalar() {
+        Ok(s) => {
+            ptr::write_unaligned(out as *mut Fr, s);
+            0
+        }
+        Err(_) => 1,
+    }
+}
+unsafe extern "C" fn read_squeeze_trampoline<T: TranscriptRead>(user: *mut c_void, out: *mut c_void) -> c_int {
+    let b = &mut *(user as *mut ReadBridge<T>);
+    ptr::write_unaligned(out as *mut Fr, b.t.squeeze_challenge());
+    0
+}
+
+/// `verify_proof(params, vk, SingleStrategy::new(params), &[instances], &mut transcript)` for ANY reading transcript
+/// (h2hip_plonk_verify_proof_transcript); arguments as for `verify_proof`.  A read that fails, or hands over a bad value, rejects the proof
+/// (`Ok(false)`); trailing input is the reader's business.  -> (accepted, the proof's KZG accumulator (W', outer): accepted <=> well-formed and
+/// e(W', s_g2) * e(-outer, g2) = 1, what an aggregator defers instead of pairing; the identity twice for a malformed proof).
+pub fn verify_proof_with_transcript<T: TranscriptRead>(params: h2hip_base_circuit_params, phases: &PhaseCounts, fixed_commitments: &[G1Affine],
+                                                       permutation_commitments: &[G1Affine], transcript_repr: Fr, g1: G1Affine, g2: &[u8; 128],
+                                                       s_g2: &[u8; 128], instances: &[&[Fr]], transcript: &mut T)
+                                                       -> Result<(bool, [G1Affine; 2]), HipError> {
+    let phased = if phases.is_first_phase_only() { None } else { Some(phases.to_c(&params)?) };
+    let rlc = phases.to_c_rlc(&params)?;
+    let mut shape = h2hip_plonk_shape::default();
+    match (&rlc, &phased) {
+        (Some(rp), _) => check(unsafe { h2hip_plonk_shape_of_rlc(rp, &mut shape) })?,
+        (None, Some(pp)) => check(unsafe { h2hip_plonk_shape_of_phased(pp, &mut shape) })?,
+        (None, None) => check(unsafe { h2hip_plonk_shape_of(&params, &mut shape) })?,
+    }
+    if fixed_commitments.len() != shape.num_fixed_total as usize || permutation_commitments.len() != shape.num_perm_columns as usize {
+        return Err(invalid(format!("verify_proof: {} fixed / {} permutation commitments, the shape has {} / {}", fixed_commitments.len(),
+                                   permutation_commitments.len(), shape.num_fixed_total, shape.num_perm_columns)));
+    }
+    if instances.len() != params.num_instance as usize {
+        return Err(invalid(format!("verify_proof: {} instance columns, the circuit has {}", instances.len(), params.num_instance)));
+    }
+    let ins: Vec<*const c_void> = instances.iter().map(|c| c.as_ptr().cast()).collect();
+    let lens: Vec<usize> = instances.iter().map(|c| c.len()).collect();
+    let (kind, params_ptr): (c_int, *const c_void) = match (&rlc, &phased) {
+        (Some(rp), _) => (H2HIP_CIRCUIT_RLC, (rp as *const h2hip_rlc_circuit_params).cast()),
+        (None, Some(pp)) => (H2HIP_CIRCUIT_PHASED, (pp as *const h2hip_phased_circuit_params).cast()),
+        (None, None) => (H2HIP_CIRCUIT_BASE, (&params as *const h2hip_base_circuit_params).cast()),
+    };
+    let mut bridge = ReadBridge { t: transcript, err: None };
+    let cb = h2hip_transcript {
+        user: (&mut bridge as *mut ReadBridge<T>).cast(),
+        common_point: None,
+        write_point: None,
+        common_scalar: Some(read_common_scalar_trampoline::<T>),
+        write_scalar: None,
+        read_point: Some(read_point_trampoline::<T>),
+        read_scalar: Some(read_scalar_trampoline::<T>),
+        squeeze_challenge: Some(read_squeeze_trampoline::<T>),
+    };
+    let mut ok: c_int = 0;
+    let mut acc = [G1Affine::default(); 2];
+    let rc = unsafe {
+        h2hip_plonk_verify_proof_transcript(kind, params_ptr, fixed_commitments.as_ptr().cast(), permutation_commitments.as_ptr().cast(),
+                                            fr_ptr(&transcript_repr), (&g1 as *const G1Affine).cast(), g2.as_ptr().cast(), s_g2.as_ptr().cast(),
+                                            ins.as_ptr(), lens.as_ptr(), &cb, &mut ok, acc.as_mut_ptr().cast())
+    };
+    if let (true, Some(message)) = (rc != H2HIP_OK, bridge.err.take()) {
+        return Err(HipError { code: rc, message });
+    }
+    check(rc)?;
+    Ok((ok != 0, acc))
 }
 /// `verify_proof(params, vk, SingleStrategy::new(params), &[instances], &mut Blake2bRead::init(proof))` (check_proof,
 /// halo2-base/src/utils/testing.rs:64-88): `g1` = params.get_g()[0], `g2` / `s_g2` = the verifier half of the SRS in RawBytes form.

@@ -344,7 +344,7 @@ static int keygen_common(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const h2hip_bases *
             h2hip_chacha_rng wr;
             uint8_t seed[32] = {0};
             h2hip_chacha_rng_init(&wr, seed, 8);
-            std::vector<uint8_t> throwaway;
+            Transcript throwaway;
             const Fr saved = pk->transcript_repr;
             pk->transcript_repr = Fr::zero();
             const int wrc = create_proof_impl(ctx, pk, adv.data(), true, inst.data(), inst_len.data(), h2hip_chacha_rng_fill, &wr, throwaway, nullptr);
@@ -482,23 +482,19 @@ void h2hip_array_rng_fill(void *user, void *out_fr, size_t n) {
 }
 
 
-static int create_proof_entry(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, int advice_on_device, const void *const *instances_host,
-                              const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, const h2hip_phase_witness *witness,
-                              uint8_t *proof_out, size_t proof_cap, size_t *proof_len, double *stage_ms) {
-    H2_DEVICE_GUARD(ctx);
-    H2_REQUIRE(ctx && pk && advice && rng && proof_out && proof_len, "NULL argument");
+// one proof over `tr`, behind the argument checks every entry shares; on failure every stream of the proof is drained
+static int create_proof_run(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, int advice_on_device, const void *const *instances_host,
+                            const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, const h2hip_phase_witness *witness,
+                            ProverTranscript &tr, double *stage_ms) {
     H2_REQUIRE(pk->ctx == ctx, "the proving key belongs to another context");
     H2_REQUIRE(pk->have_repr, "h2hip_plonk_pk_set_transcript_repr has not been called");
     H2_REQUIRE(pk->sh.p.num_instance == 0 || instance_lens, "instance_lens is required");
-    const size_t need = 32 * (size_t)(pk->sh.num_commitments() + pk->sh.num_evals());
-    H2_REQUIRE(proof_cap >= need, "proof buffer too small");
     if (rng == h2hip_chacha_rng_fill) {   // the library's own generator: the device fill reads its state, so check it once, here
         const h2hip_chacha_rng *cr = (const h2hip_chacha_rng *)rng_user;
         H2_REQUIRE(cr, "h2hip_chacha_rng_fill needs its h2hip_chacha_rng as rng_user");
         H2_REQUIRE(cr->rounds == 8 || cr->rounds == 12 || cr->rounds == 20, "h2hip_chacha_rng: rounds must be 8, 12 or 20");
     }
-    std::vector<uint8_t> proof;
-    int rc = create_proof_impl(ctx, pk, advice, advice_on_device != 0, instances_host, instance_lens, rng, rng_user, proof, stage_ms, witness);
+    int rc = create_proof_impl(ctx, pk, advice, advice_on_device != 0, instances_host, instance_lens, rng, rng_user, tr, stage_ms, witness);
     if (pk->side && ctx->profiling && ctx->prof_filter.empty()) prof_fold_child(ctx, pk->side);   // (the lanes' timers are folded when the table is read)
     if (rc != H2HIP_OK) {
         sync_proof_streams(ctx, pk);   // nothing of the failed proof may still run on buffers that go back to the pool
@@ -514,8 +510,20 @@ static int create_proof_entry(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *co
             pk->exch_next = pk->exch_sizes.size();
             set_error("%s", msg.c_str());
         }
-        return rc;
     }
+    return rc;
+}
+
+static int create_proof_entry(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, int advice_on_device, const void *const *instances_host,
+                              const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, const h2hip_phase_witness *witness,
+                              uint8_t *proof_out, size_t proof_cap, size_t *proof_len, double *stage_ms) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && pk && advice && rng && proof_out && proof_len, "NULL argument");
+    const size_t need = 32 * (size_t)(pk->sh.num_commitments() + pk->sh.num_evals());
+    H2_REQUIRE(proof_cap >= need, "proof buffer too small");
+    Transcript tr;
+    H2_CHK(create_proof_run(ctx, pk, advice, advice_on_device, instances_host, instance_lens, rng, rng_user, witness, tr, stage_ms));
+    const std::vector<uint8_t> &proof = tr.proof;
     if (proof.size() != need) {
         set_error("create_proof: internal error: proof has %zu bytes, expected %zu", proof.size(), need);
         return H2HIP_ERR_INVALID;
@@ -540,6 +548,20 @@ int h2hip_plonk_create_proof_phased(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const vo
     H2_REQUIRE(!pk || pk->sh.phase_cols.size() <= 1 || (witness && witness->fill), "h2hip_plonk_create_proof_phased: a later phase needs the witness callback");
     return create_proof_entry(ctx, pk, advice, advice_on_device, instances_host, instance_lens, rng, rng_user, witness, proof_out, proof_cap, proof_len,
                               stage_ms);
+}
+
+// create_proof over the caller's transcript (include/h2hip.h): the same run, every transcript operation through the callbacks
+int h2hip_plonk_create_proof_transcript(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, int advice_on_device,
+                                        const void *const *instances_host, const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user,
+                                        const h2hip_phase_witness *witness, const h2hip_transcript *t, double *stage_ms) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx && pk && advice && rng && t, "NULL argument");
+    H2_REQUIRE(t->common_scalar && t->write_point && t->write_scalar && t->squeeze_challenge,
+               "h2hip_plonk_create_proof_transcript: the transcript lacks common_scalar, write_point, write_scalar or squeeze_challenge");
+    H2_REQUIRE(!pk->comm, "h2hip_plonk_create_proof_transcript: the key is sharded (h2hip_plonk_pk_set_sharding); sharded proofs use the built-in transcript");
+    H2_REQUIRE(pk->sh.phase_cols.size() <= 1 || (witness && witness->fill), "h2hip_plonk_create_proof_transcript: a later phase needs the witness callback");
+    CallbackTranscript tr(t);
+    return create_proof_run(ctx, pk, advice, advice_on_device, instances_host, instance_lens, rng, rng_user, witness, tr, stage_ms);
 }
 
 // MockProver's verdict on the GPU (include/h2hip.h): the key's layout as a WitnessCheckJob for witness_check.hip

@@ -1,5 +1,5 @@
 // What the prover's translation units share: the constraint-system shape, the evaluation domain, the proving key with its buffer pool,
-// and the Blake2b transcript.  plonk.hip: shape construction's callers, keygen, sharding set-up, the C entry points.  plonk_prove.hip: one
+// and (transcript.h) the transcript interface.  plonk.hip: shape construction's callers, keygen, sharding set-up, the C entry points.  plonk_prove.hip: one
 // proof (ProofRun) and SHPLONK's bookkeeping.
 #pragma once
 #include <algorithm>
@@ -10,6 +10,7 @@
 #include "blake2b.h"
 #include "host_field.h"
 #include "internal.h"
+#include "transcript.h"
 
 namespace h2 {
 namespace plonk {
@@ -310,49 +311,6 @@ struct Scope {
     }
 };
 
-// ---------------------------------------------------------------------------------------------- transcript
-static const unsigned SIGN_BIT = 6, INF_BIT = 7;   // compressed G1: sign(y) and identity flags in the top byte (halo2curves new_curve_impl!; the
-                                                   // positions are UNVERIFIED for halo2curves-axiom 0.7.3, see oracle/transcript.py)
-struct Transcript {   // Blake2bWrite<Vec<u8>, G1Affine, Challenge255<_>>  
-    Blake2b st;
-    std::vector<uint8_t> proof;
-    Transcript() : st(64, "Halo2-Transcript") {}
-    void common_scalar(const Fr &s) {
-        uint8_t b[33];
-        b[0] = 0x02;
-        fr_repr(s, b + 1);
-        st.update(b, 33);
-    }
-    void write_scalar(const Fr &s) {
-        common_scalar(s);
-        uint8_t b[32];
-        fr_repr(s, b);
-        proof.insert(proof.end(), b, b + 32);
-    }
-    int write_point(const G1Affine &p) {
-        if (p.x.is_zero() && p.y.is_zero()) {   // upstream: io::Error "cannot write points at infinity to the transcript"
-            set_error("create_proof: a commitment is the point at infinity and cannot be written to the transcript");
-            return H2HIP_ERR_INVALID;
-        }
-        uint8_t b[65];
-        b[0] = 0x01;
-        fq_repr(p.x, b + 1);
-        fq_repr(p.y, b + 33);
-        st.update(b, 65);
-        uint8_t c[32];
-        memcpy(c, b + 1, 32);
-        c[31] |= (uint8_t)((b[33] & 1) << SIGN_BIT);
-        proof.insert(proof.end(), c, c + 32);
-        return H2HIP_OK;
-    }
-    Fr squeeze_challenge() {
-        uint8_t z = 0x00, d[64];
-        st.update(&z, 1);
-        st.digest(d);
-        return fr_from_uniform_bytes(d);
-    }
-};
-
 static inline G1Affine jacobian_to_affine(const G1Jac &p) {
     G1Affine r;
     if (p.z.is_zero()) {
@@ -367,8 +325,9 @@ static inline G1Affine jacobian_to_affine(const G1Jac &p) {
 }
 
 // plonk_prove.hip: one proof.  Nothing of the run stays on the context: its callbacks into the batch MSM are arguments of the commitment calls.
+// `tr`: the built-in Blake2b transcript (the caller takes its bytes) or the adapter over the caller's callbacks.
 int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, bool advice_on_device, const void *const *instances,
-                      const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, std::vector<uint8_t> &proof_out, double *stage_ms,
+                      const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, ProverTranscript &tr, double *stage_ms,
                       const h2hip_phase_witness *witness = nullptr);
 
 }  // namespace plonk

@@ -270,7 +270,7 @@ struct Commit {
     h2hip_ctx *ctx;
     h2hip_plonk_pk *pk;
     ShardLink *link;
-    Transcript *tr;
+    ProverTranscript *tr;
     // `bases_per_col`: empty = all columns over `bases`.  `hooks` (optional; BatchMsmHooks, internal.h): every hook given to a commitment that
     // succeeds has run exactly once when it returns
     int points_multi(const h2hip_bases *bases, const std::vector<const h2hip_bases *> &bases_per_col, const std::vector<const void *> &cols, size_t len,
@@ -469,7 +469,7 @@ struct ProofRun {
     const hipStream_t st;
     Scope sc;
     Laps laps;
-    Transcript tr;
+    ProverTranscript &tr;
     RngStage stage;
     ShardLink link;
     Commit commit;
@@ -504,10 +504,11 @@ struct ProofRun {
     std::vector<Query> queries;             // the multiopen's queries in upstream's order
 
     ProofRun(h2hip_ctx *ctx_, h2hip_plonk_pk *pk_, const void *const *advice_, bool advice_on_device_, const void *const *instances_,
-             const size_t *instance_lens_, h2hip_rng_fill_fn rng_, void *rng_user_, double *stage_ms_, const h2hip_phase_witness *witness_)
+             const size_t *instance_lens_, h2hip_rng_fill_fn rng_, void *rng_user_, ProverTranscript &tr_, double *stage_ms_,
+             const h2hip_phase_witness *witness_)
         : ctx(ctx_), pk(pk_), sh(pk_->sh), dom(pk_->dom), advice(advice_), advice_on_device(advice_on_device_), instances(instances_),
           instance_lens(instance_lens_), rng(rng_), rng_user(rng_user_), stage_ms(stage_ms_), witness(witness_), n(sh.n), k(sh.k), ek(sh.extended_k),
-          bf(sh.blinding_factors), u(sh.usable_rows), ne((size_t)1 << ek), st(ctx_->stream), sc(&pk_->pool), laps(ctx_, stage_ms_),
+          bf(sh.blinding_factors), u(sh.usable_rows), ne((size_t)1 << ek), st(ctx_->stream), sc(&pk_->pool), laps(ctx_, stage_ms_), tr(tr_),
           stage{ctx_, pk_, &sc, rng_, rng_user_}, link{ctx_, pk_}, commit{ctx_, pk_, &link, &tr}, side{ctx_, pk_, &sc},
           sharded_any(link.on()), qshard(sharded_any && pk_->shard_quotient), pshard(sharded_any && pk_->shard_products),
           overlap(!sharded_any && ctx_->plonk_tail_overlap != 0 && !sh.dyn && !sh.phased),
@@ -581,8 +582,7 @@ struct ProofRun {
         if ((overlap || side_sharded) && !pk->side_ev) H2_HIPCHK(hipEventCreateWithFlags(&pk->side_ev, hipEventDisableTiming));
         if (overlap && !pk->side_ev1) H2_HIPCHK(hipEventCreateWithFlags(&pk->side_ev1, hipEventDisableTiming));
         link.schedule(sh, qshard);
-        tr.common_scalar(pk->transcript_repr);   // vk.hash_into(transcript)
-        return H2HIP_OK;
+        return tr.common_scalar(pk->transcript_repr);   // vk.hash_into(transcript)
     }
 
     // ---- 2. instance columns: values are hashed, not committed (KZG: QUERY_INSTANCE = false)
@@ -593,7 +593,7 @@ struct ProofRun {
             H2_REQUIRE(len == 0 || (instances && instances[i]), "NULL instance column");
             std::vector<Fr> vals(len ? len : 1);   // the caller's buffer need not be aligned like Fr
             if (len) memcpy(vals.data(), instances[i], sizeof(Fr) * len);
-            for (size_t j = 0; j < len; ++j) tr.common_scalar(vals[j]);
+            for (size_t j = 0; j < len; ++j) H2_CHK(tr.common_scalar(vals[j]));
             H2_CHK(sc.take(n, &inst[i].lagrange));
             H2_HIPCHK(hipMemsetAsync(inst[i].lagrange, 0, sizeof(Fr) * n, st));
             H2_CHK(stage.put(inst[i].lagrange, vals.data(), len));
@@ -770,7 +770,7 @@ struct ProofRun {
         }
         H2_CHK(commit.points(pk->g_lagrange, cols, n, pts, &hooks));
         for (size_t i = 0; i < adv.size(); ++i) H2_CHK(tr.write_point(pts[i]));
-        theta = tr.squeeze_challenge();   // (BaseConfig: every lookup is a single expression, theta does not enter the values)
+        H2_CHK(tr.squeeze_challenge(theta));   // (BaseConfig: every lookup is a single expression, theta does not enter the values)
         for (size_t i = adv.size(); i < pts.size(); ++i) H2_CHK(tr.write_point(pts[i]));
         laps.lap(ST_COMMIT_ROUND1);
         return H2HIP_OK;
@@ -782,7 +782,7 @@ struct ProofRun {
         std::vector<const void *> acols;
         for (Forms &f : adv) acols.push_back(f.lagrange);
         H2_CHK(commit.batch(pk->g_lagrange, acols, n));
-        theta = tr.squeeze_challenge();
+        H2_CHK(tr.squeeze_challenge(theta));
         H2_CHK(sc.take(n, &dyn_table));
         std::vector<const Fr *> ccols;
         std::vector<Fr *> couts;
@@ -825,10 +825,14 @@ struct ProofRun {
             std::vector<const void *> pc(pcols.size());
             for (size_t i = 0; i < pcols.size(); ++i) pc[i] = adv[pcols[i]].lagrange;
             H2_CHK(commit.batch(pk->g_lagrange, pc, n));
-            for (uint32_t c = 0; c < sh.phase_challenges[ph]; ++c) challenges.push_back(tr.squeeze_challenge());
+            for (uint32_t c = 0; c < sh.phase_challenges[ph]; ++c) {
+                Fr ch;
+                H2_CHK(tr.squeeze_challenge(ch));
+                challenges.push_back(ch);
+            }
         }
         laps.lap(ST_COMMIT_ROUND1);
-        theta = tr.squeeze_challenge();
+        H2_CHK(tr.squeeze_challenge(theta));
         H2_CHK(permute_lookups());
         laps.lap(ST_LOOKUP_PERMUTE);
         H2_CHK(commit.batch(pk->g_lagrange, lookup_cols, n));
@@ -840,8 +844,8 @@ struct ProofRun {
     // are laid out back to back and go through one batched inversion and one prefix product: over the concatenated sets that prefix product
     // IS the chain z_i(0) = z_{i-1}(last usable row), so neither a host round trip nor a rescaling pass is needed.
     int grand_products() {
-        beta = tr.squeeze_challenge();
-        gamma = tr.squeeze_challenge();
+        H2_CHK(tr.squeeze_challenge(beta));
+        H2_CHK(tr.squeeze_challenge(gamma));
         H2_CHK(pshard ? products_by_row_range() : products_local());
         laps.lap(ST_PRODUCTS);
         return H2HIP_OK;
@@ -1165,8 +1169,7 @@ struct ProofRun {
         for (size_t i = 0; i + 1 < pts.size(); ++i) H2_CHK(tr.write_point(pts[i]));
         laps.lap(ST_COMMIT_PRODUCTS);
         H2_CHK(tr.write_point(pts.back()));   // the random polynomial's commitment
-        y = tr.squeeze_challenge();
-        return H2HIP_OK;
+        return tr.squeeze_challenge(y);
     }
 
     // ---- 10. join of the side stream, the grand products' coefficient and extended forms, h(X)'s accumulator
@@ -1328,8 +1331,7 @@ struct ProofRun {
         for (uint32_t i = 0; i < sh.quotient_pieces; ++i) cols.push_back(acc + (size_t)i * n);
         H2_CHK(commit.batch(pk->g, cols, n));
         laps.lap(ST_COMMIT_H);
-        x = tr.squeeze_challenge();
-        return H2HIP_OK;
+        return tr.squeeze_challenge(x);
     }
 
     // ---- 13. evaluations: every (polynomial, point) pair of the round goes through ONE batched launch; the transcript then takes the
@@ -1425,7 +1427,7 @@ struct ProofRun {
             }
             for (size_t i = 0; i < evq.size(); ++i) evq[i].eval = vals[i];
         }
-        for (size_t i = 0; i < n_written; ++i) tr.write_scalar(evq[i].eval);
+        for (size_t i = 0; i < n_written; ++i) H2_CHK(tr.write_scalar(evq[i].eval));
         // the multiopen's query list in upstream's order: advice, permutation (sets at x / x_next, then sets.rev().skip(1) at x_last), lookups
         // (product, permuted input, permuted table at x; permuted input at x_inv; product at x_next), fixed, permutation polynomials, h, random
         auto ask = [&](size_t i) {
@@ -1469,12 +1471,13 @@ struct ProofRun {
     // evaluations at the roots (32 bytes per (set, root) pair), and each divides its range with the carry assembled from the ranges above
     // (h2hip_fr_kate_division_range_dev).  The same for the final division of the linearisation by (X - u).
     int shplonk() {
-        const Fr yq = tr.squeeze_challenge();
+        Fr yq, v, uq;
+        H2_CHK(tr.squeeze_challenge(yq));
         std::vector<RotationSet> sets;
         std::vector<Fr> super_points;
         construct_intermediate_sets(queries, sets, super_points);
         H2_REQUIRE(!sets.empty(), "more than 64 distinct opening points");
-        const Fr v = tr.squeeze_challenge();
+        H2_CHK(tr.squeeze_challenge(v));
         const size_t lo = link.lo(n), hi = link.hi(n);
         const size_t L = hi - lo;   // coefficients held here (everything on one GPU)
         // S_i(X) = sum_j y^j P_ij(X) (kept for the linearisation), r_i(X) = sum_j y^j * interpolant of P_ij on the set's points
@@ -1554,7 +1557,7 @@ struct ProofRun {
             }
         }
         H2_CHK(commit.batch(pk->g, std::vector<const void *>(1, h_x), n));
-        const Fr uq = tr.squeeze_challenge();
+        H2_CHK(tr.squeeze_challenge(uq));
         // linearisation L(X) = sum_i v^i Z_{T\S_i}(u) (S_i(X) - r_i(u)) - Z_T(u) h(X), which vanishes at u
         Fr *l_x = buf_a;
         Fr const0 = Fr::zero(), z_diff_0 = Fr::one();
@@ -1604,9 +1607,9 @@ struct ProofRun {
 };
 
 int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, bool advice_on_device, const void *const *instances,
-                      const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, std::vector<uint8_t> &proof_out, double *stage_ms,
+                      const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user, ProverTranscript &tr, double *stage_ms,
                       const h2hip_phase_witness *witness) {
-    ProofRun run(ctx, pk, advice, advice_on_device, instances, instance_lens, rng, rng_user, stage_ms, witness);
+    ProofRun run(ctx, pk, advice, advice_on_device, instances, instance_lens, rng, rng_user, tr, stage_ms, witness);
     H2_CHK(run.set_up());
     H2_CHK(run.instance_columns());
     H2_CHK(run.advice_columns());
@@ -1619,9 +1622,7 @@ int create_proof_impl(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *adv
     H2_CHK(run.quotient());
     H2_CHK(run.h_pieces());
     H2_CHK(run.evaluations());
-    H2_CHK(run.shplonk());
-    proof_out.swap(run.tr.proof);
-    return H2HIP_OK;
+    return run.shplonk();
 }
 
 }  // namespace plonk

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "blake2b.h"
+#include "transcript.h"
 #include "verifier_internal.h"
 
 namespace h2 {
@@ -253,11 +254,10 @@ static G1Affine g1_neg(const G1Affine &p) {
 
 // ---------------------------------------------------------------------------------------------- transcript (Blake2bRead)
 static const unsigned SIGN_BIT = 6, INF_BIT = 7;
-struct Reader {
+struct Reader final : TranscriptReader {
     Blake2b st;
     const uint8_t *p;
     size_t len, pos = 0;
-    bool ok = true;
     const DecodedPoints *pre;   // the points already decompressed, in reading order (the batch verifier), or nullptr
     size_t pre_pos = 0;
     Reader(const uint8_t *proof, size_t n, const DecodedPoints *decoded = nullptr) : st(64, "Halo2-Transcript"), p(proof), len(n), pre(decoded) {}
@@ -269,13 +269,13 @@ struct Reader {
         memcpy(b + 33, cy.l, 32);
         st.update(b, 65);
     }
-    void common_scalar(const Fr &s) {
+    void common_scalar(const Fr &s) override {
         uint8_t b[33];
         b[0] = 0x02;
         fr_repr(s, b + 1);
         st.update(b, 33);
     }
-    Fr read_scalar() {
+    Fr read_scalar() override {
         Fr c = Fr::zero();
         if (pos + 32 > len) {
             ok = false;
@@ -291,7 +291,7 @@ struct Reader {
         common_scalar(m);
         return m;
     }
-    G1Affine read_point() {
+    G1Affine read_point() override {
         G1Affine r;
         r.x = Fq::zero();
         r.y = Fq::zero();
@@ -344,12 +344,13 @@ struct Reader {
         common_point(r);
         return r;
     }
-    Fr squeeze_challenge() {
+    Fr squeeze_challenge() override {
         uint8_t z = 0x00, d[64];
         st.update(&z, 1);
         st.digest(d);
         return fr_from_uniform_bytes(d);
     }
+    bool exhausted() const override { return pos == len; }   // trailing bytes make a proof malformed
 };
 
 }  // namespace verifier
@@ -480,6 +481,11 @@ size_t proof_words(const VShape &vs, std::vector<uint32_t> *point_words) {
 // derive: the transcript replay, the quotient identity rebuilt from the openings, SHPLONK's folded opening as a list of (commitment, scalar)
 int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
            const DecodedPoints *pre, Derived *out, int *well_formed) {
+    Reader tr(proof, proof_len, pre);
+    return derive(vs, vk, instances_host, instance_lens, tr, out, well_formed);
+}
+int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, TranscriptReader &tr, Derived *out,
+           int *well_formed) {
     const h2hip_plonk_shape &sh = vs.sh;
     *well_formed = 0;
     const uint32_t k = vs.k, n = 1u << k, bf = sh.blinding_factors;
@@ -500,7 +506,6 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
     delta = fe_to_mont(delta);
     const Fr one = Fr::one();
 
-    Reader tr(proof, proof_len, pre);
     tr.common_scalar(repr);
     std::vector<std::vector<Fr>> inst(vs.num_instance);
     for (uint32_t i = 0; i < vs.num_instance; ++i) {
@@ -564,6 +569,7 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
         l.aie = tr.read_scalar();
         l.se = tr.read_scalar();
     }
+    if (tr.err != H2HIP_OK) return tr.err;   // the caller's transcript failed
     if (!tr.ok) return H2HIP_OK;   // malformed proof
     // ---- the quotient identity at x
     const Fr xn = fe_pow_u64(x, n);
@@ -700,7 +706,8 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
     const G1Affine h1 = tr.read_point();
     const Fr u = tr.squeeze_challenge();
     const G1Affine h2 = tr.read_point();
-    if (!tr.ok || tr.pos != proof_len) return H2HIP_OK;   // malformed or trailing bytes
+    if (tr.err != H2HIP_OK) return tr.err;
+    if (!tr.ok || !tr.exhausted()) return H2HIP_OK;   // malformed or trailing bytes
     out->terms.clear();
     Fr r_outer = Fr::zero(), z_0 = Fr::zero(), z_0_diff_inv = Fr::zero(), vpow = one;
     for (size_t i = 0; i < sets.size(); ++i) {
@@ -929,6 +936,44 @@ int h2hip_plonk_verify_proof_rlc(const h2hip_rlc_circuit_params *params, const v
     H2_CHK(vshape_rlc(params, vs));
     return verify_one(vs, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, instances_host, instance_lens, proof, proof_len,
                       accepted);
+}
+
+// verify_proof over the caller's transcript (include/h2hip.h): derive over the callback reader, the scalar multiplications on the host, one
+// pairing; acc_out receives (W', outer), the pair the pairing decides
+int h2hip_plonk_verify_proof_transcript(int kind, const void *params, const void *fixed_commitments, const void *permutation_commitments,
+                                        const void *transcript_repr, const void *g1, const void *g2, const void *s_g2,
+                                        const void *const *instances_host, const size_t *instance_lens, const h2hip_transcript *t, int *accepted,
+                                        void *acc_out) {
+    H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && t && accepted, "NULL argument");
+    *accepted = 0;
+    if (acc_out) memset(acc_out, 0, 2 * sizeof(G1Affine));
+    H2_REQUIRE(t->common_scalar && t->read_point && t->read_scalar && t->squeeze_challenge,
+               "h2hip_plonk_verify_proof_transcript: the transcript lacks common_scalar, read_point, read_scalar or squeeze_challenge");
+    VShape vs;
+    if (kind == H2HIP_CIRCUIT_BASE) {
+        H2_CHK(vshape_base((const h2hip_base_circuit_params *)params, vs));
+    } else if (kind == H2HIP_CIRCUIT_DYN) {
+        H2_CHK(vshape_dyn((const h2hip_dyn_circuit_params *)params, vs));
+    } else if (kind == H2HIP_CIRCUIT_PHASED) {
+        H2_CHK(vshape_phased((const h2hip_phased_circuit_params *)params, vs));
+    } else if (kind == H2HIP_CIRCUIT_RLC) {
+        H2_CHK(vshape_rlc((const h2hip_rlc_circuit_params *)params, vs));
+    } else {
+        H2_REQUIRE(false, "unknown circuit kind (H2HIP_CIRCUIT_BASE / _DYN / _PHASED / _RLC)");
+    }
+    const VKey vk = {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2};
+    H2_CHK(check_key(vs, vk, instances_host, instance_lens));
+    CallbackReader tr(t);
+    Derived d;
+    int well_formed = 0;
+    H2_CHK(derive(vs, vk, instances_host, instance_lens, tr, &d, &well_formed));
+    if (!well_formed) return H2HIP_OK;   // a malformed proof is a rejection
+    const G1Affine outer = outer_on_host(vk, d);
+    if (acc_out) {
+        memcpy(acc_out, &d.w, sizeof(G1Affine));
+        memcpy((uint8_t *)acc_out + sizeof(G1Affine), &outer, sizeof(G1Affine));
+    }
+    return pairing_verdict(vk, d.w, outer, accepted);
 }
 
 // e(P_0, Q_0) * ... * e(P_{n-1}, Q_{n-1}) == 1 — the "final CPU-side pairing" of the north star as an entry of its own (the verifier above ends in

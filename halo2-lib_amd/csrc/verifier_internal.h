@@ -9,6 +9,7 @@
 
 #include "host_field.h"
 #include "internal.h"
+#include "transcript.h"
 
 namespace h2 {
 namespace verifier {
@@ -68,6 +69,10 @@ int check_key(const VShape &vs, const VKey &vk, const void *const *instances_hos
 // non-canonical scalar, a bad point, an instance column longer than usable_rows, x on the domain, a zero z_diff.
 int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
            const DecodedPoints *pre, Derived *out, int *well_formed);
+// the same over any reader (transcript.h): the built-in Blake2b reader above, or the adapter over the caller's callbacks.  A reader whose
+// err is set makes derive return it.
+int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, TranscriptReader &tr, Derived *out,
+           int *well_formed);
 G1Affine outer_on_host(const VKey &vk, const Derived &d);                                 // the terms' sum by host double-and-add
 int pairing_verdict(const VKey &vk, const G1Affine &left, const G1Affine &outer, int *accepted);   // e(left, s_g2) * e(-outer, g2) == 1
 // derive + finish for one proof: what h2hip_plonk_verify_proof* compute

@@ -143,6 +143,9 @@ _PROTOS = {
                                         C.POINTER(C.c_double)]),
     "h2hip_plonk_create_proof_phased": (_int, [_vp, _vp, C.POINTER(_vp), _int, C.POINTER(_vp), C.POINTER(_sz), _vp, _vp, _vp, _vp, _sz,
                                                 C.POINTER(_sz), C.POINTER(C.c_double)]),
+    "h2hip_plonk_create_proof_transcript": (_int, [_vp, _vp, C.POINTER(_vp), _int, C.POINTER(_vp), C.POINTER(_sz), _vp, _vp, _vp, _vp,
+                                                    C.POINTER(C.c_double)]),
+    "h2hip_plonk_verify_proof_transcript": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_sz), _vp, C.POINTER(_int), _vp]),
     "h2hip_divide_by_vanishing_poly_dev": (_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "h2hip_lookup_permute_dev": (_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "h2hip_lookup_sorted_table_bytes": (_sz, [_sz]),

@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <exception>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -506,6 +507,97 @@ inline bool verify_proof(const ProvingKey &pk, const h2hip_base_circuit_params &
     check(h2hip_plonk_verify_proof(&params, pk.fixed_commitments().data(), pk.permutation_commitments().empty() ? &dummy : pk.permutation_commitments().data(),
                                    &transcript_repr, &g1, g2, s_g2, ins.empty() ? nullptr : ins.data(), lens.empty() ? nullptr : lens.data(), proof.data(),
                                    proof.size(), &ok));
+    return ok != 0;
+}
+
+// The caller's transcript: upstream's TranscriptWrite / TranscriptRead with its challenge, as an abstract class.  The proof's byte encoding is
+// the implementation's: write_* absorb and serialise, read_* parse and absorb, common_* only absorb.  Points and scalars cross in Montgomery
+// form.  An operation fails by throwing; one a transcript does not serve keeps the default, which throws.  The methods run on the calling
+// thread while the proof is in flight: they must not call into the library with the proof's Backend.
+struct Transcript {
+    virtual ~Transcript() {}
+    virtual void common_point(const G1Affine &) { throw Error(H2HIP_ERR_INVALID, "transcript: common_point is not served"); }
+    virtual void common_scalar(const Fr &) { throw Error(H2HIP_ERR_INVALID, "transcript: common_scalar is not served"); }
+    virtual void write_point(const G1Affine &) { throw Error(H2HIP_ERR_INVALID, "transcript: write_point is not served"); }
+    virtual void write_scalar(const Fr &) { throw Error(H2HIP_ERR_INVALID, "transcript: write_scalar is not served"); }
+    virtual G1Affine read_point() { throw Error(H2HIP_ERR_INVALID, "transcript: read_point is not served"); }
+    virtual Fr read_scalar() { throw Error(H2HIP_ERR_INVALID, "transcript: read_scalar is not served"); }
+    virtual Fr squeeze_challenge() { throw Error(H2HIP_ERR_INVALID, "transcript: squeeze_challenge is not served"); }
+};
+namespace detail {
+// h2hip_transcript over a Transcript: no exception crosses the C frames — the first one is kept, the callback returns 1
+struct TranscriptBridge {
+    Transcript *t;
+    std::exception_ptr error;
+    template <class F>
+    int guard(F f) {
+        try {
+            f();
+            return 0;
+        } catch (...) {
+            if (!error) error = std::current_exception();
+            return 1;
+        }
+    }
+    static TranscriptBridge &of(void *user) { return *static_cast<TranscriptBridge *>(user); }
+    h2hip_transcript callbacks() {
+        h2hip_transcript c;
+        c.user = this;
+        c.common_point = [](void *u, const void *p) { return of(u).guard([&] { of(u).t->common_point(*static_cast<const G1Affine *>(p)); }); };
+        c.write_point = [](void *u, const void *p) { return of(u).guard([&] { of(u).t->write_point(*static_cast<const G1Affine *>(p)); }); };
+        c.common_scalar = [](void *u, const void *s) { return of(u).guard([&] { of(u).t->common_scalar(*static_cast<const Fr *>(s)); }); };
+        c.write_scalar = [](void *u, const void *s) { return of(u).guard([&] { of(u).t->write_scalar(*static_cast<const Fr *>(s)); }); };
+        c.read_point = [](void *u, void *o) { return of(u).guard([&] { *static_cast<G1Affine *>(o) = of(u).t->read_point(); }); };
+        c.read_scalar = [](void *u, void *o) { return of(u).guard([&] { *static_cast<Fr *>(o) = of(u).t->read_scalar(); }); };
+        c.squeeze_challenge = [](void *u, void *o) { return of(u).guard([&] { *static_cast<Fr *>(o) = of(u).t->squeeze_challenge(); }); };
+        return c;
+    }
+};
+}  // namespace detail
+
+// create_proof(params, pk, &[circuit], &[instances], rng, &mut transcript) for any transcript (h2hip_plonk_create_proof_transcript): the proof's
+// bytes are the transcript's.  An exception thrown inside the transcript aborts the proof and is rethrown here; the key serves the next proof.
+template <class Rng>
+inline void create_proof_with_transcript(Backend &b, const ProvingKey &pk, const std::vector<std::vector<Fr>> &advice,
+                                         const std::vector<std::vector<Fr>> &instances, Rng &rng, Transcript &transcript) {
+    std::vector<const void *> adv, ins;
+    std::vector<size_t> lens;
+    for (auto &c : advice) adv.push_back(c.data());
+    for (auto &c : instances) {
+        ins.push_back(c.data());
+        lens.push_back(c.size());
+    }
+    if (adv.size() != pk.shape().num_advice_total) throw Error(H2HIP_ERR_INVALID, "create_proof: wrong number of advice columns");
+    auto tramp = [](void *user, void *out, size_t n) { (*static_cast<Rng *>(user))(static_cast<Fr *>(out), n); };
+    detail::TranscriptBridge bridge{&transcript, nullptr};
+    const h2hip_transcript cb = bridge.callbacks();
+    const int rc = h2hip_plonk_create_proof_transcript(b.raw(), pk.raw(), adv.data(), 0, ins.empty() ? nullptr : ins.data(),
+                                                       lens.empty() ? nullptr : lens.data(), +tramp, &rng, nullptr, &cb, nullptr);
+    if (rc != H2HIP_OK && bridge.error) std::rethrow_exception(bridge.error);
+    check(rc);
+}
+
+// verify_proof over any transcript (h2hip_plonk_verify_proof_transcript).  A read that throws, or hands over a bad value, rejects the proof;
+// an exception in common_scalar or squeeze_challenge is rethrown.  accumulator (optional): the pair (W', outer) the pairing decides.
+inline bool verify_proof_with_transcript(const ProvingKey &pk, const h2hip_base_circuit_params &params, const Fr &transcript_repr, const G1Affine &g1,
+                                         const uint8_t g2[128], const uint8_t s_g2[128], const std::vector<std::vector<Fr>> &instances,
+                                         Transcript &transcript, G1Affine accumulator[2] = nullptr) {
+    std::vector<const void *> ins;
+    std::vector<size_t> lens;
+    for (auto &c : instances) {
+        ins.push_back(c.data());
+        lens.push_back(c.size());
+    }
+    int ok = 0;
+    G1Affine dummy{};
+    detail::TranscriptBridge bridge{&transcript, nullptr};
+    const h2hip_transcript cb = bridge.callbacks();
+    const int rc = h2hip_plonk_verify_proof_transcript(H2HIP_CIRCUIT_BASE, &params, pk.fixed_commitments().data(),
+                                                       pk.permutation_commitments().empty() ? &dummy : pk.permutation_commitments().data(), &transcript_repr,
+                                                       &g1, g2, s_g2, ins.empty() ? nullptr : ins.data(), lens.empty() ? nullptr : lens.data(), &cb, &ok,
+                                                       accumulator);
+    if (rc != H2HIP_OK && bridge.error) std::rethrow_exception(bridge.error);
+    check(rc);
     return ok != 0;
 }
 

@@ -177,6 +177,82 @@ class _PhaseWitness(C.Structure):   # h2hip_phase_witness
     _fields_ = [("fill", _vp), ("user", _vp)]
 
 
+_TR_IN_FN = C.CFUNCTYPE(C.c_int, _vp, _vp)    # h2hip_transcript_point_fn / h2hip_transcript_scalar_fn
+_TR_OUT_FN = C.CFUNCTYPE(C.c_int, _vp, _vp)   # h2hip_transcript_read_fn
+
+
+class _Transcript(C.Structure):   # h2hip_transcript
+    _fields_ = [("user", _vp), ("common_point", _vp), ("write_point", _vp), ("common_scalar", _vp), ("write_scalar", _vp), ("read_point", _vp),
+                ("read_scalar", _vp), ("squeeze_challenge", _vp)]
+
+
+Q_MOD = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
+_MONT = 1 << 256
+
+
+def _mont_in(ptr, mod) -> int:
+    """the integer behind 4 Montgomery limbs at ptr"""
+    v = int.from_bytes(C.string_at(ptr, 32), "little")
+    return v * pow(_MONT, -1, mod) % mod
+
+
+def _mont_out(ptr, v: int, mod):
+    """v (an int in [0, mod)) as 4 Montgomery limbs at ptr; anything else is written as it stands, for the library to refuse"""
+    raw = int(v) * _MONT % mod if 0 <= int(v) < mod else int(v) & (_MONT - 1)
+    C.memmove(ptr, raw.to_bytes(32, "little"), 32)
+
+
+def _transcript_trampolines(obj, err: list):
+    """(h2hip_transcript, the callback objects to keep alive) over a Python transcript: an object with some of common_point / write_point((x, y)),
+    common_scalar / write_scalar(int), read_point() -> (x, y), read_scalar() -> int, squeeze_challenge() -> int, as oracle/transcript.py's
+    classes have them.  A method the object lacks stays NULL.  An exception inside a method makes the callback return 1; it is kept in err."""
+    q_inv, r_inv = pow(_MONT, -1, Q_MOD), pow(_MONT, -1, R_MOD)
+
+    def guard(fn):
+        def run(_user, ptr):
+            try:
+                fn(ptr)
+                return 0
+            except BaseException as e:   # never unwind through the C frames
+                err.append(e)
+                return 1
+        return run
+
+    def point_in(method):
+        def fn(ptr):
+            b = C.string_at(ptr, 64)
+            method((int.from_bytes(b[:32], "little") * q_inv % Q_MOD, int.from_bytes(b[32:], "little") * q_inv % Q_MOD))
+        return fn
+
+    def scalar_in(method):
+        return lambda ptr: method(int.from_bytes(C.string_at(ptr, 32), "little") * r_inv % R_MOD)
+
+    def point_out(method):
+        def fn(ptr):
+            P = method()
+            if P is None:   # the identity: all-zero, which the library rejects
+                C.memset(ptr, 0, 64)
+                return
+            _mont_out(ptr, P[0], Q_MOD)
+            _mont_out(ptr + 32, P[1], Q_MOD)
+        return fn
+
+    def scalar_out(method):
+        return lambda ptr: _mont_out(ptr, method(), R_MOD)
+
+    wrap = {"common_point": (_TR_IN_FN, point_in), "write_point": (_TR_IN_FN, point_in), "common_scalar": (_TR_IN_FN, scalar_in),
+            "write_scalar": (_TR_IN_FN, scalar_in), "read_point": (_TR_OUT_FN, point_out), "read_scalar": (_TR_OUT_FN, scalar_out),
+            "squeeze_challenge": (_TR_OUT_FN, scalar_out)}
+    t, keep = _Transcript(), []
+    for name, (proto, make) in wrap.items():
+        method = getattr(obj, name, None)
+        if method is not None:
+            cb = proto(guard(make(method)))
+            keep.append(cb)
+            setattr(t, name, C.cast(cb, _vp))
+    return t, keep
+
+
 class _ArrayRngState(C.Structure):   # h2hip_array_rng
     _fields_ = [("values", _vp), ("count", C.c_size_t), ("pos", C.c_size_t), ("exhausted", C.c_int)]
 
@@ -315,13 +391,17 @@ def keygen(kzg: ParamsKZG, params, fixed: Sequence[np.ndarray], copies) -> Provi
 
 
 def create_proof(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarray], rng, timings: Optional[dict] = None,
-                 advice_on_device: bool = False, phase_witness=None, phase_witness_dev=None) -> bytes:
+                 advice_on_device: bool = False, phase_witness=None, phase_witness_dev=None, transcript=None) -> bytes:
     """create_proof for one circuit: advice columns (host (n,4) arrays, or device pointers with advice_on_device), instance columns
     ((m,4) arrays), rng = ArrayRng / ChaChaRng / CallbackRng.  Returns the proof bytes (Blake2bWrite::finalize).
     A PhasedCircuitParams key takes phase 0's columns in `advice`; phase_witness(phase, challenges: list[int]) -> list returns each later
     phase's columns (host (n,4) arrays or device pointers to n Fr) given every challenge squeezed so far.  An RlcCircuitParams key likewise;
     its phase-1 column list ends with the RLC columns.  phase_witness_dev(phase, challenges: list[int], column_ptrs: list[int]) instead writes
-    the phase's zeroed device columns in place (rlc_fill_chains, `_dev` functions on the key's context, completed device copies)."""
+    the phase's zeroed device columns in place (rlc_fill_chains, `_dev` functions on the key's context, completed device copies).
+    transcript: the caller's transcript object (h2hip_plonk_create_proof_transcript) with common_scalar(int), write_point((x, y)),
+    write_scalar(int) and squeeze_challenge() -> int, as oracle/transcript.py's Blake2bWrite has them; its methods run while the proof is in
+    flight and must not use pk's context.  The proof's bytes are then the transcript's: the call returns transcript.finalize() if the object
+    has it, else None.  An exception raised inside a method aborts the proof and is re-raised here."""
     ctx, sh = pk.ctx, pk.shape
     n = 1 << pk.params.k
     phased = isinstance(pk.params, (PhasedCircuitParams, RlcCircuitParams))
@@ -357,6 +437,10 @@ def create_proof(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarra
     stage = (C.c_double * PLONK_STAGES)() if timings is not None else None
     if phased:
         wit = _phase_witness_trampoline(ctx, n, phase_witness, err, phase_witness_dev)
+    if transcript is not None:   # one entry for every kind of key; it returns no bytes
+        tr = _transcript_trampolines(transcript, err)
+        entry = lambda *a: ctx.lib.h2hip_plonk_create_proof_transcript(*a[:8], C.byref(wit[0]) if phased else None, C.byref(tr[0]), a[11])
+    elif phased:
         entry = lambda *a: ctx.lib.h2hip_plonk_create_proof_phased(*a[:8], C.byref(wit[0]), *a[8:])
     else:
         entry = ctx.lib.h2hip_plonk_create_proof
@@ -384,6 +468,8 @@ def create_proof(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarra
             name = ctx.lib.h2hip_plonk_stage_name(i).decode()
             timings[name] = timings.get(name, 0.0) + stage[i]
     del keep
+    if transcript is not None:
+        return transcript.finalize() if hasattr(transcript, "finalize") else None
     return proof[: plen.value].tobytes()
 
 
@@ -422,10 +508,24 @@ def _phase_witness_trampoline(ctx: Context, n: int, phase_witness, err: list, ph
     return _PhaseWitness(C.cast(cb, _vp), None), cb
 
 
-def verify_proof(pk: ProvingKey, instances: Sequence[np.ndarray], proof: bytes) -> bool:
+_CIRCUIT_RLC = 3   # H2HIP_CIRCUIT_RLC: h2hip_plonk_verify_proof_transcript only
+
+
+def verify_proof(pk: ProvingKey, instances: Sequence[np.ndarray], proof: Optional[bytes] = None, transcript=None, want_accumulator: bool = False):
     """verify_proof with the key's verifying half (VerifierSHPLONK, SingleStrategy) — check_proof of halo2-base/src/utils/testing.rs:64-88.
-    Host code inside libh2hip; needs the G2 half of the SRS (ParamsKZG.g2_raw)."""
+    Host code inside libh2hip; needs the G2 half of the SRS (ParamsKZG.g2_raw).
+    transcript: instead of `proof`, the caller's reading transcript (h2hip_plonk_verify_proof_transcript) with common_scalar(int), read_point()
+    -> (x, y), read_scalar() -> int and squeeze_challenge() -> int, as oracle/transcript.py's Blake2bRead has them.  A read that raises, or
+    returns a bad value, rejects the proof (the exception is dropped: a malformed proof is not an error); an exception in common_scalar or
+    squeeze_challenge is re-raised.  If the object has exhausted(), input left over rejects the proof.  want_accumulator: return (accepted,
+    acc) with acc the (2, 8) uint64 pair (W', outer) the pairing decides (zeros when the proof is malformed)."""
     ctx, kzg = pk.ctx, pk.kzg
+    if transcript is not None:
+        if proof is not None:
+            raise ValueError("verify_proof: give proof or transcript, not both")
+        return _verify_proof_transcript(pk, instances, transcript, want_accumulator)
+    if want_accumulator:
+        raise ValueError("verify_proof: want_accumulator needs transcript=")
     if len(kzg.g2_raw) != 256:
         raise ValueError("verify_proof: the ParamsKZG carries no G2 elements (g2_raw)")
     inst = [_fe(c) for c in instances]
@@ -458,6 +558,38 @@ def verify_proof(pk: ProvingKey, instances: Sequence[np.ndarray], proof: bytes) 
                                               _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128), ip, il,
                                               _vp(buf.ctypes.data), len(buf), C.byref(ok)))
     return bool(ok.value)
+
+
+def _verify_proof_transcript(pk: ProvingKey, instances, transcript, want_accumulator: bool):
+    ctx, kzg = pk.ctx, pk.kzg
+    if len(kzg.g2_raw) != 256:
+        raise ValueError("verify_proof: the ParamsKZG carries no G2 elements (g2_raw)")
+    inst = [_fe(c) for c in instances]
+    if len(inst) != pk.params.num_instance:
+        raise ValueError("verify_proof: need %d instance columns" % pk.params.num_instance)
+    ip = (_vp * max(len(inst), 1))(*[_vp(c.ctypes.data) for c in inst])
+    il = (C.c_size_t * max(len(inst), 1))(*[len(c) for c in inst])
+    g0 = ctx.bases_download(kzg.g)[:1].copy() if not hasattr(kzg, "_g0") else kzg._g0
+    kzg._g0 = g0
+    g2 = np.frombuffer(kzg.g2_raw, dtype=np.uint8).copy()
+    pc = pk.permutation_commitments if len(pk.permutation_commitments) else np.zeros((1, 8), dtype=np.uint64)
+    kind = _CIRCUIT_RLC if isinstance(pk.params, RlcCircuitParams) else _CIRCUIT_KINDS[type(pk.params)]
+    err = []
+    tr, keep = _transcript_trampolines(transcript, err)
+    ok = C.c_int(0)
+    acc = np.zeros((2, 8), dtype=np.uint64)
+    rc = ctx.lib.h2hip_plonk_verify_proof_transcript(kind, C.cast(C.byref(pk.params), _vp), _ptr(np.ascontiguousarray(pk.fixed_commitments)),
+                                                     _ptr(np.ascontiguousarray(pc)), _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data),
+                                                     _vp(g2.ctypes.data + 128), ip if inst else None, il if inst else None, C.byref(tr),
+                                                     C.byref(ok), _ptr(acc))
+    del keep
+    if rc != 0 and err:   # the transcript failed where no proof byte is involved
+        raise err[0]
+    ctx._chk(rc)
+    accepted = bool(ok.value)
+    if accepted and hasattr(transcript, "exhausted") and not transcript.exhausted():
+        accepted = False
+    return (accepted, acc) if want_accumulator else accepted
 
 
 _CIRCUIT_KINDS = {BaseCircuitParams: 0, DynLookupCircuitParams: 1, PhasedCircuitParams: 2}   # H2HIP_CIRCUIT_BASE / _DYN / _PHASED (RLC keys: not batched)

@@ -688,6 +688,39 @@ int h2hip_plonk_create_proof_phased(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const vo
                                     const void *const *instances_host, const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user,
                                     const h2hip_phase_witness *witness, uint8_t *proof_out, size_t proof_cap, size_t *proof_len, double *stage_ms);
 
+/* ---- a caller-supplied transcript.  Upstream's create_proof / verify_proof are generic over the transcript (T: TranscriptWrite<_, E> /
+ * TranscriptRead<_, E>); the entries above serve Blake2bWrite / Blake2bRead + Challenge255.  Like the RNG, the transcript is the caller's:
+ * with h2hip_transcript the library calls back for every transcript operation, in upstream's order, and never sees the proof's bytes.
+ * Values cross as everywhere else in the ABI: a point is 64 B (Montgomery x, y), a scalar or challenge one Montgomery Fr (4 x u64).
+ * The proof's byte encoding belongs to the transcript: write_* absorb the value AND serialise it into the caller's own buffer; read_* parse the
+ * next value from the caller's buffer (decompressing, if the encoding compresses), absorb it and hand it over; common_* only absorb;
+ * squeeze_challenge writes the next challenge.  Every callback returns 0, or non-zero for a failure of that operation.
+ * Callbacks run on the calling thread.  They may run while the library has work in flight on the context's streams, so they must not call
+ * into the library with that context (h2hip_blake2b and the other host-only entries that take no context are fine). */
+typedef int (*h2hip_transcript_point_fn)(void *user, const void *g1_affine);       /* 64 B: Montgomery x, y */
+typedef int (*h2hip_transcript_scalar_fn)(void *user, const void *fr);              /* Montgomery Fr */
+typedef int (*h2hip_transcript_read_fn)(void *user, void *out);                     /* read_point: 64 B out; read_scalar / squeeze_challenge: Fr out */
+typedef struct h2hip_transcript {
+    void *user;
+    h2hip_transcript_point_fn common_point, write_point;
+    h2hip_transcript_scalar_fn common_scalar, write_scalar;
+    h2hip_transcript_read_fn read_point, read_scalar, squeeze_challenge;
+} h2hip_transcript;
+
+/* create_proof over the caller's transcript, for a key of any of the four configurations: exactly the proof h2hip_plonk_create_proof /
+ * h2hip_plonk_create_proof_phased compute (same device schedule, same RNG draws), with every transcript operation going to `t`.  witness follows
+ * h2hip_plonk_create_proof_phased's rules: NULL for a key with one phase.  Needs t->common_scalar, write_point, write_scalar and
+ * squeeze_challenge: a missing one is H2HIP_ERR_INVALID before any device work.  Returns no bytes: they are in the caller's transcript.
+ *   - A callback that returns non-zero aborts the proof with H2HIP_ERR_INVALID; h2hip_last_error names the operation and how many calls of
+ *     that operation the proof had made, counting from 1 ("write_point #7").  The proof leaves by the path a commitment at infinity takes:
+ *     every stream is drained, and the key and the context serve the next proof.
+ *   - A commitment at infinity is refused by the library (H2HIP_ERR_INVALID) in front of write_point, as Blake2bWrite refuses it.
+ *   - A squeeze_challenge result that is not a canonical Fr (limbs >= r) is H2HIP_ERR_INVALID: the caller's transcript is broken.
+ *   - A key with h2hip_plonk_pk_set_sharding applied is H2HIP_ERR_INVALID. */
+int h2hip_plonk_create_proof_transcript(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const void *const *advice, int advice_on_device,
+                                        const void *const *instances_host, const size_t *instance_lens, h2hip_rng_fill_fn rng, void *rng_user,
+                                        const h2hip_phase_witness *witness, const h2hip_transcript *t, double *stage_ms);
+
 /* ---- witness check: what MockProver::run(k, &circuit, instances).verify() answers (halo2-base/src/utils/testing.rs:183-188), specialised to the
  * one gate form and the lookup forms of the three configurations above; not a generic expression evaluator.  Over the usable rows r < usable_rows,
  * exactly in Fr (advice rows >= usable_rows are ignored, as create_proof ignores them):
@@ -762,6 +795,22 @@ int h2hip_plonk_verify_batch(h2hip_ctx *ctx, int kind, const void *params, const
                              const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, size_t num_proofs,
                              const void *const *instances_host, const size_t *instance_lens, const uint8_t *const *proofs, const size_t *proof_lens,
                              h2hip_rng_fill_fn rng, void *rng_user, int *accepted, uint8_t *rejected_out, void *acc_out);
+
+/* verify_proof over the caller's transcript (see h2hip_transcript).  kind / params: H2HIP_CIRCUIT_BASE / _DYN / _PHASED with their params
+ * struct as for h2hip_plonk_verify_batch, or H2HIP_CIRCUIT_RLC with an h2hip_rlc_circuit_params, which this entry alone accepts.  vk, SRS
+ * and instance arguments as for h2hip_plonk_verify_proof (a configuration without instance columns passes NULL).  Needs t->common_scalar,
+ * read_point, read_scalar and squeeze_challenge (H2HIP_ERR_INVALID otherwise).  Host code.
+ *   - A non-zero return from read_point / read_scalar, or a read value that is off the curve, the identity, or not canonical (limbs >= the
+ *     modulus), is a REJECTION (*accepted = 0, H2HIP_OK), as malformed bytes are for the built-in reader; no callback runs after it.
+ *   - A non-zero return from common_scalar or squeeze_challenge, or a squeezed value that is not a canonical Fr, is H2HIP_ERR_INVALID.
+ *   - Trailing input is the reader's business: the library cannot see it.
+ * acc_out (optional, 2 x 64 B affine, identity all-zero; zeroed when the proof is malformed): the proof's own KZG accumulator (W', outer):
+ * *accepted <=> well-formed and e(W', s_g2) * e(-outer, g2) = 1 — what an aggregator defers instead of pairing. */
+#define H2HIP_CIRCUIT_RLC 3
+int h2hip_plonk_verify_proof_transcript(int kind, const void *params, const void *fixed_commitments, const void *permutation_commitments,
+                                        const void *transcript_repr, const void *g1, const void *g2, const void *s_g2,
+                                        const void *const *instances_host, const size_t *instance_lens, const h2hip_transcript *t, int *accepted,
+                                        void *acc_out);
 
 /* The final CPU-side pairing check of the north star as an entry of its own: *is_one = 1 iff prod_i e(P_i, Q_i) == 1 in Fq12 (what
  * DualMSM::check / halo2curves' multi_miller_loop + final_exponentiation decide for KZG's two pairs).  g1_points: n x 64 B G1Affine

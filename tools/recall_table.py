@@ -11,7 +11,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P, V, L, S = "halo2-lib_amd/csrc/plonk.hip", "halo2-lib_amd/csrc/verifier.hip", "halo2-lib_amd/csrc/lookup.hip", "halo2-lib_amd/csrc/srs.hip"
-PI, PP = "halo2-lib_amd/csrc/plonk_internal.h", "halo2-lib_amd/csrc/plonk_prove.hip"   # the shape / key / transcript; one proof (ProofRun)
+PI, PP = "halo2-lib_amd/csrc/plonk_internal.h", "halo2-lib_amd/csrc/plonk_prove.hip"   # the shape / key; one proof (ProofRun)
+TR = "halo2-lib_amd/csrc/transcript.h"   # the transcript interface and its built-in Blake2b writer
 OP, OT, OB = "oracle/plonk.py", "oracle/transcript.py", "oracle/bn254.py"
 HP, VR, PL = "halo2-lib_amd/halo2_proofs.py", "halo2-lib_amd/virtual_region.py", "halo2-lib_amd/plonk.py"
 RG, OC = "halo2-lib_amd/csrc/rng.hip", "oracle/chacha.py"
@@ -40,11 +41,11 @@ ITEMS = [
      [(PP, "static void construct_intermediate_sets(")], [(OP, "def construct_intermediate_sets(queries):")],
      "both functions (the verifier in verifier.hip shares the product's)"),
     ("compressed G1 flag bits", "32-byte little-endian x with sign(y) in bit 6 and the identity flag in bit 7 of byte 31",
-     [(PI, "static const unsigned SIGN_BIT = 6, INF_BIT = 7;"), (V, "static const unsigned SIGN_BIT = 6, INF_BIT = 7;")], [(OT, "SIGN_BIT, INF_BIT = 6, 7")],
+     [(TR, "static const unsigned SIGN_BIT = 6, INF_BIT = 7;"), (V, "static const unsigned SIGN_BIT = 6, INF_BIT = 7;")], [(OT, "SIGN_BIT, INF_BIT = 6, 7")],
      "the two constants (three places); SRS files in `Processed` encoding pass the positions as arguments (`h2hip_g1_decompress_batch_dev`)"),
     ("transcript framing", "Blake2b-512 personalised `Halo2-Transcript`; prefix bytes 0x01 point (x, y canonical LE), 0x02 scalar, 0x00 before a squeeze of a CLONE; challenge = 64-byte digest reduced mod r",
-     [(PI, "struct Transcript {   // Blake2bWrite")], [(OT, "def squeeze_challenge(self) -> int:")],
-     "`Transcript` (plonk_internal.h) / `TranscriptRead` (verifier.hip) and oracle/transcript.py; the hash itself is pinned by RFC 7693 (tests/test_external_vectors.py)"),
+     [(TR, "struct Transcript final : ProverTranscript {   // Blake2bWrite")], [(OT, "def squeeze_challenge(self) -> int:")],
+     "`Transcript` (transcript.h) / `TranscriptRead` (verifier.hip) and oracle/transcript.py; the hash itself is pinned by RFC 7693 (tests/test_external_vectors.py)"),
     ("`vk.transcript_repr`", "an INPUT (`h2hip_plonk_pk_set_transcript_repr`): upstream hashes the Debug rendering of the pinned verifying key, which only Rust can produce; Python uses a stand-in of the same construction",
      [(P, "int h2hip_plonk_pk_set_transcript_repr("), (PL, "def transcript_repr(params: BaseCircuitParams")], [(OP, "def transcript_repr_for(shape: Shape")],
      "nothing in the library: the Rust shim passes `vk.transcript_repr()`"),
