@@ -16,6 +16,7 @@ from oracle import bn254 as O
 from oracle import c_oracle as CO
 from oracle import plonk as P
 from tests import witness_check_oracle as W
+from tests import witness_edge_checks as WE
 from tests.dyn_lookup_util import oracle_shape, ram_circuit, rng_budget, srs
 from tests.phases_util import PhasedCircuit, shape_params
 from tests.util import PreDrawnRng, R
@@ -297,3 +298,50 @@ def test_struct_layout_and_messages(ctx):
         assert total > 0 and fails == []
     finally:
         b.free()
+
+
+# ---- the kernels' edges (tests/witness_edge_checks.py, shared with the GPU suite)
+@pytest.mark.parametrize("single", [False, True], ids=["lookup_advice", "q_lookup"])
+def test_range_membership_whole_field(ctx, single):
+    WE.check_range_membership(ctx, 8, 6, single)
+
+
+@pytest.fixture(scope="module")
+def mask_case(ctx):
+    c = WE.MaskBlockCase(ctx, (10, 6, 3, 1, 1, 8))   # 20 mask columns of 1024 units: two and a half blocks
+    yield c
+    c.free()
+
+
+@pytest.mark.parametrize("pattern", ["a", "b", "c", "d", "e"])
+def test_failure_list_across_mask_blocks(ctx, mask_case, pattern):
+    assert mask_case.blocks == 3
+    WE.check_mask_blocks(ctx, mask_case, pattern)
+
+
+@pytest.mark.parametrize("key_cols", [1, 2, 3])
+def test_dyn_equal_key_neighbours(ctx, key_cols):
+    WE.check_dyn_neighbours(ctx, key_cols)
+
+
+@pytest.mark.parametrize("key_cols", [1, 2, 3])
+def test_dyn_equal_key_runs(ctx, key_cols):
+    WE.check_dyn_runs(ctx, key_cols)
+
+
+def test_copy_peers_above_255(ctx):
+    WE.check_wide_copy_peers(ctx, (6, 200, 60, 1, 0, 4))   # 261 permutation columns
+
+
+def test_hand_built_key_gates_at_the_last_rows(ctx):
+    WE.check_hand_built_key(ctx)
+
+
+def test_device_advice_garbage_behind_usable_rows(ctx):
+    WE.check_device_advice_garbage(ctx)
+
+
+def test_rlc_gate_at_the_last_rows(ctx):
+    from tests import rlc_checks as RC
+
+    WE.check_rlc_gate_edge(ctx, RC.EMU_K, 4)

@@ -15,6 +15,7 @@ from halo2_lib_amd import testing as T
 from oracle import bn254 as O
 from oracle import plonk as P
 from tests import witness_check_oracle as W
+from tests import witness_edge_checks as WE
 from tests.dyn_lookup_util import oracle_shape, ram_circuit, srs
 from tests.golden import make_proof_goldens as M
 from tests.phases_util import PhasedCircuit, shape_params
@@ -186,3 +187,49 @@ def test_phased_k10_against_oracle(ctx):
     finally:
         pk.free()
         kzg.free()
+
+
+# ---- the kernels' edges (tests/witness_edge_checks.py, shared with the CPU-emulated suite)
+@pytest.mark.parametrize("k, lb", [(8, 6), (12, 11)])
+@pytest.mark.parametrize("single", [False, True], ids=["lookup_advice", "q_lookup"])
+def test_range_membership_whole_field(ctx, k, lb, single):
+    WE.check_range_membership(ctx, k, lb, single)
+
+
+@pytest.fixture(scope="module", params=[(10, 6, 3, 1, 1, 8), (14, 1, 1, 1, 1, 8)], ids=["20_columns_k10", "5_columns_k14"])
+def mask_case(request, ctx):
+    c = WE.MaskBlockCase(ctx, request.param)   # two and a half blocks with the lookups across a boundary; two blocks per column
+    yield c
+    c.free()
+
+
+@pytest.mark.parametrize("pattern", ["a", "b", "c", "d", "e"])
+def test_failure_list_across_mask_blocks(ctx, mask_case, pattern):
+    assert mask_case.blocks == (3 if mask_case.sh.k == 10 else 10)
+    WE.check_mask_blocks(ctx, mask_case, pattern)
+
+
+@pytest.mark.parametrize("key_cols", [1, 2, 3])
+def test_dyn_equal_key_neighbours(ctx, key_cols):
+    WE.check_dyn_neighbours(ctx, key_cols)
+
+
+@pytest.mark.parametrize("key_cols", [1, 2, 3])
+def test_dyn_equal_key_runs(ctx, key_cols):
+    WE.check_dyn_runs(ctx, key_cols)
+
+
+def test_copy_peers_above_255(ctx):
+    WE.check_wide_copy_peers(ctx, (11, 291, 53, 1, 0, 10))   # the wide k = 11 shape: 345 permutation columns
+
+
+def test_hand_built_key_gates_at_the_last_rows(ctx):
+    WE.check_hand_built_key(ctx)
+
+
+def test_device_advice_garbage_behind_usable_rows(ctx):
+    WE.check_device_advice_garbage(ctx)
+
+
+def test_rlc_gate_at_the_last_rows(ctx):
+    WE.check_rlc_gate_edge(ctx, 7, 4)
