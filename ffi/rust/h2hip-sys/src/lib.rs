@@ -84,6 +84,23 @@ pub struct h2hip_rlc_chain {
     pub value_offset: u64,
 }
 pub const H2HIP_RLC_CARRY: u32 = 1;
+/// one piece of h2hip_gate_fill_chains_dev: a head piece (flags 0 or H2HIP_GATE_START_A) or the continuation of the piece before it, after a
+/// column break (H2HIP_GATE_CARRY) or directly below it (H2HIP_GATE_JOIN); operand i is a_dev[a_offset + i * a_stride], b_dev[b_offset + i * b_stride]
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct h2hip_gate_chain {
+    pub column: u32,
+    pub row: u32,
+    pub len: u32,
+    pub flags: u32,
+    pub a_offset: u64,
+    pub b_offset: u64,
+    pub a_stride: u32,
+    pub b_stride: u32,
+}
+pub const H2HIP_GATE_CARRY: u32 = 1;
+pub const H2HIP_GATE_JOIN: u32 = 2;
+pub const H2HIP_GATE_START_A: u32 = 4;
 /// a later phase's witness: `fill(user, phase, challenges, num_challenges, columns_dev, num_columns)` (include/h2hip.h states the contract)
 pub type h2hip_phase_witness_fn = Option<unsafe extern "C" fn(user: *mut c_void, phase: u32, challenges_fr: *const c_void, num_challenges: usize,
                                                               columns_dev: *const *mut c_void, num_columns: usize) -> c_int>;
@@ -331,6 +348,8 @@ extern "C" {
                                   fixed_host: *const *const c_void, copies: *const u32, ncopies: usize, out: *mut *mut h2hip_plonk_pk) -> c_int;
     pub fn h2hip_rlc_fill_chains_dev(ctx: *mut h2hip_ctx, columns_dev: *const *mut c_void, num_columns: usize, usable_rows: usize, values_dev: *const c_void,
                                      num_values: usize, chains_host: *const h2hip_rlc_chain, count: usize, gamma: *const c_void) -> c_int;
+    pub fn h2hip_gate_fill_chains_dev(ctx: *mut h2hip_ctx, columns_dev: *const *mut c_void, num_columns: usize, usable_rows: usize, a_dev: *const c_void,
+                                      a_len: usize, b_dev: *const c_void, b_len: usize, chains_host: *const h2hip_gate_chain, count: usize) -> c_int;
     pub fn h2hip_quotient_rlc_gate_batch_dev(ctx: *mut h2hip_ctx, acc_dev: *mut c_void, q_dev: *const *const c_void, a_dev: *const *const c_void,
                                              count: usize, ext_k: u32, k: u32, gamma: *const c_void, y: *const c_void) -> c_int;
     pub fn h2hip_plonk_pk_free(ctx: *mut h2hip_ctx, pk: *mut h2hip_plonk_pk);

@@ -165,6 +165,14 @@ pub fn assigned_resolve<'b>(be: &'b Backend, num: &DeviceVec<'b>, den: &DeviceVe
     check(unsafe { h2hip_assigned_resolve_dev(be.ctx, out.ptr, num.ptr, den.ptr, num.len) })?;
     Ok(out)
 }
+/// `GateChip::inner_product*` / `sum` / `select_by_indicator` / `select_from_idx` as cells (halo2-base/src/gates/flex_gate/mod.rs:412, 709-753,
+/// 940-1110): s_0, a_1, b_1, s_1, ... with s_i = s_{i-1} + a_i * b_i for every piece of `chains`, written into `columns` from the operands
+/// `a` and `b`, which may be other columns of the proof (include/h2hip.h states the piece forms and the refusals).
+/// Safety: every pointer of `columns` is a device column of at least `usable_rows` elements on `be`'s device (the phase-witness callback's).
+pub unsafe fn gate_fill_chains(be: &Backend, columns: &[*mut c_void], usable_rows: usize, a: &DeviceVec, b: &DeviceVec, chains: &[h2hip_gate_chain])
+                               -> Result<(), HipError> {
+    check(h2hip_gate_fill_chains_dev(be.ctx, columns.as_ptr(), columns.len(), usable_rows, a.ptr, a.len, b.ptr, b.len, chains.as_ptr(), chains.len()))
+}
 /// `ff::BatchInvert` on a resident column, in place
 pub fn batch_invert(be: &Backend, a: &mut DeviceVec) -> Result<(), HipError> {
     check(unsafe { h2hip_fr_batch_invert_dev(be.ctx, a.ptr, a.len) })

@@ -120,6 +120,7 @@ _PROTOS = {
     "h2hip_plonk_shape_of_rlc": (_int, [_vp, _vp]),
     "h2hip_plonk_keygen_rlc": (_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, C.POINTER(_vp)]),
     "h2hip_rlc_fill_chains_dev": (_int, [_vp, C.POINTER(_vp), _sz, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "h2hip_gate_fill_chains_dev": (_int, [_vp, C.POINTER(_vp), _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz]),
     "h2hip_quotient_rlc_gate_batch_dev": (_int, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _sz, _u32, _u32, _vp, _vp]),
     "h2hip_plonk_pk_free": (None, [_vp, _vp]),
     "h2hip_plonk_pk_commitments": (_int, [_vp, _vp, _vp]),

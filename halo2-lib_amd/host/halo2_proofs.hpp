@@ -651,6 +651,17 @@ inline std::pair<std::vector<Fr>, std::vector<Fr>> permute_expression_pair(Backe
 }  // namespace lookup
 }  // namespace plonk
 
+// ---- halo2-base's GateChip bulk operations (gates/flex_gate/mod.rs), as device-filled cells -------------------------------
+namespace flex_gate {
+// the cells s_0, a_1, b_1, s_1, ... (s_i = s_{i-1} + a_i * b_i) of inner_product*, sum, select_by_indicator and select_from_idx for every
+// piece of `chains`, written into `columns` (device columns, e.g. the phase-witness callback's) on the backend's stream; a and b: device
+// pointers to a_len / b_len elements, which may lie inside a column (include/h2hip.h states the piece forms and the refusals)
+inline void fill_chains(Backend &b, const std::vector<void *> &columns, size_t usable_rows, const void *a_dev, size_t a_len, const void *b_dev,
+                        size_t b_len, const std::vector<h2hip_gate_chain> &chains) {
+    check(h2hip_gate_fill_chains_dev(b.raw(), columns.data(), columns.size(), usable_rows, a_dev, a_len, b_dev, b_len, chains.data(), chains.size()));
+}
+}  // namespace flex_gate
+
 // ---- halo2-base's PoseidonHasher (poseidon/hasher/mod.rs), batched over messages ------------------------------------
 namespace poseidon {
 class PoseidonHasher {

@@ -757,3 +757,26 @@ def rlc_fill_chains(ctx: Context, columns: Sequence[int], usable_rows: int, valu
     cols = (_vp * max(len(columns), 1))(*[_vp(int(p)) for p in columns])
     ctx._chk(ctx.lib.h2hip_rlc_fill_chains_dev(ctx.handle, cols, len(columns), usable_rows, _vp(vptr), num_values, arr, len(chains),
                                                _ptr(fr_limbs(int(gamma) % R_MOD))))
+
+
+class GateChainStruct(C.Structure):   # h2hip_gate_chain
+    _fields_ = [("column", C.c_uint32), ("row", C.c_uint32), ("len", C.c_uint32), ("flags", C.c_uint32), ("a_offset", C.c_uint64),
+                ("b_offset", C.c_uint64), ("a_stride", C.c_uint32), ("b_stride", C.c_uint32)]
+
+
+GATE_CARRY, GATE_JOIN, GATE_START_A = 1, 2, 4
+
+
+def gate_fill_chains(ctx: Context, columns: Sequence[int], usable_rows: int, a_dev, a_len: int, b_dev, b_len: int, chains: Sequence) -> None:
+    """h2hip_gate_fill_chains_dev: the flex-gate chain cells s_0, a_1, b_1, s_1, ... (s_i = s_{i-1} + a_i * b_i: inner products, sums,
+    select_by_indicator, select_from_idx) for every piece of `chains`, written into the device columns `columns` (pointers to Fr columns, e.g.
+    the column_ptrs of phase_witness_dev).  chains: (column, row, len, flags, a_offset, b_offset, a_stride, b_stride) tuples, flags 0 (head piece),
+    GATE_START_A (head piece whose first left operand is the start), GATE_CARRY (continues the piece before it after a column break) or GATE_JOIN
+    (continues it directly below), or a ctypes array of GateChainStruct built once for a table used in every proof; operand i of a piece is
+    element a_offset + i * a_stride of a_dev (b alike).  a_dev / b_dev: device pointers (or
+    objects with data_ptr()) to a_len / b_len Fr elements; they may point into a column.  Stream-ordered on the context's stream."""
+    aptr = int(a_dev.data_ptr()) if hasattr(a_dev, "data_ptr") else int(a_dev)
+    bptr = int(b_dev.data_ptr()) if hasattr(b_dev, "data_ptr") else int(b_dev)
+    arr = chains if isinstance(chains, C.Array) else (GateChainStruct * max(len(chains), 1))(*[GateChainStruct(*[int(x) for x in c]) for c in chains])
+    cols = (_vp * max(len(columns), 1))(*[_vp(int(p)) for p in columns])
+    ctx._chk(ctx.lib.h2hip_gate_fill_chains_dev(ctx.handle, cols, len(columns), usable_rows, _vp(aptr), a_len, _vp(bptr), b_len, arr, len(chains)))

@@ -516,7 +516,8 @@ typedef struct h2hip_phase_witness {
  *   gates                folded by y in the order flex gates, RLC gates (column order), permutation argument, lookups
  * The gate's degree is 2 + selector: degree, extended_k and the blinding factors (6) are base's.  LIMITS: base.num_challenges_per_phase[0] >= 1;
  * 1 <= num_rlc_advice <= 64 (0 is H2HIP_ERR_INVALID: such a circuit uses h2hip_phased_circuit_params); phase 1 always has columns, which the
- * contiguity rule counts; lookups query no challenge; RLC of variable length (a length cell) is the circuit's business.  Keygen: the selector
+ * contiguity rule counts; lookups query no challenge; RLC of variable length (a length cell) selects among the running sums in phase-1 gate columns, whose
+ * cells h2hip_gate_fill_chains_dev writes from the sums where h2hip_rlc_fill_chains_dev left them.  Keygen: the selector
  * rule covers the union of the q_enable and q_rlc columns (every pair shares an enabled row), and a q_rlc enabled on a row r with
  * r + 2 >= usable_rows is H2HIP_ERR_INVALID.  Single-GPU only (h2hip_plonk_pk_set_sharding returns H2HIP_ERR_INVALID); not accepted by
  * h2hip_plonk_verify_batch.  Proofs go through h2hip_plonk_create_proof_phased: `advice` is phase 0's columns, the callback's phase-1 column
@@ -544,6 +545,45 @@ typedef struct h2hip_rlc_chain {
 #define H2HIP_RLC_CARRY 1
 int h2hip_rlc_fill_chains_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const void *values_dev,
                               size_t num_values, const h2hip_rlc_chain *chains_host, size_t count, const void *gamma);
+/* Flex-gate chains written on the device: the cells of GateChip::inner_product / inner_product_left / inner_product_with_sums, sum,
+ * select_by_indicator and select_from_idx [UPSTREAM: halo2-base/src/gates/flex_gate/mod.rs:412, 709-753, 940-1110] and of RangeChip's limb
+ * recomposition, which all write
+ *       s_0, a_1, b_1, s_1, a_2, b_2, s_2, ...      s_i = s_{i-1} + a_i * b_i   (mod r)
+ * i.e. overlapping flex gates q * (a + b*c - d) at every third row.  chains_host lists `count` pieces; operand i of a piece is
+ * a_dev[a_offset + i * a_stride] and b_dev[b_offset + i * b_stride] (offsets and strides in Fr elements; a stride of 0 is one constant
+ * operand).  a_dev / b_dev are plain device pointers and may point into a column of the proof (the running sums of an RLC head piece lie at
+ * stride 2 in its column; indicator bits in a phase-0 column).  A chain is a head piece followed by any number of carry or join pieces, in
+ * list order; the cells run from (column, row) downwards:
+ *   head piece   (flags == 0)            0, a_0, b_0, s_0, ..., a_{len-1}, b_{len-1}, s_{len-1} with s_0 = a_0 * b_0          (3 len + 1 cells)
+ *   head piece   (H2HIP_GATE_START_A)    a_0, a_1, b_1, s_1, ..., s_{len-1} with s_0 = a_0: the "b starts with Constant(1)" case of
+ *                                        inner_product_simple (:953-962).  b_0 is not read (with len > 1, b_offset must still lie inside b_len)   (3 len - 2 cells)
+ *   carry piece  (H2HIP_GATE_CARRY)      s_prev, a_0, b_0, s_0', ...: continues the piece before it in the list after a column break; the break
+ *                                        cell is duplicated at the top, as assign_witnesses does (threads/single_phase.rs:300-307)   (3 len + 1 cells)
+ *   join piece   (H2HIP_GATE_JOIN)       a_0, b_0, s_0', ...: continues the piece before it directly below that piece's last cell, in the same
+ *                                        column, so that one chain can change where its operands come from (an RLC chain with a carry
+ *                                        piece of its own is read as head + join)                                             (3 len cells)
+ * The fill computes the arithmetic form.  select_by_indicator's "sum = a where the bit is set" equals s + a*b under that function's own
+ * assumptions (b a 0/1 indicator with at most one bit set); s + a*b satisfies the gate whatever the operands are.  Computing the operands
+ * (idx_to_indicator, range-check limbs) stays with the circuit.
+ * H2HIP_ERR_INVALID with a message, before anything is launched or uploaded (the columns are then untouched): a NULL argument; unknown flags
+ * or more than one of CARRY / JOIN / START_A; CARRY or JOIN on piece 0; len == 0; a column index >= num_columns or a NULL column; row + the
+ * cell count > usable_rows; a join piece that is not in the previous piece's column at the row after its last cell; an operand index
+ * outside a_len / b_len (computed in 64 bits); more than 2^32 pairs in one call; two pieces whose cells overlap; an operand range that
+ * overlaps a cell this call writes.  The last check is conservative: it compares address intervals (a piece's first to last operand address
+ * against every piece's cells, sorted and swept), so a strided read that interleaves with written cells without touching one is refused
+ * too.  Cells not addressed are not touched.  columns_dev: HOST array of device columns.  count == 0 is H2HIP_OK without device work.
+ * Stream-ordered on the context's stream: a segmented additive scan over the pieces' products (per tile, over the tile totals) and one
+ * placement kernel; the piece table and the column pointers are the only uploads. */
+typedef struct h2hip_gate_chain {
+    uint32_t column, row, len, flags;
+    uint64_t a_offset, b_offset;
+    uint32_t a_stride, b_stride;
+} h2hip_gate_chain;
+#define H2HIP_GATE_CARRY 1
+#define H2HIP_GATE_JOIN 2
+#define H2HIP_GATE_START_A 4
+int h2hip_gate_fill_chains_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const void *a_dev, size_t a_len,
+                               const void *b_dev, size_t b_len, const h2hip_gate_chain *chains_host, size_t count);
 /* The RLC gates' terms of the quotient numerator on the extended domain, folded in order for j < count:
  *      acc[i] = acc[i]*y + q_j[i]*(a_j[i]*gamma + a_j[i+s] - a_j[i+2s]),  s = 2^(ext_k-k), indices mod 2^ext_k.
  * q_dev / a_dev: HOST arrays of device pointers; 64 columns per launch. */
