@@ -101,6 +101,19 @@ pub struct h2hip_gate_chain {
 pub const H2HIP_GATE_CARRY: u32 = 1;
 pub const H2HIP_GATE_JOIN: u32 = 2;
 pub const H2HIP_GATE_START_A: u32 = 4;
+/// one unit of h2hip_poseidon_fill_hashes_dev: fix_len_array_squeeze over `len` inputs, its cells from (column, row) downwards; input i is
+/// inputs_dev[input_offset + i * input_stride]
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct h2hip_poseidon_hash {
+    pub column: u32,
+    pub row: u32,
+    pub input_offset: u64,
+    pub input_stride: u32,
+    pub flags: u32,
+}
+pub const H2HIP_POSEIDON_ABSORB_ONLY: u32 = 1;
+pub const H2HIP_POSEIDON_WITH_CONSTS: u32 = 2;
 /// a later phase's witness: `fill(user, phase, challenges, num_challenges, columns_dev, num_columns)` (include/h2hip.h states the contract)
 pub type h2hip_phase_witness_fn = Option<unsafe extern "C" fn(user: *mut c_void, phase: u32, challenges_fr: *const c_void, num_challenges: usize,
                                                               columns_dev: *const *mut c_void, num_columns: usize) -> c_int>;
@@ -280,6 +293,14 @@ extern "C" {
     pub fn h2hip_poseidon_hash_batch_dev(ctx: *mut h2hip_ctx, digests_dev: *mut c_void, inputs_dev: *const c_void, max_len: usize, lens_dev: *const u32, n: usize) -> c_int;
     pub fn h2hip_poseidon_merkle_tree_dev(ctx: *mut h2hip_ctx, nodes_dev: *mut c_void, leaves_dev: *const c_void, log_leaves: u32) -> c_int;
     pub fn h2hip_poseidon_spec_generate(t: u32, r_f: u32, r_p: u32, round_constants_out: *mut c_void, mds_out: *mut c_void) -> c_int;
+    pub fn h2hip_poseidon_spec_optimize(t: u32, r_f: u32, r_p: u32, round_constants: *const c_void, mds: *const c_void, start_out: *mut c_void,
+                                        partial_out: *mut c_void, end_out: *mut c_void, pre_sparse_mds_out: *mut c_void, sparse_out: *mut c_void) -> c_int;
+    pub fn h2hip_poseidon_set_optimized_spec(ctx: *mut h2hip_ctx, t: u32, r_f: u32, r_p: u32, start: *const c_void, partial: *const c_void, end: *const c_void,
+                                             mds: *const c_void, pre_sparse_mds: *const c_void, sparse: *const c_void) -> c_int;
+    pub fn h2hip_poseidon_trace_layout(t: u32, r_f: u32, r_p: u32, len: u32, flags: u32, num_cells: *mut usize, state_out_offsets: *mut u32) -> c_int;
+    pub fn h2hip_poseidon_fill_hashes_dev(ctx: *mut h2hip_ctx, columns_dev: *const *mut c_void, num_columns: usize, usable_rows: usize,
+                                          break_points_host: *const u32, inputs_dev: *const c_void, inputs_len: usize, len: u32, states_in_dev: *const c_void,
+                                          states_out_dev: *mut c_void, hashes_host: *const h2hip_poseidon_hash, count: usize) -> c_int;
     // polynomial linear combinations (multiopen), h(X) = numerator / (X^n - 1)
     pub fn h2hip_fr_axpy_dev(ctx: *mut h2hip_ctx, y_dev: *mut c_void, a: *const c_void, x_dev: *const c_void, n: usize) -> c_int;
     pub fn h2hip_fr_scale_dev(ctx: *mut h2hip_ctx, y_dev: *mut c_void, s: *const c_void, n: usize) -> c_int;

@@ -303,6 +303,43 @@ impl<'b> PoseidonHasher<'b> {
         check(unsafe { h2hip_poseidon_merkle_tree_dev(self.be.ctx, nodes.ptr, leaves.ptr, log_leaves) })?;
         Ok(nodes)
     }
+    /// makes this hasher's `OptimizedPoseidonSpec` (derived by `h2hip_poseidon_spec_optimize`) the context's, for `fill_hashes`; a caller
+    /// that holds a spec object of its own passes that object's arrays to `h2hip_poseidon_set_optimized_spec` instead
+    pub fn select_optimized(&self) -> Result<(), HipError> {
+        let (t, half, r_p) = (self.t as usize, (self.r_f / 2) as usize, self.r_p as usize);
+        let mut start = vec![Fr::zero(); (half + 1) * t];
+        let mut partial = vec![Fr::zero(); r_p + 1];
+        let mut end = vec![Fr::zero(); half * t];
+        let mut pre = vec![Fr::zero(); t * t];
+        let mut sparse = vec![Fr::zero(); r_p * (2 * t - 1) + 1];
+        check(unsafe {
+            h2hip_poseidon_spec_optimize(self.t, self.r_f, self.r_p, self.round_constants.as_ptr().cast(), self.mds.as_ptr().cast(),
+                                         start.as_mut_ptr().cast(), partial.as_mut_ptr().cast(), end.as_mut_ptr().cast(), pre.as_mut_ptr().cast(),
+                                         sparse.as_mut_ptr().cast())
+        })?;
+        check(unsafe {
+            h2hip_poseidon_set_optimized_spec(self.be.ctx, self.t, self.r_f, self.r_p, start.as_ptr().cast(), partial.as_ptr().cast(), end.as_ptr().cast(),
+                                              self.mds.as_ptr().cast(), pre.as_ptr().cast(), sparse.as_ptr().cast())
+        })
+    }
+    /// (the cells one unit of `len` inputs writes, the offsets of its t final-state cells; [1] is the digest)
+    pub fn trace_layout(&self, len: u32, flags: u32) -> Result<(usize, Vec<u32>), HipError> {
+        let mut cells = 0usize;
+        let mut offsets = vec![0u32; self.t as usize];
+        check(unsafe { h2hip_poseidon_trace_layout(self.t, self.r_f, self.r_p, len, flags, &mut cells, offsets.as_mut_ptr()) })?;
+        Ok((cells, offsets))
+    }
+    /// every gate cell of `hash_fix_len_array` over `len` inputs for each unit of `hashes`, written into `columns` across `break_points`
+    /// (`columns.len() - 1` entries, or None); inputs and states may lie inside the columns (include/h2hip.h states the cells and the refusals).
+    /// Safety: every pointer of `columns` is a device column of at least `usable_rows` elements on the backend's device; `states_in` /
+    /// `states_out` are null or point to `hashes.len() * t` elements there.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn fill_hashes(&self, columns: &[*mut c_void], usable_rows: usize, break_points: Option<&[u32]>, inputs: *const c_void, inputs_len: usize,
+                              len: u32, hashes: &[h2hip_poseidon_hash], states_in: *const c_void, states_out: *mut c_void) -> Result<(), HipError> {
+        assert!(break_points.map_or(true, |b| b.len() + 1 == columns.len()));
+        check(h2hip_poseidon_fill_hashes_dev(self.be.ctx, columns.as_ptr(), columns.len(), usable_rows, break_points.map_or(ptr::null(), |b| b.as_ptr()),
+                                             inputs, inputs_len, len, states_in, states_out, hashes.as_ptr(), hashes.len()))
+    }
 }
 /// `poly * scalar` / `poly += other * scalar` of the multiopen argument
 pub fn axpy(be: &Backend, y: &mut DeviceVec, a: Fr, x: &DeviceVec) -> Result<(), HipError> {

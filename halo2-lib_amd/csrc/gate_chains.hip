@@ -9,8 +9,6 @@
 // GATE_J pairs (the sums as if nothing entered the tile, and the tile's total); over the tile totals, one workgroup (the value that enters
 // every tile); and the placement kernel, which adds a tile's incoming value to the positions whose chain began before the tile and writes
 // the a, b and s cells per piece form.  No workgroup waits for another; no atomics.
-#include <algorithm>
-
 #include "internal.h"
 
 namespace h2 {
@@ -159,11 +157,6 @@ __global__ __launch_bounds__(256) void gate_place_kernel(Fr *const *__restrict__
     }
 }
 
-struct ByteRange {
-    uintptr_t lo, hi;   // [lo, hi)
-    bool operator<(const ByteRange &o) const { return lo < o.lo; }
-};
-
 }  // namespace h2
 
 using namespace h2;
@@ -216,19 +209,8 @@ extern "C" int h2hip_gate_fill_chains_dev(h2hip_ctx *ctx, void *const *columns_d
     H2_REQUIRE(total <= ((uint64_t)1 << 32), "more than 2^32 pairs in one call");
     // the cells of two pieces are disjoint, and no operand range (first to last address read, whatever the stride) meets a written cell:
     // address intervals, sorted (a layout engine's pieces mostly arrive sorted) and swept
-    auto sorted = [](std::vector<ByteRange> &v) {
-        if (!std::is_sorted(v.begin(), v.end())) std::sort(v.begin(), v.end());
-    };
-    sorted(written);
-    for (size_t j = 1; j < count; ++j) H2_REQUIRE(written[j - 1].hi <= written[j].lo, "two pieces' cells overlap");
-    for (std::vector<ByteRange> *reads : {&a_reads, &b_reads}) {
-        sorted(*reads);
-        size_t w = 0;
-        for (const ByteRange &r : *reads) {
-            while (w < count && written[w].hi <= r.lo) ++w;   // (the reads' starts ascend: what ends before this one ends before every later one)
-            H2_REQUIRE(w == count || written[w].lo >= r.hi, "an operand range overlaps cells this call writes");
-        }
-    }
+    const char *clash = byte_ranges_clash(written, {&a_reads, &b_reads}, "two pieces' cells overlap");
+    H2_REQUIRE(!clash, clash);
     const uint32_t ntiles = (uint32_t)((total + GATE_TILE - 1) / GATE_TILE);
     // ---- workspace: [piece table][column pointers] and [s][tile sums][tile cuts]
     const size_t table_bytes = sizeof(GatePiece) * table.size(), ptr_off = (table_bytes + 255) / 256 * 256, ptr_bytes = sizeof(void *) * num_columns;

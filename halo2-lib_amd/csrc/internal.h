@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <algorithm>
 #include <functional>
 #include <map>
 #include <string>
@@ -72,10 +73,11 @@ struct h2hip_ctx {
     int num_cus = 256;
     // scratch
     enum { WS_NTT = 0, WS_DIGITS, WS_COUNTS, WS_OFFSETS, WS_CURSOR, WS_SKEY, WS_SVAL, WS_BUCKETS, WS_PKEY0, WS_PVAL0, WS_PKEY1,
-           WS_PVAL1, WS_SEG, WS_WIN, WS_OUT, WS_SCAN, WS_TMP0, WS_TMP1, WS_TMP2, WS_STAGE, WS_POSEIDON, WS_FBTABLE, WS_BATCH, WS_LK0, WS_LK1, WS_LK2, WS_LK3, WS_LK4, WS_LK5, WS_VANISH, WS_BATCH_BUCKETS, WS_COUNT };
+           WS_PVAL1, WS_SEG, WS_WIN, WS_OUT, WS_SCAN, WS_TMP0, WS_TMP1, WS_TMP2, WS_STAGE, WS_POSEIDON, WS_FBTABLE, WS_BATCH, WS_LK0, WS_LK1, WS_LK2, WS_LK3, WS_LK4, WS_LK5, WS_VANISH, WS_BATCH_BUCKETS, WS_POSEIDON_OPT, WS_COUNT };
     h2::DevBuf ws[WS_COUNT];
     std::vector<h2::TwiddleSet> twiddles;
     uint32_t pos_t = 0, pos_rf = 0, pos_rp = 0;   // Poseidon spec resident in ws[WS_POSEIDON]
+    uint32_t popt_t = 0, popt_rf = 0, popt_rp = 0;   // the optimised Poseidon spec resident in ws[WS_POSEIDON_OPT] (poseidon_trace.hip)
     bool msm_lds_attr_set = false, lookup_lds_attr_set = false, ntt_lds_attr_set = false;   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done for this context's device
     // ---- tuning knobs (h2hip_set_param), in H2_KNOB_TABLE's order
     int msm_window_bits = 0;   // 0 = auto
@@ -273,6 +275,31 @@ inline Fr ld_fr(const void *p) {   // a field element out of the caller's (possi
     Fr r;
     memcpy(&r, p, sizeof(Fr));
     return r;
+}
+// Address intervals [lo, hi) of the fills that write cells from operands lying in the same columns (gate_chains.hip, poseidon_trace.hip): the
+// written intervals must be pairwise disjoint, and no operand interval (first to last address read, whatever the stride) may meet one.  Sorted
+// (a layout engine's pieces mostly arrive sorted) and swept; nullptr when all is well, else the reason.
+struct ByteRange {
+    uintptr_t lo, hi;
+    bool operator<(const ByteRange &o) const { return lo < o.lo; }
+};
+inline const char *byte_ranges_clash(std::vector<ByteRange> &written, std::initializer_list<std::vector<ByteRange> *> reads, const char *written_msg) {
+    auto sorted = [](std::vector<ByteRange> &v) {
+        if (!std::is_sorted(v.begin(), v.end())) std::sort(v.begin(), v.end());
+    };
+    sorted(written);
+    const size_t count = written.size();
+    for (size_t j = 1; j < count; ++j)
+        if (written[j - 1].hi > written[j].lo) return written_msg;
+    for (std::vector<ByteRange> *rd : reads) {
+        sorted(*rd);
+        size_t w = 0;
+        for (const ByteRange &r : *rd) {
+            while (w < count && written[w].hi <= r.lo) ++w;   // (the reads' starts ascend: what ends before this one ends before every later one)
+            if (w < count && written[w].lo < r.hi) return "an operand range overlaps cells this call writes";
+        }
+    }
+    return nullptr;
 }
 struct OmegaTable;   // fr29.cuh
 int ntt_pow_table(h2hip_ctx *ctx, uint32_t log_n, const Fr &omega, OmegaTable *out);   // ntt.hip: the cached (log_n, omega) power table for pow_lookup

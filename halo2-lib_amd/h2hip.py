@@ -157,6 +157,10 @@ _PROTOS = {
     "h2hip_poseidon_hash_batch_dev": (_int, [_vp, _vp, _vp, _sz, C.POINTER(_u32), _sz]),
     "h2hip_poseidon_merkle_tree_dev": (_int, [_vp, _vp, _vp, _u32]),
     "h2hip_poseidon_spec_generate": (_int, [_u32, _u32, _u32, _vp, _vp]),
+    "h2hip_poseidon_spec_optimize": (_int, [_u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "h2hip_poseidon_set_optimized_spec": (_int, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "h2hip_poseidon_trace_layout": (_int, [_u32, _u32, _u32, _u32, _u32, C.POINTER(_sz), C.POINTER(_u32)]),
+    "h2hip_poseidon_fill_hashes_dev": (_int, [_vp, C.POINTER(_vp), _sz, _sz, C.POINTER(_u32), _vp, _sz, _u32, _vp, _vp, _vp, _sz]),
     "h2hip_plonk_check_witness": (_int, [_vp, _vp, C.POINTER(_vp), _int, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_sz)]),
     "h2hip_plonk_check_witness_challenges": (_int, [_vp, _vp, C.POINTER(_vp), _int, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "h2hip_plonk_verify_proof_rlc": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, C.POINTER(_int)]),

@@ -677,6 +677,38 @@ class PoseidonHasher {
     std::vector<Fr> hash_var_len_array(const std::vector<Fr> &inputs, size_t max_len, const std::vector<uint32_t> &lens) const {
         return run(inputs, max_len, &lens, lens.size());
     }
+    // ---- the in-circuit form: every gate cell of hash_fix_len_array, written into device columns (include/h2hip.h states the cells)
+    struct OptimizedSpec {   // OptimizedPoseidonSpec: constants.start / partial / end, pre_sparse_mds, per partial round row then col_hat
+        std::vector<Fr> start, partial, end, pre_sparse_mds, sparse;
+    };
+    OptimizedSpec optimized_spec() const {
+        const size_t half = r_f_ / 2;
+        OptimizedSpec o{std::vector<Fr>((half + 1) * t_), std::vector<Fr>(r_p_ + 1), std::vector<Fr>(half * t_), std::vector<Fr>((size_t)t_ * t_),
+                        std::vector<Fr>((size_t)r_p_ * (2 * t_ - 1) + 1)};
+        check(h2hip_poseidon_spec_optimize(t_, r_f_, r_p_, rc_.data(), mds_.data(), o.start.data(), o.partial.data(), o.end.data(), o.pre_sparse_mds.data(),
+                                           o.sparse.data()));
+        return o;
+    }
+    // makes this hasher's optimised spec the context's (once per context, not per call)
+    void select_optimized() const {
+        const OptimizedSpec o = optimized_spec();
+        check(h2hip_poseidon_set_optimized_spec(be_->raw(), t_, r_f_, r_p_, o.start.data(), o.partial.data(), o.end.data(), mds_.data(),
+                                                o.pre_sparse_mds.data(), o.sparse.data()));
+    }
+    // -> the cells one unit writes; state_out_offsets: t entries, [1] the digest
+    size_t trace_layout(uint32_t len, uint32_t flags, std::vector<uint32_t> &state_out_offsets) const {
+        size_t cells = 0;
+        state_out_offsets.assign(t_, 0);
+        check(h2hip_poseidon_trace_layout(t_, r_f_, r_p_, len, flags, &cells, state_out_offsets.data()));
+        return cells;
+    }
+    // break_points: columns.size() - 1 entries or empty (no breaks); states_in_dev / states_out_dev: nullptr or hashes.size() * t elements
+    void fill_hashes(const std::vector<void *> &columns, size_t usable_rows, const std::vector<uint32_t> &break_points, const void *inputs_dev,
+                     size_t inputs_len, uint32_t len, const std::vector<h2hip_poseidon_hash> &hashes, const void *states_in_dev = nullptr,
+                     void *states_out_dev = nullptr) const {
+        check(h2hip_poseidon_fill_hashes_dev(be_->raw(), columns.data(), columns.size(), usable_rows, break_points.empty() ? nullptr : break_points.data(),
+                                             inputs_dev, inputs_len, len, states_in_dev, states_out_dev, hashes.data(), hashes.size()));
+    }
 
   private:
     std::vector<Fr> run(const std::vector<Fr> &inputs, size_t max_len, const std::vector<uint32_t> *lens, size_t n) const {

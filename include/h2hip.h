@@ -400,6 +400,68 @@ int h2hip_poseidon_merkle_tree_dev(h2hip_ctx *ctx, void *nodes_dev, const void *
 /* The spec PoseidonHasher / pse-poseidon derive from (T, R_F, R_P) alone, secure-MDS index 0: Grain-LFSR round constants
  * [(r_f + r_p)][t] and the Cauchy MDS [t][t], Montgomery Fr, in the textbook (unoptimised) form set_spec takes.  Host only. */
 int h2hip_poseidon_spec_generate(uint32_t t, uint32_t r_f, uint32_t r_p, void *round_constants_out, void *mds_out);
+/* ---- In-circuit Poseidon traces written on the device.  A circuit that CONSTRAINS a hash needs every cell PoseidonHasher::hash_fix_len_array
+ * / PoseidonSponge::squeeze write into the gate columns (fix_len_array_squeeze, halo2-base/src/poseidon/hasher/mod.rs:344-361), not the digest.
+ *
+ * The in-circuit permutation is OptimizedPoseidonSpec's (hasher/state.rs:35-83).  h2hip_poseidon_spec_optimize (host only) derives it from the
+ * textbook arrays set_spec takes (hasher/spec.rs:108-175, mds.rs:118-171: inverse, transpose, factorise), all Montgomery Fr:
+ *   start_out [r_f/2 + 1][t], partial_out [r_p], end_out [r_f/2 - 1][t]     constants.start / partial / end
+ *   pre_sparse_mds_out [t][t]                                              row major, like mds
+ *   sparse_out [r_p][2t - 1]                                               per partial round: SparseMDSMatrix row [t], then col_hat [t - 1]
+ * h2hip_poseidon_set_optimized_spec keeps such a spec on the context (a Rust caller passes the arrays its own spec object holds); it is
+ * independent of the textbook spec of h2hip_poseidon_set_spec.  t in {3, 5}.  Both refuse a spec in which a row of mds, pre_sparse_mds or a
+ * sparse `row` begins with 1: inner_product_simple writes another cell form when its right operand starts with Constant(1)
+ * (flex_gate/mod.rs:953-962); no spec PoseidonHasher derives has such a row, and the fill does not guess that form.
+ *
+ * One unit = fix_len_array_squeeze over `len` inputs from a given state: permutation(chunk, None) per chunk of RATE = t - 1 inputs and, when
+ * len is a multiple of RATE (0 included) and H2HIP_POSEIDON_ABSORB_ONLY is not set, one more on the empty chunk.  Its cells, in the reference's
+ * order, every one as a canonical (fully reduced) Montgomery Fr; a Constant(c) cell holds c, a copy of an earlier cell holds its value:
+ *   WITH_CONSTS          2^64, 0, .., 0                          the t load_constant cells of PoseidonState::default (hasher/mod.rs:48)
+ *   per permutation over m inputs (state.rs:124-161, flex_gate/mod.rs:158-168, 412-435):
+ *     add                s_0, pre_0, 1, s_0 + pre_0
+ *     sum, i = 1..m      s_i, in_i, 1, s_i + in_i, pre_i, 1, s_i + in_i + pre_i
+ *     add, i = m+1..t-1  s_i, c, 1, s_i + c                      c = pre_i, plus the padding 1 for i = m + 1
+ *     then r_f/2 - 1 times [S-boxes with start[r]; mds], S-boxes with start[r_f/2]; pre_sparse_mds, r_p times [S-box of s_0 with partial[r];
+ *     sparse r], r_f/2 - 1 times [S-boxes with end[r]; mds], S-boxes with 0; mds, where
+ *     S-box of x with c (mul, mul, mul_add: state.rs:97-106)     0, x, x, x^2,  0, x^2, x^2, x^4,  c, x, x^4, x^5 + c
+ *     a matrix (apply_mds), per row                              0, s_0, m_0, s_0 m_0, s_1, m_1, s_0 m_0 + s_1 m_1, ...        (1 + 3t cells)
+ *     sparse (apply_sparse_mds)                                  the row's inner product, then per i = 1..t-1:  s_i, s_0, col_hat_i, s_0 col_hat_i + s_i
+ * A permutation over m inputs has 4 + 7m + 4(t-1-m) + r_f (12t + t(1+3t)) + r_p (12 + (1+3t) + 4(t-1)) cells: 2,250 + 3m for t = 3 (8, 57).
+ * h2hip_poseidon_trace_layout (host only, pure) reports the cells of one unit and the offsets, inside its run of cells, of the t final-state
+ * cells; offset [1] is the digest state.s[1].  It refuses unknown flags and a unit without a permutation (len == 0 with ABSORB_ONLY).
+ *
+ * h2hip_poseidon_fill_hashes_dev writes `count` units of one `len`.  Input i of a unit is inputs_dev[input_offset + i * input_stride]
+ * (Fr elements); states_in_dev == NULL starts every unit from [2^64, 0, ..], else unit j starts from states_in_dev[j t .. j t + t);
+ * states_out_dev (or NULL) receives the final states densely.  inputs_dev / states_in_dev are plain device pointers and may point into columns
+ * of the proof (a previous level's digest cells lie at a stride); dependent levels are separate, stream-ordered calls.  With states_in_dev and
+ * ABSORB_ONLY the sponge and compact-chunk forms (hasher/mod.rs:262-288) are expressible; their selects and is_final logic, hash_var_len_array
+ * and hash_compact_input stay with the circuit.  Placement follows assign_witnesses (threads/single_phase.rs:273-312): the cells run down
+ * from (column, row); when the cell just written sits at break_points_host[column] it is written again at row 0 of column + 1 and the run
+ * goes on at row 1 (that copy is never itself a break cell); a unit may cross several breaks.  break_points_host: num_columns - 1 entries, or
+ * NULL: no breaks, every unit stays in its column.
+ * H2HIP_ERR_INVALID with a message, before anything is launched or uploaded (the columns are then untouched): a NULL mandatory argument
+ * (inputs_dev may be NULL when len == 0); no optimised spec set; unknown flags; a unit without a permutation; a column index >= num_columns or
+ * a NULL column; a run that leaves the usable rows or the last column; a break point >= usable_rows; an input index outside inputs_len
+ * (computed in 64 bits); two units whose cells overlap, break copies and states_out_dev included; an operand range (a unit's first to last
+ * input address, states_in_dev) that overlaps a cell this call writes — address intervals, sorted and swept, conservative as for
+ * h2hip_gate_fill_chains_dev.  Cells not addressed are not touched.  columns_dev: HOST array of device columns.  count == 0 is H2HIP_OK
+ * without device work.  Stream-ordered on the context's stream: one kernel, one lane per unit; the unit table, the column pointers and the
+ * break points are the only uploads. */
+typedef struct h2hip_poseidon_hash {
+    uint32_t column, row;
+    uint64_t input_offset;
+    uint32_t input_stride, flags;
+} h2hip_poseidon_hash;
+#define H2HIP_POSEIDON_ABSORB_ONLY 1
+#define H2HIP_POSEIDON_WITH_CONSTS 2
+int h2hip_poseidon_spec_optimize(uint32_t t, uint32_t r_f, uint32_t r_p, const void *round_constants, const void *mds, void *start_out, void *partial_out,
+                                 void *end_out, void *pre_sparse_mds_out, void *sparse_out);
+int h2hip_poseidon_set_optimized_spec(h2hip_ctx *ctx, uint32_t t, uint32_t r_f, uint32_t r_p, const void *start, const void *partial, const void *end,
+                                      const void *mds, const void *pre_sparse_mds, const void *sparse);
+int h2hip_poseidon_trace_layout(uint32_t t, uint32_t r_f, uint32_t r_p, uint32_t len, uint32_t flags, size_t *num_cells, uint32_t *state_out_offsets);
+int h2hip_poseidon_fill_hashes_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const uint32_t *break_points_host,
+                                   const void *inputs_dev, size_t inputs_len, uint32_t len, const void *states_in_dev, void *states_out_dev,
+                                   const h2hip_poseidon_hash *hashes_host, size_t count);
 
 /* ---- a1: plonk::create_proof for halo2-base circuits, resident on the GPU -------------------------------------------------
  * Replaces create_proof::<KZGCommitmentScheme<Bn256>, ProverSHPLONK<_>, Challenge255<_>, _, Blake2bWrite<_, _, _>, _> as the
