@@ -112,6 +112,18 @@ pub struct h2hip_poseidon_hash {
     pub input_stride: u32,
     pub flags: u32,
 }
+/// one unit of h2hip_range_fill_checks_dev: the range check of values_dev[a_offset] (of a + 2^shift_bits - values_dev[b_offset] with
+/// H2HIP_RANGE_LESS_THAN), its gate cells from (column, row) downwards, its lookup cells from queue position lookup_slot
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct h2hip_range_check {
+    pub column: u32,
+    pub row: u32,
+    pub a_offset: u64,
+    pub b_offset: u64,
+    pub lookup_slot: u64,
+}
+pub const H2HIP_RANGE_LESS_THAN: u32 = 1;
 pub const H2HIP_POSEIDON_ABSORB_ONLY: u32 = 1;
 pub const H2HIP_POSEIDON_WITH_CONSTS: u32 = 2;
 /// a later phase's witness: `fill(user, phase, challenges, num_challenges, columns_dev, num_columns)` (include/h2hip.h states the contract)
@@ -371,6 +383,12 @@ extern "C" {
                                      num_values: usize, chains_host: *const h2hip_rlc_chain, count: usize, gamma: *const c_void) -> c_int;
     pub fn h2hip_gate_fill_chains_dev(ctx: *mut h2hip_ctx, columns_dev: *const *mut c_void, num_columns: usize, usable_rows: usize, a_dev: *const c_void,
                                       a_len: usize, b_dev: *const c_void, b_len: usize, chains_host: *const h2hip_gate_chain, count: usize) -> c_int;
+    pub fn h2hip_range_check_layout(range_bits: u32, lookup_bits: u32, flags: u32, num_cells: *mut usize, num_lookup_cells: *mut usize,
+                                    last_limb_offset: *mut u32) -> c_int;
+    pub fn h2hip_range_fill_checks_dev(ctx: *mut h2hip_ctx, columns_dev: *const *mut c_void, num_columns: usize, usable_rows: usize,
+                                       break_points_host: *const u32, lookup_columns_dev: *const *mut c_void, num_lookup_columns: usize,
+                                       values_dev: *const c_void, values_len: usize, range_bits: u32, lookup_bits: u32, shift_bits: u32, flags: u32,
+                                       checks_host: *const h2hip_range_check, count: usize) -> c_int;
     pub fn h2hip_quotient_rlc_gate_batch_dev(ctx: *mut h2hip_ctx, acc_dev: *mut c_void, q_dev: *const *const c_void, a_dev: *const *const c_void,
                                              count: usize, ext_k: u32, k: u32, gamma: *const c_void, y: *const c_void) -> c_int;
     pub fn h2hip_plonk_pk_free(ctx: *mut h2hip_ctx, pk: *mut h2hip_plonk_pk);

@@ -173,6 +173,25 @@ pub unsafe fn gate_fill_chains(be: &Backend, columns: &[*mut c_void], usable_row
                                -> Result<(), HipError> {
     check(h2hip_gate_fill_chains_dev(be.ctx, columns.as_ptr(), columns.len(), usable_rows, a.ptr, a.len, b.ptr, b.len, chains.as_ptr(), chains.len()))
 }
+/// `RangeChip::_range_check` as cells (halo2-base/src/gates/range/mod.rs:512-564; behind check_less_than's / is_less_than's seven cells with
+/// `H2HIP_RANGE_LESS_THAN`): the limb decomposition and the tail gate of every unit of `checks` at one width, written down `columns` across
+/// `break_points`, and the limbs' copies into `lookup_columns` at each unit's queue position; the checked values are elements of `values`,
+/// which may be a column of the proof (include/h2hip.h states the cell form and the refusals).
+/// Safety: every pointer of `columns` and `lookup_columns` is a device column of at least `usable_rows` elements on `be`'s device.
+pub unsafe fn range_fill_checks(be: &Backend, columns: &[*mut c_void], usable_rows: usize, break_points: Option<&[u32]>,
+                                lookup_columns: &[*mut c_void], values: &DeviceVec, range_bits: u32, lookup_bits: u32, shift_bits: u32, flags: u32,
+                                checks: &[h2hip_range_check]) -> Result<(), HipError> {
+    assert!(break_points.map_or(true, |b| b.len() + 1 == columns.len()));
+    check(h2hip_range_fill_checks_dev(be.ctx, columns.as_ptr(), columns.len(), usable_rows, break_points.map_or(ptr::null(), |b| b.as_ptr()),
+                                      lookup_columns.as_ptr(), lookup_columns.len(), values.ptr, values.len, range_bits, lookup_bits, shift_bits, flags,
+                                      checks.as_ptr(), checks.len()))
+}
+/// (gate cells of one unit, its lookup cells, the offset of the last-limb cell among the gate cells or None when the unit has none of its own)
+pub fn range_check_layout(range_bits: u32, lookup_bits: u32, flags: u32) -> Result<(usize, usize, Option<u32>), HipError> {
+    let (mut cells, mut lookups, mut last) = (0usize, 0usize, 0u32);
+    check(unsafe { h2hip_range_check_layout(range_bits, lookup_bits, flags, &mut cells, &mut lookups, &mut last) })?;
+    Ok((cells, lookups, if last == u32::MAX { None } else { Some(last) }))
+}
 /// `ff::BatchInvert` on a resident column, in place
 pub fn batch_invert(be: &Backend, a: &mut DeviceVec) -> Result<(), HipError> {
     check(unsafe { h2hip_fr_batch_invert_dev(be.ctx, a.ptr, a.len) })

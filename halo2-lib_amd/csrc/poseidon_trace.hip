@@ -279,25 +279,8 @@ int h2hip_poseidon_fill_hashes_dev(h2hip_ctx *ctx, void *const *columns_dev, siz
         uint64_t cells = trace_unit_cells(t, r_f, r_p, len, h.flags);
         H2_REQUIRE(cells < ((uint64_t)1 << 31), "a unit of 2^31 cells or more");
         // the unit's run, column by column, as the kernel's TraceOut walks it
-        size_t c = h.column;
-        uint64_t r = h.row;
-        while (cells) {   // (zero only behind a break on the unit's last cell)
-            H2_REQUIRE(r < usable_rows, "a unit's cells leave the usable rows");
-            const bool brk = break_points_host && c + 1 < num_columns && break_points_host[c] >= r;
-            const uint64_t room = brk ? break_points_host[c] - r + 1 : usable_rows - r, take = cells < room ? cells : room;
-            const uintptr_t w = (uintptr_t)columns_dev[c] + sizeof(Fr) * r;
-            written.push_back(ByteRange{w, w + sizeof(Fr) * (uintptr_t)take});
-            cells -= take;
-            if (!brk || take < room) {
-                H2_REQUIRE(cells == 0, break_points_host && c + 1 == num_columns ? "a unit's cells leave the last column" : "a unit's cells leave the usable rows");
-                break;
-            }
-            // the cell at the break point was written: it is written again at row 0 of the next column, and the run goes on at row 1
-            ++c;
-            H2_REQUIRE(columns_dev[c], "a unit's column index is out of range (or the column is NULL)");
-            written.push_back(ByteRange{(uintptr_t)columns_dev[c], (uintptr_t)columns_dev[c] + sizeof(Fr)});
-            r = 1;
-        }
+        const char *left = run_byte_ranges(columns_dev, num_columns, usable_rows, break_points_host, h.column, h.row, cells, written);
+        H2_REQUIRE(!left, left);
         if (len) {   // input indices in 64 bits: (len - 1) * stride < 2^64, and the sum is checked against inputs_len without wrapping
             const uint64_t span = (uint64_t)(len - 1) * h.input_stride;
             H2_REQUIRE(h.input_offset < inputs_len && span < inputs_len - h.input_offset, "a unit's inputs lie outside inputs_len");

@@ -662,6 +662,29 @@ inline void fill_chains(Backend &b, const std::vector<void *> &columns, size_t u
 }
 }  // namespace flex_gate
 
+// ---- halo2-base's RangeChip (gates/range/mod.rs), as device-filled cells ---------------------------------------------------
+namespace range {
+struct CheckLayout {
+    size_t num_cells, num_lookup_cells;
+    uint32_t last_limb_offset;   // UINT32_MAX: the unit has no last-limb cell of its own (one limb, no LESS_THAN prefix)
+};
+inline CheckLayout check_layout(uint32_t range_bits, uint32_t lookup_bits, uint32_t flags = 0) {
+    CheckLayout l{0, 0, 0};
+    check(h2hip_range_check_layout(range_bits, lookup_bits, flags, &l.num_cells, &l.num_lookup_cells, &l.last_limb_offset));
+    return l;
+}
+// the gate cells of _range_check (behind check_less_than's / is_less_than's seven cells with H2HIP_RANGE_LESS_THAN) for every unit of
+// `checks` at one width, written down `columns` across `break_points` (columns.size() - 1 entries or empty: no breaks), and the limbs' copies
+// into `lookup_columns` at each unit's queue position; values_dev may lie inside a column (include/h2hip.h states the cells and the refusals)
+inline void fill_checks(Backend &b, const std::vector<void *> &columns, size_t usable_rows, const std::vector<uint32_t> &break_points,
+                        const std::vector<void *> &lookup_columns, const void *values_dev, size_t values_len, uint32_t range_bits, uint32_t lookup_bits,
+                        const std::vector<h2hip_range_check> &checks, uint32_t shift_bits = 0, uint32_t flags = 0) {
+    check(h2hip_range_fill_checks_dev(b.raw(), columns.data(), columns.size(), usable_rows, break_points.empty() ? nullptr : break_points.data(),
+                                      lookup_columns.data(), lookup_columns.size(), values_dev, values_len, range_bits, lookup_bits, shift_bits, flags,
+                                      checks.data(), checks.size()));
+}
+}  // namespace range
+
 // ---- halo2-base's PoseidonHasher (poseidon/hasher/mod.rs), batched over messages ------------------------------------
 namespace poseidon {
 class PoseidonHasher {

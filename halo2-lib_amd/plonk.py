@@ -19,7 +19,7 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from .h2hip import WITNESS_COPY, WITNESS_GATE, WITNESS_LOOKUP, Context, WitnessFailureStruct, _fe, _ptr
+from .h2hip import WITNESS_COPY, WITNESS_GATE, WITNESS_LOOKUP, Context, H2HipError, WitnessFailureStruct, _fe, _ptr, load_library
 from .halo2_proofs import ParamsKZG, R_MOD, fr_int, fr_limbs
 
 _vp = C.c_void_p
@@ -780,3 +780,47 @@ def gate_fill_chains(ctx: Context, columns: Sequence[int], usable_rows: int, a_d
     arr = chains if isinstance(chains, C.Array) else (GateChainStruct * max(len(chains), 1))(*[GateChainStruct(*[int(x) for x in c]) for c in chains])
     cols = (_vp * max(len(columns), 1))(*[_vp(int(p)) for p in columns])
     ctx._chk(ctx.lib.h2hip_gate_fill_chains_dev(ctx.handle, cols, len(columns), usable_rows, _vp(aptr), a_len, _vp(bptr), b_len, arr, len(chains)))
+
+
+class RangeCheckStruct(C.Structure):   # h2hip_range_check
+    _fields_ = [("column", C.c_uint32), ("row", C.c_uint32), ("a_offset", C.c_uint64), ("b_offset", C.c_uint64), ("lookup_slot", C.c_uint64)]
+
+
+RANGE_LESS_THAN = 1
+
+
+def range_check_table(units: Sequence) -> C.Array:
+    """a ctypes table of h2hip_range_check from (column, row, a_offset, b_offset, lookup_slot) tuples: build it once for a layout used in every
+    proof (a table of thousands of structs costs milliseconds to build)"""
+    return (RangeCheckStruct * max(len(units), 1))(*[RangeCheckStruct(*[int(x) for x in u]) for u in units])
+
+
+def range_check_layout(range_bits: int, lookup_bits: int, flags: int = 0, lib=None):
+    """h2hip_range_check_layout -> (gate cells of one unit, its lookup cells, the offset of the last-limb cell inside the gate cells or None
+    when the unit has no such cell of its own: one limb without the LESS_THAN prefix)"""
+    lib = lib or load_library()
+    cells, lookups, last = C.c_size_t(0), C.c_size_t(0), C.c_uint32(0)
+    code = lib.h2hip_range_check_layout(range_bits, lookup_bits, flags, C.byref(cells), C.byref(lookups), C.byref(last))
+    if code != 0:
+        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    return cells.value, lookups.value, None if last.value == 0xFFFFFFFF else last.value
+
+
+def range_fill_checks(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], lookup_columns: Sequence[int],
+                      values_dev, values_len: int, range_bits: int, lookup_bits: int, units, shift_bits: int = 0, flags: int = 0) -> None:
+    """h2hip_range_fill_checks_dev: the gate cells of RangeChip::_range_check at `range_bits` (behind check_less_than's / is_less_than's seven
+    cells with RANGE_LESS_THAN) for every unit, written down the device columns `columns` from each unit's (column, row) across the break
+    points, and the copies of the limbs into `lookup_columns` at each unit's queue position.  units: (column, row, a_offset, b_offset,
+    lookup_slot) tuples or a table from range_check_table() built once; the checked value is values_dev[a_offset] (a + 2^shift_bits -
+    values_dev[b_offset] with RANGE_LESS_THAN).  values_dev: a device pointer (or an object with data_ptr()), which may point into a column.
+    Stream-ordered on the context's stream."""
+    cols = (_vp * max(len(columns), 1))(*[_vp(int(p)) if p else None for p in columns])
+    lks = (_vp * max(len(lookup_columns), 1))(*[_vp(int(p)) if p else None for p in lookup_columns])
+    bps = None
+    if break_points is not None:
+        assert len(break_points) == len(columns) - 1, "one break point per column but the last"
+        bps = (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
+    arr = units if isinstance(units, C.Array) else range_check_table(units)
+    vptr = int(values_dev.data_ptr()) if hasattr(values_dev, "data_ptr") else int(values_dev or 0)
+    ctx._chk(ctx.lib.h2hip_range_fill_checks_dev(ctx.handle, cols, len(columns), usable_rows, bps, lks, len(lookup_columns), _vp(vptr) if vptr else None,
+                                                 values_len, range_bits, lookup_bits, shift_bits, flags, C.cast(arr, _vp), len(units)))

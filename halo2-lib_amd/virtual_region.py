@@ -15,6 +15,7 @@ Restated from (file:line in /root/reference/halo2-base/src):
   gates/circuit/builder.rs:260-288, 291-309, 327-375  calculate_params, assign_instances, assign_lookups_in_phase
   gates/circuit/mod.rs:159-203      BaseCircuitBuilder::synthesize (order: gate threads, lookups, copy manager, instances)
   gates/range/mod.rs:154-170        load_lookup_table
+  gates/range/mod.rs:476-635        RangeChip: limb_bases, _range_check, check_less_than (the definition of h2hip_range_fill_checks_dev's cells)
   gates/flex_gate/mod.rs:158-168, 246-277, 346-353, 1149-1190 (inner_product_simple)   the gate layouts used by the tests' tiny GateChip
 
 First phase only (h2hip_base_circuit_params is single-phase: include/h2hip.h).  Values are canonical integers mod r here; `synthesize`
@@ -438,15 +439,82 @@ class GateChip:
         return ctx.last()
 
 
+FR_CAPACITY = 253                                                         # F::CAPACITY of bn256's Fr: 2^253 < r
+
+
 class RangeChip:
-    """range_check of a cell that is already < 2^lookup_bits: queue it for the lookup (range/mod.rs:487-496)"""
+    """RangeChip (range/mod.rs:476-687) with the reference's cell order and lookup queue order: add_cell_to_lookup for a cell that is already
+    < 2^lookup_bits, range_check / _range_check (limb decomposition, the tail gate on the last limb) and check_less_than"""
 
     def __init__(self, lookup_bits: int, lookup_manager: LookupAnyManager):
         self.lookup_bits, self.lookup_manager = lookup_bits, lookup_manager
+        # range/mod.rs:477-485: Constant(1), Constant(2^lb), Constant(2^(2 lb)), ...
+        self.limb_bases = [Constant(pow(2, i * lookup_bits, R_MOD)) for i in range(max(FR_CAPACITY // lookup_bits, 1) + 1)]
 
     def add_cell_to_lookup(self, ctx: Context, a: AssignedValue):
         assert a.value < (1 << self.lookup_bits)
         self.lookup_manager.add_lookup(ctx.tag(), a)
+
+    def _queue(self, ctx: Context, a: AssignedValue):
+        """range/mod.rs:491-495: the reference queues whatever it is given (the lookup argument, not the chip, refuses a value outside the table)"""
+        self.lookup_manager.add_lookup(ctx.tag(), a)
+
+    @staticmethod
+    def _inner_product_from_one(ctx: Context, a: Sequence, b: Sequence[Constant]) -> AssignedValue:
+        """inner_product_simple when b starts with Constant(1) (flex_gate/mod.rs:953-962): | a0 | a1 | b1 | s1 | a2 | b2 | s2 | ..., a gate on a0
+        and on every running sum but the last"""
+        a = [_q(v) for v in a]
+        assert len(a) == len(b) and len(a) >= 2 and b[0].value == 1
+        s = a[0].value % R_MOD
+        cells = [a[0]]
+        for x, y in zip(a[1:], b[1:]):
+            s = (s + x.value * y.value) % R_MOD
+            cells += [x, y, Witness(s)]
+        ctx.assign_region(cells, [3 * i for i in range(len(a) - 1)])
+        return ctx.last()
+
+    def _range_check(self, ctx: Context, a: AssignedValue, range_bits: int) -> AssignedValue:
+        """range/mod.rs:512-564 -> the last (highest) limb.  decompose_fe_to_u64_limbs truncates: a value that does not fit gets the limbs of
+        its low num_limbs * lookup_bits bits, and the copy constraint between a and the sum then fails."""
+        assert range_bits > 0, "range_bits == 0 is assert_is_const, not a range check"
+        lb = self.lookup_bits
+        num_limbs, rem_bits = -(-range_bits // lb), range_bits % lb
+        assert num_limbs * lb <= FR_CAPACITY and len(self.limb_bases) >= num_limbs
+        if num_limbs == 1:
+            self._queue(ctx, a)
+            last_limb = a
+        else:
+            limbs = [Witness((a.value >> (i * lb)) & ((1 << lb) - 1)) for i in range(num_limbs)]
+            row_offset = len(ctx.advice)
+            acc = self._inner_product_from_one(ctx, limbs, self.limb_bases[:num_limbs])
+            ctx.constrain_equal(a, acc)
+            self._queue(ctx, ctx.get(row_offset))
+            for i in range(num_limbs - 1):
+                self._queue(ctx, ctx.get(row_offset + 1 + 3 * i))
+            last_limb = ctx.get(row_offset + 1 + 3 * (num_limbs - 2))
+        if rem_bits == 1:      # assert_bit: | 0 | x | x | x |
+            ctx.assign_region([Constant(0), Existing(last_limb), Existing(last_limb), Existing(last_limb)], [0])
+        elif rem_bits > 1:
+            check = GateChip.mul(ctx, last_limb, Constant(1 << (lb - rem_bits)))
+            self._queue(ctx, check)
+        return last_limb
+
+    def range_check(self, ctx: Context, a: AssignedValue, range_bits: int):
+        self._range_check(ctx, a, range_bits)
+
+    def _shifted_difference(self, ctx: Context, a, b, shift_bits: int) -> AssignedValue:
+        """the seven cells in front of check_less_than's / is_less_than's range check (range/mod.rs:617-632, 662-680):
+        | a + 2^shift - b | b | 1 | a + 2^shift | -2^shift | 1 | a | -> the first of them"""
+        a, b = _q(a), _q(b)
+        pow_of_two = 1 << shift_bits
+        shift_a = (pow_of_two + a.value) % R_MOD
+        ctx.assign_region([Witness((shift_a - b.value) % R_MOD), b, Constant(1), Witness(shift_a), Constant(-pow_of_two % R_MOD), Constant(1), a], [0, 3])
+        return ctx.get(-7)
+
+    def check_less_than(self, ctx: Context, a, b, num_bits: int):
+        """range/mod.rs:604-635"""
+        assert num_bits < FR_CAPACITY, "num_bits must leave one native-field bit of headroom for check_less_than"
+        self.range_check(ctx, self._shifted_difference(ctx, a, b, num_bits), num_bits)
 
 
 def _q(v):

@@ -646,6 +646,53 @@ typedef struct h2hip_gate_chain {
 #define H2HIP_GATE_START_A 4
 int h2hip_gate_fill_chains_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const void *a_dev, size_t a_len,
                                const void *b_dev, size_t b_len, const h2hip_gate_chain *chains_host, size_t count);
+/* Range checks written on the device: every gate cell of RangeChip::_range_check [halo2-base/src/gates/range/mod.rs:512-564], optionally
+ * behind the cells of check_less_than / is_less_than (:604-687), and the copies into the lookup-advice columns, for `count` cells of ONE
+ * width per call.  range_bits, lookup_bits, shift_bits and flags are parameters of the call (different widths are separate, stream-ordered
+ * calls).  With L = ceil(range_bits / lookup_bits) limbs, lb = lookup_bits and rem = range_bits mod lookup_bits, one unit's gate cells are, in
+ * the reference's order, every one a canonical (fully reduced) Montgomery Fr; a Constant(c) cell holds c, a copy of an earlier cell its value:
+ *   H2HIP_RANGE_LESS_THAN   a + 2^shift_bits - b, b, 1, a + 2^shift_bits, -2^shift_bits, 1, a        (7 cells, arithmetic in Fr)
+ *                           a = values_dev[a_offset], b = values_dev[b_offset]; the checked value v is the first of these cells.
+ *                           check_less_than: shift_bits = range_bits = num_bits; is_less_than: shift_bits = padded_bits, range_bits =
+ *                           padded_bits + lookup_bits (its closing is_zero stays with the circuit).  Without the flag v = values_dev[a_offset],
+ *                           b_offset is not read and there are no such cells (the copy constraint between v and the sum is keygen's).
+ *   decomposition (L >= 2)  l_0, l_1, 2^lb, s_1, l_2, 2^(2 lb), s_2, ..., s_{L-1}                    (3 L - 2 cells)
+ *                           inner_product_simple's "b starts with Constant(1)" form (flex_gate/mod.rs:953-962): l_i = bits [i lb, (i+1) lb)
+ *                           of the canonical integer of v, s_i = its low (i+1) lb bits.  A value that does not fit gets the limbs of its low
+ *                           L lb bits, as decompose_fe_to_u64_limbs truncates, and s_{L-1} != v: not a refusal, the witness check names the copy.
+ *   tail (rem >= 1)         on x = the last limb (v itself when L = 1): rem = 1: 0, x, x, x (assert_bit); rem > 1: 0, x, 2^(lb-rem),
+ *                           x 2^(lb-rem) (mul)                                                         (4 cells)
+ * Lookup cells, in the order _range_check queues them: v when L = 1, else l_0 .. l_{L-1}; then the tail's product when rem > 1.  Cell j of a
+ * unit has queue position p = lookup_slot + j and goes to lookup_columns_dev[p mod num_lookup_columns] at row p / num_lookup_columns
+ * (LookupAnyManager::assign_raw, virtual_region/lookups.rs:129-156); the caller derives lookup_slot from its manager's tag order, as it
+ * derives (column, row) from its threads.  values_dev is a plain device pointer and may point into a column of the proof.
+ * h2hip_range_check_layout (host only, pure) reports the gate cells and the lookup cells of one unit and the offset, inside the unit's run of
+ * gate cells, of the last-limb cell (UINT32_MAX when the unit has no such cell of its own: L = 1 without the prefix).
+ * Placement of the gate cells follows assign_witnesses (threads/single_phase.rs:273-312): the cells run down from (column, row); when the
+ * cell just written sits at break_points_host[column] it is written again at row 0 of column + 1 and the run goes on at row 1 (that copy is
+ * never itself a break cell); a unit may cross several breaks.  break_points_host: num_columns - 1 entries, or NULL: no breaks.
+ * H2HIP_ERR_INVALID with a message, before anything is launched or uploaded (all columns are then untouched): a NULL mandatory argument
+ * (columns_dev may be NULL when the units have no gate cells); unknown flags; range_bits == 0; lookup_bits outside 1 .. 63; L lb > 253
+ * (F::CAPACITY); shift_bits > 253 with LESS_THAN; num_lookup_columns == 0 or a NULL lookup column; for units with gate cells a column index
+ * >= num_columns or a NULL column, a run that leaves the usable rows or the last column, a break point >= usable_rows; an operand index
+ * outside values_len; a lookup row >= usable_rows; count (L + 1) > 2^32; two units whose lookup slot ranges intersect (exact, in queue
+ * positions); two units whose gate cells overlap, break copies included; a gate cell and a lookup cell of the call at one address; an
+ * operand address inside anything the call writes — the last three on address intervals, sorted and swept, conservative as for
+ * h2hip_gate_fill_chains_dev.  Cells not addressed are not touched.  columns_dev / lookup_columns_dev: HOST arrays of device columns.
+ * count == 0 is H2HIP_OK without device work.  Stream-ordered on the context's stream: one kernel, one lane per (unit, slot) with a slot per
+ * limb and one for the tail; the unit table, the column pointers, the break points and the table of powers of two are the only uploads. */
+typedef struct h2hip_range_check {
+    uint32_t column, row;        /* first gate cell of the unit (ignored when the unit has no gate cells) */
+    uint64_t a_offset, b_offset; /* values_dev indices; b_offset is read only with H2HIP_RANGE_LESS_THAN */
+    uint64_t lookup_slot;        /* index of the unit's first cell in the flat lookup queue */
+} h2hip_range_check;             /* 32 bytes */
+#define H2HIP_RANGE_LESS_THAN 1
+int h2hip_range_check_layout(uint32_t range_bits, uint32_t lookup_bits, uint32_t flags, size_t *num_cells, size_t *num_lookup_cells,
+                             uint32_t *last_limb_offset);
+int h2hip_range_fill_checks_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const uint32_t *break_points_host,
+                                void *const *lookup_columns_dev, size_t num_lookup_columns, const void *values_dev, size_t values_len,
+                                uint32_t range_bits, uint32_t lookup_bits, uint32_t shift_bits, uint32_t flags,
+                                const h2hip_range_check *checks_host, size_t count);
 /* The RLC gates' terms of the quotient numerator on the extended domain, folded in order for j < count:
  *      acc[i] = acc[i]*y + q_j[i]*(a_j[i]*gamma + a_j[i+s] - a_j[i+2s]),  s = 2^(ext_k-k), indices mod 2^ext_k.
  * q_dev / a_dev: HOST arrays of device pointers; 64 columns per launch. */
