@@ -124,6 +124,35 @@ pub struct h2hip_range_check {
     pub lookup_slot: u64,
 }
 pub const H2HIP_RANGE_LESS_THAN: u32 = 1;
+/// the non-native field of h2hip_fp_mul_fill_dev: num_limbs limbs of limb_bits bits, the modulus as a little-endian integer; flags must be 0
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct h2hip_fp_params {
+    pub limb_bits: u32,
+    pub num_limbs: u32,
+    pub lookup_bits: u32,
+    pub flags: u32,
+    pub modulus: [u8; 48],
+}
+/// one unit of h2hip_fp_mul_fill_dev: FpChip::mul of the CRT integers at values_dev[a_offset ..] and values_dev[b_offset ..] (num_limbs limbs, then
+/// the native residue), its run of cells from (column, row) downwards
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct h2hip_fp_mul {
+    pub column: u32,
+    pub row: u32,
+    pub a_offset: u64,
+    pub b_offset: u64,
+}
+/// one gap of a unit of h2hip_fp_mul_fill_dev: the range check of results entry result_index at range_bits, num_cells cells from cell_offset
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct h2hip_fp_mul_range {
+    pub cell_offset: u32,
+    pub num_cells: u32,
+    pub range_bits: u32,
+    pub result_index: u32,
+}
 pub const H2HIP_POSEIDON_ABSORB_ONLY: u32 = 1;
 pub const H2HIP_POSEIDON_WITH_CONSTS: u32 = 2;
 /// a later phase's witness: `fill(user, phase, challenges, num_challenges, columns_dev, num_columns)` (include/h2hip.h states the contract)
@@ -389,6 +418,15 @@ extern "C" {
                                        break_points_host: *const u32, lookup_columns_dev: *const *mut c_void, num_lookup_columns: usize,
                                        values_dev: *const c_void, values_len: usize, range_bits: u32, lookup_bits: u32, shift_bits: u32, flags: u32,
                                        checks_host: *const h2hip_range_check, count: usize) -> c_int;
+    pub fn h2hip_fp_mul_layout(params: *const h2hip_fp_params, num_cells: *mut usize, num_own_cells: *mut usize, num_lookup_cells: *mut usize,
+                               ranges: *mut h2hip_fp_mul_range, out_cell_offsets: *mut u32) -> c_int;
+    pub fn h2hip_fp_mul_fill_dev(ctx: *mut h2hip_ctx, columns_dev: *const *mut c_void, num_columns: usize, usable_rows: usize,
+                                 break_points_host: *const u32, params: *const h2hip_fp_params, values_dev: *const c_void, values_len: usize,
+                                 results_dev: *mut c_void, results_len: usize, units_host: *const h2hip_fp_mul, count: usize) -> c_int;
+    pub fn h2hip_trace_seek(break_points_host: *const u32, num_columns: usize, column: u32, row: u32, offset: u64, column_out: *mut u32,
+                            row_out: *mut u32) -> c_int;
+    pub fn h2hip_fp_mul_range_checks(break_points_host: *const u32, num_columns: usize, params: *const h2hip_fp_params, units_host: *const h2hip_fp_mul,
+                                     lookup_slots_host: *const u64, count: usize, checks_out: *mut h2hip_range_check) -> c_int;
     pub fn h2hip_quotient_rlc_gate_batch_dev(ctx: *mut h2hip_ctx, acc_dev: *mut c_void, q_dev: *const *const c_void, a_dev: *const *const c_void,
                                              count: usize, ext_k: u32, k: u32, gamma: *const c_void, y: *const c_void) -> c_int;
     pub fn h2hip_plonk_pk_free(ctx: *mut h2hip_ctx, pk: *mut h2hip_plonk_pk);

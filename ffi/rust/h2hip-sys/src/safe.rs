@@ -192,6 +192,42 @@ pub fn range_check_layout(range_bits: u32, lookup_bits: u32, flags: u32) -> Resu
     check(unsafe { h2hip_range_check_layout(range_bits, lookup_bits, flags, &mut cells, &mut lookups, &mut last) })?;
     Ok((cells, lookups, if last == u32::MAX { None } else { Some(last) }))
 }
+/// `FpChip::mul` as cells (halo2-ecc/src/fields/mod.rs:188-196: mul_no_carry::crt, then carry_mod::crt) for every unit of `units`: the own cells
+/// written down `columns` across `break_points`, the cells of the nine range checks left as gaps for `range_fill_checks` over `results`
+/// (3 k + 1 elements per unit: o_i, out_native, q_i + B, -c_i + 2^rb); operands are k + 1 consecutive elements of `values` (include/h2hip.h
+/// states the cell form and the refusals).
+/// Safety: every pointer of `columns` is a device column of at least `usable_rows` elements on `be`'s device.
+pub unsafe fn fp_mul_fill(be: &Backend, columns: &[*mut c_void], usable_rows: usize, break_points: Option<&[u32]>, params: &h2hip_fp_params,
+                          values: &DeviceVec, results: Option<&mut DeviceVec>, units: &[h2hip_fp_mul]) -> Result<(), HipError> {
+    assert!(break_points.map_or(true, |b| b.len() + 1 == columns.len()));
+    let (rptr, rlen) = results.map_or((ptr::null_mut(), 0), |r| (r.ptr, r.len));
+    check(h2hip_fp_mul_fill_dev(be.ctx, columns.as_ptr(), columns.len(), usable_rows, break_points.map_or(ptr::null(), |b| b.as_ptr()), params,
+                                values.ptr, values.len, rptr, rlen, units.as_ptr(), units.len()))
+}
+/// (cells of one unit, its own cells, the lookup cells of its range checks, the 3 k gaps in context order, the offsets of o_i and out_native)
+pub fn fp_mul_layout(params: &h2hip_fp_params) -> Result<(usize, usize, usize, Vec<h2hip_fp_mul_range>, Vec<u32>), HipError> {
+    let (mut cells, mut own, mut lookups) = (0usize, 0usize, 0usize);
+    let (mut ranges, mut outs) = ([h2hip_fp_mul_range::default(); 12], [0u32; 5]);
+    check(unsafe { h2hip_fp_mul_layout(params, &mut cells, &mut own, &mut lookups, ranges.as_mut_ptr(), outs.as_mut_ptr()) })?;
+    let k = params.num_limbs as usize;
+    Ok((cells, own, lookups, ranges[..3 * k].to_vec(), outs[..k + 1].to_vec()))
+}
+/// the 3 k range units of every unit of `units`, gap-major (`[j * units.len() + u]`): what `range_fill_checks` takes, five calls over the results
+pub fn fp_mul_range_checks(break_points: Option<&[u32]>, num_columns: usize, params: &h2hip_fp_params, units: &[h2hip_fp_mul], lookup_slots: &[u64])
+                           -> Result<Vec<h2hip_range_check>, HipError> {
+    assert!(break_points.map_or(true, |b| b.len() + 1 == num_columns) && lookup_slots.len() == units.len());
+    let mut out = vec![h2hip_range_check::default(); 3 * params.num_limbs as usize * units.len()];
+    check(unsafe { h2hip_fp_mul_range_checks(break_points.map_or(ptr::null(), |b| b.as_ptr()), num_columns, params, units.as_ptr(), lookup_slots.as_ptr(),
+                                             units.len(), out.as_mut_ptr()) })?;
+    Ok(out)
+}
+/// where cell `offset` of a run laid down from (column, row) lies under assign_witnesses' break rule
+pub fn trace_seek(break_points: Option<&[u32]>, num_columns: usize, column: u32, row: u32, offset: u64) -> Result<(u32, u32), HipError> {
+    assert!(break_points.map_or(true, |b| b.len() + 1 == num_columns));
+    let (mut c, mut r) = (0u32, 0u32);
+    check(unsafe { h2hip_trace_seek(break_points.map_or(ptr::null(), |b| b.as_ptr()), num_columns, column, row, offset, &mut c, &mut r) })?;
+    Ok((c, r))
+}
 /// `ff::BatchInvert` on a resident column, in place
 pub fn batch_invert(be: &Backend, a: &mut DeviceVec) -> Result<(), HipError> {
     check(unsafe { h2hip_fr_batch_invert_dev(be.ctx, a.ptr, a.len) })

@@ -685,6 +685,47 @@ inline void fill_checks(Backend &b, const std::vector<void *> &columns, size_t u
 }
 }  // namespace range
 
+// ---- halo2-ecc's FpChip (fields/fp.rs, fields/mod.rs:188-196), as device-filled cells -------------------------------------------
+namespace fp {
+struct MulLayout {
+    size_t num_cells = 0, num_own_cells = 0, num_lookup_cells = 0;
+    std::vector<h2hip_fp_mul_range> ranges;      // the 3 k gaps in context order: o, q, c
+    std::vector<uint32_t> out_cell_offsets;      // o_0 .. o_{k-1}, out_native
+};
+inline MulLayout mul_layout(const h2hip_fp_params &p) {
+    MulLayout l;
+    l.ranges.resize(12);
+    l.out_cell_offsets.resize(5);
+    check(h2hip_fp_mul_layout(&p, &l.num_cells, &l.num_own_cells, &l.num_lookup_cells, l.ranges.data(), l.out_cell_offsets.data()));
+    l.ranges.resize(3 * (size_t)p.num_limbs);
+    l.out_cell_offsets.resize((size_t)p.num_limbs + 1);
+    return l;
+}
+// where cell `offset` of a run from (column, row) lies under assign_witnesses' break rule (break_points: num_columns - 1 entries or empty)
+inline std::pair<uint32_t, uint32_t> trace_seek(const std::vector<uint32_t> &break_points, size_t num_columns, uint32_t column, uint32_t row, uint64_t offset) {
+    uint32_t c = 0, r = 0;
+    check(h2hip_trace_seek(break_points.empty() ? nullptr : break_points.data(), num_columns, column, row, offset, &c, &r));
+    return {c, r};
+}
+// the 3 k range units of every unit, gap-major ([j * units.size() + u]): what range::fill_checks takes, five calls over results_dev
+inline std::vector<h2hip_range_check> mul_range_checks(const std::vector<uint32_t> &break_points, size_t num_columns, const h2hip_fp_params &p,
+                                                       const std::vector<h2hip_fp_mul> &units, const std::vector<uint64_t> &lookup_slots) {
+    std::vector<h2hip_range_check> out(3 * (size_t)p.num_limbs * units.size());
+    check(h2hip_fp_mul_range_checks(break_points.empty() ? nullptr : break_points.data(), num_columns, &p, units.data(), lookup_slots.data(), units.size(),
+                                    out.data()));
+    return out;
+}
+// the own cells of FpChip::mul (mul_no_carry::crt, then carry_mod::crt) for every unit, written down `columns` across `break_points`; the cells
+// of the nine range checks stay gaps for range::fill_checks over results_dev (may be null; 3 k + 1 elements per unit).  Operands: k + 1
+// consecutive elements of values_dev (include/h2hip.h states the cells and the refusals)
+inline void mul_fill(Backend &b, const std::vector<void *> &columns, size_t usable_rows, const std::vector<uint32_t> &break_points,
+                     const h2hip_fp_params &p, const void *values_dev, size_t values_len, void *results_dev, size_t results_len,
+                     const std::vector<h2hip_fp_mul> &units) {
+    check(h2hip_fp_mul_fill_dev(b.raw(), columns.data(), columns.size(), usable_rows, break_points.empty() ? nullptr : break_points.data(), &p,
+                                values_dev, values_len, results_dev, results_len, units.data(), units.size()));
+}
+}  // namespace fp
+
 // ---- halo2-base's PoseidonHasher (poseidon/hasher/mod.rs), batched over messages ------------------------------------
 namespace poseidon {
 class PoseidonHasher {

@@ -824,3 +824,121 @@ def range_fill_checks(ctx: Context, columns: Sequence[int], usable_rows: int, br
     vptr = int(values_dev.data_ptr()) if hasattr(values_dev, "data_ptr") else int(values_dev or 0)
     ctx._chk(ctx.lib.h2hip_range_fill_checks_dev(ctx.handle, cols, len(columns), usable_rows, bps, lks, len(lookup_columns), _vp(vptr) if vptr else None,
                                                  values_len, range_bits, lookup_bits, shift_bits, flags, C.cast(arr, _vp), len(units)))
+
+
+class FpParamsStruct(C.Structure):   # h2hip_fp_params
+    _fields_ = [("limb_bits", C.c_uint32), ("num_limbs", C.c_uint32), ("lookup_bits", C.c_uint32), ("flags", C.c_uint32), ("modulus", C.c_uint8 * 48)]
+
+
+class FpMulStruct(C.Structure):   # h2hip_fp_mul
+    _fields_ = [("column", C.c_uint32), ("row", C.c_uint32), ("a_offset", C.c_uint64), ("b_offset", C.c_uint64)]
+
+
+class FpMulRangeStruct(C.Structure):   # h2hip_fp_mul_range
+    _fields_ = [("cell_offset", C.c_uint32), ("num_cells", C.c_uint32), ("range_bits", C.c_uint32), ("result_index", C.c_uint32)]
+
+
+def fp_params(limb_bits: int, num_limbs: int, lookup_bits: int, modulus: int, flags: int = 0) -> FpParamsStruct:
+    """h2hip_fp_params for a non-native field of modulus p < 2^384 in num_limbs limbs of limb_bits bits"""
+    return FpParamsStruct(limb_bits, num_limbs, lookup_bits, flags, (C.c_uint8 * 48)(*int(modulus).to_bytes(48, "little")))
+
+
+def fp_mul_table(units: Sequence) -> C.Array:
+    """a ctypes table of h2hip_fp_mul from (column, row, a_offset, b_offset) tuples: build it once for a layout used in every proof"""
+    return (FpMulStruct * max(len(units), 1))(*[FpMulStruct(*[int(x) for x in u]) for u in units])
+
+
+class FpMulLayout(NamedTuple):
+    """h2hip_fp_mul_layout: the cells of one FpChip::mul unit, its own cells (the rest are the gaps of its range checks), the lookup cells of
+    those checks, ranges = [(cell_offset, num_cells, range_bits, result_index)] of the 3 k gaps in context order (o, q, c: the lookup queue
+    order) and the offsets of the o_i cells and of out_native"""
+    num_cells: int
+    num_own_cells: int
+    num_lookup_cells: int
+    ranges: list
+    out_cell_offsets: list
+
+
+def fp_mul_layout(params: FpParamsStruct, lib=None) -> FpMulLayout:
+    lib = lib or load_library()
+    cells, own, lookups = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    ranges, outs = (FpMulRangeStruct * 12)(), (C.c_uint32 * 5)()
+    code = lib.h2hip_fp_mul_layout(C.cast(C.pointer(params), _vp), C.byref(cells), C.byref(own), C.byref(lookups), C.cast(ranges, _vp), outs)
+    if code != 0:
+        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    k = params.num_limbs
+    return FpMulLayout(cells.value, own.value, lookups.value, [(r.cell_offset, r.num_cells, r.range_bits, r.result_index) for r in ranges[:3 * k]],
+                       list(outs[:k + 1]))
+
+
+def trace_seek(break_points: Optional[Sequence[int]], num_columns: int, column: int, row: int, offset: int, lib=None):
+    """h2hip_trace_seek: the (column, row) of cell `offset` of a run laid down from (column, row) as assign_witnesses does (the cell on a break
+    point: its first position; the cell behind it lies at row 1 of the next column)"""
+    lib = lib or load_library()
+    bps = None
+    if break_points is not None:
+        assert len(break_points) == num_columns - 1, "one break point per column but the last"
+        bps = (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
+    c, r = C.c_uint32(0), C.c_uint32(0)
+    code = lib.h2hip_trace_seek(bps, num_columns, column, row, offset, C.byref(c), C.byref(r))
+    if code != 0:
+        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    return c.value, r.value
+
+
+def fp_mul_fill(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], params: FpParamsStruct, values_dev,
+                values_len: int, results_dev, results_len: int, units, count: Optional[int] = None) -> None:
+    """h2hip_fp_mul_fill_dev: the own cells of FpChip::mul (mul_no_carry::crt, then carry_mod::crt) for every unit, written down the device
+    columns from each unit's (column, row) across the break points; the cells of the nine range checks are left as gaps.  units: (column, row,
+    a_offset, b_offset) tuples or a table from fp_mul_table(); an operand is the k + 1 Fr of values_dev from its offset (k limbs, then the
+    native residue).  results_dev (or None): 3 k + 1 Fr per unit — o_i, out_native, q_i + B, -c_i + 2^rb.  count: the units of a table
+    to fill (default: all).  Stream-ordered on the context's stream."""
+    cols = (_vp * max(len(columns), 1))(*[_vp(int(p)) if p else None for p in columns])
+    bps = None
+    if break_points is not None:
+        assert len(break_points) == len(columns) - 1, "one break point per column but the last"
+        bps = (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
+    arr = units if isinstance(units, C.Array) else fp_mul_table(units)
+    vptr = int(values_dev.data_ptr()) if hasattr(values_dev, "data_ptr") else int(values_dev or 0)
+    rptr = int(results_dev.data_ptr()) if hasattr(results_dev, "data_ptr") else int(results_dev or 0)
+    ctx._chk(ctx.lib.h2hip_fp_mul_fill_dev(ctx.handle, cols, len(columns), usable_rows, bps, C.cast(C.pointer(params), _vp), _vp(vptr) if vptr else None,
+                                           values_len, _vp(rptr) if rptr else None, results_len, C.cast(arr, _vp), len(units) if count is None else count))
+
+
+def fp_mul_range_tables(break_points: Optional[Sequence[int]], num_columns: int, params: FpParamsStruct, units, lookup_slots: Sequence[int], lib=None) -> list:
+    """h2hip_fp_mul_range_checks: [(width, range_check_table)] of the range checks of `units` ((column, row, a_offset, b_offset) tuples or a
+    table from fp_mul_table()), five tables of one width each in context order (the checks of o_i, of the last o, of q_i + B, of the last q,
+    of -c_i + 2^rb), all made by one library call: each check's (column, row) by trace_seek's walk from its unit's first cell, its value at
+    results index u (3 k + 1) + result_index, its lookup_slot from lookup_slots[u].  Build it once for a layout used in every proof."""
+    lib = lib or load_library()
+    k, count = params.num_limbs, len(lookup_slots)
+    arr = units if isinstance(units, C.Array) else fp_mul_table(units)
+    bps = None
+    if break_points is not None:
+        assert len(break_points) == num_columns - 1, "one break point per column but the last"
+        bps = (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
+    checks = (RangeCheckStruct * max(3 * k * count, 1))()
+    code = lib.h2hip_fp_mul_range_checks(bps, num_columns, C.cast(C.pointer(params), _vp), C.cast(arr, _vp), (C.c_uint64 * max(count, 1))(*lookup_slots), count,
+                                         C.cast(checks, _vp))
+    if code != 0:
+        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    widths = [r[2] for r in fp_mul_layout(params, lib).ranges]
+    tables = []
+    for j0, j1 in ((0, k - 1), (k - 1, k), (k, 2 * k - 1), (2 * k - 1, 2 * k), (2 * k, 3 * k)):   # gap-major: the gaps of one width are consecutive
+        if count:
+            tables.append((widths[j0], (RangeCheckStruct * ((j1 - j0) * count)).from_buffer(checks, C.sizeof(RangeCheckStruct) * j0 * count)))
+    return tables
+
+
+def fp_mul_fill_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], lookup_columns: Sequence[int],
+                            params: FpParamsStruct, values_dev, values_len: int, results_dev, results_len: int, units, lookup_slots: Sequence[int] = (),
+                            range_tables: Optional[list] = None) -> None:
+    """fp_mul_fill, then five range_fill_checks calls (one per group of gaps of one width) from results_dev: the whole run of every unit and
+    its lookup cells.  units: (column, row, a_offset, b_offset) tuples or a table from fp_mul_table(); lookup_slots[u]: the queue position of
+    unit u's first lookup cell (not read with range_tables, the result of fp_mul_range_tables() built once for the layout)."""
+    assert results_dev, "the range checks read results_dev"
+    arr = units if isinstance(units, C.Array) else fp_mul_table(units)
+    tables = range_tables if range_tables is not None else fp_mul_range_tables(break_points, len(columns), params, arr, lookup_slots, ctx.lib)
+    fp_mul_fill(ctx, columns, usable_rows, break_points, params, values_dev, values_len, results_dev, results_len, arr, len(units))
+    for bits, table in tables:
+        range_fill_checks(ctx, columns, usable_rows, break_points, lookup_columns, results_dev, results_len, bits, params.lookup_bits, table)

@@ -693,6 +693,69 @@ int h2hip_range_fill_checks_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t
                                 void *const *lookup_columns_dev, size_t num_lookup_columns, const void *values_dev, size_t values_len,
                                 uint32_t range_bits, uint32_t lookup_bits, uint32_t shift_bits, uint32_t flags,
                                 const h2hip_range_check *checks_host, size_t count);
+/* FpChip::mul written on the device [halo2-ecc/src/fields/mod.rs:188-196]: mul_no_carry::crt [bigint/mul_no_carry.rs] followed by
+ * carry_mod::crt [bigint/carry_mod.rs, with bigint/check_carry_to_zero.rs and evaluate_native, bigint/mod.rs:66-74] for `count` pairs of proper
+ * CRT integers lying on the device: k = num_limbs limbs of n = limb_bits bits, then the native residue, k + 1 consecutive Fr of values_dev from
+ * a_offset / b_offset.  One unit's run, in the reference's cell order, every cell a canonical Montgomery Fr (a Constant(c) cell holds c, a copy
+ * of an earlier cell its value); a_i, b_i the operand limbs, m_i the limbs of p, m_nat = p mod r, q_i / o_i the limbs of quotient and
+ * remainder, ip(x; y) = inner_product_simple's form from Constant(0): 0, x_0, y_0, s_0, x_1, y_1, s_1, ... (3 len + 1 cells):
+ *   S1_i, i < k   ip(a_0 .. a_i; b_i .. b_0), the last cell P_i                                              [mul_no_carry.rs:24-32]
+ *   S2            0, a_nat, b_nat, N = a_nat b_nat                                                          [:45]
+ *   S3_i, i < k   ip(q_0 .. q_i; m_i .. m_0), the last cell prod_i; then -1, P_i, prod_i - P_i, 1, o_i,
+ *                 check_i = prod_i - P_i + o_i (Fr arithmetic)                                              [carry_mod.rs:100-134]
+ *   S4_i          a gap: the range check of o_i at n bits, the last at bits(p) - n (k - 1)                  [:139-142]
+ *   S5_i          q_i, B, 1, q_i + B with B = 2^n, the last 2^quot_last_limb_bits; then a gap: the range check of that sum at n + 1
+ *                 bits, the last at quot_last_limb_bits + 1                                                 [:145-153]
+ *   S6_i          check_i, -c_i, 2^n, -c_{i-1} (0 for i = 0); -c_i, 2^rb, 1, -c_i + 2^rb; then a gap: the range check of that sum at
+ *                 rb + 1 bits                                                                               [check_carry_to_zero.rs:64-85]
+ *   S7            q_0, q_1, 2^n, s_1, ..., s_{k-1}  (3 k - 2 cells: evaluate_native, "b starts with Constant(1)")
+ *   S8            the same over o_i; the last cell is out_native
+ *   S9            m_nat, quot_native, N                                                                     [carry_mod.rs:181-184]
+ * 3 k^2 + 29 k + 3 own cells.  quot_max_bits = n k - 1 + 254 - 1 - bits(p), quot_last_limb_bits = quot_max_bits - n (k - 1); with
+ * max_limb_bits = max(max(n, ceil(log2 k) + 2 n) + 1, 2 n + bit_length(k)), rb = floor((max_limb_bits - n + 1 + lb) / lb) lb - 1 (lb =
+ * lookup_bits).  The fill writes the own cells and leaves the gaps untouched: h2hip_range_fill_checks_dev writes them from results_dev.
+ * The integers, defined for every input: A = sum (canon(a_i) mod 2^n) 2^(n i), B alike; (Q, O) = floor divmod of A B by p; q_i, o_i the low k
+ * limbs of Q and O (decompose_bigint drops the rest); P_i, prod_i in Fr from the operand values themselves; c_i = trunc-toward-zero
+ * ((signed(check_i) + c_{i-1}) / 2^n) with signed() = fe_to_bigint (values above r / 2 are negative).
+ * results_dev (may be NULL): unit u gets 3 k + 1 Fr at index u (3 k + 1): o_0 .. o_{k-1}, out_native (a CRT integer a later call may read as
+ * an operand), q_i + B for i < k, -c_i + 2^rb for i < k.
+ * h2hip_fp_mul_layout (host only, pure): the unit's cells, its own cells, the lookup cells of its nine range checks; ranges[3 k] = each gap's
+ * offset in the run, its cells, its width and the results entry it checks, in context order (o, then q, then c: the lookup queue order);
+ * out_cell_offsets[k + 1] = the offsets of the o_i cells and of out_native.  h2hip_trace_seek (host only, pure): where cell `offset` of a run
+ * from (column, row) lies under the break rule of h2hip_range_fill_checks_dev (the cell on a break point: its first position).
+ * h2hip_fp_mul_range_checks (host only, pure): the 3 k count range units of `count` units in one call, checks_out[j count + u] = gap j of
+ * unit u (so the units of one gap, and with them of one width, are consecutive): (column, row) by that walk, a_offset = u (3 k + 1) + the
+ * gap's results index, lookup_slot = lookup_slots_host[u] + the lookup cells of the unit's gaps before j.  Gaps 0 .. k-2, k-1, k .. 2k-2,
+ * 2k-1 and 2k .. 3k-1 have one width each: five h2hip_range_fill_checks_dev calls over results_dev fill them.
+ * H2HIP_ERR_INVALID with a message, before anything is launched or uploaded (all columns and results_dev are then untouched): a NULL mandatory
+ * argument; flags != 0; n outside 64 .. 127; k outside 2 .. 4; n k > 320; ceil(log2 k) + 2 n > 252; p = 0 or p not needing exactly k limbs;
+ * quot_max_bits >= n k (together the last three always refuse k = 2: n <= 125 gives n k <= 250, and quot_max_bits < n k needs bits(p) >= 253); a limb of p equal to 1; lookup_bits outside 1 .. 63; one of the five widths whose limbs take more than 253 bits; a
+ * column index >= num_columns or a NULL column; a run that leaves the usable rows or the last column; a break point >= usable_rows; an
+ * operand index + k >= values_len; results_len < count (3 k + 1); count (4 k + 3) > 2^32; two units' cells overlapping (break copies and
+ * gaps included); an operand range or the results range overlapping anything the call writes, the results overlapping operands of the call
+ * (address intervals, conservative as for h2hip_range_fill_checks_dev).  count == 0 is H2HIP_OK without device work.  Stream-ordered on the
+ * context's stream: two kernels (one lane per unit; one lane per (unit, slot), 4 k + 3 slots); the unit table, the column pointers, the break
+ * points and a table of constants are the only uploads. */
+typedef struct h2hip_fp_params {
+    uint32_t limb_bits, num_limbs, lookup_bits, flags;   /* n, k, lb; flags must be 0 */
+    uint8_t modulus[48];                                 /* p, little-endian integer */
+} h2hip_fp_params;                                       /* 64 bytes */
+typedef struct h2hip_fp_mul {
+    uint32_t column, row;        /* first cell of the unit's run */
+    uint64_t a_offset, b_offset; /* values_dev indices of the two CRT integers */
+} h2hip_fp_mul;                  /* 24 bytes */
+typedef struct h2hip_fp_mul_range {
+    uint32_t cell_offset, num_cells, range_bits, result_index;
+} h2hip_fp_mul_range;
+int h2hip_fp_mul_layout(const h2hip_fp_params *params, size_t *num_cells, size_t *num_own_cells, size_t *num_lookup_cells,
+                        h2hip_fp_mul_range *ranges, uint32_t *out_cell_offsets);
+int h2hip_fp_mul_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const uint32_t *break_points_host,
+                          const h2hip_fp_params *params, const void *values_dev, size_t values_len, void *results_dev, size_t results_len,
+                          const h2hip_fp_mul *units_host, size_t count);
+int h2hip_trace_seek(const uint32_t *break_points_host, size_t num_columns, uint32_t column, uint32_t row, uint64_t offset,
+                     uint32_t *column_out, uint32_t *row_out);
+int h2hip_fp_mul_range_checks(const uint32_t *break_points_host, size_t num_columns, const h2hip_fp_params *params, const h2hip_fp_mul *units_host,
+                              const uint64_t *lookup_slots_host, size_t count, h2hip_range_check *checks_out);
 /* The RLC gates' terms of the quotient numerator on the extended domain, folded in order for j < count:
  *      acc[i] = acc[i]*y + q_j[i]*(a_j[i]*gamma + a_j[i+s] - a_j[i+2s]),  s = 2^(ext_k-k), indices mod 2^ext_k.
  * q_dev / a_dev: HOST arrays of device pointers; 64 columns per launch. */
