@@ -221,6 +221,36 @@ pub fn fp_mul_range_checks(break_points: Option<&[u32]>, num_columns: usize, par
                                              units.len(), out.as_mut_ptr()) })?;
     Ok(out)
 }
+/// `ec_add_unequal` (non-strict, op = H2HIP_EC_ADD_UNEQUAL) or `ec_double` (H2HIP_EC_DOUBLE) of halo2-ecc as cells for every unit of `units`:
+/// the own cells written down `columns` across `break_points`, the cells of the 9 k range checks left as gaps for `range_fill_checks` over
+/// `results` (9 k + 3 elements per unit: x3, y3, lambda, then per reduction q_i + B and -c_i + 2^rb); a point is 2 (k + 1) consecutive
+/// elements of `values` (include/h2hip.h states the cell form and the refusals).
+/// Safety: every pointer of `columns` is a device column of at least `usable_rows` elements on `be`'s device.
+pub unsafe fn ec_fill(be: &Backend, columns: &[*mut c_void], usable_rows: usize, break_points: Option<&[u32]>, params: &h2hip_fp_params, op: u32,
+                      values: &DeviceVec, results: Option<&mut DeviceVec>, units: &[h2hip_ec_op]) -> Result<(), HipError> {
+    assert!(break_points.map_or(true, |b| b.len() + 1 == columns.len()));
+    let (rptr, rlen) = results.map_or((ptr::null_mut(), 0), |r| (r.ptr, r.len));
+    check(h2hip_ec_fill_dev(be.ctx, columns.as_ptr(), columns.len(), usable_rows, break_points.map_or(ptr::null(), |b| b.as_ptr()), params, op,
+                            values.ptr, values.len, rptr, rlen, units.as_ptr(), units.len()))
+}
+/// (cells of one unit, its own cells, the lookup cells of its range checks, the 9 k gaps in context order, the offsets of the cells of x3, y3, lambda)
+pub fn ec_layout(params: &h2hip_fp_params, op: u32) -> Result<(usize, usize, usize, Vec<h2hip_fp_mul_range>, Vec<u32>), HipError> {
+    let (mut cells, mut own, mut lookups) = (0usize, 0usize, 0usize);
+    let (mut ranges, mut outs) = ([h2hip_fp_mul_range::default(); 36], [0u32; 15]);
+    check(unsafe { h2hip_ec_layout(params, op, &mut cells, &mut own, &mut lookups, ranges.as_mut_ptr(), outs.as_mut_ptr()) })?;
+    let k = params.num_limbs as usize;
+    Ok((cells, own, lookups, ranges[..9 * k].to_vec(), outs[..3 * (k + 1)].to_vec()))
+}
+/// the 9 k range units of every unit of `units`, grouped by width (the distinct widths of `ec_layout`'s gaps in the order of first appearance),
+/// unit by unit inside a width: what `range_fill_checks` takes, one call per width over the results
+pub fn ec_range_checks(break_points: Option<&[u32]>, num_columns: usize, params: &h2hip_fp_params, op: u32, units: &[h2hip_ec_op], lookup_slots: &[u64])
+                       -> Result<Vec<h2hip_range_check>, HipError> {
+    assert!(break_points.map_or(true, |b| b.len() + 1 == num_columns) && lookup_slots.len() == units.len());
+    let mut out = vec![h2hip_range_check::default(); 9 * params.num_limbs as usize * units.len()];
+    check(unsafe { h2hip_ec_range_checks(break_points.map_or(ptr::null(), |b| b.as_ptr()), num_columns, params, op, units.as_ptr(), lookup_slots.as_ptr(),
+                                         units.len(), out.as_mut_ptr()) })?;
+    Ok(out)
+}
 /// where cell `offset` of a run laid down from (column, row) lies under assign_witnesses' break rule
 pub fn trace_seek(break_points: Option<&[u32]>, num_columns: usize, column: u32, row: u32, offset: u64) -> Result<(u32, u32), HipError> {
     assert!(break_points.map_or(true, |b| b.len() + 1 == num_columns));

@@ -151,9 +151,68 @@ H2_HD Fr mp_low_limb(const uint32_t (&x)[N], uint32_t n) {   // the low n <= 127
     return range_low_bits(c, n);
 }
 
+// (Q, O) = floor divmod of X < 2^S by p through mu = floor(2^S / p), S = 64 WA: the estimate floor(X mu / 2^S) is Q or Q - 1, so the correction
+// loop runs at most once; its bound is two.  Q mod 2^(32 (WA + 1)): limbs past k are dropped anyway.
+template <int WA>
+H2_HD void fp_barrett(const uint32_t (&X)[2 * WA], const uint32_t (&p)[FP_P_WORDS], const uint32_t (&mu_)[FP_MU_WORDS], uint32_t (&Q)[WA + 1],
+                      uint32_t (&O)[WA + 1]) {
+    constexpr int WR = WA + 1;
+    uint32_t pw[WR];
+    static_for<WR>([&](auto j) H2_INL { pw[decltype(j)::value] = p[decltype(j)::value]; });
+    {
+        uint32_t mu[FP_MU_WORDS];
+        static_for<(int)FP_MU_WORDS>([&](auto j) H2_INL { mu[decltype(j)::value] = mu_[decltype(j)::value]; });
+        mp_mul_words<2 * WA, (int)FP_MU_WORDS, 2 * WA, WR>(X, mu, Q);
+        uint32_t QP[WR], XL[WR];
+        mp_mul_low<WR>(Q, pw, QP);
+        static_for<WR>([&](auto j) H2_INL { XL[decltype(j)::value] = X[decltype(j)::value]; });
+        mp_sub<WR>(XL, QP, O);   // < 2 p < 2^(32 WR)
+    }
+    static_for<2>([&](auto) H2_INL {
+        uint32_t D[WR];
+        const unsigned below = mp_sub<WR>(O, pw, D);
+        unsigned c = below ? 0u : 1u;
+        static_for<WR>([&](auto j) H2_INL {
+            O[decltype(j)::value] = below ? O[decltype(j)::value] : D[decltype(j)::value];
+            Q[decltype(j)::value] = addc32(Q[decltype(j)::value], 0, c);
+        });
+    });
+}
+// one step of check_carry_to_zero's chain: cw holds c_{i-1} in 288-bit two's complement and gets c_i = trunc((signed(check) + c_{i-1}) / 2^n)
+// (|signed(check)| < 2^253, |c_i| < 2^190), signed() as fe_to_bigint: above (r - 1) / 2 is negative -> -c_i (Montgomery)
+H2_HD Fr fp_carry_step(const Fr &check, uint32_t (&cw)[9], uint32_t n) {
+    const Fr c = fe_from_mont(check);
+    unsigned br = 0;
+    static_for<9>([&](auto j0) H2_INL {   // 2 c >= r ?
+        constexpr int j = decltype(j0)::value;
+        const uint32_t two_c = (j < 8 ? c.l[j < 8 ? j : 0] << 1 : 0u) | (j > 0 ? c.l[j > 0 ? j - 1 : 0] >> 31 : 0u);
+        subb32(two_c, j < 8 ? FrP::m(j < 8 ? j : 0) : 0u, br);
+    });
+    const bool neg = br == 0;
+    uint32_t v[9];
+    br = 0;
+    static_for<8>([&](auto j0) H2_INL {
+        constexpr int j = decltype(j0)::value;
+        const uint32_t d = subb32(c.l[j], FrP::m(j), br);
+        v[j] = neg ? d : c.l[j];
+    });
+    v[8] = neg ? 0xFFFFFFFFu : 0u;
+    unsigned cy = 0;
+    static_for<9>([&](auto j) H2_INL { v[decltype(j)::value] = addc32(v[decltype(j)::value], cw[decltype(j)::value], cy); });
+    const uint32_t sign = v[8] >> 31;
+    mp_neg_if<9>(v, sign);   // the magnitude: the division truncates toward zero
+    mp_shr<9>(v, n);
+    Fr cm;
+    static_for<8>([&](auto j) H2_INL { cm.l[decltype(j)::value] = v[decltype(j)::value]; });
+    cm = fe_to_mont(cm);
+    const Fr negc = sign ? cm : fe_neg(cm);
+    static_for<9>([&](auto j) H2_INL { cw[decltype(j)::value] = v[decltype(j)::value]; });
+    mp_neg_if<9>(cw, sign);
+    return negc;
+}
+
 // ---- the big-integer step of one unit: the record and the results entries
-// A = sum (canon(a_i) mod 2^n) 2^(n i), B alike; (Q, O) = floor divmod of A B by p through mu = floor(2^S / p), S = 64 WA >= 2 n k: the estimate
-// floor(A B mu / 2^S) is Q or Q - 1 (A B < 2^S), so the correction loop below runs at most once; its bound is two.  q_i, o_i: the low k limbs.
+// A = sum (canon(a_i) mod 2^n) 2^(n i), B alike; (Q, O) = floor divmod of A B < 2^S by p (fp_barrett, S = 64 WA >= 2 n k).  q_i, o_i: the low k limbs.
 template <int K>
 H2_HD void fp_solve_unit(const FpCall &fc, const h2hip_fp_mul &unit, uint32_t u) {
     constexpr int WA = K == 2 ? 8 : 10, WR = WA + 1;
@@ -181,26 +240,8 @@ H2_HD void fp_solve_unit(const FpCall &fc, const h2hip_fp_mul &unit, uint32_t u)
         });
         mp_mul<WA, WA>(A, B, X);
     }
-    uint32_t Q[WR], O[WR], pw[WR];
-    static_for<WR>([&](auto j) H2_INL { pw[decltype(j)::value] = fc.p[decltype(j)::value]; });
-    {
-        uint32_t mu[FP_MU_WORDS];
-        static_for<(int)FP_MU_WORDS>([&](auto j) H2_INL { mu[decltype(j)::value] = fc.mu[decltype(j)::value]; });
-        mp_mul_words<2 * WA, (int)FP_MU_WORDS, 2 * WA, WR>(X, mu, Q);   // (Q mod 2^(32 WR): limbs past k are dropped anyway)
-        uint32_t QP[WR], XL[WR];
-        mp_mul_low<WR>(Q, pw, QP);
-        static_for<WR>([&](auto j) H2_INL { XL[decltype(j)::value] = X[decltype(j)::value]; });
-        mp_sub<WR>(XL, QP, O);   // < 2 p < 2^(32 WR)
-    }
-    static_for<2>([&](auto) H2_INL {
-        uint32_t D[WR];
-        const unsigned below = mp_sub<WR>(O, pw, D);
-        unsigned c = below ? 0u : 1u;
-        static_for<WR>([&](auto j) H2_INL {
-            O[decltype(j)::value] = below ? O[decltype(j)::value] : D[decltype(j)::value];
-            Q[decltype(j)::value] = addc32(Q[decltype(j)::value], 0, c);
-        });
-    });
+    uint32_t Q[WR], O[WR];
+    fp_barrett<WA>(X, fc.p, fc.mu, Q, O);
     Fr *rec = fc.rec + (size_t)u * fp_record_len(K);
     Fr *res = fc.results ? fc.results + (size_t)u * fp_result_len(K) : nullptr;
     Fr q[K], o[K];
@@ -217,8 +258,7 @@ H2_HD void fp_solve_unit(const FpCall &fc, const h2hip_fp_mul &unit, uint32_t u)
             res[K + 1 + i] = fe_add(q[i], i == K - 1 ? cs[2 * K] : cs[K + 1]);
         }
     });
-    // P_i, prod_i and check_i in Fr from the operand values themselves; the carries c_i = trunc((signed(check_i) + c_{i-1}) / 2^n) in 288-bit
-    // two's complement (|signed(check_i)| < 2^253, |c_i| < 2^190), signed() as fe_to_bigint: above (r - 1) / 2 is negative
+    // P_i, prod_i and check_i in Fr from the operand values themselves; the carries by fp_carry_step
     uint32_t cw[9];
     static_for<9>([&](auto j) H2_INL { cw[decltype(j)::value] = 0; });
     static_for<K>([&](auto i0) H2_INL {
@@ -232,35 +272,9 @@ H2_HD void fp_solve_unit(const FpCall &fc, const h2hip_fp_mul &unit, uint32_t u)
         const Fr check = fe_add(fe_sub(prod, P), o[i]);
         rec[3 * K + i] = P;
         rec[4 * K + i] = check;
-        const Fr c = fe_from_mont(check);
-        unsigned br = 0;
-        static_for<9>([&](auto j0) H2_INL {   // 2 c >= r ?
-            constexpr int j = decltype(j0)::value;
-            const uint32_t two_c = (j < 8 ? c.l[j < 8 ? j : 0] << 1 : 0u) | (j > 0 ? c.l[j > 0 ? j - 1 : 0] >> 31 : 0u);
-            subb32(two_c, j < 8 ? FrP::m(j < 8 ? j : 0) : 0u, br);
-        });
-        const bool neg = br == 0;
-        uint32_t v[9];
-        br = 0;
-        static_for<8>([&](auto j0) H2_INL {
-            constexpr int j = decltype(j0)::value;
-            const uint32_t d = subb32(c.l[j], FrP::m(j), br);
-            v[j] = neg ? d : c.l[j];
-        });
-        v[8] = neg ? 0xFFFFFFFFu : 0u;
-        unsigned cy = 0;
-        static_for<9>([&](auto j) H2_INL { v[decltype(j)::value] = addc32(v[decltype(j)::value], cw[decltype(j)::value], cy); });
-        const uint32_t sign = v[8] >> 31;
-        mp_neg_if<9>(v, sign);   // the magnitude: the division truncates toward zero
-        mp_shr<9>(v, n);
-        Fr cm;
-        static_for<8>([&](auto j) H2_INL { cm.l[decltype(j)::value] = v[decltype(j)::value]; });
-        cm = fe_to_mont(cm);
-        const Fr negc = sign ? cm : fe_neg(cm);
+        const Fr negc = fp_carry_step(check, cw, n);
         rec[2 * K + i] = negc;
         if (res) res[2 * K + 1 + i] = fe_add(negc, cs[2 * K + 1]);
-        static_for<9>([&](auto j) H2_INL { cw[decltype(j)::value] = v[decltype(j)::value]; });
-        mp_neg_if<9>(cw, sign);
     });
     Fr qn = q[0], on = o[0];
     static_for<K - 1>([&](auto i0) H2_INL {

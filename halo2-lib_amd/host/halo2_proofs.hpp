@@ -724,6 +724,37 @@ inline void mul_fill(Backend &b, const std::vector<void *> &columns, size_t usab
     check(h2hip_fp_mul_fill_dev(b.raw(), columns.data(), columns.size(), usable_rows, break_points.empty() ? nullptr : break_points.data(), &p,
                                 values_dev, values_len, results_dev, results_len, units.data(), units.size()));
 }
+// ---- EccChip's ec_add_unequal (non-strict) and ec_double as cells (include/h2hip.h states the form and the refusals)
+struct EcLayout {
+    size_t num_cells = 0, num_own_cells = 0, num_lookup_cells = 0;
+    std::vector<h2hip_fp_mul_range> ranges;      // the 9 k gaps in context order
+    std::vector<uint32_t> out_cell_offsets;      // the cells of x3, y3, lambda (k limbs and the native each)
+};
+inline EcLayout ec_layout(const h2hip_fp_params &p, uint32_t op) {
+    EcLayout l;
+    l.ranges.resize(36);
+    l.out_cell_offsets.resize(15);
+    check(h2hip_ec_layout(&p, op, &l.num_cells, &l.num_own_cells, &l.num_lookup_cells, l.ranges.data(), l.out_cell_offsets.data()));
+    l.ranges.resize(9 * (size_t)p.num_limbs);
+    l.out_cell_offsets.resize(3 * ((size_t)p.num_limbs + 1));
+    return l;
+}
+// the 9 k range units of every unit, grouped by width (order of first appearance among ec_layout's gaps), unit by unit inside a width
+inline std::vector<h2hip_range_check> ec_range_checks(const std::vector<uint32_t> &break_points, size_t num_columns, const h2hip_fp_params &p, uint32_t op,
+                                                      const std::vector<h2hip_ec_op> &units, const std::vector<uint64_t> &lookup_slots) {
+    std::vector<h2hip_range_check> out(9 * (size_t)p.num_limbs * units.size());
+    check(h2hip_ec_range_checks(break_points.empty() ? nullptr : break_points.data(), num_columns, &p, op, units.data(), lookup_slots.data(), units.size(),
+                                out.data()));
+    return out;
+}
+// the own cells of one curve operation per unit, written down `columns` across `break_points`; the cells of the 9 k range checks stay gaps for
+// range::fill_checks over results_dev (may be null; 9 k + 3 elements per unit).  A point: 2 (k + 1) consecutive elements of values_dev
+inline void ec_fill(Backend &b, const std::vector<void *> &columns, size_t usable_rows, const std::vector<uint32_t> &break_points,
+                    const h2hip_fp_params &p, uint32_t op, const void *values_dev, size_t values_len, void *results_dev, size_t results_len,
+                    const std::vector<h2hip_ec_op> &units) {
+    check(h2hip_ec_fill_dev(b.raw(), columns.data(), columns.size(), usable_rows, break_points.empty() ? nullptr : break_points.data(), &p, op,
+                            values_dev, values_len, results_dev, results_len, units.data(), units.size()));
+}
 }  // namespace fp
 
 // ---- halo2-base's PoseidonHasher (poseidon/hasher/mod.rs), batched over messages ------------------------------------

@@ -942,3 +942,100 @@ def fp_mul_fill_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: i
     fp_mul_fill(ctx, columns, usable_rows, break_points, params, values_dev, values_len, results_dev, results_len, arr, len(units))
     for bits, table in tables:
         range_fill_checks(ctx, columns, usable_rows, break_points, lookup_columns, results_dev, results_len, bits, params.lookup_bits, table)
+
+
+class EcOpStruct(C.Structure):   # h2hip_ec_op
+    _fields_ = [("column", C.c_uint32), ("row", C.c_uint32), ("p_offset", C.c_uint64), ("q_offset", C.c_uint64)]
+
+
+EC_ADD_UNEQUAL, EC_DOUBLE = 0, 1
+
+
+def ec_op_table(units: Sequence) -> C.Array:
+    """a ctypes table of h2hip_ec_op from (column, row, p_offset, q_offset) tuples: build it once for a layout used in every proof"""
+    return (EcOpStruct * max(len(units), 1))(*[EcOpStruct(*[int(x) for x in u]) for u in units])
+
+
+class EcLayout(NamedTuple):
+    """h2hip_ec_layout: the cells of one ec_add_unequal / ec_double unit, its own cells (the rest are the gaps of its range checks), the lookup
+    cells of those checks, ranges = [(cell_offset, num_cells, range_bits, result_index)] of the 9 k gaps in context order (the lookup queue
+    order) and the offsets of the cells of x3, y3 and lambda (k limb cells and the native cell each)"""
+    num_cells: int
+    num_own_cells: int
+    num_lookup_cells: int
+    ranges: list
+    out_cell_offsets: list
+
+
+def ec_layout(params: FpParamsStruct, op: int, lib=None) -> EcLayout:
+    lib = lib or load_library()
+    cells, own, lookups = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    ranges, outs = (FpMulRangeStruct * 36)(), (C.c_uint32 * 15)()
+    code = lib.h2hip_ec_layout(C.cast(C.pointer(params), _vp), op, C.byref(cells), C.byref(own), C.byref(lookups), C.cast(ranges, _vp), outs)
+    if code != 0:
+        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    k = params.num_limbs
+    return EcLayout(cells.value, own.value, lookups.value, [(r.cell_offset, r.num_cells, r.range_bits, r.result_index) for r in ranges[:9 * k]],
+                    list(outs[:3 * (k + 1)]))
+
+
+def ec_fill(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], params: FpParamsStruct, op: int, values_dev,
+            values_len: int, results_dev, results_len: int, units, count: Optional[int] = None) -> None:
+    """h2hip_ec_fill_dev: the own cells of ec_add_unequal (non-strict, op = EC_ADD_UNEQUAL) or ec_double (EC_DOUBLE) for every unit, written down
+    the device columns from each unit's (column, row) across the break points; the cells of the 9 k range checks are left as gaps.  units:
+    (column, row, p_offset, q_offset) tuples or a table from ec_op_table(); a point is the 2 (k + 1) Fr of values_dev from its offset (x's k
+    limbs and native residue, then y's).  results_dev (or None): 9 k + 3 Fr per unit — x3, y3 (a point a later call may read), lambda, then
+    per reduction q_i + B and -c_i + 2^rb.  count: the units of a table to fill (default: all).  Stream-ordered on the context's stream."""
+    cols = (_vp * max(len(columns), 1))(*[_vp(int(p)) if p else None for p in columns])
+    bps = None
+    if break_points is not None:
+        assert len(break_points) == len(columns) - 1, "one break point per column but the last"
+        bps = (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
+    arr = units if isinstance(units, C.Array) else ec_op_table(units)
+    vptr = int(values_dev.data_ptr()) if hasattr(values_dev, "data_ptr") else int(values_dev or 0)
+    rptr = int(results_dev.data_ptr()) if hasattr(results_dev, "data_ptr") else int(results_dev or 0)
+    ctx._chk(ctx.lib.h2hip_ec_fill_dev(ctx.handle, cols, len(columns), usable_rows, bps, C.cast(C.pointer(params), _vp), op, _vp(vptr) if vptr else None,
+                                       values_len, _vp(rptr) if rptr else None, results_len, C.cast(arr, _vp), len(units) if count is None else count))
+
+
+def ec_range_tables(break_points: Optional[Sequence[int]], num_columns: int, params: FpParamsStruct, op: int, units, lookup_slots: Sequence[int],
+                    lib=None) -> list:
+    """h2hip_ec_range_checks: [(width, range_check_table)] of the range checks of `units` ((column, row, p_offset, q_offset) tuples or a table
+    from ec_op_table()), one table per distinct width in the order of first appearance among ec_layout's ranges, all made by one library call;
+    inside a table the checks run unit by unit (rows and lookup slots ascend).  lookup_slots[u]: the queue position of unit u's first lookup
+    cell.  Build it once for a layout used in every proof."""
+    lib = lib or load_library()
+    k, count = params.num_limbs, len(lookup_slots)
+    arr = units if isinstance(units, C.Array) else ec_op_table(units)
+    bps = None
+    if break_points is not None:
+        assert len(break_points) == num_columns - 1, "one break point per column but the last"
+        bps = (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
+    checks = (RangeCheckStruct * max(9 * k * count, 1))()
+    code = lib.h2hip_ec_range_checks(bps, num_columns, C.cast(C.pointer(params), _vp), op, C.cast(arr, _vp), (C.c_uint64 * max(count, 1))(*lookup_slots),
+                                     count, C.cast(checks, _vp))
+    if code != 0:
+        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    widths: dict = {}
+    for r in ec_layout(params, op, lib).ranges:
+        widths[r[2]] = widths.get(r[2], 0) + 1             # (a dict keeps the order of first appearance)
+    tables, at = [], 0
+    for bits, gaps in widths.items():
+        if count:
+            tables.append((bits, (RangeCheckStruct * (gaps * count)).from_buffer(checks, C.sizeof(RangeCheckStruct) * at)))
+        at += gaps * count
+    return tables
+
+
+def ec_fill_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], lookup_columns: Sequence[int],
+                        params: FpParamsStruct, op: int, values_dev, values_len: int, results_dev, results_len: int, units,
+                        lookup_slots: Sequence[int] = (), range_tables: Optional[list] = None) -> None:
+    """ec_fill, then one range_fill_checks call per width group from results_dev: the whole run of every unit and its lookup cells.
+    lookup_slots[u]: the queue position of unit u's first lookup cell (not read with range_tables, the result of ec_range_tables() built once
+    for the layout)."""
+    assert results_dev, "the range checks read results_dev"
+    arr = units if isinstance(units, C.Array) else ec_op_table(units)
+    tables = range_tables if range_tables is not None else ec_range_tables(break_points, len(columns), params, op, arr, lookup_slots, ctx.lib)
+    ec_fill(ctx, columns, usable_rows, break_points, params, op, values_dev, values_len, results_dev, results_len, arr, len(units))
+    for bits, table in tables:
+        range_fill_checks(ctx, columns, usable_rows, break_points, lookup_columns, results_dev, results_len, bits, params.lookup_bits, table)

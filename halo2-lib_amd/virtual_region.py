@@ -416,6 +416,13 @@ class GateChip:
         return ctx.assign_region_last([a, b, Constant(1), Witness((a.value + b.value) % R_MOD)], [0])
 
     @staticmethod
+    def sub(ctx: Context, a, b) -> AssignedValue:
+        """| a - b | b | 1 | a | (flex_gate/mod.rs:184-196) -> the first cell"""
+        a, b = _q(a), _q(b)
+        ctx.assign_region([Witness((a.value - b.value) % R_MOD), b, Constant(1), a], [0])
+        return ctx.get(-4)
+
+    @staticmethod
     def mul(ctx: Context, a, b) -> AssignedValue:
         a, b = _q(a), _q(b)
         return ctx.assign_region_last([Constant(0), a, b, Witness(a.value * b.value % R_MOD)], [0])

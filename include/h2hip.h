@@ -756,6 +756,63 @@ int h2hip_trace_seek(const uint32_t *break_points_host, size_t num_columns, uint
                      uint32_t *column_out, uint32_t *row_out);
 int h2hip_fp_mul_range_checks(const uint32_t *break_points_host, size_t num_columns, const h2hip_fp_params *params, const h2hip_fp_mul *units_host,
                               const uint64_t *lookup_slots_host, size_t count, h2hip_range_check *checks_out);
+/* EccChip's ec_add_unequal (is_strict = false) and ec_double written on the device [halo2-ecc/src/ecc/mod.rs:153-179, :302-327] for `count`
+ * units over the limb layout of h2hip_fp_params, k = 3 or 4.  A point is 2 (k + 1) consecutive Fr of values_dev: x's k limbs and native
+ * residue, then y's; P lies at p_offset, Q at q_offset (ignored for DOUBLE).  One unit's run is the reference's, cell for cell, every cell a
+ * canonical Montgomery Fr; a CRT value below is its k limb cells followed by its native cell, ip(x; y) as for h2hip_fp_mul_fill_dev:
+ *   sub(a, b)     per cell j <= k of the two values: a_j - b_j, b_j, 1, a_j     (4 (k + 1) cells) [bigint/sub_no_carry.rs:14-33, gate.sub
+ *                 halo2-base/src/gates/flex_gate/mod.rs:184-196]
+ *   smul(a, c)    per cell: 0, a_j, c, c a_j                                     (4 (k + 1) cells) [bigint/scalar_mul_no_carry.rs:16-35]
+ *   mul(a, b)     S1_i (i < k) and S2 of h2hip_fp_mul_fill_dev over the cells of a and b          [bigint/mul_no_carry.rs:24-32, :45]
+ *   load(l)       l_0 .. l_{k-1}; l_0, l_1, 2^n, s_1, ..., s_{k-1} (evaluate_native, the last cell the native); then k gaps: the range
+ *                 checks of l_i at n bits, the last at bits(p) - n (k - 1)       (4 k - 2 own cells) [fields/fp.rs:187-197, :321-339]
+ *   zero(a)       per i < k: ip(q_0 .. q_i; m_i .. m_0), -1, a_i, prod_i - a_i = check_i; per i: q_i, B, 1, q_i + B and a gap (n + 1 bits,
+ *                 the last quot_last_limb_bits + 1); per i: check_i, -c_i, 2^n, -c_{i-1}; -c_i, 2^rb, 1, -c_i + 2^rb and a gap (rb + 1
+ *                 bits); q's evaluate_native; 0, m_nat, quot_native, a_nat        [bigint/check_carry_mod_to_zero.rs:71-124]
+ *   carry(a)      S3 .. S9 of h2hip_fp_mul_fill_dev with the cell a_i in place of P_i and a_nat in place of N [bigint/carry_mod.rs:100-184]
+ * ADD_UNEQUAL: dx = sub(Q.x, P.x); dy = sub(Q.y, P.y); load(lambda); ld = mul(lambda, dx); zero(sub(ld, dy)) [divide_unsafe,
+ *   fields/mod.rs:217-238]; x3 = carry(sub(sub(mul(lambda, lambda), P.x), Q.x)); y3 = carry(sub(mul(lambda, sub(P.x, x3)), P.y)).
+ * DOUBLE: y2 = smul(P.y, 2); x3_ = smul(P.x, 3); num = mul(x3_, P.x); load(lambda); zero(sub(mul(lambda, y2), num)); l2 = mul(lambda, lambda);
+ *   x2 = smul(P.x, 2); x3 = carry(sub(l2, x2)); y3 = carry(sub(mul(lambda, sub(P.x, x3)), P.y)).
+ * At k = 3 a unit has 458 (ADD_UNEQUAL) or 483 (DOUBLE) own cells and 9 k gaps.  max_limb_bits is threaded as the reference threads it (+1
+ * per sub, + ceil(log2 c) per smul, ceil(log2 k) + a + b per mul) and gives each reduction its own rb: from max(a, 2 n + bit_length(k)) for
+ * zero, max(max(n, a) + 1, 2 n + bit_length(k)) for carry, rb = floor((that - n + 1 + lb) / lb) lb - 1.  Fp::NUM_BITS in load is bits(p): for
+ * a prime field the two are the same number by definition, so no accepted modulus differs.
+ * The integers, defined for every input (nothing is asserted; a bad witness is the witness checker's business): an operand integer is X =
+ * sum (canon(x_i) mod 2^n) 2^(n i); no-carry values are exact signed integers over those; limb and native cells are Fr arithmetic over the
+ * operand cells themselves.  lambda = (num mod p) (den mod p)^-1 mod p with den = X2 - X1, num = Y2 - Y1 (DOUBLE: 2 Y, 3 X^2), 0 where den has
+ * no inverse.  (Q, O) = FLOOR divmod of the signed value by p; q_i = the low k limbs of |Q|, negated in Fr when Q < 0 (decompose_bigint); o_i
+ * the low k limbs of O; c_i as for h2hip_fp_mul_fill_dev.  x3's integer in y3 is the O of x3's reduction.
+ * results_dev (may be NULL): unit u gets 9 k + 3 Fr at index u (9 k + 3): x3 and y3 (k + 1 each: a point in operand form, a later call may read
+ * it), lambda (k + 1), then per reduction r < 3 (zero, x3's carry, y3's carry) q_i + B for i < k and -c_i + 2^rb_r for i < k, at 3 k + 3 + 2 k r.
+ * h2hip_ec_layout (host only, pure): the unit's cells, own cells and lookup cells; ranges[9 k]: each gap's offset, cells, width and the results
+ * entry it checks, in context order (the lookup queue order): lambda_i; zero's q then c; x3's o, q, c; y3's o, q, c.  out_cell_offsets[3 (k + 1)]:
+ * the cells of x3 (o_i, out_native), of y3, of lambda (its witness cells, its native).
+ * h2hip_ec_range_checks (host only, pure): the 9 k count range units of `count` units in one call, grouped by width: group g holds the gaps
+ * of the g-th distinct range_bits of h2hip_ec_layout's ranges (order of first appearance; at most seven: n, lambda's and o's last limb,
+ * n + 1, the last q, up to three carry widths), groups lie one behind the other (group g starts at count times the gaps of the groups before
+ * it), and INSIDE a group the checks run unit by unit, a unit's gaps in context order: rows and lookup slots ascend.  a_offset = u (9 k + 3) +
+ * the gap's results index, lookup_slot = lookup_slots_host[u] + the lookup cells of the unit's gaps before it.  One
+ * h2hip_range_fill_checks_dev call per group over results_dev fills them.
+ * H2HIP_ERR_INVALID with a message, before anything is launched or uploaded (all columns and results_dev are then untouched): the refusals of
+ * h2hip_fp_mul_fill_dev applied to this unit (its run, its 2 (k + 1)-element operands, results_len < count (9 k + 3), count times the unit's
+ * segments > 2^32), and: an unknown op; k < 3; bits(p) > 256 or p even (lambda's inversion); n k > 318 (3 X^2 would pass 2^640); ceil(log2 k) +
+ * a + b > 252 for a product the op makes; a width whose limbs take more than 253 bits.  count == 0 is H2HIP_OK without device work.
+ * Stream-ordered on the context's stream: two kernels (one lane per unit; one lane per (unit, segment)); the unit table, the column
+ * pointers, the break points, the constants and the segment table are the only uploads. */
+#define H2HIP_EC_ADD_UNEQUAL 0   /* ecc/mod.rs ec_add_unequal, is_strict = false */
+#define H2HIP_EC_DOUBLE 1        /* ecc/mod.rs ec_double */
+typedef struct h2hip_ec_op {
+    uint32_t column, row;        /* first cell of the unit's run */
+    uint64_t p_offset, q_offset; /* values_dev indices of the two points; q_offset is ignored for H2HIP_EC_DOUBLE */
+} h2hip_ec_op;                   /* 24 bytes */
+int h2hip_ec_layout(const h2hip_fp_params *params, uint32_t op, size_t *num_cells, size_t *num_own_cells, size_t *num_lookup_cells,
+                    h2hip_fp_mul_range *ranges, uint32_t *out_cell_offsets);
+int h2hip_ec_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const uint32_t *break_points_host,
+                      const h2hip_fp_params *params, uint32_t op, const void *values_dev, size_t values_len, void *results_dev, size_t results_len,
+                      const h2hip_ec_op *units_host, size_t count);
+int h2hip_ec_range_checks(const uint32_t *break_points_host, size_t num_columns, const h2hip_fp_params *params, uint32_t op,
+                          const h2hip_ec_op *units_host, const uint64_t *lookup_slots_host, size_t count, h2hip_range_check *checks_out);
 /* The RLC gates' terms of the quotient numerator on the extended domain, folded in order for j < count:
  *      acc[i] = acc[i]*y + q_j[i]*(a_j[i]*gamma + a_j[i+s] - a_j[i+2s]),  s = 2^(ext_k-k), indices mod 2^ext_k.
  * q_dev / a_dev: HOST arrays of device pointers; 64 columns per launch. */
