@@ -54,12 +54,11 @@ struct EcSeg {
 
 // what one call's lanes share
 struct EcCall {
-    Fr *const *cols;
-    const uint32_t *bps;
+    TraceCols tc;
     const Fr *values, *consts;
     Fr *results, *rec;
     const EcSeg *segs;
-    uint32_t last_col, n, k, nsegs;
+    uint32_t n, k;
     uint32_t p[FP_P_WORDS], mu[FP_MU_WORDS];   // wave-uniform: the modulus and its Barrett constant, 32-bit words
     int32_t p30[9];                            // the modulus in 30-bit limbs and -p^-1 mod 2^30, for the division steps
     uint32_t neg_pinv30;
@@ -440,11 +439,7 @@ H2_HD void ec_place_slot(const EcCall &ec, const h2hip_ec_op &unit, uint32_t u, 
     const Fr *rr = rec + ec_red_base(k, sg.red), *q = rr, *check = rr + k + 1, *negc = rr + 2 * k + 1;
     const Fr zero = Fr::zero(), one = Fr::one();
     const uint32_t i = sg.i;
-    TraceOut out;
-    out.cols = ec.cols;
-    out.bps = ec.bps;
-    out.last_col = ec.last_col;
-    range_seek(out, unit.column, unit.row, sg.off);
+    TraceOut out = trace_at(ec.tc, unit.column, unit.row, sg.off);
     switch (sg.type) {
     case EC_SUB:   // per cell of the registers: out = a - b, b, 1, a
         for (uint32_t j = 0; j <= k; ++j) {
@@ -680,12 +675,11 @@ inline const char *ec_prepare(const h2hip_fp_params &pr, uint32_t op, EcShape &s
         consts[ec_c_neg1(k)] = fcs[2 * k + 3];
         consts[ec_c_two(k)] = fe_add(Fr::one(), Fr::one());
         consts[ec_c_two(k) + 1] = fe_add(consts[ec_c_two(k)], Fr::one());
-        for (uint32_t r = 0; r < 3; ++r) consts[ec_c_rb(k, r)] = fp_pow2_mont(sh.rb[r]);
+        for (uint32_t r = 0; r < 3; ++r) consts[ec_c_rb(k, r)] = pow2_mont(sh.rb[r]);
     }
     if (ec) {
         ec->n = n;
         ec->k = k;
-        ec->nsegs = sh.nsegs;
         for (uint32_t j = 0; j < FP_P_WORDS; ++j) ec->p[j] = fc.p[j];
         for (uint32_t j = 0; j < FP_MU_WORDS; ++j) ec->mu[j] = fc.mu[j];
         for (int i = 0; i < 9; ++i) {

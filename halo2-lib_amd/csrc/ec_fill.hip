@@ -9,6 +9,7 @@
 // segment) writes a segment's cells through TraceOut from the record.  No LDS, no atomics, no workgroup waits for another.
 #include "internal.h"
 #include "ec_fill.cuh"
+#include "trace_host.h"
 
 namespace h2 {
 
@@ -57,25 +58,14 @@ int h2hip_ec_range_checks(const uint32_t *break_points_host, size_t num_columns,
     EcShape sh;
     const char *bad = ec_prepare(*params, op, sh, nullptr, nullptr);
     H2_REQUIRE(!bad, bad);
-    uint32_t width[EC_MAX_GAPS], group_of[EC_MAX_GAPS], gaps_in[EC_MAX_GAPS], lk_before[EC_MAX_GAPS], lk = 0;
+    // width group by width group; inside a group unit-major: rows and lookup slots ascend with the units
+    uint32_t width[EC_MAX_GAPS], group_of[EC_MAX_GAPS], gaps_in[EC_MAX_GAPS], rank[EC_MAX_GAPS], seen[EC_MAX_GAPS] = {0};
     const uint32_t ng = ec_width_groups(sh, width, group_of, gaps_in);
-    size_t start[EC_MAX_GAPS], next[EC_MAX_GAPS];
+    size_t start[EC_MAX_GAPS];
     for (uint32_t g = 0; g < ng; ++g) start[g] = g ? start[g - 1] + (size_t)gaps_in[g - 1] * count : 0;
-    for (uint32_t j = 0; j < sh.ngaps; ++j) {
-        lk_before[j] = lk;
-        lk += sh.gap_lookups[j];
-    }
-    for (uint32_t g = 0; g < ng; ++g) next[g] = start[g];
-    for (size_t u = 0; u < count; ++u)   // unit-major inside a width: rows and lookup slots ascend with the units
-        for (uint32_t j = 0; j < sh.ngaps; ++j) {
-            h2hip_range_check &c = checks_out[next[group_of[j]]++];
-            const int r = h2hip_trace_seek(break_points_host, num_columns, units_host[u].column, units_host[u].row, sh.gaps[j].cell_offset, &c.column, &c.row);
-            if (r != H2HIP_OK) return r;
-            c.a_offset = (uint64_t)u * ec_result_len(sh.k) + sh.gaps[j].result_index;
-            c.b_offset = 0;
-            c.lookup_slot = lookup_slots_host[u] + lk_before[j];
-        }
-    return H2HIP_OK;
+    for (uint32_t j = 0; j < sh.ngaps; ++j) rank[j] = seen[group_of[j]]++;
+    return fp_gap_checks(break_points_host, num_columns, sh.gaps, sh.gap_lookups, sh.ngaps, ec_result_len(sh.k), units_host, lookup_slots_host, count, checks_out,
+                         [&](size_t u, uint32_t j) { return start[group_of[j]] + u * gaps_in[group_of[j]] + rank[j]; });
 }
 
 int h2hip_ec_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const uint32_t *break_points_host,
@@ -91,59 +81,43 @@ int h2hip_ec_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_colum
     Fr consts[EC_CONSTS];
     const char *bad = ec_prepare(*params, op, sh, &ec, consts);
     H2_REQUIRE(!bad, bad);
-    const uint32_t k = sh.k, slots = sh.nsegs, cells = sh.total, k1 = k + 1, point = 2 * k1;
+    const uint32_t k = sh.k, slots = sh.nsegs, cells = sh.total, point = 2 * (k + 1);
     const bool two = op == H2HIP_EC_ADD_UNEQUAL;
     H2_REQUIRE(count <= ((uint64_t)1 << 32) / slots, "more than 2^32 slots (count * the unit's segments) in one call");
-    H2_REQUIRE(num_columns >= 1 && num_columns < 0xFFFFFFFFu, "num_columns out of range");
-    H2_REQUIRE(usable_rows <= 0xFFFFFFFFu, "usable_rows out of range");
+    TraceRuns runs{columns_dev, num_columns, usable_rows, break_points_host};
+    bad = runs.args_bad();
+    H2_REQUIRE(!bad, bad);
     H2_REQUIRE(values_len <= SIZE_MAX / sizeof(Fr) && results_len <= SIZE_MAX / sizeof(Fr), "values_len / results_len is no count of field elements");
-    if (break_points_host)
-        for (size_t c = 0; c + 1 < num_columns; ++c) H2_REQUIRE(break_points_host[c] < usable_rows, "a break point >= usable_rows");
     H2_REQUIRE(!results_dev || results_len / ec_result_len(k) >= count, "results_len < count * (9 num_limbs + 3)");
-    std::vector<ByteRange> written, reads;
-    written.reserve(count + 9);
+    std::vector<ByteRange> reads;
+    runs.written.reserve(count + 9);
     reads.reserve(2 * count);
     for (size_t j = 0; j < count; ++j) {
         const h2hip_ec_op &u = units_host[j];
-        H2_REQUIRE(u.column < num_columns && columns_dev[u.column], "a unit's column index is out of range (or the column is NULL)");
-        // the unit's whole run, gaps included, column by column, as the kernel's TraceOut walks it
-        const char *left = run_byte_ranges(columns_dev, num_columns, usable_rows, break_points_host, u.column, u.row, cells, written);
-        H2_REQUIRE(!left, left);
-        H2_REQUIRE(u.p_offset < values_len && point - 1 < values_len - u.p_offset && (!two || (u.q_offset < values_len && point - 1 < values_len - u.q_offset)),
+        bad = runs.run(u.column, u.row, cells);   // the unit's whole run, gaps included
+        H2_REQUIRE(!bad, bad);
+        H2_REQUIRE(operand_range(values_dev, values_len, u.p_offset, point - 1, reads) && (!two || operand_range(values_dev, values_len, u.q_offset, point - 1, reads)),
                    "a unit's operand lies outside values_len");
-        reads.push_back(ByteRange{(uintptr_t)values_dev + sizeof(Fr) * u.p_offset, (uintptr_t)values_dev + sizeof(Fr) * (u.p_offset + point)});
-        if (two) reads.push_back(ByteRange{(uintptr_t)values_dev + sizeof(Fr) * u.q_offset, (uintptr_t)values_dev + sizeof(Fr) * (u.q_offset + point)});
     }
     // two units' cells are disjoint; the results lie in none of them; no operand lies in anything written.  Address intervals, sorted and swept.
-    const char *clash = byte_ranges_clash(written, {}, "two units' cells overlap (break copies and the range checks' gaps included)");
-    H2_REQUIRE(!clash, clash);
-    if (results_dev) written.push_back(ByteRange{(uintptr_t)results_dev, (uintptr_t)results_dev + sizeof(Fr) * ec_result_len(k) * count});
-    clash = byte_ranges_clash(written, {&reads}, "the results overlap cells this call writes");
-    H2_REQUIRE(!clash, clash);
-    // ---- workspace: [unit table][column pointers][break points][constants][segments], and the records
-    const auto align = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t table_bytes = sizeof(h2hip_ec_op) * count, ptr_off = align(table_bytes), ptr_bytes = sizeof(void *) * num_columns;
-    const size_t bp_off = align(ptr_off + ptr_bytes), bp_bytes = break_points_host ? sizeof(uint32_t) * (num_columns - 1) : 0;
-    const size_t cs_off = align(bp_off + bp_bytes), cs_bytes = sizeof(Fr) * EC_CONSTS;
-    const size_t sg_off = align(cs_off + cs_bytes), sg_bytes = sizeof(EcSeg) * slots;
-    char *tabs = nullptr;
+    bad = byte_ranges_clash(runs.written, {}, "two units' cells overlap (break copies and the range checks' gaps included)");
+    H2_REQUIRE(!bad, bad);
+    if (results_dev) runs.written.push_back(ByteRange{(uintptr_t)results_dev, (uintptr_t)results_dev + sizeof(Fr) * ec_result_len(k) * count});
+    bad = byte_ranges_clash(runs.written, {&reads}, "the results overlap cells this call writes");
+    H2_REQUIRE(!bad, bad);
+    // ---- tables: [unit table][column pointers][break points][constants][segments], and the records
+    DevTables t;
     Fr *rec = nullptr;
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_TMP1, sg_off + sg_bytes, (void **)&tabs));
     H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_TMP2, sizeof(Fr) * ec_record_len(k) * count, (void **)&rec));
-    H2_CHK(upload_jobs(ctx, tabs, units_host, table_bytes));
-    H2_CHK(upload_jobs(ctx, tabs + ptr_off, columns_dev, ptr_bytes));
-    H2_CHK(upload_jobs(ctx, tabs + bp_off, break_points_host, bp_bytes));
-    H2_CHK(upload_jobs(ctx, tabs + cs_off, consts, cs_bytes));
-    H2_CHK(upload_jobs(ctx, tabs + sg_off, sh.segs, sg_bytes));
-    ec.cols = (Fr *const *)(tabs + ptr_off);
-    ec.bps = bp_bytes ? (const uint32_t *)(tabs + bp_off) : nullptr;
+    H2_CHK(pack_tables(ctx, {{units_host, sizeof(h2hip_ec_op) * count}, columns_table(runs), breaks_table(runs), {consts, sizeof(Fr) * EC_CONSTS},
+                             {sh.segs, sizeof(EcSeg) * slots}}, t));
+    ec.tc = t.tc;
     ec.values = (const Fr *)values_dev;
-    ec.consts = (const Fr *)(tabs + cs_off);
-    ec.segs = (const EcSeg *)(tabs + sg_off);
+    ec.consts = (const Fr *)t.at[3];
+    ec.segs = (const EcSeg *)t.at[4];
     ec.results = (Fr *)results_dev;
     ec.rec = rec;
-    ec.last_col = (uint32_t)(num_columns - 1);
-    const h2hip_ec_op *units = (const h2hip_ec_op *)tabs;
+    const h2hip_ec_op *units = (const h2hip_ec_op *)t.at[0];
     const dim3 solve_grid((uint32_t)((count + EC_SOLVE_BLOCK - 1) / EC_SOLVE_BLOCK)), solve_block(EC_SOLVE_BLOCK);
     prof_begin(ctx, "ec_solve_kernel");
     if (k == 3 && two)

@@ -4,7 +4,8 @@
 // in a loop on one host thread.  fp_prepare is what the host derives from h2hip_fp_params once per call.
 #pragma once
 #include "internal.h"
-#include "range_fill.cuh"   // TraceOut, range_seek, range_low_bits, range_unit_cells / range_unit_lookups
+#include "range_fill.cuh"   // range_low_bits, range_unit_cells / range_unit_lookups, pow2_mont
+#include "trace_place.cuh"
 
 namespace h2 {
 
@@ -20,11 +21,10 @@ constexpr uint32_t FP_NUM_BITS = 254, FP_CAPACITY = 253;   // F::NUM_BITS, F::CA
 
 // what one call's lanes share.  consts (canonical Montgomery Fr): [m_i, i < k][2^(n i), i < k][2^quot_last_limb_bits][2^rb][m_nat][-1]
 struct FpCall {
-    Fr *const *cols;
-    const uint32_t *bps;
+    TraceCols tc;
     const Fr *values, *consts;
     Fr *results, *rec;
-    uint32_t last_col, n, k;
+    uint32_t n, k;
     uint32_t gap_o, gap_ol, gap_q, gap_ql, gap_c;   // cells of the range checks of o_i (the last), q_i + B (the last), -c_i + 2^rb
     uint32_t p[FP_P_WORDS], mu[FP_MU_WORDS];        // wave-uniform: the modulus and its Barrett constant, 32-bit words
 };
@@ -296,12 +296,9 @@ H2_HD void fp_place_slot(const FpCall &fc, const h2hip_fp_mul &unit, uint32_t u,
     const Fr *q = rec, *o = rec + k, *negc = rec + 2 * k, *P = rec + 3 * k, *check = rec + 4 * k;
     const Fr zero = Fr::zero(), one = Fr::one();
     TraceOut out;
-    out.cols = fc.cols;
-    out.bps = fc.bps;
-    out.last_col = fc.last_col;
     if (slot < k) {   // ip(a_0 .. a_i; b_i .. b_0)
         const uint32_t i = slot;
-        range_seek(out, unit.column, unit.row, fp_tri(i) + 4 * i);
+        out = trace_at(fc.tc, unit.column, unit.row, fp_tri(i) + 4 * i);
         Fr acc = zero;
         out.put(acc);
         for (uint32_t j = 0; j <= i; ++j) {
@@ -312,18 +309,18 @@ H2_HD void fp_place_slot(const FpCall &fc, const h2hip_fp_mul &unit, uint32_t u,
             out.put(acc);
         }
     } else if (slot == k) {   // 0, a_nat, b_nat, N; and the three cells behind out_native: m_nat, quot_native, N
-        range_seek(out, unit.column, unit.row, lay.off2);
+        out = trace_at(fc.tc, unit.column, unit.row, lay.off2);
         out.put(zero);
         out.put(va[k]);
         out.put(vb[k]);
         out.put(rec[5 * k]);
-        range_seek(out, unit.column, unit.row, lay.off9);
+        out = trace_at(fc.tc, unit.column, unit.row, lay.off9);
         out.put(cs[2 * k + 2]);
         out.put(rec[5 * k + 1]);
         out.put(rec[5 * k]);
     } else if (slot <= 2 * k) {   // ip(q_0 .. q_i; m_i .. m_0), then -1, P_i, prod_i - P_i, 1, o_i, check_i
         const uint32_t i = slot - k - 1;
-        range_seek(out, unit.column, unit.row, lay.base3 + fp_tri(i) + 10 * i);
+        out = trace_at(fc.tc, unit.column, unit.row, lay.base3 + fp_tri(i) + 10 * i);
         Fr acc = zero;
         out.put(acc);
         for (uint32_t j = 0; j <= i; ++j) {
@@ -342,7 +339,7 @@ H2_HD void fp_place_slot(const FpCall &fc, const h2hip_fp_mul &unit, uint32_t u,
     } else if (slot <= 3 * k) {   // q_i, B, 1, q_i + B
         const uint32_t i = slot - 2 * k - 1;
         const Fr base = i == k - 1 ? cs[2 * k] : cs[k + 1];
-        range_seek(out, unit.column, unit.row, lay.base5 + i * (4 + fc.gap_q));
+        out = trace_at(fc.tc, unit.column, unit.row, lay.base5 + i * (4 + fc.gap_q));
         out.put(q[i]);
         out.put(base);
         out.put(one);
@@ -350,7 +347,7 @@ H2_HD void fp_place_slot(const FpCall &fc, const h2hip_fp_mul &unit, uint32_t u,
     } else if (slot <= 4 * k) {   // check_i, -c_i, 2^n, -c_{i-1}; -c_i, 2^rb, 1, -c_i + 2^rb
         const uint32_t i = slot - 3 * k - 1;
         const Fr nc = negc[i], shift = cs[2 * k + 1];
-        range_seek(out, unit.column, unit.row, lay.base6 + i * (8 + fc.gap_c));
+        out = trace_at(fc.tc, unit.column, unit.row, lay.base6 + i * (8 + fc.gap_c));
         out.put(check[i]);
         out.put(nc);
         out.put(cs[k + 1]);
@@ -363,7 +360,7 @@ H2_HD void fp_place_slot(const FpCall &fc, const h2hip_fp_mul &unit, uint32_t u,
         out.put(fe_add(nc, shift));
     } else {   // evaluate_native: x_0, x_1, 2^n, s_1, ... over q, then over o
         const Fr *x = slot == 4 * k + 1 ? q : o;
-        range_seek(out, unit.column, unit.row, slot == 4 * k + 1 ? lay.off7 : lay.off8);
+        out = trace_at(fc.tc, unit.column, unit.row, slot == 4 * k + 1 ? lay.off7 : lay.off8);
         Fr acc = x[0];
         out.put(acc);
         for (uint32_t j = 1; j < k; ++j) {
@@ -379,20 +376,17 @@ H2_HD void fp_place_slot(const FpCall &fc, const h2hip_fp_mul &unit, uint32_t u,
 // ---- what the host derives from the parameters, once per call (host only)
 struct FpShape {
     uint32_t n, k, lb, rb, out_last_bits, quot_last_bits;
-    uint32_t width[5];     // n, out_last_bits, n + 1, quot_last_bits + 1, rb + 1
-    uint32_t gap[5], lookups[5];
+    uint32_t gap[5];       // cells of a range check of n, out_last_bits, n + 1, quot_last_bits + 1, rb + 1 bits
     FpLayout lay;
+    // the 3 k gaps in context order (the lookup queue order): o_i (behind S3), q_i + B (behind its four cells), -c_i + 2^rb (behind its eight)
+    h2hip_fp_mul_range gaps[3 * FP_MAX_K];
+    uint32_t gap_lookups[3 * FP_MAX_K];
     size_t own, num_lookups;
 };
 inline uint32_t fp_words_bits(const uint32_t *w, int nw) {
     for (int j = nw - 1; j >= 0; --j)
         if (w[j]) return 32u * j + 32u - (uint32_t)__builtin_clz(w[j]);
     return 0;
-}
-inline Fr fp_pow2_mont(uint32_t e) {   // e <= 253
-    Fr r = Fr::zero();
-    r.l[e >> 5] = 1u << (e & 31);
-    return fe_to_mont(r);
 }
 // nullptr when the parameters are served, else the reason.  fc (optional): n, k, the gaps, p, mu; consts (optional): FP_CONSTS entries
 inline const char *fp_prepare(const h2hip_fp_params &pr, FpShape &sh, FpCall *fc, Fr *consts) {
@@ -437,29 +431,33 @@ inline const char *fp_prepare(const h2hip_fp_params &pr, FpShape &sh, FpCall *fc
     sh.quot_last_bits = quot_max_bits - n * (k - 1);
     const uint32_t a_max = log2_ceil + 2 * n, max_limb_bits = std::max(std::max(n, a_max) + 1, 2 * n + bit_len);
     sh.rb = (max_limb_bits - n + 1 + lb) / lb * lb - 1;
-    sh.width[0] = n;
-    sh.width[1] = sh.out_last_bits;
-    sh.width[2] = n + 1;
-    sh.width[3] = sh.quot_last_bits + 1;
-    sh.width[4] = sh.rb + 1;
+    const uint32_t width[5] = {n, sh.out_last_bits, n + 1, sh.quot_last_bits + 1, sh.rb + 1};
+    uint32_t lookups[5];
     for (int j = 0; j < 5; ++j) {
-        const uint32_t L = (sh.width[j] + lb - 1) / lb, rem = sh.width[j] % lb;
+        const uint32_t L = (width[j] + lb - 1) / lb, rem = width[j] % lb;
         if ((uint64_t)L * lb > FP_CAPACITY) return "the limbs of a range check take more than 253 bits (F::CAPACITY)";
         sh.gap[j] = range_unit_cells(L, rem, 0);
-        sh.lookups[j] = range_unit_lookups(L, rem);
+        lookups[j] = range_unit_lookups(L, rem);
     }
     sh.lay = fp_layout(k, sh.gap[0], sh.gap[1], sh.gap[2], sh.gap[3], sh.gap[4]);
     sh.own = 3 * k * k + 29 * k + 3;
-    sh.num_lookups = (size_t)(k - 1) * (sh.lookups[0] + sh.lookups[2]) + sh.lookups[1] + sh.lookups[3] + (size_t)k * sh.lookups[4];
+    sh.num_lookups = 0;
+    for (uint32_t j = 0; j < 3 * k; ++j) {
+        const uint32_t i = j % k, grp = j / k, w = 2 * grp + (grp < 2 && i == k - 1 ? 1 : 0);   // (the last o and the last q have a width of their own)
+        const uint32_t off = grp == 0 ? sh.lay.base4 + i * sh.gap[0] : grp == 1 ? sh.lay.base5 + i * (4 + sh.gap[2]) + 4 : sh.lay.base6 + i * (8 + sh.gap[4]) + 8;
+        sh.gaps[j] = h2hip_fp_mul_range{off, sh.gap[w], width[w], grp == 0 ? i : grp * k + 1 + i};
+        sh.gap_lookups[j] = lookups[w];
+        sh.num_lookups += lookups[w];
+    }
     if (consts) {
         Fr m_nat = Fr::zero();
         for (uint32_t i = 0; i < k; ++i) {
             consts[i] = m[i];
-            consts[k + i] = fp_pow2_mont(n * i);
+            consts[k + i] = pow2_mont(n * i);
             m_nat = fe_add(m_nat, fe_mul(m[i], consts[k + i]));
         }
-        consts[2 * k] = fp_pow2_mont(sh.quot_last_bits);
-        consts[2 * k + 1] = fp_pow2_mont(sh.rb);
+        consts[2 * k] = pow2_mont(sh.quot_last_bits);
+        consts[2 * k + 1] = pow2_mont(sh.rb);
         consts[2 * k + 2] = m_nat;
         consts[2 * k + 3] = fe_neg(Fr::one());
     }
@@ -493,6 +491,27 @@ inline const char *fp_prepare(const h2hip_fp_params &pr, FpShape &sh, FpCall *fc
         for (uint32_t j = 0; j < FP_MU_WORDS; ++j) fc->mu[j] = mu[j];
     }
     return nullptr;
+}
+
+// The h2hip_range_check of every gap of every unit (h2hip_fp_mul or h2hip_ec_op: column and row lead both), entry (u, j) written to
+// out[index(u, j)]: its first cell by h2hip_trace_seek's walk from the unit's first cell, its value at results entry u result_len +
+// result_index, its lookup cells behind those of the unit's gaps before it.  -> H2HIP_OK, or h2hip_trace_seek's refusal
+template <class Unit, class Index>
+inline int fp_gap_checks(const uint32_t *break_points, size_t num_columns, const h2hip_fp_mul_range *gaps, const uint32_t *gap_lookups, uint32_t ngaps,
+                         uint32_t result_len, const Unit *units, const uint64_t *lookup_slots, size_t count, h2hip_range_check *out, Index index) {
+    for (size_t u = 0; u < count; ++u) {
+        uint64_t slot = lookup_slots[u];
+        for (uint32_t j = 0; j < ngaps; ++j) {
+            h2hip_range_check &c = out[index(u, j)];
+            const int r = h2hip_trace_seek(break_points, num_columns, units[u].column, units[u].row, gaps[j].cell_offset, &c.column, &c.row);
+            if (r != H2HIP_OK) return r;
+            c.a_offset = (uint64_t)u * result_len + gaps[j].result_index;
+            c.b_offset = 0;
+            c.lookup_slot = slot;
+            slot += gap_lookups[j];
+        }
+    }
+    return H2HIP_OK;
 }
 
 }  // namespace h2

@@ -10,6 +10,7 @@
 // every tile); and the placement kernel, which adds a tile's incoming value to the positions whose chain began before the tile and writes
 // the a, b and s cells per piece form.  No workgroup waits for another; no atomics.
 #include "internal.h"
+#include "trace_host.h"   // ByteRange, pack_tables
 
 namespace h2 {
 
@@ -213,14 +214,12 @@ extern "C" int h2hip_gate_fill_chains_dev(h2hip_ctx *ctx, void *const *columns_d
     H2_REQUIRE(!clash, clash);
     const uint32_t ntiles = (uint32_t)((total + GATE_TILE - 1) / GATE_TILE);
     // ---- workspace: [piece table][column pointers] and [s][tile sums][tile cuts]
-    const size_t table_bytes = sizeof(GatePiece) * table.size(), ptr_off = (table_bytes + 255) / 256 * 256, ptr_bytes = sizeof(void *) * num_columns;
-    char *tabs = nullptr, *scan = nullptr;
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_TMP1, ptr_off + ptr_bytes, (void **)&tabs));
+    DevTables tabs;
+    char *scan = nullptr;
     const size_t s_bytes = sizeof(Fr) * (size_t)total, sum_bytes = sizeof(Fr) * (size_t)ntiles;
     H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_TMP0, s_bytes + sum_bytes + sizeof(uint32_t) * (size_t)ntiles, (void **)&scan));
-    H2_CHK(upload_jobs(ctx, tabs, table.data(), table_bytes));
-    H2_CHK(upload_jobs(ctx, tabs + ptr_off, columns_dev, ptr_bytes));
-    const GatePiece *t = (const GatePiece *)tabs;
+    H2_CHK(pack_tables(ctx, {{table.data(), sizeof(GatePiece) * table.size()}, {columns_dev, sizeof(void *) * num_columns, HostTable::COLUMNS}}, tabs));
+    const GatePiece *t = (const GatePiece *)tabs.at[0];
     Fr *s = (Fr *)scan, *tile_sum = (Fr *)(scan + s_bytes);
     uint32_t *tile_cut = (uint32_t *)(scan + s_bytes + sum_bytes);
     const uint32_t cnt = (uint32_t)count;
@@ -229,7 +228,7 @@ extern "C" int h2hip_gate_fill_chains_dev(h2hip_ctx *ctx, void *const *columns_d
     hipLaunchKernelGGL(gate_scan_sums_kernel, dim3(1), dim3(GATE_SUMS_LANES), 0, ctx->stream, tile_sum, (const uint32_t *)tile_cut, ntiles);
     prof_end(ctx);
     prof_begin(ctx, "gate_place_kernel");
-    hipLaunchKernelGGL(gate_place_kernel, dim3(grid_for(ctx, (size_t)total)), dim3(256), 0, ctx->stream, (Fr *const *)(tabs + ptr_off), (const Fr *)a_dev,
+    hipLaunchKernelGGL(gate_place_kernel, dim3(grid_for(ctx, (size_t)total)), dim3(256), 0, ctx->stream, tabs.tc.cols, (const Fr *)a_dev,
                        (const Fr *)b_dev, (const Fr *)s, (const Fr *)tile_sum, t, cnt, total);
     prof_end(ctx);
     H2_HIPCHK(hipGetLastError());

@@ -276,56 +276,6 @@ inline Fr ld_fr(const void *p) {   // a field element out of the caller's (possi
     memcpy(&r, p, sizeof(Fr));
     return r;
 }
-// Address intervals [lo, hi) of the fills that write cells from operands lying in the same columns (gate_chains.hip, poseidon_trace.hip): the
-// written intervals must be pairwise disjoint, and no operand interval (first to last address read, whatever the stride) may meet one.  Sorted
-// (a layout engine's pieces mostly arrive sorted) and swept; nullptr when all is well, else the reason.
-struct ByteRange {
-    uintptr_t lo, hi;
-    bool operator<(const ByteRange &o) const { return lo < o.lo; }
-};
-inline const char *byte_ranges_clash(std::vector<ByteRange> &written, std::initializer_list<std::vector<ByteRange> *> reads, const char *written_msg) {
-    auto sorted = [](std::vector<ByteRange> &v) {
-        if (!std::is_sorted(v.begin(), v.end())) std::sort(v.begin(), v.end());
-    };
-    sorted(written);
-    const size_t count = written.size();
-    for (size_t j = 1; j < count; ++j)
-        if (written[j - 1].hi > written[j].lo) return written_msg;
-    for (std::vector<ByteRange> *rd : reads) {
-        sorted(*rd);
-        size_t w = 0;
-        for (const ByteRange &r : *rd) {
-            while (w < count && written[w].hi <= r.lo) ++w;   // (the reads' starts ascend: what ends before this one ends before every later one)
-            if (w < count && written[w].lo < r.hi) return "an operand range overlaps cells this call writes";
-        }
-    }
-    return nullptr;
-}
-// The address intervals of a run of `cells` gate cells laid down from (column c, row r) as assign_witnesses does (threads/single_phase.rs:273-312),
-// appended to `written`: down the column; the cell written at the column's break point is written again at row 0 of the next column and the
-// run goes on at row 1 (the copy is never itself a break cell).  The host side of poseidon_trace.cuh's TraceOut (poseidon_trace.hip,
-// range_fill.hip).  nullptr when the run fits, else the reason.  break_points: num_columns - 1 entries, each checked < usable_rows by the caller, or NULL.
-inline const char *run_byte_ranges(void *const *columns_dev, size_t num_columns, size_t usable_rows, const uint32_t *break_points, size_t c, uint64_t r,
-                                   uint64_t cells, std::vector<ByteRange> &written) {
-    while (cells) {   // (zero only behind a break on the run's last cell)
-        if (r >= usable_rows) return "a unit's cells leave the usable rows";
-        const bool brk = break_points && c + 1 < num_columns && break_points[c] >= r;
-        const uint64_t room = brk ? break_points[c] - r + 1 : usable_rows - r, take = cells < room ? cells : room;
-        const uintptr_t w = (uintptr_t)columns_dev[c] + sizeof(Fr) * r;
-        written.push_back(ByteRange{w, w + sizeof(Fr) * (uintptr_t)take});
-        cells -= take;
-        if (!brk || take < room) {
-            if (cells) return break_points && c + 1 == num_columns ? "a unit's cells leave the last column" : "a unit's cells leave the usable rows";
-            break;
-        }
-        // the cell at the break point was written: it is written again at row 0 of the next column, and the run goes on at row 1
-        ++c;
-        if (!columns_dev[c]) return "a unit's column index is out of range (or the column is NULL)";
-        written.push_back(ByteRange{(uintptr_t)columns_dev[c], (uintptr_t)columns_dev[c] + sizeof(Fr)});
-        r = 1;
-    }
-    return nullptr;
-}
 struct OmegaTable;   // fr29.cuh
 int ntt_pow_table(h2hip_ctx *ctx, uint32_t log_n, const Fr &omega, OmegaTable *out);   // ntt.hip: the cached (log_n, omega) power table for pow_lookup
 

@@ -2,6 +2,7 @@
 // trace_unit in one lane per unit, tools/poseidon_host_fill.cpp in a loop on one host thread.
 #pragma once
 #include "internal.h"
+#include "trace_place.cuh"   // TraceOut: assign_witnesses' placement of a run of cells
 
 namespace h2 {
 
@@ -10,28 +11,6 @@ namespace h2 {
 struct PoseidonOptDev {
     const Fr *start, *partial, *end, *mds, *pre, *sparse, *init0;
     uint32_t half, r_p;
-};
-
-// Where a lane's next cell goes (assign_witnesses, threads/single_phase.rs:273-312): down the column; the cell written at the column's
-// break point is written again at row 0 of the next column and the run goes on at row 1.  `left` = cells up to and including the break
-// cell of this column (a unit has fewer than 2^31 cells: without a break ahead the count never reaches zero).
-struct TraceOut {
-    Fr *const *cols;
-    const uint32_t *bps;
-    Fr *p;
-    uint32_t col, last_col, left;
-    H2_HD void seek(uint32_t row) {
-        p = cols[col] + row;
-        left = (bps && col < last_col && bps[col] >= row) ? bps[col] - row + 1 : 0xFFFFFFFFu;
-    }
-    H2_HD void put(const Fr &v) {
-        *p++ = v;
-        if (--left == 0) {   // (the copy itself is never a break cell: assign_witnesses goes on at row 1 without looking)
-            ++col;
-            cols[col][0] = v;
-            seek(1);
-        }
-    }
 };
 
 // x^5 + c as x_power5_with_constant writes it (state.rs:97-106): | 0 x x x2 | 0 x2 x2 x4 | c x x4 x*x4+c |
@@ -144,15 +123,10 @@ H2_HD void trace_permutation(TraceOut &o, Fr (&s)[T], const Fr *x, uint32_t x_st
 
 // one unit: fix_len_array_squeeze over `len` inputs, from PoseidonState::default or unit u's row of states_in
 template <int T>
-H2_HD void trace_unit(Fr *const *cols, const uint32_t *bps, uint32_t last_col, const Fr *inputs, uint32_t len, const Fr *states_in, Fr *states_out,
-                      const h2hip_poseidon_hash &unit, uint32_t u, const PoseidonOptDev &sp) {
+H2_HD void trace_unit(const TraceCols &tc, const Fr *inputs, uint32_t len, const Fr *states_in, Fr *states_out, const h2hip_poseidon_hash &unit, uint32_t u,
+                      const PoseidonOptDev &sp) {
     constexpr uint32_t RATE = T - 1;
-    TraceOut o;
-    o.cols = cols;
-    o.bps = bps;
-    o.col = unit.column;
-    o.last_col = last_col;
-    o.seek(unit.row);
+    TraceOut o = trace_at(tc, unit.column, unit.row);
     Fr s[T];
     s[0] = *sp.init0;
     static_for<T - 1>([&](auto k) { s[k + 1] = Fr::zero(); });

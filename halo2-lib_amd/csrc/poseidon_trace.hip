@@ -10,6 +10,7 @@
 #include "internal.h"
 #include "host_field.h"
 #include "poseidon_trace.cuh"
+#include "trace_host.h"
 
 namespace h2 {
 
@@ -42,11 +43,10 @@ static inline uint64_t trace_unit_cells(uint32_t t, uint32_t r_f, uint32_t r_p, 
 
 // inputs / states_in may point into the columns (at cells this call does not write: the host checked)
 template <int T>
-__global__ __launch_bounds__(TRACE_BLOCK) void poseidon_trace_kernel(Fr *const *__restrict__ cols, const uint32_t *__restrict__ bps, uint32_t last_col,
-                                                                     const Fr *inputs, uint32_t len, const Fr *states_in, Fr *states_out,
+__global__ __launch_bounds__(TRACE_BLOCK) void poseidon_trace_kernel(TraceCols tc, const Fr *inputs, uint32_t len, const Fr *states_in, Fr *states_out,
                                                                      const h2hip_poseidon_hash *__restrict__ units, uint32_t count, PoseidonOptDev sp) {
     const uint32_t u = blockIdx.x * TRACE_BLOCK + threadIdx.x;
-    if (u < count) trace_unit<T>(cols, bps, last_col, inputs, len, states_in, states_out, units[u], u, sp);
+    if (u < count) trace_unit<T>(tc, inputs, len, states_in, states_out, units[u], u, sp);
 }
 
 // ------------------------------------------------------------------ the optimised spec (host)
@@ -263,43 +263,34 @@ int h2hip_poseidon_fill_hashes_dev(h2hip_ctx *ctx, void *const *columns_dev, siz
     if (!count) return H2HIP_OK;
     // ---- every check before anything is launched or uploaded
     H2_REQUIRE(ctx->popt_t != 0, "no optimised spec set: call h2hip_poseidon_set_optimized_spec first");
-    H2_REQUIRE(num_columns >= 1 && num_columns < 0xFFFFFFFFu, "num_columns out of range");
+    TraceRuns runs{columns_dev, num_columns, usable_rows, break_points_host};
+    const char *bad = runs.args_bad(SIZE_MAX);   // (this fill has never bounded usable_rows: its rows are the units' own)
+    H2_REQUIRE(!bad, bad);
     H2_REQUIRE(inputs_len <= SIZE_MAX / sizeof(Fr), "inputs_len is no count of field elements");
     const uint32_t t = ctx->popt_t, r_f = ctx->popt_rf, r_p = ctx->popt_rp;
-    if (break_points_host)
-        for (size_t c = 0; c + 1 < num_columns; ++c) H2_REQUIRE(break_points_host[c] < usable_rows, "a break point >= usable_rows");
-    std::vector<ByteRange> written, in_reads, st_reads;
-    written.reserve(count + 8);
+    std::vector<ByteRange> in_reads, st_reads;
+    runs.written.reserve(count + 8);
     in_reads.reserve(count);
     for (size_t j = 0; j < count; ++j) {
         const h2hip_poseidon_hash &h = hashes_host[j];
         H2_REQUIRE((h.flags & ~TRACE_FLAGS) == 0, "unknown flags");
         H2_REQUIRE(trace_perms(t, len, h.flags) >= 1, "a unit without a permutation (len == 0 with ABSORB_ONLY)");
-        H2_REQUIRE(h.column < num_columns && columns_dev[h.column], "a unit's column index is out of range (or the column is NULL)");
-        uint64_t cells = trace_unit_cells(t, r_f, r_p, len, h.flags);
+        const uint64_t cells = trace_unit_cells(t, r_f, r_p, len, h.flags);
         H2_REQUIRE(cells < ((uint64_t)1 << 31), "a unit of 2^31 cells or more");
-        // the unit's run, column by column, as the kernel's TraceOut walks it
-        const char *left = run_byte_ranges(columns_dev, num_columns, usable_rows, break_points_host, h.column, h.row, cells, written);
-        H2_REQUIRE(!left, left);
-        if (len) {   // input indices in 64 bits: (len - 1) * stride < 2^64, and the sum is checked against inputs_len without wrapping
-            const uint64_t span = (uint64_t)(len - 1) * h.input_stride;
-            H2_REQUIRE(h.input_offset < inputs_len && span < inputs_len - h.input_offset, "a unit's inputs lie outside inputs_len");
-            in_reads.push_back(ByteRange{(uintptr_t)inputs_dev + sizeof(Fr) * h.input_offset, (uintptr_t)inputs_dev + sizeof(Fr) * (h.input_offset + span + 1)});
-        }
+        bad = runs.run(h.column, h.row, cells);
+        H2_REQUIRE(!bad, bad);
+        // input indices in 64 bits: (len - 1) * stride < 2^64, and the sum is checked against inputs_len without wrapping
+        H2_REQUIRE(!len || operand_range(inputs_dev, inputs_len, h.input_offset, (uint64_t)(len - 1) * h.input_stride, in_reads),
+                   "a unit's inputs lie outside inputs_len");
     }
     const size_t st_bytes = sizeof(Fr) * count * t;
-    if (states_out_dev) written.push_back(ByteRange{(uintptr_t)states_out_dev, (uintptr_t)states_out_dev + st_bytes});
+    if (states_out_dev) runs.written.push_back(ByteRange{(uintptr_t)states_out_dev, (uintptr_t)states_out_dev + st_bytes});
     if (states_in_dev) st_reads.push_back(ByteRange{(uintptr_t)states_in_dev, (uintptr_t)states_in_dev + st_bytes});
-    const char *clash = byte_ranges_clash(written, {&in_reads, &st_reads}, "two units' cells overlap (or a unit's cells and states_out_dev)");
-    H2_REQUIRE(!clash, clash);
-    // ---- workspace: [unit table][column pointers][break points]
-    const size_t table_bytes = sizeof(h2hip_poseidon_hash) * count, ptr_off = (table_bytes + 255) / 256 * 256, ptr_bytes = sizeof(void *) * num_columns;
-    const size_t bp_off = (ptr_off + ptr_bytes + 255) / 256 * 256, bp_bytes = break_points_host ? sizeof(uint32_t) * (num_columns - 1) : 0;
-    char *tabs = nullptr;
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_TMP1, bp_off + bp_bytes, (void **)&tabs));
-    H2_CHK(upload_jobs(ctx, tabs, hashes_host, table_bytes));
-    H2_CHK(upload_jobs(ctx, tabs + ptr_off, columns_dev, ptr_bytes));
-    H2_CHK(upload_jobs(ctx, tabs + bp_off, break_points_host, bp_bytes));
+    bad = byte_ranges_clash(runs.written, {&in_reads, &st_reads}, "two units' cells overlap (or a unit's cells and states_out_dev)");
+    H2_REQUIRE(!bad, bad);
+    // ---- tables: [unit table][column pointers][break points]
+    DevTables tabs;
+    H2_CHK(pack_tables(ctx, {{hashes_host, sizeof(h2hip_poseidon_hash) * count}, columns_table(runs), breaks_table(runs)}, tabs));
     const Fr *base = (const Fr *)ctx->ws[h2hip_ctx::WS_POSEIDON_OPT].p;
     const uint32_t half = r_f / 2;
     PoseidonOptDev sp;
@@ -312,15 +303,14 @@ int h2hip_poseidon_fill_hashes_dev(h2hip_ctx *ctx, void *const *columns_dev, siz
     sp.init0 = sp.sparse + (size_t)r_p * (2 * t - 1);
     sp.half = half;
     sp.r_p = r_p;
-    const uint32_t *bps = bp_bytes ? (const uint32_t *)(tabs + bp_off) : nullptr;
     const dim3 grid((uint32_t)((count + TRACE_BLOCK - 1) / TRACE_BLOCK)), blk(TRACE_BLOCK);
     prof_begin(ctx, "poseidon_trace_kernel");
     if (t == 3)
-        hipLaunchKernelGGL(poseidon_trace_kernel<3>, grid, blk, 0, ctx->stream, (Fr *const *)(tabs + ptr_off), bps, (uint32_t)(num_columns - 1), (const Fr *)inputs_dev,
-                           len, (const Fr *)states_in_dev, (Fr *)states_out_dev, (const h2hip_poseidon_hash *)tabs, (uint32_t)count, sp);
+        hipLaunchKernelGGL(poseidon_trace_kernel<3>, grid, blk, 0, ctx->stream, tabs.tc, (const Fr *)inputs_dev, len, (const Fr *)states_in_dev,
+                           (Fr *)states_out_dev, (const h2hip_poseidon_hash *)tabs.at[0], (uint32_t)count, sp);
     else
-        hipLaunchKernelGGL(poseidon_trace_kernel<5>, grid, blk, 0, ctx->stream, (Fr *const *)(tabs + ptr_off), bps, (uint32_t)(num_columns - 1), (const Fr *)inputs_dev,
-                           len, (const Fr *)states_in_dev, (Fr *)states_out_dev, (const h2hip_poseidon_hash *)tabs, (uint32_t)count, sp);
+        hipLaunchKernelGGL(poseidon_trace_kernel<5>, grid, blk, 0, ctx->stream, tabs.tc, (const Fr *)inputs_dev, len, (const Fr *)states_in_dev,
+                           (Fr *)states_out_dev, (const h2hip_poseidon_hash *)tabs.at[0], (uint32_t)count, sp);
     prof_end(ctx);
     H2_HIPCHK(hipGetLastError());
     return H2HIP_OK;

@@ -2,19 +2,19 @@
 // range_slot in one lane per (unit, slot), tools/range_host_fill.cpp in a loop on one host thread.
 #pragma once
 #include "internal.h"
-#include "poseidon_trace.cuh"   // TraceOut: assign_witnesses' placement of a run of cells
+#include "trace_place.cuh"   // TraceOut: assign_witnesses' placement of a run of cells
 
 namespace h2 {
 
-constexpr uint32_t RANGE_PREFIX = 7;   // the cells of check_less_than / is_less_than in front of the range check
+constexpr uint32_t RANGE_PREFIX = 7;       // the cells of check_less_than / is_less_than in front of the range check
+constexpr uint32_t RANGE_CAPACITY = 253;   // F::CAPACITY: 2^253 < r
 
 // what one call's lanes share.  pows: [2^(i lb), i < L][2^(lb - rem)][2^shift_bits][-2^shift_bits], canonical Montgomery Fr
 struct RangeCall {
-    Fr *const *cols;
-    const uint32_t *bps;
+    TraceCols tc;
     Fr *const *lk_cols;
     const Fr *values, *pows;
-    uint32_t last_col, num_lk_cols, L, lb, rem, prefix;   // prefix: RANGE_PREFIX with H2HIP_RANGE_LESS_THAN, else 0
+    uint32_t num_lk_cols, L, lb, rem, prefix;   // prefix: RANGE_PREFIX with H2HIP_RANGE_LESS_THAN, else 0
 };
 
 // cells of one unit: the prefix, l_0 l_1 2^lb s_1 ... (3 L - 2, only for L >= 2), the tail gate (4, only for rem >= 1)
@@ -51,19 +51,6 @@ H2_HD Fr range_from_u64(uint64_t x) {
     return fe_to_mont(r);
 }
 
-// where cell `off` of the run that starts at (col, row) goes: TraceOut's walk, whole columns at a time
-H2_HD void range_seek(TraceOut &o, uint32_t col, uint32_t row, uint32_t off) {
-    o.col = col;
-    for (;;) {
-        o.seek(row);
-        if (off < o.left) break;   // (left = 2^32 - 1 without a break ahead; a unit has fewer than 2^31 cells)
-        off -= o.left;
-        ++o.col;
-        row = 1;
-    }
-    o.p += off;
-    if (o.left != 0xFFFFFFFFu) o.left -= off;
-}
 // lookup cell j of the unit: queue position p = lookup_slot + j lies in column p mod num_lk_cols at row p / num_lk_cols (assign_raw, lookups.rs:129-156)
 H2_HD void range_lookup_put(const RangeCall &rc, const h2hip_range_check &unit, uint32_t j, const Fr &v) {
     const uint64_t p = unit.lookup_slot + j;
@@ -80,16 +67,11 @@ H2_HD void range_slot(const RangeCall &rc, const h2hip_range_check &unit, uint32
         shifted = fe_add(a, rc.pows[L + 1]);
         v = fe_sub(shifted, b);
     }
-    TraceOut o;
-    o.cols = rc.cols;
-    o.bps = rc.bps;
-    o.last_col = rc.last_col;
     if (slot == 0) {
         Fr l0 = v;
         if (L >= 2) l0 = range_from_u64(range_bits_at(fe_from_mont(v), 0, lb));
         if (rc.prefix || L >= 2) {
-            o.col = unit.column;
-            o.seek(unit.row);
+            TraceOut o = trace_at(rc.tc, unit.column, unit.row);
             if (rc.prefix) {
                 const Fr one = Fr::one();
                 o.put(v);
@@ -106,14 +88,14 @@ H2_HD void range_slot(const RangeCall &rc, const h2hip_range_check &unit, uint32
     } else if (slot < L) {
         const Fr c = fe_from_mont(v);
         const Fr li = range_from_u64(range_bits_at(c, slot * lb, lb)), si = fe_to_mont(range_low_bits(c, (slot + 1) * lb));
-        range_seek(o, unit.column, unit.row, rc.prefix + 1 + 3 * (slot - 1));
+        TraceOut o = trace_at(rc.tc, unit.column, unit.row, rc.prefix + 1 + 3 * (slot - 1));
         o.put(li);
         o.put(rc.pows[slot]);
         o.put(si);
         range_lookup_put(rc, unit, slot, li);
     } else {   // rem >= 1
         const Fr x = L >= 2 ? range_from_u64(range_bits_at(fe_from_mont(v), (L - 1) * lb, lb)) : v;
-        range_seek(o, unit.column, unit.row, rc.prefix + range_decomp_cells(L));
+        TraceOut o = trace_at(rc.tc, unit.column, unit.row, rc.prefix + range_decomp_cells(L));
         o.put(Fr::zero());
         o.put(x);
         if (rc.rem == 1) {   // assert_bit: | 0 | x | x | x |
@@ -126,6 +108,36 @@ H2_HD void range_slot(const RangeCall &rc, const h2hip_range_check &unit, uint32
             range_lookup_put(rc, unit, L, prod);
         }
     }
+}
+
+// ---- what the host derives from the parameters, once per call (host only)
+inline Fr pow2_mont(uint32_t e) {   // e <= RANGE_CAPACITY
+    Fr r = Fr::zero();
+    r.l[e >> 5] = 1u << (e & 31);
+    return fe_to_mont(r);
+}
+// nullptr when the parameters are served, else the reason.  rc: L, lb, rem, prefix; pows (optional): the table, and rc.pows points at it (a
+// device call uploads it and points rc.pows at the copy)
+inline const char *range_prepare(uint32_t range_bits, uint32_t lookup_bits, uint32_t shift_bits, uint32_t flags, RangeCall &rc, std::vector<Fr> *pows) {
+    if (flags & ~(uint32_t)H2HIP_RANGE_LESS_THAN) return "unknown flags";
+    if (range_bits == 0) return "range_bits == 0 (a constant check, not a range check)";
+    if (lookup_bits < 1 || lookup_bits > 63) return "lookup_bits outside 1 .. 63";
+    if (((uint64_t)range_bits + lookup_bits - 1) / lookup_bits * lookup_bits > RANGE_CAPACITY) return "the limbs take more than 253 bits (F::CAPACITY)";
+    if ((flags & H2HIP_RANGE_LESS_THAN) && shift_bits > RANGE_CAPACITY) return "shift_bits above 253 (F::CAPACITY)";
+    const uint32_t L = (range_bits + lookup_bits - 1) / lookup_bits, rem = range_bits % lookup_bits;
+    rc.L = L;
+    rc.lb = lookup_bits;
+    rc.rem = rem;
+    rc.prefix = (flags & H2HIP_RANGE_LESS_THAN) ? RANGE_PREFIX : 0;
+    if (pows) {
+        pows->resize(L + 3);
+        for (uint32_t i = 0; i < L; ++i) (*pows)[i] = pow2_mont(i * lookup_bits);
+        (*pows)[L] = pow2_mont(rem ? lookup_bits - rem : 0);
+        (*pows)[L + 1] = pow2_mont(rc.prefix ? shift_bits : 0);
+        (*pows)[L + 2] = fe_neg((*pows)[L + 1]);
+        rc.pows = pows->data();
+    }
+    return nullptr;
 }
 
 }  // namespace h2

@@ -10,11 +10,11 @@
 // fe_to_mont, the constant from the uploaded power table, 32-byte stores.  No LDS, no atomics, no workgroup waits for another.
 #include "internal.h"
 #include "range_fill.cuh"
+#include "trace_host.h"
 
 namespace h2 {
 
 constexpr uint32_t RANGE_BLOCK = 256;
-constexpr uint32_t RANGE_CAPACITY = 253;   // F::CAPACITY: 2^253 < r
 
 static_assert(sizeof(h2hip_range_check) == 32, "the unit table is uploaded as the caller laid it out");
 
@@ -26,20 +26,6 @@ __global__ __launch_bounds__(RANGE_BLOCK) void range_fill_kernel(RangeCall rc, c
     range_slot(rc, units[u], (uint32_t)(g - (uint64_t)u * slots));
 }
 
-static Fr pow2_mont(uint32_t e) {   // e <= RANGE_CAPACITY
-    Fr r = Fr::zero();
-    r.l[e >> 5] = 1u << (e & 31);
-    return fe_to_mont(r);
-}
-static const char *range_params_bad(uint32_t range_bits, uint32_t lookup_bits, uint32_t shift_bits, uint32_t flags) {
-    if (flags & ~(uint32_t)H2HIP_RANGE_LESS_THAN) return "unknown flags";
-    if (range_bits == 0) return "range_bits == 0 (a constant check, not a range check)";
-    if (lookup_bits < 1 || lookup_bits > 63) return "lookup_bits outside 1 .. 63";
-    if (((uint64_t)range_bits + lookup_bits - 1) / lookup_bits * lookup_bits > RANGE_CAPACITY) return "the limbs take more than 253 bits (F::CAPACITY)";
-    if ((flags & H2HIP_RANGE_LESS_THAN) && shift_bits > RANGE_CAPACITY) return "shift_bits above 253 (F::CAPACITY)";
-    return nullptr;
-}
-
 }  // namespace h2
 
 using namespace h2;
@@ -48,9 +34,10 @@ extern "C" {
 
 int h2hip_range_check_layout(uint32_t range_bits, uint32_t lookup_bits, uint32_t flags, size_t *num_cells, size_t *num_lookup_cells, uint32_t *last_limb_offset) {
     H2_REQUIRE(num_cells && num_lookup_cells && last_limb_offset, "NULL argument");
-    const char *bad = range_params_bad(range_bits, lookup_bits, 0, flags);
+    RangeCall rc;
+    const char *bad = range_prepare(range_bits, lookup_bits, 0, flags, rc, nullptr);
     H2_REQUIRE(!bad, bad);
-    const uint32_t L = (range_bits + lookup_bits - 1) / lookup_bits, rem = range_bits % lookup_bits, prefix = (flags & H2HIP_RANGE_LESS_THAN) ? RANGE_PREFIX : 0;
+    const uint32_t L = rc.L, rem = rc.rem, prefix = rc.prefix;
     *num_cells = range_unit_cells(L, rem, prefix);
     *num_lookup_cells = range_unit_lookups(L, rem);
     // the last limb: l_{L-1} of the decomposition; with L = 1 the checked cell itself, which the unit writes only as the prefix's first cell
@@ -66,37 +53,37 @@ int h2hip_range_fill_checks_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t
     if (!count) return H2HIP_OK;
     // ---- every check before anything is launched or uploaded
     H2_REQUIRE(checks_host && lookup_columns_dev && values_dev, "NULL argument");
-    const char *bad = range_params_bad(range_bits, lookup_bits, shift_bits, flags);
+    RangeCall rc;
+    std::vector<Fr> pows;
+    const char *bad = range_prepare(range_bits, lookup_bits, shift_bits, flags, rc, &pows);
     H2_REQUIRE(!bad, bad);
-    const uint32_t L = (range_bits + lookup_bits - 1) / lookup_bits, rem = range_bits % lookup_bits, prefix = (flags & H2HIP_RANGE_LESS_THAN) ? RANGE_PREFIX : 0;
+    const uint32_t L = rc.L, rem = rc.rem, prefix = rc.prefix;
     const uint32_t cells = range_unit_cells(L, rem, prefix), nlk = range_unit_lookups(L, rem), slots = range_unit_slots(L, rem);
     H2_REQUIRE(count <= ((uint64_t)1 << 32) / (L + 1), "more than 2^32 slots (count * (limbs + 1)) in one call");
     H2_REQUIRE(num_lookup_columns >= 1 && num_lookup_columns < 0xFFFFFFFFu, "num_lookup_columns out of range (no lookup column)");
     for (size_t c = 0; c < num_lookup_columns; ++c) H2_REQUIRE(lookup_columns_dev[c], "a NULL lookup column");
     H2_REQUIRE(usable_rows <= 0xFFFFFFFFu, "usable_rows out of range");
     H2_REQUIRE(values_len <= SIZE_MAX / sizeof(Fr), "values_len is no count of field elements");
+    // (a unit of one limb without the prefix has no gate cell: such a call has no gate columns)
+    TraceRuns gates{columns_dev, cells ? num_columns : 0, usable_rows, cells ? break_points_host : nullptr};
     if (cells) {
         H2_REQUIRE(columns_dev, "NULL argument");
-        H2_REQUIRE(num_columns >= 1 && num_columns < 0xFFFFFFFFu, "num_columns out of range");
-        if (break_points_host)
-            for (size_t c = 0; c + 1 < num_columns; ++c) H2_REQUIRE(break_points_host[c] < usable_rows, "a break point >= usable_rows");
+        bad = gates.args_bad();
+        H2_REQUIRE(!bad, bad);
     }
     const uint64_t lk_room = (uint64_t)usable_rows * num_lookup_columns;   // queue positions whose row is usable
-    std::vector<ByteRange> gates, reads;
+    std::vector<ByteRange> reads;
     std::vector<uint64_t> lk_slots(count);
-    gates.reserve(cells ? count + 8 : 0);
+    gates.written.reserve(cells ? count + 8 : 0);
     reads.reserve(prefix ? 2 * count : count);
     for (size_t j = 0; j < count; ++j) {
         const h2hip_range_check &u = checks_host[j];
         if (cells) {
-            H2_REQUIRE(u.column < num_columns && columns_dev[u.column], "a unit's column index is out of range (or the column is NULL)");
-            // the unit's run, column by column, as the kernel's TraceOut walks it
-            const char *left = run_byte_ranges(columns_dev, num_columns, usable_rows, break_points_host, u.column, u.row, cells, gates);
-            H2_REQUIRE(!left, left);
+            bad = gates.run(u.column, u.row, cells);
+            H2_REQUIRE(!bad, bad);
         }
-        H2_REQUIRE(u.a_offset < values_len && (!prefix || u.b_offset < values_len), "a unit's operand lies outside values_len");
-        reads.push_back(ByteRange{(uintptr_t)values_dev + sizeof(Fr) * u.a_offset, (uintptr_t)values_dev + sizeof(Fr) * (u.a_offset + 1)});
-        if (prefix) reads.push_back(ByteRange{(uintptr_t)values_dev + sizeof(Fr) * u.b_offset, (uintptr_t)values_dev + sizeof(Fr) * (u.b_offset + 1)});
+        H2_REQUIRE(operand_range(values_dev, values_len, u.a_offset, 0, reads) && (!prefix || operand_range(values_dev, values_len, u.b_offset, 0, reads)),
+                   "a unit's operand lies outside values_len");
         H2_REQUIRE(u.lookup_slot < lk_room && nlk <= lk_room - u.lookup_slot, "a unit's lookup cells leave the usable rows");
         lk_slots[j] = u.lookup_slot;
     }
@@ -106,10 +93,10 @@ int h2hip_range_fill_checks_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t
     // the gate cells of two units are disjoint; then no gate cell lies where a lookup cell does (a unit's positions in one lookup column are
     // one run of rows; runs of units sorted by slot ascend in every column); then no operand lies in anything written.  Address intervals,
     // sorted and swept.
-    const char *clash = byte_ranges_clash(gates, {}, "two units' gate cells overlap (break copies included)");
-    H2_REQUIRE(!clash, clash);
+    bad = byte_ranges_clash(gates.written, {}, "two units' gate cells overlap (break copies included)");
+    H2_REQUIRE(!bad, bad);
     std::vector<ByteRange> written;
-    written.reserve(gates.size() + count * (nlk < num_lookup_columns ? nlk : num_lookup_columns));
+    written.reserve(gates.written.size() + count * (nlk < num_lookup_columns ? nlk : num_lookup_columns));
     for (size_t c = 0; c < num_lookup_columns; ++c)
         for (size_t j = 0; j < count; ++j) {
             const uint64_t p = lk_slots[j], first = p + (c + num_lookup_columns - p % num_lookup_columns) % num_lookup_columns;
@@ -117,44 +104,22 @@ int h2hip_range_fill_checks_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t
             const uint64_t r0 = first / num_lookup_columns, r1 = (p + nlk - 1 - c) / num_lookup_columns;
             written.push_back(ByteRange{(uintptr_t)lookup_columns_dev[c] + sizeof(Fr) * r0, (uintptr_t)lookup_columns_dev[c] + sizeof(Fr) * (r1 + 1)});
         }
-    written.insert(written.end(), gates.begin(), gates.end());
-    clash = byte_ranges_clash(written, {&reads}, "a gate cell and a lookup cell of the call at one address (or two lookup columns overlap)");
-    H2_REQUIRE(!clash, clash);
-    // ---- workspace: [unit table][gate column pointers][lookup column pointers][break points][powers]
-    const auto align = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t ncols = cells ? num_columns : 0;
-    const size_t table_bytes = sizeof(h2hip_range_check) * count, ptr_off = align(table_bytes), ptr_bytes = sizeof(void *) * ncols;
-    const size_t lk_off = align(ptr_off + ptr_bytes), lk_bytes = sizeof(void *) * num_lookup_columns;
-    const size_t bp_off = align(lk_off + lk_bytes), bp_bytes = (cells && break_points_host) ? sizeof(uint32_t) * (num_columns - 1) : 0;
-    const size_t pow_off = align(bp_off + bp_bytes), pow_bytes = sizeof(Fr) * (L + 3);
-    std::vector<Fr> pows(L + 3);
-    for (uint32_t i = 0; i < L; ++i) pows[i] = pow2_mont(i * lookup_bits);
-    pows[L] = pow2_mont(rem ? lookup_bits - rem : 0);
-    pows[L + 1] = pow2_mont(prefix ? shift_bits : 0);
-    pows[L + 2] = fe_neg(pows[L + 1]);
-    char *tabs = nullptr;
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_TMP1, pow_off + pow_bytes, (void **)&tabs));
-    H2_CHK(upload_jobs(ctx, tabs, checks_host, table_bytes));
-    H2_CHK(upload_jobs(ctx, tabs + ptr_off, columns_dev, ptr_bytes));
-    H2_CHK(upload_jobs(ctx, tabs + lk_off, lookup_columns_dev, lk_bytes));
-    H2_CHK(upload_jobs(ctx, tabs + bp_off, break_points_host, bp_bytes));
-    H2_CHK(upload_jobs(ctx, tabs + pow_off, pows.data(), pow_bytes));
-    RangeCall rc;
-    rc.cols = (Fr *const *)(tabs + ptr_off);
-    rc.bps = bp_bytes ? (const uint32_t *)(tabs + bp_off) : nullptr;
-    rc.lk_cols = (Fr *const *)(tabs + lk_off);
+    written.insert(written.end(), gates.written.begin(), gates.written.end());
+    bad = byte_ranges_clash(written, {&reads}, "a gate cell and a lookup cell of the call at one address (or two lookup columns overlap)");
+    H2_REQUIRE(!bad, bad);
+    // ---- tables: [unit table][gate column pointers][lookup column pointers][break points][powers]
+    DevTables t;
+    H2_CHK(pack_tables(ctx, {{checks_host, sizeof(h2hip_range_check) * count}, columns_table(gates), {lookup_columns_dev, sizeof(void *) * num_lookup_columns},
+                             breaks_table(gates), {pows.data(), sizeof(Fr) * pows.size()}}, t));
+    rc.tc = t.tc;
+    rc.lk_cols = (Fr *const *)t.at[2];
     rc.values = (const Fr *)values_dev;
-    rc.pows = (const Fr *)(tabs + pow_off);
-    rc.last_col = ncols ? (uint32_t)(ncols - 1) : 0;
+    rc.pows = (const Fr *)t.at[4];
     rc.num_lk_cols = (uint32_t)num_lookup_columns;
-    rc.L = L;
-    rc.lb = lookup_bits;
-    rc.rem = rem;
-    rc.prefix = prefix;
     const uint64_t lanes = (uint64_t)count * slots;
     prof_begin(ctx, "range_fill_kernel");
     hipLaunchKernelGGL(range_fill_kernel, dim3((uint32_t)((lanes + RANGE_BLOCK - 1) / RANGE_BLOCK)), dim3(RANGE_BLOCK), 0, ctx->stream, rc,
-                       (const h2hip_range_check *)tabs, slots, lanes);
+                       (const h2hip_range_check *)t.at[0], slots, lanes);
     prof_end(ctx);
     H2_HIPCHK(hipGetLastError());
     return H2HIP_OK;

@@ -738,6 +738,39 @@ def assert_satisfied(pk: ProvingKey, advice: Sequence, instances: Sequence[np.nd
         raise AssertionError("witness not satisfied: %d failure%s\n" % (total, "" if total == 1 else "s") + "\n".join(map(str, fails)) + more)
 
 
+# ---- argument marshalling of the device fills
+def _col_array(columns: Sequence) -> C.Array:
+    """the column pointer array of a fill (a missing column as NULL)"""
+    return (_vp * max(len(columns), 1))(*[_vp(int(p)) if p else None for p in columns])
+
+
+def _bp_array(break_points: Optional[Sequence[int]], num_columns: int):
+    if break_points is None:
+        return None
+    assert len(break_points) == num_columns - 1, "one break point per column but the last"
+    return (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
+
+
+def _dev_ptr(x):
+    """a device pointer (or an object with data_ptr()) as c_void_p, None / 0 as NULL"""
+    v = int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x or 0)
+    return _vp(v) if v else None
+
+
+def _as_table(units, build) -> C.Array:
+    return units if isinstance(units, C.Array) else build(units)
+
+
+def _struct_table(struct, units: Sequence) -> C.Array:
+    return (struct * max(len(units), 1))(*[struct(*[int(x) for x in u]) for u in units])
+
+
+def _raise_on(code: int, lib) -> None:
+    """the raise of a library call made without a context"""
+    if code != 0:
+        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+
+
 class RlcChainStruct(C.Structure):   # h2hip_rlc_chain
     _fields_ = [("column", C.c_uint32), ("row", C.c_uint32), ("len", C.c_uint32), ("flags", C.c_uint32), ("value_offset", C.c_uint64)]
 
@@ -752,11 +785,8 @@ def rlc_fill_chains(ctx: Context, columns: Sequence[int], usable_rows: int, valu
     an object with data_ptr() / nbytes (a torch tensor of Montgomery limbs).  gamma: an int.  Stream-ordered on the context's stream."""
     if num_values is None:
         num_values = int(values_dev.numel() * values_dev.element_size()) // 32
-    vptr = int(values_dev.data_ptr()) if hasattr(values_dev, "data_ptr") else int(values_dev)
-    arr = (RlcChainStruct * max(len(chains), 1))(*[RlcChainStruct(int(c[0]), int(c[1]), int(c[2]), int(c[3]), int(c[4])) for c in chains])
-    cols = (_vp * max(len(columns), 1))(*[_vp(int(p)) for p in columns])
-    ctx._chk(ctx.lib.h2hip_rlc_fill_chains_dev(ctx.handle, cols, len(columns), usable_rows, _vp(vptr), num_values, arr, len(chains),
-                                               _ptr(fr_limbs(int(gamma) % R_MOD))))
+    ctx._chk(ctx.lib.h2hip_rlc_fill_chains_dev(ctx.handle, _col_array(columns), len(columns), usable_rows, _dev_ptr(values_dev), num_values,
+                                               _struct_table(RlcChainStruct, chains), len(chains), _ptr(fr_limbs(int(gamma) % R_MOD))))
 
 
 class GateChainStruct(C.Structure):   # h2hip_gate_chain
@@ -775,11 +805,9 @@ def gate_fill_chains(ctx: Context, columns: Sequence[int], usable_rows: int, a_d
     (continues it directly below), or a ctypes array of GateChainStruct built once for a table used in every proof; operand i of a piece is
     element a_offset + i * a_stride of a_dev (b alike).  a_dev / b_dev: device pointers (or
     objects with data_ptr()) to a_len / b_len Fr elements; they may point into a column.  Stream-ordered on the context's stream."""
-    aptr = int(a_dev.data_ptr()) if hasattr(a_dev, "data_ptr") else int(a_dev)
-    bptr = int(b_dev.data_ptr()) if hasattr(b_dev, "data_ptr") else int(b_dev)
-    arr = chains if isinstance(chains, C.Array) else (GateChainStruct * max(len(chains), 1))(*[GateChainStruct(*[int(x) for x in c]) for c in chains])
-    cols = (_vp * max(len(columns), 1))(*[_vp(int(p)) for p in columns])
-    ctx._chk(ctx.lib.h2hip_gate_fill_chains_dev(ctx.handle, cols, len(columns), usable_rows, _vp(aptr), a_len, _vp(bptr), b_len, arr, len(chains)))
+    arr = _as_table(chains, lambda c: _struct_table(GateChainStruct, c))
+    ctx._chk(ctx.lib.h2hip_gate_fill_chains_dev(ctx.handle, _col_array(columns), len(columns), usable_rows, _dev_ptr(a_dev), a_len, _dev_ptr(b_dev), b_len, arr,
+                                                len(chains)))
 
 
 class RangeCheckStruct(C.Structure):   # h2hip_range_check
@@ -792,7 +820,7 @@ RANGE_LESS_THAN = 1
 def range_check_table(units: Sequence) -> C.Array:
     """a ctypes table of h2hip_range_check from (column, row, a_offset, b_offset, lookup_slot) tuples: build it once for a layout used in every
     proof (a table of thousands of structs costs milliseconds to build)"""
-    return (RangeCheckStruct * max(len(units), 1))(*[RangeCheckStruct(*[int(x) for x in u]) for u in units])
+    return _struct_table(RangeCheckStruct, units)
 
 
 def range_check_layout(range_bits: int, lookup_bits: int, flags: int = 0, lib=None):
@@ -801,8 +829,7 @@ def range_check_layout(range_bits: int, lookup_bits: int, flags: int = 0, lib=No
     lib = lib or load_library()
     cells, lookups, last = C.c_size_t(0), C.c_size_t(0), C.c_uint32(0)
     code = lib.h2hip_range_check_layout(range_bits, lookup_bits, flags, C.byref(cells), C.byref(lookups), C.byref(last))
-    if code != 0:
-        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    _raise_on(code, lib)
     return cells.value, lookups.value, None if last.value == 0xFFFFFFFF else last.value
 
 
@@ -814,16 +841,10 @@ def range_fill_checks(ctx: Context, columns: Sequence[int], usable_rows: int, br
     lookup_slot) tuples or a table from range_check_table() built once; the checked value is values_dev[a_offset] (a + 2^shift_bits -
     values_dev[b_offset] with RANGE_LESS_THAN).  values_dev: a device pointer (or an object with data_ptr()), which may point into a column.
     Stream-ordered on the context's stream."""
-    cols = (_vp * max(len(columns), 1))(*[_vp(int(p)) if p else None for p in columns])
-    lks = (_vp * max(len(lookup_columns), 1))(*[_vp(int(p)) if p else None for p in lookup_columns])
-    bps = None
-    if break_points is not None:
-        assert len(break_points) == len(columns) - 1, "one break point per column but the last"
-        bps = (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
-    arr = units if isinstance(units, C.Array) else range_check_table(units)
-    vptr = int(values_dev.data_ptr()) if hasattr(values_dev, "data_ptr") else int(values_dev or 0)
-    ctx._chk(ctx.lib.h2hip_range_fill_checks_dev(ctx.handle, cols, len(columns), usable_rows, bps, lks, len(lookup_columns), _vp(vptr) if vptr else None,
-                                                 values_len, range_bits, lookup_bits, shift_bits, flags, C.cast(arr, _vp), len(units)))
+    arr = _as_table(units, range_check_table)
+    ctx._chk(ctx.lib.h2hip_range_fill_checks_dev(ctx.handle, _col_array(columns), len(columns), usable_rows, _bp_array(break_points, len(columns)),
+                                                 _col_array(lookup_columns), len(lookup_columns), _dev_ptr(values_dev), values_len, range_bits, lookup_bits,
+                                                 shift_bits, flags, C.cast(arr, _vp), len(units)))
 
 
 class FpParamsStruct(C.Structure):   # h2hip_fp_params
@@ -845,7 +866,7 @@ def fp_params(limb_bits: int, num_limbs: int, lookup_bits: int, modulus: int, fl
 
 def fp_mul_table(units: Sequence) -> C.Array:
     """a ctypes table of h2hip_fp_mul from (column, row, a_offset, b_offset) tuples: build it once for a layout used in every proof"""
-    return (FpMulStruct * max(len(units), 1))(*[FpMulStruct(*[int(x) for x in u]) for u in units])
+    return _struct_table(FpMulStruct, units)
 
 
 class FpMulLayout(NamedTuple):
@@ -864,8 +885,7 @@ def fp_mul_layout(params: FpParamsStruct, lib=None) -> FpMulLayout:
     cells, own, lookups = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
     ranges, outs = (FpMulRangeStruct * 12)(), (C.c_uint32 * 5)()
     code = lib.h2hip_fp_mul_layout(C.cast(C.pointer(params), _vp), C.byref(cells), C.byref(own), C.byref(lookups), C.cast(ranges, _vp), outs)
-    if code != 0:
-        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    _raise_on(code, lib)
     k = params.num_limbs
     return FpMulLayout(cells.value, own.value, lookups.value, [(r.cell_offset, r.num_cells, r.range_bits, r.result_index) for r in ranges[:3 * k]],
                        list(outs[:k + 1]))
@@ -875,14 +895,9 @@ def trace_seek(break_points: Optional[Sequence[int]], num_columns: int, column: 
     """h2hip_trace_seek: the (column, row) of cell `offset` of a run laid down from (column, row) as assign_witnesses does (the cell on a break
     point: its first position; the cell behind it lies at row 1 of the next column)"""
     lib = lib or load_library()
-    bps = None
-    if break_points is not None:
-        assert len(break_points) == num_columns - 1, "one break point per column but the last"
-        bps = (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
     c, r = C.c_uint32(0), C.c_uint32(0)
-    code = lib.h2hip_trace_seek(bps, num_columns, column, row, offset, C.byref(c), C.byref(r))
-    if code != 0:
-        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    code = lib.h2hip_trace_seek(_bp_array(break_points, num_columns), num_columns, column, row, offset, C.byref(c), C.byref(r))
+    _raise_on(code, lib)
     return c.value, r.value
 
 
@@ -893,16 +908,10 @@ def fp_mul_fill(ctx: Context, columns: Sequence[int], usable_rows: int, break_po
     a_offset, b_offset) tuples or a table from fp_mul_table(); an operand is the k + 1 Fr of values_dev from its offset (k limbs, then the
     native residue).  results_dev (or None): 3 k + 1 Fr per unit — o_i, out_native, q_i + B, -c_i + 2^rb.  count: the units of a table
     to fill (default: all).  Stream-ordered on the context's stream."""
-    cols = (_vp * max(len(columns), 1))(*[_vp(int(p)) if p else None for p in columns])
-    bps = None
-    if break_points is not None:
-        assert len(break_points) == len(columns) - 1, "one break point per column but the last"
-        bps = (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
-    arr = units if isinstance(units, C.Array) else fp_mul_table(units)
-    vptr = int(values_dev.data_ptr()) if hasattr(values_dev, "data_ptr") else int(values_dev or 0)
-    rptr = int(results_dev.data_ptr()) if hasattr(results_dev, "data_ptr") else int(results_dev or 0)
-    ctx._chk(ctx.lib.h2hip_fp_mul_fill_dev(ctx.handle, cols, len(columns), usable_rows, bps, C.cast(C.pointer(params), _vp), _vp(vptr) if vptr else None,
-                                           values_len, _vp(rptr) if rptr else None, results_len, C.cast(arr, _vp), len(units) if count is None else count))
+    arr = _as_table(units, fp_mul_table)
+    ctx._chk(ctx.lib.h2hip_fp_mul_fill_dev(ctx.handle, _col_array(columns), len(columns), usable_rows, _bp_array(break_points, len(columns)),
+                                           C.cast(C.pointer(params), _vp), _dev_ptr(values_dev), values_len, _dev_ptr(results_dev), results_len,
+                                           C.cast(arr, _vp), len(units) if count is None else count))
 
 
 def fp_mul_range_tables(break_points: Optional[Sequence[int]], num_columns: int, params: FpParamsStruct, units, lookup_slots: Sequence[int], lib=None) -> list:
@@ -912,16 +921,11 @@ def fp_mul_range_tables(break_points: Optional[Sequence[int]], num_columns: int,
     results index u (3 k + 1) + result_index, its lookup_slot from lookup_slots[u].  Build it once for a layout used in every proof."""
     lib = lib or load_library()
     k, count = params.num_limbs, len(lookup_slots)
-    arr = units if isinstance(units, C.Array) else fp_mul_table(units)
-    bps = None
-    if break_points is not None:
-        assert len(break_points) == num_columns - 1, "one break point per column but the last"
-        bps = (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
+    arr = _as_table(units, fp_mul_table)
     checks = (RangeCheckStruct * max(3 * k * count, 1))()
-    code = lib.h2hip_fp_mul_range_checks(bps, num_columns, C.cast(C.pointer(params), _vp), C.cast(arr, _vp), (C.c_uint64 * max(count, 1))(*lookup_slots), count,
+    code = lib.h2hip_fp_mul_range_checks(_bp_array(break_points, num_columns), num_columns, C.cast(C.pointer(params), _vp), C.cast(arr, _vp), (C.c_uint64 * max(count, 1))(*lookup_slots), count,
                                          C.cast(checks, _vp))
-    if code != 0:
-        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    _raise_on(code, lib)
     widths = [r[2] for r in fp_mul_layout(params, lib).ranges]
     tables = []
     for j0, j1 in ((0, k - 1), (k - 1, k), (k, 2 * k - 1), (2 * k - 1, 2 * k), (2 * k, 3 * k)):   # gap-major: the gaps of one width are consecutive
@@ -937,7 +941,7 @@ def fp_mul_fill_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: i
     its lookup cells.  units: (column, row, a_offset, b_offset) tuples or a table from fp_mul_table(); lookup_slots[u]: the queue position of
     unit u's first lookup cell (not read with range_tables, the result of fp_mul_range_tables() built once for the layout)."""
     assert results_dev, "the range checks read results_dev"
-    arr = units if isinstance(units, C.Array) else fp_mul_table(units)
+    arr = _as_table(units, fp_mul_table)
     tables = range_tables if range_tables is not None else fp_mul_range_tables(break_points, len(columns), params, arr, lookup_slots, ctx.lib)
     fp_mul_fill(ctx, columns, usable_rows, break_points, params, values_dev, values_len, results_dev, results_len, arr, len(units))
     for bits, table in tables:
@@ -953,7 +957,7 @@ EC_ADD_UNEQUAL, EC_DOUBLE = 0, 1
 
 def ec_op_table(units: Sequence) -> C.Array:
     """a ctypes table of h2hip_ec_op from (column, row, p_offset, q_offset) tuples: build it once for a layout used in every proof"""
-    return (EcOpStruct * max(len(units), 1))(*[EcOpStruct(*[int(x) for x in u]) for u in units])
+    return _struct_table(EcOpStruct, units)
 
 
 class EcLayout(NamedTuple):
@@ -972,8 +976,7 @@ def ec_layout(params: FpParamsStruct, op: int, lib=None) -> EcLayout:
     cells, own, lookups = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
     ranges, outs = (FpMulRangeStruct * 36)(), (C.c_uint32 * 15)()
     code = lib.h2hip_ec_layout(C.cast(C.pointer(params), _vp), op, C.byref(cells), C.byref(own), C.byref(lookups), C.cast(ranges, _vp), outs)
-    if code != 0:
-        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    _raise_on(code, lib)
     k = params.num_limbs
     return EcLayout(cells.value, own.value, lookups.value, [(r.cell_offset, r.num_cells, r.range_bits, r.result_index) for r in ranges[:9 * k]],
                     list(outs[:3 * (k + 1)]))
@@ -986,16 +989,10 @@ def ec_fill(ctx: Context, columns: Sequence[int], usable_rows: int, break_points
     (column, row, p_offset, q_offset) tuples or a table from ec_op_table(); a point is the 2 (k + 1) Fr of values_dev from its offset (x's k
     limbs and native residue, then y's).  results_dev (or None): 9 k + 3 Fr per unit — x3, y3 (a point a later call may read), lambda, then
     per reduction q_i + B and -c_i + 2^rb.  count: the units of a table to fill (default: all).  Stream-ordered on the context's stream."""
-    cols = (_vp * max(len(columns), 1))(*[_vp(int(p)) if p else None for p in columns])
-    bps = None
-    if break_points is not None:
-        assert len(break_points) == len(columns) - 1, "one break point per column but the last"
-        bps = (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
-    arr = units if isinstance(units, C.Array) else ec_op_table(units)
-    vptr = int(values_dev.data_ptr()) if hasattr(values_dev, "data_ptr") else int(values_dev or 0)
-    rptr = int(results_dev.data_ptr()) if hasattr(results_dev, "data_ptr") else int(results_dev or 0)
-    ctx._chk(ctx.lib.h2hip_ec_fill_dev(ctx.handle, cols, len(columns), usable_rows, bps, C.cast(C.pointer(params), _vp), op, _vp(vptr) if vptr else None,
-                                       values_len, _vp(rptr) if rptr else None, results_len, C.cast(arr, _vp), len(units) if count is None else count))
+    arr = _as_table(units, ec_op_table)
+    ctx._chk(ctx.lib.h2hip_ec_fill_dev(ctx.handle, _col_array(columns), len(columns), usable_rows, _bp_array(break_points, len(columns)),
+                                       C.cast(C.pointer(params), _vp), op, _dev_ptr(values_dev), values_len, _dev_ptr(results_dev), results_len,
+                                       C.cast(arr, _vp), len(units) if count is None else count))
 
 
 def ec_range_tables(break_points: Optional[Sequence[int]], num_columns: int, params: FpParamsStruct, op: int, units, lookup_slots: Sequence[int],
@@ -1006,16 +1003,11 @@ def ec_range_tables(break_points: Optional[Sequence[int]], num_columns: int, par
     cell.  Build it once for a layout used in every proof."""
     lib = lib or load_library()
     k, count = params.num_limbs, len(lookup_slots)
-    arr = units if isinstance(units, C.Array) else ec_op_table(units)
-    bps = None
-    if break_points is not None:
-        assert len(break_points) == num_columns - 1, "one break point per column but the last"
-        bps = (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
+    arr = _as_table(units, ec_op_table)
     checks = (RangeCheckStruct * max(9 * k * count, 1))()
-    code = lib.h2hip_ec_range_checks(bps, num_columns, C.cast(C.pointer(params), _vp), op, C.cast(arr, _vp), (C.c_uint64 * max(count, 1))(*lookup_slots),
+    code = lib.h2hip_ec_range_checks(_bp_array(break_points, num_columns), num_columns, C.cast(C.pointer(params), _vp), op, C.cast(arr, _vp), (C.c_uint64 * max(count, 1))(*lookup_slots),
                                      count, C.cast(checks, _vp))
-    if code != 0:
-        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    _raise_on(code, lib)
     widths: dict = {}
     for r in ec_layout(params, op, lib).ranges:
         widths[r[2]] = widths.get(r[2], 0) + 1             # (a dict keeps the order of first appearance)
@@ -1034,7 +1026,7 @@ def ec_fill_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: int, 
     lookup_slots[u]: the queue position of unit u's first lookup cell (not read with range_tables, the result of ec_range_tables() built once
     for the layout)."""
     assert results_dev, "the range checks read results_dev"
-    arr = units if isinstance(units, C.Array) else ec_op_table(units)
+    arr = _as_table(units, ec_op_table)
     tables = range_tables if range_tables is not None else ec_range_tables(break_points, len(columns), params, op, arr, lookup_slots, ctx.lib)
     ec_fill(ctx, columns, usable_rows, break_points, params, op, values_dev, values_len, results_dev, results_len, arr, len(units))
     for bits, table in tables:

@@ -9,7 +9,8 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from .h2hip import Context, H2HipError, _ptr, load_library, poseidon_spec_generate
+from .h2hip import Context, _ptr, load_library, poseidon_spec_generate
+from .plonk import _as_table, _bp_array, _col_array, _dev_ptr, _raise_on
 
 _vp = C.c_void_p
 ABSORB_ONLY, WITH_CONSTS = 1, 2   # H2HIP_POSEIDON_*
@@ -39,8 +40,7 @@ def spec_optimize(t: int, r_f: int, r_p: int, round_constants: np.ndarray, mds: 
     z = lambda *shape: np.zeros(shape + (4,), dtype=np.uint64)
     start, partial, end, pre, sparse = z(half + 1, t), z(max(r_p, 1)), z(max(half - 1, 1), t), z(t, t), z(max(r_p, 1), 2 * t - 1)
     code = lib.h2hip_poseidon_spec_optimize(t, r_f, r_p, _ptr(rc), _ptr(m), _ptr(start), _ptr(partial), _ptr(end), _ptr(pre), _ptr(sparse))
-    if code != 0:
-        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    _raise_on(code, lib)
     return OptimizedSpec(start, partial[:r_p], end[:half - 1], m.reshape(t, t, 4).copy(), pre, sparse[:r_p])
 
 
@@ -56,8 +56,7 @@ def trace_layout(t: int, r_f: int, r_p: int, length: int, flags: int = 0, lib=No
     lib = lib or load_library()
     n, offs = C.c_size_t(0), (C.c_uint32 * t)()
     code = lib.h2hip_poseidon_trace_layout(t, r_f, r_p, length, flags, C.byref(n), offs)
-    if code != 0:
-        raise H2HipError(code, lib.h2hip_last_error().decode(errors="replace"))
+    _raise_on(code, lib)
     return n.value, list(offs)
 
 
@@ -124,12 +123,7 @@ class PoseidonHasher:
 
 def fill_hashes(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], inputs_dev, inputs_len: int, length: int,
                 hashes, states_in_dev=None, states_out_dev=None) -> None:
-    cols = (_vp * max(len(columns), 1))(*[_vp(int(p)) if p else None for p in columns])
-    bps = None
-    if break_points is not None:
-        assert len(break_points) == len(columns) - 1, "one break point per column but the last"
-        bps = (C.c_uint32 * max(len(break_points), 1))(*[int(b) for b in break_points])
-    arr = hashes if isinstance(hashes, C.Array) else hash_table(hashes)
-    ptr = lambda p: _vp(int(p)) if p else None
-    ctx._chk(ctx.lib.h2hip_poseidon_fill_hashes_dev(ctx.handle, cols, len(columns), usable_rows, bps, ptr(inputs_dev), inputs_len, length, ptr(states_in_dev),
-                                                    ptr(states_out_dev), C.cast(arr, _vp), len(hashes)))
+    arr = _as_table(hashes, hash_table)
+    ctx._chk(ctx.lib.h2hip_poseidon_fill_hashes_dev(ctx.handle, _col_array(columns), len(columns), usable_rows, _bp_array(break_points, len(columns)),
+                                                    _dev_ptr(inputs_dev), inputs_len, length, _dev_ptr(states_in_dev), _dev_ptr(states_out_dev),
+                                                    C.cast(arr, _vp), len(hashes)))

@@ -15,6 +15,7 @@ range_check calls included, so one thread holds the full run and the lookup queu
   E  a BaseConfig proof whose field multiplications two fill calls write, the second reading the first's results.
 """
 import ctypes as C
+import itertools
 import os
 import re
 
@@ -266,6 +267,37 @@ def check_layout_and_seek():
             assert e.code == ERR_INVALID
         else:
             raise AssertionError("trace_seek accepted %r" % (args,))
+
+
+def check_seek_grid():
+    """trace_seek equals the first position place() gives, exhaustively over a small grid: 1 to 3 columns of 6 usable rows, every break-point
+    vector (none included), every start (column, row), every offset that still fits.  The walk is the one the kernels' seek and the range-check
+    builders share.  The grid holds a run that starts on a break cell, breaks in consecutive columns with one cell between them (a break at
+    row 1: the copy lies at row 0), a break on the run's last cell, and the last column, which never breaks."""
+    rows, seen = 6, set()
+    for ncols in (1, 2, 3):
+        for bps in [None] + [list(b) for b in itertools.product(range(rows), repeat=ncols - 1)]:
+            for col in range(ncols):
+                for row in range(rows):
+                    first, (c, r), prev_copied = {}, (col, row), False
+                    for n in range(ncols * rows):            # grow the run cell by cell while it fits
+                        cells_at, (c, r) = place(c, r, 1, bps, ncols)
+                        if any(rr >= rows for _, _, rr in cells_at):
+                            break
+                        first[n] = cells_at[0][1:]
+                        last_copied = len(cells_at) == 2
+                        assert PL.trace_seek(bps, ncols, col, row, n) == first[n], (ncols, bps, col, row, n, first[n])
+                        if bps is not None:
+                            if n == 0 and last_copied:
+                                seen.add("starts on a break cell")
+                            if last_copied and prev_copied and first[n] == (c - 1, 1):
+                                seen.add("one cell between two breaks")
+                            if last_copied:
+                                seen.add("break on the last cell")
+                            if c == ncols - 1 and ncols > 1 and r > 1:
+                                seen.add("in the last column")
+                        prev_copied = last_copied
+    assert seen == {"starts on a break cell", "one cell between two breaks", "break on the last cell", "in the last column"}, seen
 
 
 def check_fill(ctx, n, k, lb, modulus, count, nl=1, pairs=None, seed=0xF9):

@@ -24,6 +24,10 @@ def test_layout_and_trace_seek_equal_the_definition():
     K.check_layout_and_seek()
 
 
+def test_trace_seek_equals_assign_witnesses_placement_on_an_exhaustive_grid():
+    K.check_seek_grid()
+
+
 @pytest.mark.parametrize("modulus", sorted(K.MODULI))
 @pytest.mark.parametrize("n,k,lb", K.PARAMS, ids=["%d_%d_%d" % p for p in K.PARAMS])
 def test_fill_against_its_definition(ctx, n, k, lb, modulus):

@@ -27,16 +27,14 @@ extern "C" int ec_host_fill(void *const *columns_host, size_t num_columns, const
     EcCall ec;
     Fr consts[EC_CONSTS];
     if (ec_prepare(*params, op, sh, &ec, consts)) return 1;
-    const uint32_t k = sh.k, lb = sh.fp.lb;
+    const uint32_t k = sh.k;
     std::vector<Fr> rec((size_t)ec_record_len(k) * count);
-    ec.cols = (Fr *const *)columns_host;
-    ec.bps = break_points;
+    ec.tc = TraceCols{(Fr *const *)columns_host, break_points, (uint32_t)(num_columns - 1)};
     ec.values = (const Fr *)values_host;
     ec.consts = consts;
     ec.segs = sh.segs;
     ec.results = (Fr *)results_host;
     ec.rec = rec.data();
-    ec.last_col = (uint32_t)(num_columns - 1);
     if (k == 3 && op == H2HIP_EC_ADD_UNEQUAL)
         solve_all<3, H2HIP_EC_ADD_UNEQUAL>(ec, units, count);
     else if (k == 3)
@@ -48,39 +46,21 @@ extern "C" int ec_host_fill(void *const *columns_host, size_t num_columns, const
     for (size_t u = 0; u < count; ++u)
         for (uint32_t s = 0; s < sh.nsegs; ++s) ec_place_slot(ec, units[u], (uint32_t)u, s);
     if (!lookup_columns_host) return 0;
-    for (size_t u = 0; u < count; ++u) {   // the 9 k range checks per unit, in context order
-        uint64_t slot = lookup_slots[u];
-        for (uint32_t j = 0; j < sh.ngaps; ++j) {
-            RangeCall rc;
-            rc.cols = ec.cols;
-            rc.bps = break_points;
-            rc.lk_cols = (Fr *const *)lookup_columns_host;
-            rc.values = (const Fr *)results_host;
-            rc.last_col = ec.last_col;
-            rc.num_lk_cols = (uint32_t)num_lookup_columns;
-            rc.L = (sh.gaps[j].range_bits + lb - 1) / lb;
-            rc.lb = lb;
-            rc.rem = sh.gaps[j].range_bits % lb;
-            rc.prefix = 0;
-            Fr pows[40];
-            for (uint32_t i = 0; i < rc.L; ++i) pows[i] = fp_pow2_mont(i * lb);
-            pows[rc.L] = fp_pow2_mont(rc.rem ? lb - rc.rem : 0);
-            pows[rc.L + 1] = pows[rc.L + 2] = Fr::zero();
-            rc.pows = pows;
-            TraceOut at;
-            at.cols = ec.cols;
-            at.bps = break_points;
-            at.last_col = ec.last_col;
-            range_seek(at, units[u].column, units[u].row, sh.gaps[j].cell_offset);
-            h2hip_range_check chk;
-            chk.column = at.col;
-            chk.row = (uint32_t)(at.p - ec.cols[at.col]);
-            chk.a_offset = u * ec_result_len(k) + sh.gaps[j].result_index;
-            chk.b_offset = 0;
-            chk.lookup_slot = slot;
+    uint64_t lk_before = 0;
+    for (uint32_t j = 0; j < sh.ngaps; ++j) {   // the 9 k range checks per unit, gap by gap in context order
+        RangeCall rc;
+        std::vector<Fr> pows;
+        if (range_prepare(sh.gaps[j].range_bits, sh.fp.lb, 0, 0, rc, &pows)) return 1;
+        rc.tc = ec.tc;
+        rc.lk_cols = (Fr *const *)lookup_columns_host;
+        rc.values = (const Fr *)results_host;
+        rc.num_lk_cols = (uint32_t)num_lookup_columns;
+        for (size_t u = 0; u < count; ++u) {
+            const TraceOut at = trace_at(ec.tc, units[u].column, units[u].row, sh.gaps[j].cell_offset);
+            const h2hip_range_check chk{at.col, (uint32_t)(at.p - ec.tc.cols[at.col]), u * ec_result_len(k) + sh.gaps[j].result_index, 0, lookup_slots[u] + lk_before};
             for (uint32_t s = 0; s < range_unit_slots(rc.L, rc.rem); ++s) range_slot(rc, chk, s);
-            slot += sh.gap_lookups[j];
         }
+        lk_before += sh.gap_lookups[j];
     }
     return 0;
 }
@@ -94,7 +74,7 @@ static void from_words(const uint32_t *w, uint32_t n, uint32_t k, Fr *out) {   /
         Fr c = Fr::zero();
         for (int j = 0; j < 4; ++j) c.l[j] = x[j];
         out[i] = fe_to_mont(range_low_bits(c, n));
-        nat = fe_add(nat, fe_mul(out[i], fp_pow2_mont(n * i)));
+        nat = fe_add(nat, fe_mul(out[i], pow2_mont(n * i)));
         const uint32_t ws = n >> 5, s = n & 31;
         for (uint32_t j = 0; j < 12; ++j) {
             const uint32_t lo = j + ws < 12 ? x[j + ws] : 0, hi = j + ws + 1 < 12 ? x[j + ws + 1] : 0;
@@ -116,7 +96,7 @@ int main() {
     static const char *moduli[3] = {"fffffffffffffffffffffffffffffffffffffffffffffffffffffffefffffc2f", "fffffffffffffffffffffffffffffffebaaedce6af48a03bbfd25e8cd0364141",
                                     "30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47"};
     static const uint32_t sets[4][3] = {{88, 3, 8}, {88, 3, 18}, {90, 3, 15}, {64, 4, 8}};
-    const Fr sentinel = fp_pow2_mont(253);   // (no cell of a unit holds 2^253)
+    const Fr sentinel = pow2_mont(253);   // (no cell of a unit holds 2^253)
     size_t units_run = 0;
     for (const auto &set : sets)
         for (const char *hex : moduli)
@@ -177,7 +157,7 @@ int main() {
                         units.push_back(u);
                         reduced.push_back(a < 4 && (a + b) % 12 < 4 && b < 4 && (a * b + 7) % 12 < 4);
                     }
-                values[units[0].p_offset + 1] = fp_pow2_mont(n);   // an improper limb: 2^n
+                values[units[0].p_offset + 1] = pow2_mont(n);   // an improper limb: 2^n
                 reduced[0] = 0;
                 const size_t count = units.size(), rows = 2 + count * (cells + 1) + 3;
                 std::vector<Fr> column(rows, sentinel), results(count * ec_result_len(k), sentinel);
@@ -221,6 +201,16 @@ int main() {
                         }
                     }
                 }
+                // once more with the range checks (range_prepare's RangeCall per gap): every cell of every run and every lookup cell written
+                std::vector<Fr> lk(count * sh.num_lookups + 1, sentinel);
+                std::vector<uint64_t> lk_slots(count);
+                for (size_t u = 0; u < count; ++u) lk_slots[u] = u * sh.num_lookups;
+                void *lks[1] = {lk.data()};
+                EXPECT(ec_host_fill(cols, 1, nullptr, lks, 1, &pr, op, values.data(), results.data(), units.data(), lk_slots.data(), count) == 0, "the fill with range checks refused\n");
+                size_t filled = 0, looked = 0;
+                for (size_t r = 0; r < rows; ++r) filled += column[r] != sentinel;
+                for (const Fr &c : lk) looked += c != sentinel;
+                EXPECT(filled == count * cells && looked + 1 == lk.size() && lk.back() == sentinel, "%zu cells and %zu lookup cells written with the range checks\n", filled, looked);
                 units_run += count;
             }
     printf("ec selftest: %zu units, %d failures\n", units_run, fails);

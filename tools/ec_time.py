@@ -37,7 +37,7 @@ SECP_P = (1 << 256) - (1 << 32) - 977
 
 def host_helper():
     src, lib = os.path.join(ROOT, "tools", "ec_host_fill.cpp"), os.path.join(ROOT, "tools", "ec_host_fill.so")
-    deps = [src, os.path.join(ROOT, "include", "h2hip.h")] + [os.path.join(ROOT, "halo2-lib_amd", "csrc", f) for f in ("ec_fill.cuh", "fp_mul.cuh", "range_fill.cuh")]
+    deps = [src, os.path.join(ROOT, "include", "h2hip.h")] + [os.path.join(ROOT, "halo2-lib_amd", "csrc", f) for f in ("ec_fill.cuh", "fp_mul.cuh", "range_fill.cuh", "trace_place.cuh")]
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip", "--cuda-host-only", "-std=c++17", "-O2", "-shared", "-fPIC",
                                "-Wno-unused-value", "-o", lib, src])

@@ -27,15 +27,13 @@ extern "C" int fp_mul_host_fill(void *const *columns_host, size_t num_columns, c
     FpCall fc;
     Fr consts[FP_CONSTS];
     if (fp_prepare(*params, sh, &fc, consts)) return 1;
-    const uint32_t k = sh.k, lb = sh.lb;
+    const uint32_t k = sh.k;
     std::vector<Fr> rec((size_t)fp_record_len(k) * count);
-    fc.cols = (Fr *const *)columns_host;
-    fc.bps = break_points;
+    fc.tc = TraceCols{(Fr *const *)columns_host, break_points, (uint32_t)(num_columns - 1)};
     fc.values = (const Fr *)values_host;
     fc.consts = consts;
     fc.results = (Fr *)results_host;
     fc.rec = rec.data();
-    fc.last_col = (uint32_t)(num_columns - 1);
     if (k == 2)
         solve_all<2>(fc, units, count);
     else if (k == 3)
@@ -45,48 +43,22 @@ extern "C" int fp_mul_host_fill(void *const *columns_host, size_t num_columns, c
     for (size_t u = 0; u < count; ++u)
         for (uint32_t s = 0; s < fp_unit_slots(k); ++s) fp_place_slot(fc, units[u], (uint32_t)u, s);
     if (!lookup_columns_host) return 0;
-    // the nine range checks per unit, width by width (the tables of powers the library uploads per range call)
-    for (int w = 0; w < 5; ++w) {
+    // the nine range checks per unit, gap by gap in context order (the table of powers is the one the library uploads per range call)
+    uint64_t lk_before = 0;
+    for (uint32_t j = 0; j < 3 * k; ++j) {
         RangeCall rc;
-        rc.cols = fc.cols;
-        rc.bps = break_points;
+        std::vector<Fr> pows;
+        if (range_prepare(sh.gaps[j].range_bits, sh.lb, 0, 0, rc, &pows)) return 1;
+        rc.tc = fc.tc;
         rc.lk_cols = (Fr *const *)lookup_columns_host;
         rc.values = (const Fr *)results_host;
-        rc.last_col = fc.last_col;
         rc.num_lk_cols = (uint32_t)num_lookup_columns;
-        rc.L = (sh.width[w] + lb - 1) / lb;
-        rc.lb = lb;
-        rc.rem = sh.width[w] % lb;
-        rc.prefix = 0;
-        std::vector<Fr> pows(rc.L + 3);
-        for (uint32_t i = 0; i < rc.L; ++i) pows[i] = fp_pow2_mont(i * lb);
-        pows[rc.L] = fp_pow2_mont(rc.rem ? lb - rc.rem : 0);
-        pows[rc.L + 1] = pows[rc.L + 2] = Fr::zero();
-        rc.pows = pows.data();
-        const uint32_t rslots = range_unit_slots(rc.L, rc.rem);
         for (size_t u = 0; u < count; ++u) {
-            uint64_t slot = lookup_slots[u];
-            for (uint32_t j = 0; j < 3 * k; ++j) {
-                const uint32_t i = j % k, grp = j / k, last = i == k - 1;
-                const int wj = grp == 0 ? (last ? 1 : 0) : grp == 1 ? (last ? 3 : 2) : 4;
-                const uint32_t off = grp == 0 ? sh.lay.base4 + i * sh.gap[0] : grp == 1 ? sh.lay.base5 + i * (4 + sh.gap[2]) + 4 : sh.lay.base6 + i * (8 + sh.gap[4]) + 8;
-                if (wj == w) {
-                    TraceOut at;
-                    at.cols = fc.cols;
-                    at.bps = break_points;
-                    at.last_col = fc.last_col;
-                    range_seek(at, units[u].column, units[u].row, off);
-                    h2hip_range_check chk;
-                    chk.column = at.col;
-                    chk.row = (uint32_t)(at.p - fc.cols[at.col]);
-                    chk.a_offset = u * fp_result_len(k) + (grp == 0 ? i : grp == 1 ? k + 1 + i : 2 * k + 1 + i);
-                    chk.b_offset = 0;
-                    chk.lookup_slot = slot;
-                    for (uint32_t s = 0; s < rslots; ++s) range_slot(rc, chk, s);
-                }
-                slot += sh.lookups[wj];
-            }
+            const TraceOut at = trace_at(fc.tc, units[u].column, units[u].row, sh.gaps[j].cell_offset);
+            const h2hip_range_check chk{at.col, (uint32_t)(at.p - fc.tc.cols[at.col]), u * fp_result_len(k) + sh.gaps[j].result_index, 0, lookup_slots[u] + lk_before};
+            for (uint32_t s = 0; s < range_unit_slots(rc.L, rc.rem); ++s) range_slot(rc, chk, s);
         }
+        lk_before += sh.gap_lookups[j];
     }
     return 0;
 }
@@ -100,7 +72,7 @@ static void from_words(const uint32_t *w, uint32_t n, uint32_t k, Fr *out) {   /
         Fr c = Fr::zero();
         for (int j = 0; j < 4; ++j) c.l[j] = x[j];
         out[i] = fe_to_mont(range_low_bits(c, n));
-        nat = fe_add(nat, fe_mul(out[i], fp_pow2_mont(n * i)));
+        nat = fe_add(nat, fe_mul(out[i], pow2_mont(n * i)));
         const uint32_t ws = n >> 5, s = n & 31;
         for (uint32_t j = 0; j < 12; ++j) {
             const uint32_t lo = j + ws < 12 ? x[j + ws] : 0, hi = j + ws + 1 < 12 ? x[j + ws + 1] : 0;
@@ -128,7 +100,7 @@ int main() {
     static const char *moduli[3] = {"fffffffffffffffffffffffffffffffffffffffffffffffffffffffefffffc2f", "fffffffffffffffffffffffffffffffebaaedce6af48a03bbfd25e8cd0364141",
                                     "30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47"};
     static const uint32_t sets[5][3] = {{88, 3, 8}, {88, 3, 18}, {90, 3, 15}, {91, 3, 13}, {64, 4, 8}};
-    const Fr sentinel = fp_pow2_mont(253);   // (no cell of a unit holds 2^253)
+    const Fr sentinel = pow2_mont(253);   // (no cell of a unit holds 2^253)
     size_t units_run = 0;
     for (const auto &set : sets)
         for (const char *hex : moduli) {
@@ -181,7 +153,7 @@ int main() {
             const size_t proper = units.size();
             from_words(pool[2], n, k, a);
             from_words(pool[5], n, k, b);
-            a[1] = fp_pow2_mont(n);   // an improper limb: 2^n
+            a[1] = pow2_mont(n);   // an improper limb: 2^n
             add_unit(a, b);
             from_words(pool[5], n, k, a);
             a[0] = fe_neg(Fr::one());   // r - 1
@@ -192,12 +164,8 @@ int main() {
             EXPECT(fp_mul_host_fill(cols, 1, nullptr, nullptr, 0, &pr, values.data(), results.data(), units.data(), nullptr, count) == 0, "the fill refused\n");
             // cells: own cells written, gaps and the rest untouched
             std::vector<char> own(cells, 1);
-            for (uint32_t i = 0; i < k; ++i) {
-                const bool last = i == k - 1;
-                for (uint32_t c = 0; c < sh.gap[last ? 1 : 0]; ++c) own[sh.lay.base4 + i * sh.gap[0] + c] = 0;
-                for (uint32_t c = 0; c < sh.gap[last ? 3 : 2]; ++c) own[sh.lay.base5 + i * (4 + sh.gap[2]) + 4 + c] = 0;
-                for (uint32_t c = 0; c < sh.gap[4]; ++c) own[sh.lay.base6 + i * (8 + sh.gap[4]) + 8 + c] = 0;
-            }
+            for (uint32_t j = 0; j < 3 * k; ++j)
+                for (uint32_t c = 0; c < sh.gaps[j].num_cells; ++c) own[sh.gaps[j].cell_offset + c] = 0;
             size_t written = 0;
             for (size_t r = 0; r < rows; ++r) written += column[r] != sentinel;
             EXPECT(written == count * sh.own, "%zu cells written, %zu own cells\n", written, count * sh.own);
@@ -236,6 +204,16 @@ int main() {
                     EXPECT(fe_add(run[sh.lay.off9 - 1], fe_mul(s9[0], s9[1])) == s9[2], "unit %zu: out_native + m_nat quot_native != N\n", u);
                 }
             }
+            // once more with the range checks (range_prepare's RangeCall per gap): every cell of every run and every lookup cell written
+            std::vector<Fr> lk(count * sh.num_lookups + 1, sentinel);
+            std::vector<uint64_t> lk_slots(count);
+            for (size_t u = 0; u < count; ++u) lk_slots[u] = u * sh.num_lookups;
+            void *lks[1] = {lk.data()};
+            EXPECT(fp_mul_host_fill(cols, 1, nullptr, lks, 1, &pr, values.data(), results.data(), units.data(), lk_slots.data(), count) == 0, "the fill with range checks refused\n");
+            size_t filled = 0, looked = 0;
+            for (size_t r = 0; r < rows; ++r) filled += column[r] != sentinel;
+            for (const Fr &c : lk) looked += c != sentinel;
+            EXPECT(filled == count * cells && looked + 1 == lk.size() && lk.back() == sentinel, "%zu cells and %zu lookup cells written with the range checks\n", filled, looked);
             units_run += count;
         }
     printf("fp_mul selftest: %zu units, %d failures\n", units_run, fails);

@@ -20,8 +20,9 @@ extern "C" void poseidon_host_fill_hashes(void *const *columns_host, size_t num_
     sp.init0 = sp.sparse + (size_t)r_p * (2 * t - 1);
     sp.half = half;
     sp.r_p = r_p;
+    const TraceCols tc{(Fr *const *)columns_host, break_points, (uint32_t)(num_columns - 1)};
     for (size_t j = 0; j < count; ++j) {
-        if (t == 3) trace_unit<3>((Fr *const *)columns_host, break_points, (uint32_t)(num_columns - 1), (const Fr *)inputs_host, len, nullptr, nullptr, hashes[j], (uint32_t)j, sp);
-        else trace_unit<5>((Fr *const *)columns_host, break_points, (uint32_t)(num_columns - 1), (const Fr *)inputs_host, len, nullptr, nullptr, hashes[j], (uint32_t)j, sp);
+        if (t == 3) trace_unit<3>(tc, (const Fr *)inputs_host, len, nullptr, nullptr, hashes[j], (uint32_t)j, sp);
+        else trace_unit<5>(tc, (const Fr *)inputs_host, len, nullptr, nullptr, hashes[j], (uint32_t)j, sp);
     }
 }

@@ -33,7 +33,8 @@ HBM_COPY_TBS = 6.29   # a float4 copy on this part (8.0 TB/s is the specificatio
 
 def host_helper():
     src, lib = os.path.join(ROOT, "tools", "range_host_fill.cpp"), os.path.join(ROOT, "tools", "range_host_fill.so")
-    deps = [src, os.path.join(ROOT, "include", "h2hip.h"), os.path.join(ROOT, "halo2-lib_amd", "csrc", "range_fill.cuh")]
+    deps = [src, os.path.join(ROOT, "include", "h2hip.h"), os.path.join(ROOT, "halo2-lib_amd", "csrc", "range_fill.cuh"),
+            os.path.join(ROOT, "halo2-lib_amd", "csrc", "trace_place.cuh")]
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip", "--cuda-host-only", "-std=c++17", "-O2", "-shared", "-fPIC",
                                "-Wno-unused-value", "-o", lib, src])

@@ -11,17 +11,12 @@ extern "C" void range_host_fill_checks(void *const *columns_host, size_t num_col
                                        size_t num_lookup_columns, const void *values_host, const void *pows, uint32_t range_bits, uint32_t lookup_bits,
                                        uint32_t flags, const h2hip_range_check *checks, size_t count) {
     RangeCall rc;
-    rc.cols = (Fr *const *)columns_host;
-    rc.bps = break_points;
+    if (range_prepare(range_bits, lookup_bits, 0, flags, rc, nullptr)) return;
+    rc.tc = TraceCols{(Fr *const *)columns_host, break_points, num_columns ? (uint32_t)(num_columns - 1) : 0};
     rc.lk_cols = (Fr *const *)lookup_columns_host;
     rc.values = (const Fr *)values_host;
     rc.pows = (const Fr *)pows;
-    rc.last_col = num_columns ? (uint32_t)(num_columns - 1) : 0;
     rc.num_lk_cols = (uint32_t)num_lookup_columns;
-    rc.L = (range_bits + lookup_bits - 1) / lookup_bits;
-    rc.lb = lookup_bits;
-    rc.rem = range_bits % lookup_bits;
-    rc.prefix = (flags & H2HIP_RANGE_LESS_THAN) ? RANGE_PREFIX : 0;
     const uint32_t slots = range_unit_slots(rc.L, rc.rem);
     for (size_t j = 0; j < count; ++j)
         for (uint32_t s = 0; s < slots; ++s) range_slot(rc, checks[j], s);
