@@ -339,10 +339,6 @@ int rng_chacha_fill_dev(h2hip_ctx *ctx, Fr *out_dev, size_t n, const uint8_t see
 // comm.hip: the fallible preparations of a later h2hip_comm_allgather_dev of `bytes` per rank, done ahead of time
 int comm_reserve_allgather_dev(h2hip_comm *comm, size_t bytes);
 int comm_reserve_alltoall_dev(h2hip_comm *c, size_t bytes);
-// plonk.hip: the multi-phase layout (Shape::init_phased, plonk_internal.h) for the verifier: the shape, each used phase's advice columns and challenges, whether
-// the key is multi-phase at all (otherwise it proves as the BaseConfig of `bp`), and the BaseCircuitParams of the gate / lookup-advice totals
-int plonk_phased_layout(const h2hip_phased_circuit_params &pp, h2hip_plonk_shape *shape, std::vector<std::vector<int>> *phase_cols,
-                        uint32_t challenges[H2HIP_MAX_PHASE], bool *phased, h2hip_base_circuit_params *bp, const h2hip_rlc_circuit_params *rlc = nullptr);   // rlc: the RLC configuration's layout instead (pp unused)
 int msm_reduce_cols(h2hip_ctx *ctx, const h2hip_bases *bases, uint32_t window_bits, const XYZZ29 *buckets, uint32_t ncols, XYZZ *out_dev);
 // lookup.hip: the key count a sort of u keys pads to (a power of two, at least one tile), and the bitonic network over N = lookup_padded_keys(u)
 // caller-made 32-byte keys (ascending by limb 7 .. 0; the caller pads with all-ones)

@@ -183,36 +183,27 @@ static void fill_shape(const Shape &sh, h2hip_plonk_shape *out) {
     out->num_evals = sh.num_evals();
 }
 
+static int shape_of(int kind, const void *params, h2hip_plonk_shape *out) {
+    Shape sh;
+    H2_CHK(shape_of_kind(kind, params, sh));
+    fill_shape(sh, out);
+    return H2HIP_OK;
+}
 int h2hip_plonk_shape_of(const h2hip_base_circuit_params *params, h2hip_plonk_shape *out) {
     H2_REQUIRE(params && out, "NULL argument");
-    Shape sh;
-    H2_CHK(sh.init(*params));
-    fill_shape(sh, out);
-    return H2HIP_OK;
+    return shape_of(H2HIP_CIRCUIT_BASE, params, out);
 }
-
 int h2hip_plonk_shape_of_dyn(const h2hip_dyn_circuit_params *params, h2hip_plonk_shape *out) {
     H2_REQUIRE(params && out, "NULL argument");
-    Shape sh;
-    H2_CHK(sh.init_dyn(*params));
-    fill_shape(sh, out);
-    return H2HIP_OK;
+    return shape_of(H2HIP_CIRCUIT_DYN, params, out);
 }
-
 int h2hip_plonk_shape_of_phased(const h2hip_phased_circuit_params *params, h2hip_plonk_shape *out) {
     H2_REQUIRE(params && out, "NULL argument");
-    Shape sh;
-    H2_CHK(sh.init_phased(*params));
-    fill_shape(sh, out);
-    return H2HIP_OK;
+    return shape_of(H2HIP_CIRCUIT_PHASED, params, out);
 }
-
 int h2hip_plonk_shape_of_rlc(const h2hip_rlc_circuit_params *params, h2hip_plonk_shape *out) {
     H2_REQUIRE(params && out, "NULL argument");
-    Shape sh;
-    H2_CHK(sh.init_rlc(*params));
-    fill_shape(sh, out);
-    return H2HIP_OK;
+    return shape_of(H2HIP_CIRCUIT_RLC, params, out);
 }
 
 // Shape::init gives every gate column's q_enable selector a fixed column of its own.  Upstream's compress_selectors [UPSTREAM-RECALL] would
@@ -262,8 +253,8 @@ static int check_selectors_stay_apart(const Shape &sh, const void *const *fixed_
     return H2HIP_OK;
 }
 
-static int keygen_common(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const h2hip_bases *g, const h2hip_bases *g_lagrange, const void *const *fixed_host,
-                         const uint32_t *copies, size_t ncopies, int rc, h2hip_plonk_pk **out);
+static int keygen_common(h2hip_ctx *ctx, int kind, const void *params, const h2hip_bases *g, const h2hip_bases *g_lagrange, const void *const *fixed_host,
+                         const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out);
 static void sync_proof_streams(h2hip_ctx *ctx, h2hip_plonk_pk *pk) {
     if (pk->copy_stream) hipStreamSynchronize(pk->copy_stream);
     if (pk->side) hipStreamSynchronize(pk->side->stream);
@@ -276,36 +267,34 @@ int h2hip_plonk_keygen(h2hip_ctx *ctx, const h2hip_base_circuit_params *params, 
                        const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out) {
     H2_DEVICE_GUARD(ctx);
     H2_REQUIRE(ctx && params && g && g_lagrange && fixed_host && out && (ncopies == 0 || copies), "NULL argument");
-    h2hip_plonk_pk *pk = new h2hip_plonk_pk();
-    return keygen_common(ctx, pk, g, g_lagrange, fixed_host, copies, ncopies, pk->sh.init(*params), out);
+    return keygen_common(ctx, H2HIP_CIRCUIT_BASE, params, g, g_lagrange, fixed_host, copies, ncopies, out);
 }
 
 int h2hip_plonk_keygen_dyn(h2hip_ctx *ctx, const h2hip_dyn_circuit_params *params, const h2hip_bases *g, const h2hip_bases *g_lagrange,
                            const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out) {
     H2_DEVICE_GUARD(ctx);
     H2_REQUIRE(ctx && params && g && g_lagrange && fixed_host && out && (ncopies == 0 || copies), "NULL argument");
-    h2hip_plonk_pk *pk = new h2hip_plonk_pk();
-    return keygen_common(ctx, pk, g, g_lagrange, fixed_host, copies, ncopies, pk->sh.init_dyn(*params), out);
+    return keygen_common(ctx, H2HIP_CIRCUIT_DYN, params, g, g_lagrange, fixed_host, copies, ncopies, out);
 }
 
 int h2hip_plonk_keygen_phased(h2hip_ctx *ctx, const h2hip_phased_circuit_params *params, const h2hip_bases *g, const h2hip_bases *g_lagrange,
                               const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out) {
     H2_DEVICE_GUARD(ctx);
     H2_REQUIRE(ctx && params && g && g_lagrange && fixed_host && out && (ncopies == 0 || copies), "NULL argument");
-    h2hip_plonk_pk *pk = new h2hip_plonk_pk();
-    return keygen_common(ctx, pk, g, g_lagrange, fixed_host, copies, ncopies, pk->sh.init_phased(*params), out);
+    return keygen_common(ctx, H2HIP_CIRCUIT_PHASED, params, g, g_lagrange, fixed_host, copies, ncopies, out);
 }
 
 int h2hip_plonk_keygen_rlc(h2hip_ctx *ctx, const h2hip_rlc_circuit_params *params, const h2hip_bases *g, const h2hip_bases *g_lagrange,
                            const void *const *fixed_host, const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out) {
     H2_DEVICE_GUARD(ctx);
     H2_REQUIRE(ctx && params && g && g_lagrange && fixed_host && out && (ncopies == 0 || copies), "NULL argument");
-    h2hip_plonk_pk *pk = new h2hip_plonk_pk();
-    return keygen_common(ctx, pk, g, g_lagrange, fixed_host, copies, ncopies, pk->sh.init_rlc(*params), out);
+    return keygen_common(ctx, H2HIP_CIRCUIT_RLC, params, g, g_lagrange, fixed_host, copies, ncopies, out);
 }
 
-static int keygen_common(h2hip_ctx *ctx, h2hip_plonk_pk *pk, const h2hip_bases *g, const h2hip_bases *g_lagrange, const void *const *fixed_host,
-                         const uint32_t *copies, size_t ncopies, int rc, h2hip_plonk_pk **out) {
+static int keygen_common(h2hip_ctx *ctx, int kind, const void *params, const h2hip_bases *g, const h2hip_bases *g_lagrange, const void *const *fixed_host,
+                         const uint32_t *copies, size_t ncopies, h2hip_plonk_pk **out) {
+    h2hip_plonk_pk *pk = new h2hip_plonk_pk();
+    int rc = shape_of_kind(kind, params, pk->sh);
     if (rc == H2HIP_OK && (g->n < pk->sh.n || g_lagrange->n < pk->sh.n)) {
         set_error("h2hip_plonk_keygen: the SRS holds fewer than 2^k bases");
         rc = H2HIP_ERR_INVALID;
@@ -645,15 +634,12 @@ static int check_witness_entry(h2hip_ctx *ctx, const h2hip_plonk_pk *pk_in, cons
     }
     if (rc == H2HIP_OK) {
         auto flat = [&](const ColumnRef &c) -> uint32_t { return c.kind == 0 ? (uint32_t)c.index : c.kind == 1 ? F + (uint32_t)c.index : F + A + (uint32_t)c.index; };
-        for (uint32_t g = 0; g < sh.p.num_advice; ++g) {
-            job.gate_report.push_back(sh.first_gate_advice + g);
-            job.gate_adv.push_back(F + sh.first_gate_advice + g);
-            job.gate_q.push_back((uint32_t)sh.first_q_enable_col + g);
-        }
-        for (uint32_t j = 0; j < sh.num_rlc; ++j) {   // behind the flex gates, as the prover folds them
-            job.gate_report.push_back(sh.first_rlc_advice + j);
-            job.gate_adv.push_back(F + sh.first_rlc_advice + j);
-            job.gate_q.push_back((uint32_t)sh.first_q_rlc_col + j);
+        std::vector<std::pair<int, int>> gates = sh.gates(), rlc = sh.rlc_gates();
+        gates.insert(gates.end(), rlc.begin(), rlc.end());   // behind the flex gates, as the prover folds them
+        for (const auto &g : gates) {
+            job.gate_report.push_back((uint32_t)g.second);
+            job.gate_adv.push_back(F + (uint32_t)g.second);
+            job.gate_q.push_back((uint32_t)g.first);
         }
         job.num_rlc_gates = sh.num_rlc;
         if (sh.num_rlc) job.rlc_gamma = *challenge0;
@@ -682,17 +668,3 @@ static int check_witness_entry(h2hip_ctx *ctx, const h2hip_plonk_pk *pk_in, cons
 }
 
 }  // extern "C"
-
-// (declared in internal.h: the verifier reads the multi-phase layout from here)
-int h2::plonk_phased_layout(const h2hip_phased_circuit_params &pp, h2hip_plonk_shape *shape, std::vector<std::vector<int>> *phase_cols,
-                        uint32_t challenges[H2HIP_MAX_PHASE], bool *phased, h2hip_base_circuit_params *bp, const h2hip_rlc_circuit_params *rlc) {
-    Shape sh;
-    H2_CHK(rlc ? sh.init_rlc(*rlc) : sh.init_phased(pp));
-    fill_shape(sh, shape);
-    *phased = sh.phased;
-    *bp = sh.p;
-    phase_cols->clear();
-    if (sh.phased) *phase_cols = sh.phase_cols;
-    for (int ph = 0; ph < H2HIP_MAX_PHASE; ++ph) challenges[ph] = sh.phase_challenges[ph];
-    return H2HIP_OK;
-}

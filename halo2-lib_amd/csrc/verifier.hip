@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "blake2b.h"
+#include "shplonk_sets.h"
 #include "transcript.h"
 #include "verifier_internal.h"
 
@@ -253,7 +254,6 @@ static G1Affine g1_neg(const G1Affine &p) {
 }
 
 // ---------------------------------------------------------------------------------------------- transcript (Blake2bRead)
-static const unsigned SIGN_BIT = 6, INF_BIT = 7;
 struct Reader final : TranscriptReader {
     Blake2b st;
     const uint8_t *p;
@@ -361,63 +361,6 @@ using namespace h2::verifier;
 
 namespace {
 
-struct VQuery {
-    int key;   // index into the commitment list
-    Fr point, eval;
-};
-struct VSet {
-    std::vector<Fr> points;
-    std::vector<int> keys;
-    std::vector<std::vector<Fr>> evals;
-};
-// the same grouping the prover performs (poly/kzg/multiopen/shplonk.rs::construct_intermediate_sets [UPSTREAM-RECALL])
-void intermediate_sets(const std::vector<VQuery> &queries, std::vector<VSet> &sets, std::vector<Fr> &super_points) {
-    auto less = [](const Fr &a, const Fr &b) { return fr_cmp(a, b) < 0; };
-    std::vector<Fr> pts;
-    for (auto &q : queries) pts.push_back(q.point);
-    std::sort(pts.begin(), pts.end(), less);
-    super_points.clear();
-    for (auto &p : pts)
-        if (super_points.empty() || fr_cmp(super_points.back(), p) != 0) super_points.push_back(p);
-    std::vector<int> order;
-    std::map<int, std::vector<Fr>> pset;
-    for (auto &q : queries) {
-        auto it = pset.find(q.key);
-        if (it == pset.end()) {
-            order.push_back(q.key);
-            pset[q.key] = {q.point};
-        } else {
-            bool have = false;
-            for (auto &p : it->second) have |= fr_cmp(p, q.point) == 0;
-            if (!have) it->second.push_back(q.point);
-        }
-    }
-    for (auto &kv : pset) std::sort(kv.second.begin(), kv.second.end(), less);
-    sets.clear();
-    for (int key : order) {
-        const std::vector<Fr> &ps = pset[key];
-        VSet *vs = nullptr;
-        for (auto &s : sets) {
-            bool same = s.points.size() == ps.size();
-            for (size_t i = 0; same && i < ps.size(); ++i) same = fr_cmp(s.points[i], ps[i]) == 0;
-            if (same) vs = &s;
-        }
-        if (!vs) {
-            sets.push_back(VSet());
-            vs = &sets.back();
-            vs->points = ps;
-        }
-        vs->keys.push_back(key);
-        std::vector<Fr> ev;
-        for (auto &p : ps)
-            for (auto &q : queries)
-                if (q.key == key && fr_cmp(q.point, p) == 0) {
-                    ev.push_back(q.eval);
-                    break;
-                }
-        vs->evals.push_back(ev);
-    }
-}
 // value at u of the polynomial of degree < m through (points[i], evals[i])
 Fr interpolate_at(const std::vector<Fr> &points, const std::vector<Fr> &evals, const Fr &u) {
     Fr acc = Fr::zero();
@@ -432,12 +375,6 @@ Fr interpolate_at(const std::vector<Fr> &points, const std::vector<Fr> &evals, c
     }
     return acc;
 }
-Fr fr_u64(uint64_t v) {
-    Fr a = Fr::zero();
-    a.l[0] = (uint32_t)v;
-    a.l[1] = (uint32_t)(v >> 32);
-    return fe_to_mont(a);
-}
 F2 load_f2(const uint8_t *p) {
     F2 r;
     memcpy(r.c0.l, p, 32);
@@ -450,25 +387,19 @@ F2 load_f2(const uint8_t *p) {
 namespace h2 {
 namespace verifier {
 
-int check_key(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens) {
-    H2_REQUIRE(vs.sh.num_perm_columns == 0 || vk.permutation_commitments, "NULL argument");
-    H2_REQUIRE(vs.num_instance == 0 || (instances_host && instance_lens), "NULL argument");
+int check_key(const plonk::Shape &sh, const VKey &vk, const void *const *instances_host, const size_t *instance_lens) {
+    H2_REQUIRE(sh.perm_columns.empty() || vk.permutation_commitments, "NULL argument");
+    H2_REQUIRE(sh.p.num_instance == 0 || (instances_host && instance_lens), "NULL argument");
     G2A Q2 = {load_f2((const uint8_t *)vk.g2), load_f2((const uint8_t *)vk.g2 + 64), false},
         SQ2 = {load_f2((const uint8_t *)vk.s_g2), load_f2((const uint8_t *)vk.s_g2 + 64), false};
     H2_REQUIRE(g2_on_curve(Q2) && g2_on_curve(SQ2), "g2 / s_g2 are not points of the twist");
     return H2HIP_OK;
 }
 
-size_t proof_words(const VShape &vs, std::vector<uint32_t> *point_words) {
-    const h2hip_plonk_shape &sh = vs.sh;
-    size_t advice = sh.num_advice_total;
-    if (!vs.phase_cols.empty()) {
-        advice = 0;
-        for (const auto &cols : vs.phase_cols) advice += cols.size();
-    }
-    const size_t head = advice + 3 * (size_t)sh.num_lookups + sh.num_perm_sets + 1 + sh.quotient_pieces;   // ... the random polynomial, the h pieces
-    size_t evals = vs.adv_q.size() + vs.fixed_q.size() + 1 + sh.num_perm_columns + 5 * (size_t)sh.num_lookups;
-    if (sh.num_perm_sets) evals += 3 * (size_t)sh.num_perm_sets - 1;
+// The prover writes num_commitments() points and num_evals() scalars.  (The advice commitments of a multi-phase proof come phase by phase,
+// but every advice column belongs to exactly one phase, so they are num_advice_total words in either order.)
+size_t proof_words(const plonk::Shape &sh, std::vector<uint32_t> *point_words) {
+    const size_t head = sh.num_commitments() - 2, evals = sh.num_evals();   // head: every commitment up to the h pieces
     if (point_words) {
         point_words->clear();
         for (size_t i = 0; i < head; ++i) point_words->push_back((uint32_t)i);
@@ -479,36 +410,28 @@ size_t proof_words(const VShape &vs, std::vector<uint32_t> *point_words) {
 }
 
 // derive: the transcript replay, the quotient identity rebuilt from the openings, SHPLONK's folded opening as a list of (commitment, scalar)
-int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
+int derive(const plonk::Shape &sh, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
            const DecodedPoints *pre, Derived *out, int *well_formed) {
     Reader tr(proof, proof_len, pre);
-    return derive(vs, vk, instances_host, instance_lens, tr, out, well_formed);
+    return derive(sh, vk, instances_host, instance_lens, tr, out, well_formed);
 }
-int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, TranscriptReader &tr, Derived *out,
+int derive(const plonk::Shape &sh, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, TranscriptReader &tr, Derived *out,
            int *well_formed) {
-    const h2hip_plonk_shape &sh = vs.sh;
     *well_formed = 0;
-    const uint32_t k = vs.k, n = 1u << k, bf = sh.blinding_factors;
-    const uint32_t chunk = sh.degree - 2;
-    std::vector<G1Affine> fixed_comm(sh.num_fixed_total), perm_comm(sh.num_perm_columns);
+    const uint32_t k = sh.k, n = sh.n, bf = sh.blinding_factors, chunk = sh.chunk_len;
+    const uint32_t num_instance = sh.p.num_instance, num_lookups = (uint32_t)sh.lookups.size(), num_perm_columns = (uint32_t)sh.perm_columns.size();
+    std::vector<G1Affine> fixed_comm(sh.num_fixed_total), perm_comm(num_perm_columns);
     memcpy(fixed_comm.data(), vk.fixed_commitments, sizeof(G1Affine) * fixed_comm.size());
     if (!perm_comm.empty()) memcpy(perm_comm.data(), vk.permutation_commitments, sizeof(G1Affine) * perm_comm.size());
     Fr repr;
     memcpy(&repr, vk.transcript_repr, sizeof(Fr));
-    // domain constants
-    static const uint64_t ROOT[4] = {0xd34f1ed960c37c9cULL, 0x3215cf6dd39329c8ULL, 0x98865ea93dd31f74ULL, 0x03ddb9f5166d18b7ULL};
-    static const uint64_t DELTA[4] = {0x870e56bbe533e9a2ULL, 0x5b5f898e5e963f25ULL, 0x64ec26aad4c86e71ULL, 0x09226b6e22c6f0caULL};
-    Fr omega, delta;
-    memcpy(omega.l, ROOT, 32);
-    omega = fe_to_mont(omega);
+    Fr omega = fr_from_canonical_u64x4(plonk::ROOT_OF_UNITY);
     for (uint32_t i = k; i < 28; ++i) omega = fe_sqr(omega);
-    memcpy(delta.l, DELTA, 32);
-    delta = fe_to_mont(delta);
-    const Fr one = Fr::one();
+    const Fr delta = fr_from_canonical_u64x4(plonk::DELTA), one = Fr::one();
 
     tr.common_scalar(repr);
-    std::vector<std::vector<Fr>> inst(vs.num_instance);
-    for (uint32_t i = 0; i < vs.num_instance; ++i) {
+    std::vector<std::vector<Fr>> inst(num_instance);
+    for (uint32_t i = 0; i < num_instance; ++i) {
         if (instance_lens[i] > sh.usable_rows) return H2HIP_OK;   // InstanceTooLarge: rejected
         inst[i].resize(instance_lens[i]);
         if (instance_lens[i]) memcpy(inst[i].data(), instances_host[i], sizeof(Fr) * instance_lens[i]);
@@ -516,18 +439,18 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
     }
     std::vector<G1Affine> advice_comm(sh.num_advice_total);
     std::vector<Fr> challenges;
-    if (vs.phase_cols.empty()) {
+    if (!sh.phased) {   // (also a one-phase key of the multi-phase configuration, whose phase_cols[0] is every column in index order)
         for (auto &c : advice_comm) c = tr.read_point();
     } else {   // phase by phase, each followed by its challenges (only the RLC gates query one, challenge 0)
-        for (size_t ph = 0; ph < vs.phase_cols.size(); ++ph) {
-            for (int c : vs.phase_cols[ph]) advice_comm[c] = tr.read_point();
-            for (uint32_t i = 0; i < vs.phase_challenges[ph]; ++i) challenges.push_back(tr.squeeze_challenge());
+        for (size_t ph = 0; ph < sh.phase_cols.size(); ++ph) {
+            for (int c : sh.phase_cols[ph]) advice_comm[c] = tr.read_point();
+            for (uint32_t i = 0; i < sh.phase_challenges[ph]; ++i) challenges.push_back(tr.squeeze_challenge());
         }
     }
-    if (!vs.rlc_gates.empty() && challenges.empty()) return H2HIP_OK;   // (vshape_rlc requires the challenge)
+    if (sh.num_rlc && challenges.empty()) return H2HIP_OK;   // (Shape::init_rlc requires the challenge)
     const Fr theta = tr.squeeze_challenge();
-    std::vector<G1Affine> lk_a_comm(sh.num_lookups), lk_s_comm(sh.num_lookups), lk_z_comm(sh.num_lookups), permz_comm(sh.num_perm_sets);
-    for (uint32_t i = 0; i < sh.num_lookups; ++i) {
+    std::vector<G1Affine> lk_a_comm(num_lookups), lk_s_comm(num_lookups), lk_z_comm(num_lookups), permz_comm(sh.num_perm_sets);
+    for (uint32_t i = 0; i < num_lookups; ++i) {
         lk_a_comm[i] = tr.read_point();
         lk_s_comm[i] = tr.read_point();
     }
@@ -540,14 +463,15 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
     for (auto &c : h_comm) c = tr.read_point();
     const Fr x = tr.squeeze_challenge();
     // evaluations, in the prover's order
-    std::vector<Fr> adv_ev(vs.adv_q.size());
+    const auto &adv_q = sh.advice_queries;
+    std::vector<Fr> adv_ev(adv_q.size());
     for (auto &e : adv_ev) e = tr.read_scalar();
     std::map<std::pair<int, int>, Fr> adv_at_q;
-    for (size_t i = 0; i < vs.adv_q.size(); ++i) adv_at_q[vs.adv_q[i]] = adv_ev[i];
+    for (size_t i = 0; i < adv_q.size(); ++i) adv_at_q[adv_q[i]] = adv_ev[i];
     std::vector<Fr> fixed_ev(sh.num_fixed_total, Fr::zero());
-    for (int c : vs.fixed_q) fixed_ev[c] = tr.read_scalar();
+    for (const auto &q : sh.fixed_queries) fixed_ev[q.first] = tr.read_scalar();   // (every fixed column is queried at the current row)
     const Fr random_eval = tr.read_scalar();
-    std::vector<Fr> sigma_ev(sh.num_perm_columns);
+    std::vector<Fr> sigma_ev(num_perm_columns);
     for (auto &e : sigma_ev) e = tr.read_scalar();
     struct PermEv {
         Fr e0, e1, e2;
@@ -561,7 +485,7 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
     struct LkEv {
         Fr pe, pne, ae, aie, se;
     };
-    std::vector<LkEv> lk_ev(sh.num_lookups);
+    std::vector<LkEv> lk_ev(num_lookups);
     for (auto &l : lk_ev) {
         l.pe = tr.read_scalar();
         l.pne = tr.read_scalar();
@@ -580,10 +504,10 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
     auto l_i = [&](int r) -> Fr {   // l_r(x) = (x^n - 1) * omega^r / (n * (x - omega^r))
         int64_t rr = ((int64_t)r % (int64_t)n + (int64_t)n) % (int64_t)n;
         Fr wi = fe_pow_u64(omega, (uint64_t)rr);
-        return fe_mul(fe_mul(fe_sub(xn, one), wi), fe_inv(fe_mul(fr_u64(n), fe_sub(x, wi))));
+        return fe_mul(fe_mul(fe_sub(xn, one), wi), fe_inv(fe_mul(fr_from_u64(n), fe_sub(x, wi))));
     };
     if (fe_sub(xn, one).is_zero()) return H2HIP_OK;   // x on the domain: negligible; reject rather than divide by zero
-    std::vector<Fr> inst_ev(vs.num_instance, Fr::zero());
+    std::vector<Fr> inst_ev(num_instance, Fr::zero());
     {   // l_j(x) for every instance row j, with ONE inversion (Montgomery's trick) for all the denominators n * (x - omega^j)
         size_t rows = 0;
         for (const auto &col : inst) rows = std::max(rows, col.size());
@@ -591,7 +515,7 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
         Fr wi = one, run = one;
         for (size_t j = 0; j < rows; ++j) {
             lj[j] = fe_mul(fe_sub(xn, one), wi);
-            den[j] = fe_mul(fr_u64(n), fe_sub(x, wi));
+            den[j] = fe_mul(fr_from_u64(n), fe_sub(x, wi));
             pre_prod[j] = run;
             run = fe_mul(run, den[j]);
             wi = fe_mul(wi, omega);
@@ -601,7 +525,7 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
             lj[j] = fe_mul(lj[j], fe_mul(inv, pre_prod[j]));
             inv = fe_mul(inv, den[j]);
         }
-        for (uint32_t c = 0; c < vs.num_instance; ++c)
+        for (uint32_t c = 0; c < num_instance; ++c)
             for (size_t j = 0; j < inst[c].size(); ++j) inst_ev[c] = fe_add(inst_ev[c], fe_mul(inst[c][j], lj[j]));
     }
     const Fr l_last = l_i(-(int)(bf + 1)), l_0 = l_i(0);
@@ -609,10 +533,10 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
     for (uint32_t r = 1; r <= bf; ++r) l_blind = fe_add(l_blind, l_i(-(int)(bf + 1) + (int)r));
     const Fr active = fe_sub(fe_sub(one, l_last), l_blind);
     auto adv_at = [&](int col, int r) -> Fr { return adv_at_q[{col, r}]; };
-    auto col_eval = [&](const VCol &c) -> Fr { return c.kind == 0 ? fixed_ev[c.index] : c.kind == 1 ? adv_at(c.index, 0) : inst_ev[c.index]; };
-    auto compress = [&](const std::vector<VExpr> &exprs) -> Fr {
+    auto col_eval = [&](const plonk::ColumnRef &c) -> Fr { return c.kind == 0 ? fixed_ev[c.index] : c.kind == 1 ? adv_at(c.index, 0) : inst_ev[c.index]; };
+    auto compress = [&](const std::vector<plonk::ColumnProduct> &exprs) -> Fr {
         Fr acc = Fr::zero();
-        for (const VExpr &e : exprs) {
+        for (const plonk::ColumnProduct &e : exprs) {
             Fr t = one;
             for (size_t i = 0; i < e.size(); ++i) t = i ? fe_mul(t, col_eval(e[i])) : col_eval(e[i]);
             acc = fe_add(fe_mul(acc, theta), t);
@@ -621,11 +545,11 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
     };
     Fr expected = Fr::zero();
     auto fold = [&](const Fr &term) { expected = fe_add(fe_mul(expected, y), term); };
-    for (const auto &g : vs.gates) {
+    for (const auto &g : sh.gates()) {
         const int a = g.second;
         fold(fe_mul(fixed_ev[g.first], fe_sub(fe_add(adv_at(a, 0), fe_mul(adv_at(a, 1), adv_at(a, 2))), adv_at(a, 3))));
     }
-    for (const auto &g : vs.rlc_gates) {
+    for (const auto &g : sh.rlc_gates()) {
         const int a = g.second;
         fold(fe_mul(fixed_ev[g.first], fe_sub(fe_add(fe_mul(adv_at(a, 0), challenges[0]), adv_at(a, 1)), adv_at(a, 2))));
     }
@@ -635,20 +559,22 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
         fold(fe_mul(l_last, fe_sub(fe_sqr(zl), zl)));
         for (uint32_t si = 1; si < sh.num_perm_sets; ++si) fold(fe_mul(l_0, fe_sub(perm_ev[si].e0, perm_ev[si - 1].e2)));
         for (uint32_t si = 0; si < sh.num_perm_sets; ++si) {
-            const uint32_t c0 = si * chunk, c1 = std::min<uint32_t>(c0 + chunk, sh.num_perm_columns);
+            const uint32_t c0 = si * chunk, c1 = std::min<uint32_t>(c0 + chunk, num_perm_columns);
             Fr left = perm_ev[si].e1, right = perm_ev[si].e0;
             Fr cur = fe_mul(fe_mul(beta, x), fe_pow_u64(delta, c0));
-            for (uint32_t c = c0; c < c1; ++c) left = fe_mul(left, fe_add(fe_add(col_eval(vs.perm[c]), fe_mul(beta, sigma_ev[c])), gamma));
+            for (uint32_t c = c0; c < c1; ++c) left = fe_mul(left, fe_add(fe_add(col_eval(sh.perm_columns[c]), fe_mul(beta, sigma_ev[c])), gamma));
             for (uint32_t c = c0; c < c1; ++c) {
-                right = fe_mul(right, fe_add(fe_add(col_eval(vs.perm[c]), cur), gamma));
+                right = fe_mul(right, fe_add(fe_add(col_eval(sh.perm_columns[c]), cur), gamma));
                 cur = fe_mul(cur, delta);
             }
             fold(fe_mul(active, fe_sub(left, right)));
         }
     }
-    for (uint32_t li = 0; li < sh.num_lookups; ++li) {
+    for (uint32_t li = 0; li < num_lookups; ++li) {
         const LkEv &l = lk_ev[li];
-        const Fr inp = compress(vs.lk_in[li]), tab = compress(vs.lk_tab[li]);
+        std::vector<plonk::ColumnProduct> lk_in, lk_tab;
+        sh.lookup_exprs(li, lk_in, lk_tab);
+        const Fr inp = compress(lk_in), tab = compress(lk_tab);
         fold(fe_mul(l_0, fe_sub(one, l.pe)));
         fold(fe_mul(l_last, fe_sub(fe_sqr(l.pe), l.pe)));
         fold(fe_mul(active, fe_sub(fe_mul(fe_mul(l.pne, fe_add(l.ae, beta)), fe_add(l.se, gamma)), fe_mul(fe_mul(l.pe, fe_add(inp, beta)), fe_add(tab, gamma)))));
@@ -666,13 +592,13 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
         comm.push_back({vk_slot, c});
         return (int)comm.size() - 1;
     };
-    std::vector<VQuery> queries;
+    std::vector<plonk::Query> queries;
     std::vector<int> adv_key(sh.num_advice_total);
     for (uint32_t c = 0; c < sh.num_advice_total; ++c) adv_key[c] = add_comm(advice_comm[c]);
-    for (size_t i = 0; i < vs.adv_q.size(); ++i) queries.push_back({adv_key[vs.adv_q[i].first], rot(vs.adv_q[i].second), adv_ev[i]});
+    for (size_t i = 0; i < adv_q.size(); ++i) queries.push_back({adv_key[adv_q[i].first], rot(adv_q[i].second), adv_ev[i]});
     const Fr x_next = rot(1), x_last = rot(-(int)(bf + 1)), x_inv = rot(-1);
     {
-        std::vector<VQuery> tail;
+        std::vector<plonk::Query> tail;
         for (uint32_t si = 0; si < sh.num_perm_sets; ++si) {
             int key = add_comm(permz_comm[si]);
             queries.push_back({key, x, perm_ev[si].e0});
@@ -681,7 +607,7 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
         }
         for (size_t t = tail.size(); t-- > 0;) queries.push_back(tail[t]);
     }
-    for (uint32_t li = 0; li < sh.num_lookups; ++li) {
+    for (uint32_t li = 0; li < num_lookups; ++li) {
         int kz = add_comm(lk_z_comm[li]), ka = add_comm(lk_a_comm[li]), ks = add_comm(lk_s_comm[li]);
         const LkEv &l = lk_ev[li];
         queries.push_back({kz, x, l.pe});
@@ -690,8 +616,8 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
         queries.push_back({ka, x_inv, l.aie});
         queries.push_back({kz, x_next, l.pne});
     }
-    for (int c : vs.fixed_q) queries.push_back({add_comm(fixed_comm[c], c), x, fixed_ev[c]});
-    for (uint32_t j = 0; j < sh.num_perm_columns; ++j) queries.push_back({add_comm(perm_comm[j], (int)(sh.num_fixed_total + j)), x, sigma_ev[j]});
+    for (const auto &q : sh.fixed_queries) queries.push_back({add_comm(fixed_comm[q.first], q.first), x, fixed_ev[q.first]});
+    for (uint32_t j = 0; j < num_perm_columns; ++j) queries.push_back({add_comm(perm_comm[j], (int)(sh.num_fixed_total + j)), x, sigma_ev[j]});
     // h commitment = sum_i xn^i H_i: no point arithmetic here, the pieces enter the list with scalar * xn^i
     G1Affine h_placeholder;
     h_placeholder.x = Fq::zero();
@@ -699,9 +625,12 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
     queries.push_back({add_comm(h_placeholder, -2), x, expected_h});
     queries.push_back({add_comm(random_comm), x, random_eval});
     // ---- VerifierSHPLONK
-    std::vector<VSet> sets;
+    // the grouping the prover ran.  It returns no sets beyond 64 distinct points; a verifier opens at seven at most (x and its rotations
+    // -1, 1, 2, 3 and last), so an empty result is a rejection, never an index out of range below
+    std::vector<plonk::RotationSet> sets;
     std::vector<Fr> super_points;
-    intermediate_sets(queries, sets, super_points);
+    plonk::construct_intermediate_sets(queries, sets, super_points);
+    if (sets.empty()) return H2HIP_OK;
     const Fr y2 = tr.squeeze_challenge(), v = tr.squeeze_challenge();
     const G1Affine h1 = tr.read_point();
     const Fr u = tr.squeeze_challenge();
@@ -728,9 +657,9 @@ int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, 
         }
         const Fr scale = fe_mul(vpow, z_diff);
         Fr r_inner = Fr::zero(), ypow = one;
-        for (size_t j = 0; j < sets[i].keys.size(); ++j) {
+        for (size_t j = 0; j < sets[i].polys.size(); ++j) {
             r_inner = fe_add(r_inner, fe_mul(ypow, interpolate_at(sets[i].points, sets[i].evals[j], u)));
-            const CommRef &c = comm[sets[i].keys[j]];
+            const CommRef &c = comm[sets[i].polys[j]];
             Fr s = fe_mul(scale, ypow);
             if (c.vk_slot == -2) {
                 for (const G1Affine &piece : h_comm) {
@@ -773,111 +702,34 @@ int pairing_verdict(const VKey &vk, const G1Affine &left, const G1Affine &outer,
     return H2HIP_OK;
 }
 
-int verify_one(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
-               int *accepted) {
+// derive over any reader, then the finish on the host; acc_out (optional) receives (W', outer), the pair the pairing decides
+static int verify_over(const plonk::Shape &sh, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, TranscriptReader &tr,
+                       int *accepted, void *acc_out) {
     *accepted = 0;
-    H2_CHK(check_key(vs, vk, instances_host, instance_lens));
+    H2_CHK(check_key(sh, vk, instances_host, instance_lens));
     Derived d;
     int well_formed = 0;
-    H2_CHK(derive(vs, vk, instances_host, instance_lens, proof, proof_len, nullptr, &d, &well_formed));
+    H2_CHK(derive(sh, vk, instances_host, instance_lens, tr, &d, &well_formed));
     if (!well_formed) return H2HIP_OK;   // a malformed proof is a rejection
-    return pairing_verdict(vk, d.w, outer_on_host(vk, d), accepted);
-}
-
-// FlexGateConfig + RangeConfig: num_advice gate columns, then the dedicated lookup-advice columns; the q_lookup lookup (if any) reads gate column 0
-static void base_vshape(VShape &vs, uint32_t k, uint32_t num_advice, uint32_t num_fixed, uint32_t num_instance) {
-    const h2hip_plonk_shape &sh = vs.sh;
-    vs.k = k;
-    vs.num_instance = num_instance;
-    const uint32_t nla = sh.num_advice_total - num_advice;
-    const bool with_range = sh.table_col >= 0, single = sh.q_lookup_col >= 0;
-    for (uint32_t a = 0; a < num_advice; ++a)
-        for (int r = 0; r < 4; ++r) vs.adv_q.push_back({(int)a, r});
-    for (uint32_t i = 0; i < nla; ++i) vs.adv_q.push_back({(int)(num_advice + i), 0});
-    // fixed columns in query order: constants, table, q_lookup, q_enable
-    for (uint32_t i = 0; i < num_fixed; ++i) vs.fixed_q.push_back(sh.first_constant_col + (int)i);
-    if (with_range) vs.fixed_q.push_back(sh.table_col);
-    if (single) vs.fixed_q.push_back(sh.q_lookup_col);
-    for (uint32_t i = 0; i < num_advice; ++i) vs.fixed_q.push_back(sh.first_q_enable_col + (int)i);
-    // permutation columns: constants, advice (gate then lookup), instance
-    for (uint32_t i = 0; i < num_fixed; ++i) vs.perm.push_back({0, sh.first_constant_col + (int)i});
-    for (uint32_t i = 0; i < sh.num_advice_total; ++i) vs.perm.push_back({1, (int)i});
-    for (uint32_t i = 0; i < num_instance; ++i) vs.perm.push_back({2, (int)i});
-    for (uint32_t a = 0; a < num_advice; ++a) vs.gates.push_back({sh.first_q_enable_col + (int)a, (int)a});
-    for (uint32_t li = 0; li < sh.num_lookups; ++li) {
-        const uint32_t ded = li - (single ? 1 : 0);   // index among the dedicated lookup-advice columns
-        vs.lk_in.push_back({single && li == 0 ? VExpr{{0, sh.q_lookup_col}, {1, 0}} : VExpr{{1, (int)(num_advice + ded)}}});
-        vs.lk_tab.push_back({VExpr{{0, sh.table_col}}});
+    const G1Affine outer = outer_on_host(vk, d);
+    if (acc_out) {
+        memcpy(acc_out, &d.w, sizeof(G1Affine));
+        memcpy((uint8_t *)acc_out + sizeof(G1Affine), &outer, sizeof(G1Affine));
     }
+    return pairing_verdict(vk, d.w, outer, accepted);
 }
-
-int vshape_base(const h2hip_base_circuit_params *params, VShape &vs) {
-    H2_CHK(h2hip_plonk_shape_of(params, &vs.sh));
-    base_vshape(vs, params->k, params->num_advice, params->num_fixed, params->num_instance);
-    return H2HIP_OK;
+int verify_one(const plonk::Shape &sh, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
+               int *accepted) {
+    Reader tr(proof, proof_len);
+    return verify_over(sh, vk, instances_host, instance_lens, tr, accepted, nullptr);
 }
-// the dynamic-lookup configuration (include/h2hip.h states its layout): the lookups' compressed input and table evaluations are Horner sums in
-// theta of the advice / fixed openings at x
-int vshape_dyn(const h2hip_dyn_circuit_params *params, VShape &vs) {
-    H2_CHK(h2hip_plonk_shape_of_dyn(params, &vs.sh));
-    const h2hip_plonk_shape &sh = vs.sh;
-    vs.k = params->k;
-    vs.num_instance = 0;
-    const uint32_t m = params->key_cols, L = params->lu_sets, ndyn = m * (1 + L);
-    for (uint32_t c = 0; c < ndyn; ++c) vs.adv_q.push_back({(int)c, 0});
-    for (uint32_t a = 0; a < params->num_advice; ++a)
-        for (int r = 0; r < 4; ++r) vs.adv_q.push_back({(int)(ndyn + a), r});
-    for (uint32_t c = 0; c < sh.num_fixed_total; ++c) vs.fixed_q.push_back((int)c);
-    for (uint32_t c = 0; c < ndyn; ++c) vs.perm.push_back({1, (int)c});
-    for (uint32_t i = 0; i < params->num_fixed; ++i) vs.perm.push_back({0, sh.first_constant_col + (int)i});
-    for (uint32_t a = 0; a < params->num_advice; ++a) vs.perm.push_back({1, (int)(ndyn + a)});
-    for (uint32_t a = 0; a < params->num_advice; ++a) vs.gates.push_back({sh.first_q_enable_col + (int)a, (int)(ndyn + a)});
-    for (uint32_t s = 0; s < L; ++s) {
-        std::vector<VExpr> in, tab;
-        for (uint32_t j = 0; j < m; ++j) {
-            in.push_back(VExpr{{1, (int)(m * (1 + s) + j)}});
-            tab.push_back(VExpr{{1, (int)j}});
-        }
-        in.push_back(VExpr{{0, (int)(1 + s)}});
-        tab.push_back(VExpr{{0, 0}});
-        vs.lk_in.push_back(in);
-        vs.lk_tab.push_back(tab);
-    }
-    return H2HIP_OK;
-}
-// the multi-phase configuration (include/h2hip.h states its layout): the advice commitments are read phase by phase, each phase's challenges
-// squeezed after them; one used phase without challenges is the BaseConfig of that phase's BaseCircuitParams
-int vshape_phased(const h2hip_phased_circuit_params *params, VShape &vs) {
-    h2hip_base_circuit_params bp;
-    bool phased = false;
-    H2_CHK(plonk_phased_layout(*params, &vs.sh, &vs.phase_cols, vs.phase_challenges, &phased, &bp));
-    if (!phased) {
-        vs = VShape();
-        return vshape_base(&bp, vs);
-    }
-    base_vshape(vs, bp.k, bp.num_advice, bp.num_fixed, bp.num_instance);
-    return H2HIP_OK;
-}
-// the RLC configuration (include/h2hip.h states its layout): the multi-phase layout of `base` with the RLC columns' queries, selectors, gates
-// and permutation columns behind it
-int vshape_rlc(const h2hip_rlc_circuit_params *params, VShape &vs) {
-    h2hip_base_circuit_params bp;
-    bool phased = false;
-    H2_CHK(plonk_phased_layout(params->base, &vs.sh, &vs.phase_cols, vs.phase_challenges, &phased, &bp, params));
-    const uint32_t R = params->num_rlc_advice;
-    h2hip_plonk_shape base_sh = vs.sh;   // base_vshape reads the column counts: what the layout has without the RLC columns
-    base_sh.num_advice_total -= R;
-    std::swap(vs.sh, base_sh);
-    base_vshape(vs, bp.k, bp.num_advice, bp.num_fixed, bp.num_instance);
-    std::swap(vs.sh, base_sh);
-    const int first_adv = (int)(vs.sh.num_advice_total - R), first_q = (int)(vs.sh.num_fixed_total - R);
-    for (uint32_t j = 0; j < R; ++j) {
-        for (int r = 0; r < 3; ++r) vs.adv_q.push_back({first_adv + (int)j, r});
-        vs.fixed_q.push_back(first_q + (int)j);
-        vs.perm.push_back({1, first_adv + (int)j});
-        vs.rlc_gates.push_back({first_q + (int)j, first_adv + (int)j});
-    }
-    return H2HIP_OK;
+// what the four h2hip_plonk_verify_proof* entries run behind their argument checks
+static int verify_kind(int kind, const void *params, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof,
+                       size_t proof_len, int *accepted) {
+    *accepted = 0;
+    plonk::Shape sh;
+    H2_CHK(plonk::shape_of_kind(kind, params, sh));
+    return verify_one(sh, vk, instances_host, instance_lens, proof, proof_len, accepted);
 }
 
 }  // namespace verifier
@@ -893,11 +745,8 @@ int h2hip_plonk_verify_proof(const h2hip_base_circuit_params *params, const void
                              const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
                              const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted) {
     H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
-    *accepted = 0;
-    VShape vs;
-    H2_CHK(vshape_base(params, vs));
-    return verify_one(vs, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, instances_host, instance_lens, proof, proof_len,
-                      accepted);
+    return verify_kind(H2HIP_CIRCUIT_BASE, params, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, instances_host, instance_lens, proof,
+                       proof_len, accepted);
 }
 
 // the same for the dynamic-lookup configuration (include/h2hip.h states its layout): the lookups' compressed input and table evaluations are
@@ -906,10 +755,8 @@ int h2hip_plonk_verify_proof_dyn(const h2hip_dyn_circuit_params *params, const v
                                  const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const uint8_t *proof, size_t proof_len,
                                  int *accepted) {
     H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
-    *accepted = 0;
-    VShape vs;
-    H2_CHK(vshape_dyn(params, vs));
-    return verify_one(vs, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, nullptr, nullptr, proof, proof_len, accepted);
+    return verify_kind(H2HIP_CIRCUIT_DYN, params, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, nullptr, nullptr, proof,
+                       proof_len, accepted);
 }
 
 // the same for the multi-phase configuration (include/h2hip.h states its layout): the advice commitments are read phase by phase, each phase's
@@ -918,11 +765,8 @@ int h2hip_plonk_verify_proof_phased(const h2hip_phased_circuit_params *params, c
                                     const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
                                     const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted) {
     H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
-    *accepted = 0;
-    VShape vs;
-    H2_CHK(vshape_phased(params, vs));
-    return verify_one(vs, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, instances_host, instance_lens, proof, proof_len,
-                      accepted);
+    return verify_kind(H2HIP_CIRCUIT_PHASED, params, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, instances_host, instance_lens, proof,
+                       proof_len, accepted);
 }
 
 // the same for the RLC configuration (include/h2hip.h states its layout): as the multi-phase verifier, with challenge 0 of the replay in the
@@ -931,11 +775,8 @@ int h2hip_plonk_verify_proof_rlc(const h2hip_rlc_circuit_params *params, const v
                                  const void *transcript_repr, const void *g1, const void *g2, const void *s_g2, const void *const *instances_host,
                                  const size_t *instance_lens, const uint8_t *proof, size_t proof_len, int *accepted) {
     H2_REQUIRE(params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && proof && accepted, "NULL argument");
-    *accepted = 0;
-    VShape vs;
-    H2_CHK(vshape_rlc(params, vs));
-    return verify_one(vs, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, instances_host, instance_lens, proof, proof_len,
-                      accepted);
+    return verify_kind(H2HIP_CIRCUIT_RLC, params, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, instances_host, instance_lens, proof,
+                       proof_len, accepted);
 }
 
 // verify_proof over the caller's transcript (include/h2hip.h): derive over the callback reader, the scalar multiplications on the host, one
@@ -949,31 +790,12 @@ int h2hip_plonk_verify_proof_transcript(int kind, const void *params, const void
     if (acc_out) memset(acc_out, 0, 2 * sizeof(G1Affine));
     H2_REQUIRE(t->common_scalar && t->read_point && t->read_scalar && t->squeeze_challenge,
                "h2hip_plonk_verify_proof_transcript: the transcript lacks common_scalar, read_point, read_scalar or squeeze_challenge");
-    VShape vs;
-    if (kind == H2HIP_CIRCUIT_BASE) {
-        H2_CHK(vshape_base((const h2hip_base_circuit_params *)params, vs));
-    } else if (kind == H2HIP_CIRCUIT_DYN) {
-        H2_CHK(vshape_dyn((const h2hip_dyn_circuit_params *)params, vs));
-    } else if (kind == H2HIP_CIRCUIT_PHASED) {
-        H2_CHK(vshape_phased((const h2hip_phased_circuit_params *)params, vs));
-    } else if (kind == H2HIP_CIRCUIT_RLC) {
-        H2_CHK(vshape_rlc((const h2hip_rlc_circuit_params *)params, vs));
-    } else {
-        H2_REQUIRE(false, "unknown circuit kind (H2HIP_CIRCUIT_BASE / _DYN / _PHASED / _RLC)");
-    }
-    const VKey vk = {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2};
-    H2_CHK(check_key(vs, vk, instances_host, instance_lens));
+    H2_REQUIRE(kind == H2HIP_CIRCUIT_BASE || kind == H2HIP_CIRCUIT_DYN || kind == H2HIP_CIRCUIT_PHASED || kind == H2HIP_CIRCUIT_RLC,
+               "unknown circuit kind (H2HIP_CIRCUIT_BASE / _DYN / _PHASED / _RLC)");
+    plonk::Shape sh;
+    H2_CHK(plonk::shape_of_kind(kind, params, sh));
     CallbackReader tr(t);
-    Derived d;
-    int well_formed = 0;
-    H2_CHK(derive(vs, vk, instances_host, instance_lens, tr, &d, &well_formed));
-    if (!well_formed) return H2HIP_OK;   // a malformed proof is a rejection
-    const G1Affine outer = outer_on_host(vk, d);
-    if (acc_out) {
-        memcpy(acc_out, &d.w, sizeof(G1Affine));
-        memcpy((uint8_t *)acc_out + sizeof(G1Affine), &outer, sizeof(G1Affine));
-    }
-    return pairing_verdict(vk, d.w, outer, accepted);
+    return verify_over(sh, {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2}, instances_host, instance_lens, tr, accepted, acc_out);
 }
 
 // e(P_0, Q_0) * ... * e(P_{n-1}, Q_{n-1}) == 1 — the "final CPU-side pairing" of the north star as an entry of its own (the verifier above ends in

@@ -3,50 +3,28 @@
 //           right-hand point `outer`, and the scalar on g[0] — or rejects the proof;
 //   finish  turns that into a verdict: the scalar multiplications (on the host for one proof, one device MSM for a batch) and ONE pairing
 //           e(W', s_g2) * e(-outer, g2) == 1.
+// Both read the constraint system from the prover's plonk::Shape (plonk_shape.h); every h2hip_plonk_verify_proof* entry, the transcript
+// entry and the batch entry build it with plonk::shape_of_kind from their params.
 #pragma once
 #include <utility>
 #include <vector>
 
 #include "host_field.h"
 #include "internal.h"
+#include "plonk_shape.h"
 #include "transcript.h"
 
 namespace h2 {
 namespace verifier {
-
-// What the verifier needs of a constraint system: the query lists in the prover's order, the permutation columns, the gates, and every lookup
-// as (input, table) lists of expressions, each expression a product of columns queried at the current row; a lookup's expressions are
-// compressed by Horner in theta (upstream's compress_expressions) — BaseConfig's lookups have one expression each, so theta drops out there.
-struct VCol {
-    int kind;   // 0 = fixed, 1 = advice, 2 = instance
-    int index;
-};
-using VExpr = std::vector<VCol>;   // product of columns at Rotation::cur()
-struct VShape {
-    h2hip_plonk_shape sh;
-    uint32_t k, num_instance;
-    std::vector<std::pair<int, int>> adv_q;   // (advice column, rotation)
-    std::vector<int> fixed_q;                 // fixed columns, queried at the current row
-    std::vector<VCol> perm;
-    std::vector<std::pair<int, int>> gates;   // (q_enable fixed column, advice column): q * (a + b*c - d) at rotations 0..3
-    std::vector<std::pair<int, int>> rlc_gates;   // (q_rlc fixed column, advice column): q * (a * challenge 0 + a(wX) - a(w^2 X)), folded behind `gates`
-    std::vector<std::vector<VExpr>> lk_in, lk_tab;
-    std::vector<std::vector<int>> phase_cols;   // multi-phase: the advice columns of each phase, whose commitments come phase by phase
-    uint32_t phase_challenges[H2HIP_MAX_PHASE] = {0, 0, 0};
-};
-// the VShape of each configuration (what the three h2hip_plonk_verify_proof* entries build from their params)
-int vshape_base(const h2hip_base_circuit_params *params, VShape &vs);
-int vshape_dyn(const h2hip_dyn_circuit_params *params, VShape &vs);
-int vshape_phased(const h2hip_phased_circuit_params *params, VShape &vs);
-int vshape_rlc(const h2hip_rlc_circuit_params *params, VShape &vs);
 
 // the verifying key and the SRS elements, as the entry points receive them
 struct VKey {
     const void *fixed_commitments, *permutation_commitments, *transcript_repr, *g1, *g2, *s_g2;
 };
 // A proof is a table of 32-byte words; which of them are points follows from the shape: every commitment up to the h pieces, then the
-// evaluations, then h1 and h2.  Returns the number of words of a well-formed proof; point_words (optional): the point words in reading order.
-size_t proof_words(const VShape &vs, std::vector<uint32_t> *point_words);
+// evaluations, then h1 and h2 (which Shape::num_commitments counts as its last two).  Returns the number of words of a well-formed proof;
+// point_words (optional): the point words in reading order.
+size_t proof_words(const plonk::Shape &sh, std::vector<uint32_t> *point_words);
 // a proof's points already decompressed, in reading order, each with its verdict (h2hip_g1_decompress_checked_dev: 0 ok)
 struct DecodedPoints {
     const G1Affine *pts;
@@ -64,19 +42,19 @@ struct Derived {
     Fr g0_scalar;
 };
 // argument checks common to every entry (H2HIP_ERR_INVALID): NULL key parts the shape needs, g2 / s_g2 on the twist
-int check_key(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens);
+int check_key(const plonk::Shape &sh, const VKey &vk, const void *const *instances_host, const size_t *instance_lens);
 // pre == nullptr: every point is decompressed on the host (a square root each).  *well_formed = 0 is a rejection: malformed bytes, a
 // non-canonical scalar, a bad point, an instance column longer than usable_rows, x on the domain, a zero z_diff.
-int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
+int derive(const plonk::Shape &sh, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
            const DecodedPoints *pre, Derived *out, int *well_formed);
 // the same over any reader (transcript.h): the built-in Blake2b reader above, or the adapter over the caller's callbacks.  A reader whose
 // err is set makes derive return it.
-int derive(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, TranscriptReader &tr, Derived *out,
+int derive(const plonk::Shape &sh, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, TranscriptReader &tr, Derived *out,
            int *well_formed);
 G1Affine outer_on_host(const VKey &vk, const Derived &d);                                 // the terms' sum by host double-and-add
 int pairing_verdict(const VKey &vk, const G1Affine &left, const G1Affine &outer, int *accepted);   // e(left, s_g2) * e(-outer, g2) == 1
-// derive + finish for one proof: what h2hip_plonk_verify_proof* compute
-int verify_one(const VShape &vs, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
+// derive + finish for one proof: the argument checks that need the shape, then what h2hip_plonk_verify_proof* compute
+int verify_one(const plonk::Shape &sh, const VKey &vk, const void *const *instances_host, const size_t *instance_lens, const uint8_t *proof, size_t proof_len,
                int *accepted);
 template <class P>
 inline bool canonical(const Fe<P> &a) {

@@ -60,12 +60,11 @@ struct TempBases {
     }
 };
 
-int batch_impl(h2hip_ctx *ctx, const VShape &vs, const VKey &vk, size_t num_proofs, const void *const *instances_host, const size_t *instance_lens,
+int batch_impl(h2hip_ctx *ctx, const plonk::Shape &sh, const VKey &vk, size_t num_proofs, const void *const *instances_host, const size_t *instance_lens,
                const uint8_t *const *proofs, const size_t *proof_lens, const std::vector<Fr> &rho, int *accepted, uint8_t *rejected_out, void *acc_out) {
-    const h2hip_plonk_shape &sh = vs.sh;
-    const size_t ni = vs.num_instance;
+    const size_t ni = sh.p.num_instance, num_perm_columns = sh.perm_columns.size();
     std::vector<uint32_t> point_words;
-    const size_t words = proof_words(vs, &point_words), npts = point_words.size();
+    const size_t words = proof_words(sh, &point_words), npts = point_words.size();
     std::vector<uint8_t> bad(num_proofs, 0);
     StageClock clock(ctx);
     // ---- upload every proof of the right length; decompress all their points at once
@@ -100,10 +99,10 @@ int batch_impl(h2hip_ctx *ctx, const VShape &vs, const VKey &vk, size_t num_proo
     }
     clock.lap("upload_decompress");
     // ---- derive per proof; fold the scalars
-    const size_t nvk = (size_t)sh.num_fixed_total + sh.num_perm_columns;
+    const size_t nvk = (size_t)sh.num_fixed_total + num_perm_columns;
     std::vector<G1Affine> vk_pts(nvk);
     memcpy(vk_pts.data(), vk.fixed_commitments, sizeof(G1Affine) * sh.num_fixed_total);
-    if (sh.num_perm_columns) memcpy(vk_pts.data() + sh.num_fixed_total, vk.permutation_commitments, sizeof(G1Affine) * sh.num_perm_columns);
+    if (num_perm_columns) memcpy(vk_pts.data() + sh.num_fixed_total, vk.permutation_commitments, sizeof(G1Affine) * num_perm_columns);
     std::vector<Fr> vk_scalars(nvk, Fr::zero());
     Fr g0_scalar = Fr::zero();
     std::vector<G1Affine> base_pts;   // the proofs' own points, then (below) the key's and g[0]
@@ -114,7 +113,7 @@ int batch_impl(h2hip_ctx *ctx, const VShape &vs, const VKey &vk, size_t num_proo
         const DecodedPoints pre = {pts.data() + j * npts, status.data() + j * npts, npts};
         Derived d;
         int well_formed = 0;
-        H2_CHK(derive(vs, vk, ni ? instances_host + i * ni : nullptr, ni ? instance_lens + i * ni : nullptr, proofs[i], proof_lens[i], &pre, &d, &well_formed));
+        H2_CHK(derive(sh, vk, ni ? instances_host + i * ni : nullptr, ni ? instance_lens + i * ni : nullptr, proofs[i], proof_lens[i], &pre, &d, &well_formed));
         if (!well_formed) {
             bad[i] = 1;
             continue;
@@ -168,7 +167,7 @@ int batch_impl(h2hip_ctx *ctx, const VShape &vs, const VKey &vk, size_t num_proo
     if (!pairing_ok && rejected_out) {   // the slow path, on failure only: which of the well-formed proofs is it?
         for (size_t i : good) {
             int ok = 0;
-            H2_CHK(verify_one(vs, vk, ni ? instances_host + i * ni : nullptr, ni ? instance_lens + i * ni : nullptr, proofs[i], proof_lens[i], &ok));
+            H2_CHK(verify_one(sh, vk, ni ? instances_host + i * ni : nullptr, ni ? instance_lens + i * ni : nullptr, proofs[i], proof_lens[i], &ok));
             if (!ok) bad[i] = 1;
         }
     }
@@ -191,16 +190,10 @@ int h2hip_plonk_verify_batch(h2hip_ctx *ctx, int kind, const void *params, const
     H2_REQUIRE(ctx && params && fixed_commitments && transcript_repr && g1 && g2 && s_g2 && rng && accepted && (num_proofs == 0 || (proofs && proof_lens)),
                "NULL argument");
     *accepted = 0;
-    VShape vs;
-    if (kind == H2HIP_CIRCUIT_BASE) {
-        H2_CHK(vshape_base((const h2hip_base_circuit_params *)params, vs));
-    } else if (kind == H2HIP_CIRCUIT_DYN) {
-        H2_CHK(vshape_dyn((const h2hip_dyn_circuit_params *)params, vs));
-    } else if (kind == H2HIP_CIRCUIT_PHASED) {
-        H2_CHK(vshape_phased((const h2hip_phased_circuit_params *)params, vs));
-    } else {
-        H2_REQUIRE(false, "unknown circuit kind (H2HIP_CIRCUIT_BASE / _DYN / _PHASED)");
-    }
+    // RLC keys are not batched (include/h2hip.h): the single verifier and the transcript entry take them
+    H2_REQUIRE(kind == H2HIP_CIRCUIT_BASE || kind == H2HIP_CIRCUIT_DYN || kind == H2HIP_CIRCUIT_PHASED, "unknown circuit kind (H2HIP_CIRCUIT_BASE / _DYN / _PHASED)");
+    plonk::Shape sh;
+    H2_CHK(plonk::shape_of_kind(kind, params, sh));
     const VKey vk = {fixed_commitments, permutation_commitments, transcript_repr, g1, g2, s_g2};
     if (acc_out) memset(acc_out, 0, 2 * sizeof(G1Affine));
     if (rejected_out && num_proofs) memset(rejected_out, 0, num_proofs);
@@ -208,12 +201,12 @@ int h2hip_plonk_verify_batch(h2hip_ctx *ctx, int kind, const void *params, const
         *accepted = 1;
         return H2HIP_OK;
     }
-    H2_CHK(check_key(vs, vk, instances_host, instance_lens));
+    H2_CHK(check_key(sh, vk, instances_host, instance_lens));
     for (size_t i = 0; i < num_proofs; ++i) H2_REQUIRE(proofs[i] || proof_lens[i] == 0, "NULL argument");
     std::vector<Fr> rho(num_proofs);
     rng(rng_user, rho.data(), num_proofs);   // ONE call
     for (const Fr &r : rho) H2_REQUIRE(canonical(r) && !r.is_zero(), "the rng returned a zero (or non-canonical) combiner: that proof would go unchecked");
-    return batch_impl(ctx, vs, vk, num_proofs, instances_host, instance_lens, proofs, proof_lens, rho, accepted, rejected_out, acc_out);
+    return batch_impl(ctx, sh, vk, num_proofs, instances_host, instance_lens, proofs, proof_lens, rho, accepted, rejected_out, acc_out);
 }
 
 }  // extern "C"

@@ -11,7 +11,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P, V, L, S = "halo2-lib_amd/csrc/plonk.hip", "halo2-lib_amd/csrc/verifier.hip", "halo2-lib_amd/csrc/lookup.hip", "halo2-lib_amd/csrc/srs.hip"
-PI, PP = "halo2-lib_amd/csrc/plonk_internal.h", "halo2-lib_amd/csrc/plonk_prove.hip"   # the shape / key; one proof (ProofRun)
+PI, PP = "halo2-lib_amd/csrc/plonk_shape.h", "halo2-lib_amd/csrc/plonk_prove.hip"   # the shape (prover and verifier read the one Shape); one proof (ProofRun)
+SS = "halo2-lib_amd/csrc/shplonk_sets.h"   # SHPLONK's grouping, shared by the prover and the verifier
 TR = "halo2-lib_amd/csrc/transcript.h"   # the transcript interface and its built-in Blake2b writer
 OP, OT, OB = "oracle/plonk.py", "oracle/transcript.py", "oracle/bn254.py"
 HP, VR, PL = "halo2-lib_amd/halo2_proofs.py", "halo2-lib_amd/virtual_region.py", "halo2-lib_amd/plonk.py"
@@ -38,11 +39,11 @@ ITEMS = [
      [(PP, "const Fr *tail = stage.draw(n - u);")], [(OP, "class CountingRng:")],
      "the RNG is a callback (`h2hip_rng_fill_fn`): move the `stage.draw(...)` calls of `ProofRun`'s rounds; no kernel changes"),
     ("SHPLONK rotation sets", "`construct_intermediate_sets`: commitments grouped by their set of opening points in first-appearance order, `super_point_set` in first-appearance order; challenges y, v, then u after the first commitment",
-     [(PP, "static void construct_intermediate_sets(")], [(OP, "def construct_intermediate_sets(queries):")],
-     "both functions (the verifier in verifier.hip shares the product's)"),
+     [(SS, "inline void construct_intermediate_sets(")], [(OP, "def construct_intermediate_sets(queries):")],
+     "both functions (the product's one copy serves `ProofRun` and the verifier's `derive`)"),
     ("compressed G1 flag bits", "32-byte little-endian x with sign(y) in bit 6 and the identity flag in bit 7 of byte 31",
-     [(TR, "static const unsigned SIGN_BIT = 6, INF_BIT = 7;"), (V, "static const unsigned SIGN_BIT = 6, INF_BIT = 7;")], [(OT, "SIGN_BIT, INF_BIT = 6, 7")],
-     "the two constants (three places); SRS files in `Processed` encoding pass the positions as arguments (`h2hip_g1_decompress_batch_dev`)"),
+     [(TR, "static const unsigned SIGN_BIT = 6, INF_BIT = 7;")], [(OT, "SIGN_BIT, INF_BIT = 6, 7")],
+     "the two constants (the product's pair serves the writer and the verifier's reader); SRS files in `Processed` encoding pass the positions as arguments (`h2hip_g1_decompress_batch_dev`)"),
     ("transcript framing", "Blake2b-512 personalised `Halo2-Transcript`; prefix bytes 0x01 point (x, y canonical LE), 0x02 scalar, 0x00 before a squeeze of a CLONE; challenge = 64-byte digest reduced mod r",
      [(TR, "struct Transcript final : ProverTranscript {   // Blake2bWrite")], [(OT, "def squeeze_challenge(self) -> int:")],
      "`Transcript` (transcript.h) / `TranscriptRead` (verifier.hip) and oracle/transcript.py; the hash itself is pinned by RFC 7693 (tests/test_external_vectors.py)"),
@@ -73,14 +74,14 @@ ITEMS = [
      "`virtual_region.py` (and `host/halo2_proofs.hpp`); affects the sigma polynomials (verifying key), not validity"),
     ("multi-phase advice order", "after the instances, per phase in order: the blinding rows of the phase's advice columns (column by column, index order), one blind per column, the phase's commitments in index order, then the challenges `challenge_usable_after(phase)` squeezed (Challenge255); the next phase's witness is synthesised with them; theta follows the last phase.  The advice commitments in the proof are grouped by phase, not in column order; the RNG draws the same number of values before the random polynomial",
      [(PP, "// Multi-phase keys [UPSTREAM-RECALL: create_proof's per-phase loop]")], [(PO, "# ---- advice, phase by phase [UPSTREAM-RECALL")],
-     "`ProofRun::round1_phased` (and `blind_phase`), the verifier's phase loop in `derive` (verifier.hip), and the oracle's block"),
+     "`ProofRun::round1_phased` (and `blind_phase`) with the phase loop of `derive` (verifier.hip), which replays it over the same `Shape::phase_cols`, and the oracle's block"),
     ("batch verification", "`BatchVerifier::finalize` / `AccumulatorStrategy` combine the proofs' final pairing inputs with random scalars into ONE `DualMSM` check; only the verdict is shared with upstream (no bytes), and which random scalars upstream draws, and from what, is not relied on",
      [(VB, "upstream's BatchVerifier / AccumulatorStrategy seam [UPSTREAM-RECALL")], [],
      "nothing to flip for correctness: any non-zero combiners decide the same batches except with probability ~ N/r; the combiners come through the caller's `h2hip_rng_fill_fn`"),
     ("RLC configuration (downstream's `RlcConfig` / `RlcChip`, not in the reference tree)", "`RlcConfig::configure` runs after `BaseConfig::configure`: per RLC column a SecondPhase advice column with equality enabled, a selector `q_rlc`, and the gate `q_rlc * (a * gamma + a_next - a_next2)` at rotations 0, 1, 2 with gamma = the first challenge usable after FirstPhase; so the RLC columns take the last advice indices, their selectors the last fixed columns, their permutation columns come last, and their gates fold into h(X) behind the flex gates.  `compute_rlc_fixed_len` lays a chain out as v_0, v_1, r_1, v_2, r_2, ... with r_i = r_(i-1) * gamma + v_i, and a chain that crosses a column break repeats the break cell at the top of the next column",
      [(PI, "int init_rlc(const h2hip_rlc_circuit_params &rp) {"), (PP, "if (sh.num_rlc) {   // the RLC gates follow the flex gates"), (RL, "// the cells: a head piece's v_0, v_1, r_1, v_2, r_2, ...")],
      [(RO, "def rlc(cls, params: \"PL.RlcCircuitParams\") -> \"Shape\":"), (RO, "def rlc_gate(acc, q, a, gamma: int, y, step: int, T: int = 1):")],
-     "`Shape::layout`'s `num_rlc` lines (column numbering, query and permutation order), the position of the RLC call inside `ProofRun::quotient_pass` and of the `rlc_gates` loop in `derive` (verifier.hip); the cell order is `rlc_place_kernel`'s index arithmetic"),
+     "`Shape::layout`'s `num_rlc` lines (column numbering, query and permutation order: the one place, prover and verifier read it); the fold position is the RLC call inside `ProofRun::quotient_pass` with the `rlc_gates()` loop of `derive`; the cell order is `rlc_place_kernel`'s index arithmetic"),
 ]
 
 
