@@ -165,6 +165,10 @@ pub struct h2hip_ec_op {
 }
 pub const H2HIP_EC_ADD_UNEQUAL: u32 = 0;
 pub const H2HIP_EC_DOUBLE: u32 = 1;
+pub const H2HIP_EC_SUB_UNEQUAL: u32 = 3;
+pub const H2HIP_FP_CMP_REDUCE_A: u32 = 1;
+pub const H2HIP_FP_CMP_REDUCE_B: u32 = 2;
+pub const H2HIP_FP_CMP_EQUAL: u32 = 4;
 pub const H2HIP_POSEIDON_ABSORB_ONLY: u32 = 1;
 pub const H2HIP_POSEIDON_WITH_CONSTS: u32 = 2;
 /// a later phase's witness: `fill(user, phase, challenges, num_challenges, columns_dev, num_columns)` (include/h2hip.h states the contract)
@@ -446,6 +450,13 @@ extern "C" {
                              results_dev: *mut c_void, results_len: usize, units_host: *const h2hip_ec_op, count: usize) -> c_int;
     pub fn h2hip_ec_range_checks(break_points_host: *const u32, num_columns: usize, params: *const h2hip_fp_params, op: u32,
                                  units_host: *const h2hip_ec_op, lookup_slots_host: *const u64, count: usize, checks_out: *mut h2hip_range_check) -> c_int;
+    pub fn h2hip_fp_cmp_layout(params: *const h2hip_fp_params, op: u32, num_cells: *mut usize, num_own_cells: *mut usize, num_lookup_cells: *mut usize,
+                               results_per_unit: *mut usize, ranges: *mut h2hip_fp_mul_range, out_cell_offsets: *mut u32) -> c_int;
+    pub fn h2hip_fp_cmp_fill_dev(ctx: *mut h2hip_ctx, columns_dev: *const *mut c_void, num_columns: usize, usable_rows: usize,
+                                 break_points_host: *const u32, params: *const h2hip_fp_params, op: u32, values_dev: *const c_void, values_len: usize,
+                                 results_dev: *mut c_void, results_len: usize, units_host: *const h2hip_fp_mul, count: usize) -> c_int;
+    pub fn h2hip_fp_cmp_range_checks(break_points_host: *const u32, num_columns: usize, params: *const h2hip_fp_params, op: u32,
+                                     units_host: *const h2hip_fp_mul, lookup_slots_host: *const u64, count: usize, checks_out: *mut h2hip_range_check) -> c_int;
     pub fn h2hip_quotient_rlc_gate_batch_dev(ctx: *mut h2hip_ctx, acc_dev: *mut c_void, q_dev: *const *const c_void, a_dev: *const *const c_void,
                                              count: usize, ext_k: u32, k: u32, gamma: *const c_void, y: *const c_void) -> c_int;
     pub fn h2hip_plonk_pk_free(ctx: *mut h2hip_ctx, pk: *mut h2hip_plonk_pk);

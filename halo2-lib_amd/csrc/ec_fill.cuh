@@ -1,4 +1,4 @@
-// The cells of one ec_add_unequal (non-strict) or ec_double of halo2-ecc (include/h2hip.h states the form), as host and device code.  A unit is
+// The cells of one ec_add_unequal, ec_sub_unequal (both non-strict) or ec_double of halo2-ecc (include/h2hip.h states the form), as host and device code.  A unit is
 // a fixed sequence of segments (a subtraction, one limb of a no-carry product, the load of lambda, one limb of a reduction, ...) that
 // ec_prepare lays out once per call from the parameters: the same table gives h2hip_ec_layout its numbers, the place kernel its slots and
 // h2hip_ec_range_checks its gaps.  ec_fill.hip's first kernel runs ec_solve_unit in one lane per unit (lambda by an inversion mod p, three
@@ -19,12 +19,15 @@ constexpr int EC_WA = 10;   // words of an operand integer (n k <= 318 bits) and
 // 4 + j is entry j of the unit's record.  In context order:
 //   ADD_UNEQUAL  dx dy lambda lambda*dx qc=that-dy lambda^2 that-P.x x3nc=that-Q.x x3 dx13=P.x-x3 lambda*dx13 y3nc=that-P.y y3
 //   DOUBLE       2y 3x 3x*x lambda lambda*2y qc=that-3x*x lambda^2 2x x3nc=lambda^2-2x x3 dx=P.x-x3 lambda*dx y3nc=that-P.y y3
+//   SUB_UNEQUAL  ADD_UNEQUAL's with sy = Q.y + P.y for dy and qc = lambda*dx + sy: NUM holds sy, the numerator of lambda is -sy
 template <uint32_t OP>
 struct EcRegs;
 template <>
 struct EcRegs<H2HIP_EC_ADD_UNEQUAL> {
     enum : uint32_t { DEN = 4, NUM = 5, LAM = 6, LD = 7, QC = 8, LSQ = 9, T1 = 10, X3NC = 11, X3 = 12, DX13 = 13, LDX = 14, Y3NC = 15, Y3 = 16 };
 };
+template <>
+struct EcRegs<H2HIP_EC_SUB_UNEQUAL> : EcRegs<H2HIP_EC_ADD_UNEQUAL> {};
 template <>
 struct EcRegs<H2HIP_EC_DOUBLE> {
     enum : uint32_t { DEN = 4, THREE_X = 5, NUM = 6, LAM = 7, LD = 8, QC = 9, LSQ = 10, T1 = 11, X3NC = 12, X3 = 13, DX13 = 14, LDX = 15, Y3NC = 16, Y3 = 17 };
@@ -46,7 +49,7 @@ H2_HD uint32_t ec_c_rb(uint32_t k, uint32_t r) { return 2 * k + 5 + r; }
 
 // one segment of a unit = one lane of the place kernel.  a, b: the registers read, c: the register of the result (SMUL: b is the constant's
 // index, no register); i: the limb; red: the reduction
-enum : uint8_t { EC_SUB, EC_SMUL, EC_MUL, EC_MULNAT, EC_LOAD, EC_ZC, EC_CM, EC_QSH, EC_CARRY, EC_EVALQ, EC_EVALO, EC_NATZ, EC_NATC };
+enum : uint8_t { EC_SUB, EC_SMUL, EC_MUL, EC_MULNAT, EC_LOAD, EC_ZC, EC_CM, EC_QSH, EC_CARRY, EC_EVALQ, EC_EVALO, EC_NATZ, EC_NATC, EC_ADD };
 struct EcSeg {
     uint32_t off;   // of the segment's first cell in the unit's run
     uint8_t type, i, a, b, c, red, pad0, pad1;
@@ -214,6 +217,10 @@ H2_HD void ec_sub_cells(const Fr *a, const Fr *b, Fr *out) {
     static_for<K + 1>([&](auto i) H2_INL { out[decltype(i)::value] = fe_sub(a[decltype(i)::value], b[decltype(i)::value]); });
 }
 template <int K>
+H2_HD void ec_add_cells(const Fr *a, const Fr *b, Fr *out) {
+    static_for<K + 1>([&](auto i) H2_INL { out[decltype(i)::value] = fe_add(a[decltype(i)::value], b[decltype(i)::value]); });
+}
+template <int K>
 H2_HD void ec_smul_cells(const Fr *a, const Fr &c, Fr *out) {
     static_for<K + 1>([&](auto i) H2_INL { out[decltype(i)::value] = fe_mul(a[decltype(i)::value], c); });
 }
@@ -288,17 +295,23 @@ H2_HD void ec_reduce_cells(const EcCall &ec, Fr *rec, Fr *res, const Fr *a, Fr *
     }
 }
 
-// the denominator and the numerator of lambda as integers: ADD_UNEQUAL X2 - X1 and Y2 - Y1, DOUBLE 2 Y and 3 X X
+// the denominator and the numerator of lambda as integers: ADD_UNEQUAL X2 - X1 and Y2 - Y1, SUB_UNEQUAL X2 - X1 and -(Y2 + Y1) (neg_divide_unsafe:
+// the zero check lambda den - num is then lambda (X2 - X1) + (Y2 + Y1)), DOUBLE 2 Y and 3 X X
 template <int K, uint32_t OP>
 H2_HD void ec_den_num(const EcCall &ec, const Fr *P, const Fr *Q, uint32_t (&den)[EC_WA], uint32_t &sden, uint32_t (&num)[2 * EC_WA], uint32_t &snum) {
-    if constexpr (OP == H2HIP_EC_ADD_UNEQUAL) {
+    if constexpr (OP != H2HIP_EC_DOUBLE) {
         uint32_t A[EC_WA], B[EC_WA], D[EC_WA];
         ec_load_int<K>(P, ec.n, A);
         ec_load_int<K>(Q, ec.n, B);
         sden = mp_absdiff<EC_WA>(B, A, den);
         ec_load_int<K>(P + K + 1, ec.n, A);
         ec_load_int<K>(Q + K + 1, ec.n, B);
-        snum = mp_absdiff<EC_WA>(B, A, D);
+        if constexpr (OP == H2HIP_EC_ADD_UNEQUAL)
+            snum = mp_absdiff<EC_WA>(B, A, D);
+        else {
+            mp_add<EC_WA>(B, A, D);   // Y2 + Y1 < 2^319 (n k <= 318)
+            snum = 1;
+        }
         mp_widen(D, num);
     } else {
         uint32_t A[EC_WA], T[EC_WA];
@@ -320,7 +333,7 @@ H2_HD void ec_solve_unit(const EcCall &ec, const h2hip_ec_op &unit, uint32_t u) 
     constexpr uint32_t K1 = K + 1;
     const uint32_t n = ec.n;
     const Fr *cs = ec.consts, *P = ec.values + unit.p_offset, *Q = nullptr;
-    if constexpr (OP == H2HIP_EC_ADD_UNEQUAL) Q = ec.values + unit.q_offset;   // (ignored for DOUBLE: not even formed)
+    if constexpr (OP != H2HIP_EC_DOUBLE) Q = ec.values + unit.q_offset;   // (ignored for DOUBLE: not even formed)
     Fr *rec = ec.rec + (size_t)u * ec_record_len(K);
     Fr *res = ec.results ? ec.results + (size_t)u * ec_result_len(K) : nullptr;
     const auto reg = [&](uint32_t r) H2_INL { return rec + (r - 4) * K1; };
@@ -328,6 +341,9 @@ H2_HD void ec_solve_unit(const EcCall &ec, const h2hip_ec_op &unit, uint32_t u) 
     if constexpr (OP == H2HIP_EC_ADD_UNEQUAL) {
         ec_sub_cells<K>(Q, P, reg(R::DEN));
         ec_sub_cells<K>(Q + K1, P + K1, reg(R::NUM));
+    } else if constexpr (OP == H2HIP_EC_SUB_UNEQUAL) {
+        ec_sub_cells<K>(Q, P, reg(R::DEN));
+        ec_add_cells<K>(Q + K1, P + K1, reg(R::NUM));
     } else {
         ec_smul_cells<K>(P + K1, cs[ec_c_two(K)], reg(R::DEN));
         ec_smul_cells<K>(P, cs[ec_c_two(K) + 1], reg(R::THREE_X));
@@ -368,10 +384,13 @@ H2_HD void ec_solve_unit(const EcCall &ec, const h2hip_ec_op &unit, uint32_t u) 
         lr[K] = nat;
         if (res) res[2 * K1 + K] = nat;
     }
-    // -- divide_unsafe's constraint: lambda den - num carries to zero mod p
+    // -- divide_unsafe's constraint: lambda den - num carries to zero mod p (SUB_UNEQUAL: neg_divide_unsafe's, lambda den + sy)
     {
         ec_mul_cells<K>(reg(R::LAM), reg(R::DEN), reg(R::LD));
-        ec_sub_cells<K>(reg(R::LD), reg(R::NUM), reg(R::QC));
+        if constexpr (OP == H2HIP_EC_SUB_UNEQUAL)
+            ec_add_cells<K>(reg(R::LD), reg(R::NUM), reg(R::QC));
+        else
+            ec_sub_cells<K>(reg(R::LD), reg(R::NUM), reg(R::QC));
         uint32_t Qm[EC_WA + 1], O[EC_WA + 1], sign;
         {
             uint32_t den[EC_WA], num[2 * EC_WA], lam[EC_WA], X[2 * EC_WA], sden, snum;
@@ -385,7 +404,7 @@ H2_HD void ec_solve_unit(const EcCall &ec, const h2hip_ec_op &unit, uint32_t u) 
     // -- x3 = lambda^2 - x1 - x2 (- 2 x)
     {
         ec_mul_cells<K>(reg(R::LAM), reg(R::LAM), reg(R::LSQ));
-        if constexpr (OP == H2HIP_EC_ADD_UNEQUAL) {
+        if constexpr (OP != H2HIP_EC_DOUBLE) {
             ec_sub_cells<K>(reg(R::LSQ), P, reg(R::T1));
             ec_sub_cells<K>(reg(R::T1), Q, reg(R::X3NC));
         } else {
@@ -396,7 +415,7 @@ H2_HD void ec_solve_unit(const EcCall &ec, const h2hip_ec_op &unit, uint32_t u) 
         {
             uint32_t lam[EC_WA], A[EC_WA], B[EC_WA], C[2 * EC_WA], X[2 * EC_WA];
             ec_load_int<K>(P, n, A);
-            if constexpr (OP == H2HIP_EC_ADD_UNEQUAL)
+            if constexpr (OP != H2HIP_EC_DOUBLE)
                 ec_load_int<K>(Q, n, B);
             else
                 static_for<EC_WA>([&](auto j) H2_INL { B[decltype(j)::value] = A[decltype(j)::value]; });
@@ -434,7 +453,7 @@ H2_HD void ec_place_slot(const EcCall &ec, const h2hip_ec_op &unit, uint32_t u, 
     const uint32_t k = ec.k;
     const EcSeg sg = ec.segs[slot];
     const Fr *cs = ec.consts, *rec = ec.rec + (size_t)u * ec_record_len(k);
-    // (registers 2 and 3, Q's, occur in ADD_UNEQUAL's table only; SMUL's b is no register)
+    // (registers 2 and 3, Q's, occur in ADD_UNEQUAL's and SUB_UNEQUAL's tables only; SMUL's b is no register)
     const Fr *a = ec_reg(ec, unit, rec, sg.a), *b = sg.type == EC_SMUL ? nullptr : ec_reg(ec, unit, rec, sg.b), *c = ec_reg(ec, unit, rec, sg.c);
     const Fr *rr = rec + ec_red_base(k, sg.red), *q = rr, *check = rr + k + 1, *negc = rr + 2 * k + 1;
     const Fr zero = Fr::zero(), one = Fr::one();
@@ -447,6 +466,14 @@ H2_HD void ec_place_slot(const EcCall &ec, const h2hip_ec_op &unit, uint32_t u, 
             out.put(b[j]);
             out.put(one);
             out.put(a[j]);
+        }
+        break;
+    case EC_ADD:   // per cell of the registers: a, b, 1, out = a + b
+        for (uint32_t j = 0; j <= k; ++j) {
+            out.put(a[j]);
+            out.put(b[j]);
+            out.put(one);
+            out.put(c[j]);
         }
         break;
     case EC_SMUL:   // 0, a, Constant, out
@@ -571,7 +598,11 @@ struct EcBuilder {
         s.gap_lookups[s.ngaps++] = range_unit_lookups(L, rem);
         at += range_unit_cells(L, rem, 0);
     }
-    // each returns the max_limb_bits of its result (bigint/sub_no_carry.rs:21, scalar_mul_no_carry.rs:17, mul_no_carry.rs:34)
+    // each returns the max_limb_bits of its result (bigint/sub_no_carry.rs:21, add_no_carry.rs:22, scalar_mul_no_carry.rs:17, mul_no_carry.rs:34)
+    uint32_t add(uint32_t a, uint32_t b, uint32_t out, uint32_t ma, uint32_t mb) {
+        seg(EC_ADD, 0, a, b, out, 0, 4 * (k + 1));
+        return std::max(ma, mb) + 1;
+    }
     uint32_t sub(uint32_t a, uint32_t b, uint32_t out, uint32_t ma, uint32_t mb) {
         seg(EC_SUB, 0, a, b, out, 0, 4 * (k + 1));
         return std::max(ma, mb) + 1;
@@ -624,7 +655,7 @@ struct EcBuilder {
 };
 // nullptr when the parameters and the operation are served, else the reason.  ec, consts (EC_CONSTS entries): optional
 inline const char *ec_prepare(const h2hip_fp_params &pr, uint32_t op, EcShape &sh, EcCall *ec, Fr *consts) {
-    if (op != H2HIP_EC_ADD_UNEQUAL && op != H2HIP_EC_DOUBLE) return "unknown op";
+    if (op != H2HIP_EC_ADD_UNEQUAL && op != H2HIP_EC_DOUBLE && op != H2HIP_EC_SUB_UNEQUAL) return "unknown op";
     FpCall fc;
     Fr fcs[FP_CONSTS];
     const char *bad = fp_prepare(pr, sh.fp, &fc, fcs);
@@ -638,11 +669,12 @@ inline const char *ec_prepare(const h2hip_fp_params &pr, uint32_t op, EcShape &s
     sh.k = k;
     sh.nsegs = sh.ngaps = 0;
     EcBuilder b{sh, n, k, sh.fp.lb, pbits};
-    if (op == H2HIP_EC_ADD_UNEQUAL) {   // ecc/mod.rs:153-179, fields/mod.rs:217-238
+    if (op != H2HIP_EC_DOUBLE) {   // ecc/mod.rs:153-179, fields/mod.rs:217-238; SUB_UNEQUAL: ecc/mod.rs:219-246, fields/mod.rs:256-277
         using R = EcRegs<H2HIP_EC_ADD_UNEQUAL>;
-        const uint32_t dx = b.sub(2, 0, R::DEN, n, n), dy = b.sub(3, 1, R::NUM, n, n);
+        const bool sub = op == H2HIP_EC_SUB_UNEQUAL;
+        const uint32_t dx = b.sub(2, 0, R::DEN, n, n), dy = sub ? b.add(3, 1, R::NUM, n, n) : b.sub(3, 1, R::NUM, n, n);
         b.load(R::LAM);
-        const uint32_t ld = b.mul(R::LAM, R::DEN, R::LD, n, dx), qc = b.sub(R::LD, R::NUM, R::QC, ld, dy);
+        const uint32_t ld = b.mul(R::LAM, R::DEN, R::LD, n, dx), qc = sub ? b.add(R::LD, R::NUM, R::QC, ld, dy) : b.sub(R::LD, R::NUM, R::QC, ld, dy);
         b.reduce(0, R::QC, 0, 0, qc);
         const uint32_t lsq = b.mul(R::LAM, R::LAM, R::LSQ, n, n), t1 = b.sub(R::LSQ, 0, R::T1, lsq, n), x3nc = b.sub(R::T1, 2, R::X3NC, t1, n);
         b.reduce(1, R::X3NC, R::X3, 0, x3nc);

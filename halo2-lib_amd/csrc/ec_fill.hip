@@ -1,7 +1,8 @@
-// EccChip's ec_add_unequal (non-strict) and ec_double filled on the device: every gate cell the reference writes for one curve operation on
-// points lying on the device — sub_no_carry / scalar_mul_no_carry / mul_no_carry, divide_unsafe (load_private of lambda and
-// check_carry_mod_to_zero) and two carry_mod — except the cells of its 9 k range checks, which are left as gaps for
-// h2hip_range_fill_checks_dev (halo2-ecc/src/ecc/mod.rs:153-179, :302-327, fields/mod.rs:217-238; include/h2hip.h states the cell form).
+// EccChip's ec_add_unequal, ec_sub_unequal (both non-strict) and ec_double filled on the device: every gate cell the reference writes for one
+// curve operation on points lying on the device — sub_no_carry / add_no_carry / scalar_mul_no_carry / mul_no_carry, divide_unsafe or
+// neg_divide_unsafe (load_private of lambda and check_carry_mod_to_zero) and two carry_mod — except the cells of its 9 k range checks, which
+// are left as gaps for h2hip_range_fill_checks_dev (halo2-ecc/src/ecc/mod.rs:153-179, :219-246, :302-327, fields/mod.rs:217-238, :256-277;
+// include/h2hip.h states the cell form).
 //
 // Two kernels on the context's stream, their code in ec_fill.cuh as host and device code.  ec_solve_kernel: one lane per unit, templated on
 // k and on the operation, does lambda's inversion mod p (division steps, the modulus a kernel argument) and the three signed floor divisions
@@ -82,7 +83,7 @@ int h2hip_ec_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_colum
     const char *bad = ec_prepare(*params, op, sh, &ec, consts);
     H2_REQUIRE(!bad, bad);
     const uint32_t k = sh.k, slots = sh.nsegs, cells = sh.total, point = 2 * (k + 1);
-    const bool two = op == H2HIP_EC_ADD_UNEQUAL;
+    const bool two = op != H2HIP_EC_DOUBLE, sub = op == H2HIP_EC_SUB_UNEQUAL;
     H2_REQUIRE(count <= ((uint64_t)1 << 32) / slots, "more than 2^32 slots (count * the unit's segments) in one call");
     TraceRuns runs{columns_dev, num_columns, usable_rows, break_points_host};
     bad = runs.args_bad();
@@ -120,7 +121,11 @@ int h2hip_ec_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_colum
     const h2hip_ec_op *units = (const h2hip_ec_op *)t.at[0];
     const dim3 solve_grid((uint32_t)((count + EC_SOLVE_BLOCK - 1) / EC_SOLVE_BLOCK)), solve_block(EC_SOLVE_BLOCK);
     prof_begin(ctx, "ec_solve_kernel");
-    if (k == 3 && two)
+    if (k == 3 && sub)
+        hipLaunchKernelGGL((ec_solve_kernel<3, H2HIP_EC_SUB_UNEQUAL>), solve_grid, solve_block, 0, ctx->stream, ec, units, (uint32_t)count);
+    else if (sub)
+        hipLaunchKernelGGL((ec_solve_kernel<4, H2HIP_EC_SUB_UNEQUAL>), solve_grid, solve_block, 0, ctx->stream, ec, units, (uint32_t)count);
+    else if (k == 3 && two)
         hipLaunchKernelGGL((ec_solve_kernel<3, H2HIP_EC_ADD_UNEQUAL>), solve_grid, solve_block, 0, ctx->stream, ec, units, (uint32_t)count);
     else if (k == 3)
         hipLaunchKernelGGL((ec_solve_kernel<3, H2HIP_EC_DOUBLE>), solve_grid, solve_block, 0, ctx->stream, ec, units, (uint32_t)count);

@@ -1,0 +1,133 @@
+// FpChip's comparisons filled on the device: every gate cell that enforce_less_than_p writes for one or both of two CRT integers lying on
+// the device and that big_is_equal::assign writes for the pair — gate.add of the borrow, is_less_than's seven cells, is_zero, gate.sub,
+// gate.and — except the cells of the k range checks per enforced operand, which are left as gaps for h2hip_range_fill_checks_dev
+// (halo2-ecc/src/fields/fp.rs:123-142, bigint/big_is_equal.rs, halo2-base/src/gates/range/mod.rs:646-687, flex_gate/mod.rs:789-823;
+// include/h2hip.h states the cell form).  The unit sits in front of a curve operation where the reference's check_points_are_unequal
+// puts it (ecc/mod.rs:183-202).
+//
+// Two kernels on the context's stream, their code in fp_cmp.cuh as host and device code.  fp_cmp_solve_kernel: one lane per unit, Fr
+// additions and one limb extraction per cell, no inversion.  fp_cmp_place_kernel: one lane per (unit, segment); the lane of an is_zero
+// segment inverts its own cell (up to 3 k independent inversions per unit, none waiting for another).  No LDS, no atomics, no workgroup
+// waits for another.
+#include "internal.h"
+#include "fp_cmp.cuh"
+#include "trace_host.h"
+
+namespace h2 {
+
+constexpr uint32_t CMP_SOLVE_BLOCK = 64, CMP_PLACE_BLOCK = 256;
+
+static_assert(sizeof(CmpSeg) == 8, "the segment table is uploaded as the host laid it out");
+
+__global__ __launch_bounds__(CMP_SOLVE_BLOCK) void fp_cmp_solve_kernel(CmpCall cc, const h2hip_fp_mul *__restrict__ units, uint32_t count) {
+    const uint32_t u = blockIdx.x * CMP_SOLVE_BLOCK + threadIdx.x;
+    if (u >= count) return;
+    cmp_solve_unit(cc, units[u], u);
+}
+// cc.values may point into the columns or at an earlier call's results (at cells this call does not write: the host checked)
+__global__ __launch_bounds__(CMP_PLACE_BLOCK) void fp_cmp_place_kernel(CmpCall cc, const h2hip_fp_mul *__restrict__ units, uint32_t slots, uint64_t lanes) {
+    const uint64_t g = (uint64_t)blockIdx.x * CMP_PLACE_BLOCK + threadIdx.x;
+    if (g >= lanes) return;
+    const uint32_t u = (uint32_t)(g / slots);
+    cmp_place_slot(cc, units[u], u, (uint32_t)(g - (uint64_t)u * slots));
+}
+
+}  // namespace h2
+
+using namespace h2;
+
+extern "C" {
+
+int h2hip_fp_cmp_layout(const h2hip_fp_params *params, uint32_t op, size_t *num_cells, size_t *num_own_cells, size_t *num_lookup_cells,
+                        size_t *results_per_unit, h2hip_fp_mul_range *ranges, uint32_t *out_cell_offsets) {
+    H2_REQUIRE(params && num_cells && num_own_cells && num_lookup_cells && results_per_unit && ranges && out_cell_offsets, "NULL argument");
+    CmpShape sh;
+    const char *bad = cmp_prepare(*params, op, sh, nullptr, nullptr);
+    H2_REQUIRE(!bad, bad);
+    *num_cells = sh.total;
+    *num_own_cells = sh.own;
+    *num_lookup_cells = sh.num_lookups;
+    *results_per_unit = cmp_result_len(sh.k, op);
+    for (uint32_t j = 0; j < sh.ngaps; ++j) ranges[j] = sh.gaps[j];
+    for (uint32_t j = 0; j < 3; ++j) out_cell_offsets[j] = sh.out_offsets[j];
+    return H2HIP_OK;
+}
+
+int h2hip_fp_cmp_range_checks(const uint32_t *break_points_host, size_t num_columns, const h2hip_fp_params *params, uint32_t op,
+                              const h2hip_fp_mul *units_host, const uint64_t *lookup_slots_host, size_t count, h2hip_range_check *checks_out) {
+    if (!count) return H2HIP_OK;
+    H2_REQUIRE(params && units_host && lookup_slots_host && checks_out, "NULL argument");
+    CmpShape sh;
+    const char *bad = cmp_prepare(*params, op, sh, nullptr, nullptr);
+    H2_REQUIRE(!bad, bad);
+    // one width; unit-major: rows and lookup slots ascend with the units
+    const uint32_t ngaps = sh.ngaps;
+    return fp_gap_checks(break_points_host, num_columns, sh.gaps, sh.gap_lookups, ngaps, cmp_result_len(sh.k, op), units_host, lookup_slots_host, count, checks_out,
+                         [ngaps](size_t u, uint32_t j) { return u * ngaps + j; });
+}
+
+int h2hip_fp_cmp_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const uint32_t *break_points_host,
+                          const h2hip_fp_params *params, uint32_t op, const void *values_dev, size_t values_len, void *results_dev, size_t results_len,
+                          const h2hip_fp_mul *units_host, size_t count) {
+    H2_DEVICE_GUARD(ctx);
+    H2_REQUIRE(ctx, "NULL argument");
+    if (!count) return H2HIP_OK;
+    // ---- every check before anything is launched or uploaded
+    H2_REQUIRE(columns_dev && params && values_dev && units_host, "NULL argument");
+    CmpShape sh;
+    CmpCall cc;
+    Fr consts[CMP_CONSTS];
+    const char *bad = cmp_prepare(*params, op, sh, &cc, consts);
+    H2_REQUIRE(!bad, bad);
+    const uint32_t k = sh.k, slots = sh.nsegs, cells = sh.total, nres = cmp_result_len(k, op);
+    const bool reads_a = op & (H2HIP_FP_CMP_REDUCE_A | H2HIP_FP_CMP_EQUAL), reads_b = op & (H2HIP_FP_CMP_REDUCE_B | H2HIP_FP_CMP_EQUAL);
+    H2_REQUIRE(count <= ((uint64_t)1 << 32) / slots, "more than 2^32 lanes (count * the unit's segments) in one call");
+    TraceRuns runs{columns_dev, num_columns, usable_rows, break_points_host};
+    bad = runs.args_bad();
+    H2_REQUIRE(!bad, bad);
+    H2_REQUIRE(values_len <= SIZE_MAX / sizeof(Fr) && results_len <= SIZE_MAX / sizeof(Fr), "values_len / results_len is no count of field elements");
+    H2_REQUIRE(!results_dev || results_len / nres >= count, "results_len < count * the results of a unit (h2hip_fp_cmp_layout)");
+    std::vector<ByteRange> reads;
+    runs.written.reserve(count + 9);
+    reads.reserve(2 * count);
+    for (size_t j = 0; j < count; ++j) {
+        const h2hip_fp_mul &u = units_host[j];
+        bad = runs.run(u.column, u.row, cells);   // the unit's whole run, gaps included
+        H2_REQUIRE(!bad, bad);
+        H2_REQUIRE((!reads_a || operand_range(values_dev, values_len, u.a_offset, k, reads)) && (!reads_b || operand_range(values_dev, values_len, u.b_offset, k, reads)),
+                   "a unit's operand lies outside values_len");
+    }
+    // two units' cells are disjoint; the results lie in none of them; no operand lies in anything written.  Address intervals, sorted and swept.
+    bad = byte_ranges_clash(runs.written, {}, "two units' cells overlap (break copies and the range checks' gaps included)");
+    H2_REQUIRE(!bad, bad);
+    if (results_dev) runs.written.push_back(ByteRange{(uintptr_t)results_dev, (uintptr_t)results_dev + sizeof(Fr) * nres * count});
+    bad = byte_ranges_clash(runs.written, {&reads}, "the results overlap cells this call writes");
+    H2_REQUIRE(!bad, bad);
+    // ---- tables: [unit table][column pointers][break points][constants][segments], and the records
+    DevTables t;
+    Fr *rec = nullptr;
+    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_TMP2, sizeof(Fr) * cmp_record_len(k) * count, (void **)&rec));
+    H2_CHK(pack_tables(ctx, {{units_host, sizeof(h2hip_fp_mul) * count}, columns_table(runs), breaks_table(runs), {consts, sizeof(Fr) * CMP_CONSTS},
+                             {sh.segs, sizeof(CmpSeg) * slots}}, t));
+    cc.tc = t.tc;
+    cc.values = (const Fr *)values_dev;
+    cc.consts = (const Fr *)t.at[3];
+    cc.segs = (const CmpSeg *)t.at[4];
+    cc.results = (Fr *)results_dev;
+    cc.rec = rec;
+    const h2hip_fp_mul *units = (const h2hip_fp_mul *)t.at[0];
+    prof_begin(ctx, "fp_cmp_solve_kernel");
+    hipLaunchKernelGGL(fp_cmp_solve_kernel, dim3((uint32_t)((count + CMP_SOLVE_BLOCK - 1) / CMP_SOLVE_BLOCK)), dim3(CMP_SOLVE_BLOCK), 0, ctx->stream, cc, units,
+                       (uint32_t)count);
+    prof_end(ctx);
+    H2_HIPCHK(hipGetLastError());
+    const uint64_t lanes = (uint64_t)count * slots;
+    prof_begin(ctx, "fp_cmp_place_kernel");
+    hipLaunchKernelGGL(fp_cmp_place_kernel, dim3((uint32_t)((lanes + CMP_PLACE_BLOCK - 1) / CMP_PLACE_BLOCK)), dim3(CMP_PLACE_BLOCK), 0, ctx->stream, cc,
+                       units, slots, lanes);
+    prof_end(ctx);
+    H2_HIPCHK(hipGetLastError());
+    return H2HIP_OK;
+}
+
+}  // extern "C"

@@ -952,7 +952,7 @@ class EcOpStruct(C.Structure):   # h2hip_ec_op
     _fields_ = [("column", C.c_uint32), ("row", C.c_uint32), ("p_offset", C.c_uint64), ("q_offset", C.c_uint64)]
 
 
-EC_ADD_UNEQUAL, EC_DOUBLE = 0, 1
+EC_ADD_UNEQUAL, EC_DOUBLE, EC_SUB_UNEQUAL = 0, 1, 3   # (2 is no operation: the library refuses it as unknown)
 
 
 def ec_op_table(units: Sequence) -> C.Array:
@@ -984,7 +984,8 @@ def ec_layout(params: FpParamsStruct, op: int, lib=None) -> EcLayout:
 
 def ec_fill(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], params: FpParamsStruct, op: int, values_dev,
             values_len: int, results_dev, results_len: int, units, count: Optional[int] = None) -> None:
-    """h2hip_ec_fill_dev: the own cells of ec_add_unequal (non-strict, op = EC_ADD_UNEQUAL) or ec_double (EC_DOUBLE) for every unit, written down
+    """h2hip_ec_fill_dev: the own cells of ec_add_unequal (non-strict, op = EC_ADD_UNEQUAL), ec_sub_unequal (non-strict, EC_SUB_UNEQUAL: P - Q) or
+    ec_double (EC_DOUBLE) for every unit, written down
     the device columns from each unit's (column, row) across the break points; the cells of the 9 k range checks are left as gaps.  units:
     (column, row, p_offset, q_offset) tuples or a table from ec_op_table(); a point is the 2 (k + 1) Fr of values_dev from its offset (x's k
     limbs and native residue, then y's).  results_dev (or None): 9 k + 3 Fr per unit — x3, y3 (a point a later call may read), lambda, then
@@ -1031,3 +1032,104 @@ def ec_fill_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: int, 
     ec_fill(ctx, columns, usable_rows, break_points, params, op, values_dev, values_len, results_dev, results_len, arr, len(units))
     for bits, table in tables:
         range_fill_checks(ctx, columns, usable_rows, break_points, lookup_columns, results_dev, results_len, bits, params.lookup_bits, table)
+
+
+FP_CMP_REDUCE_A, FP_CMP_REDUCE_B, FP_CMP_EQUAL = 1, 2, 4
+NO_CELL = 0xFFFFFFFF
+
+
+class FpCmpLayout(NamedTuple):
+    """h2hip_fp_cmp_layout: the cells of one comparison unit (enforce_less_than_p of a and / or b, big_is_equal of the pair, by the mask), its
+    own cells (the rest are the gaps of its range checks), their lookup cells, the results entries per unit, ranges = [(cell_offset,
+    num_cells, range_bits, result_index)] of the gaps in context order, and the offsets of the final borrow cell of a's check, of b's and of
+    the equality cell (NO_CELL where the mask has none)"""
+    num_cells: int
+    num_own_cells: int
+    num_lookup_cells: int
+    results_per_unit: int
+    ranges: list
+    out_cell_offsets: list
+
+
+def fp_cmp_layout(params: FpParamsStruct, op: int, lib=None) -> FpCmpLayout:
+    lib = lib or load_library()
+    cells, own, lookups, nres = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    ranges, outs = (FpMulRangeStruct * 8)(), (C.c_uint32 * 3)()
+    code = lib.h2hip_fp_cmp_layout(C.cast(C.pointer(params), _vp), op, C.byref(cells), C.byref(own), C.byref(lookups), C.byref(nres), C.cast(ranges, _vp), outs)
+    _raise_on(code, lib)
+    ngaps = params.num_limbs * (bool(op & FP_CMP_REDUCE_A) + bool(op & FP_CMP_REDUCE_B))
+    return FpCmpLayout(cells.value, own.value, lookups.value, nres.value,
+                       [(r.cell_offset, r.num_cells, r.range_bits, r.result_index) for r in ranges[:ngaps]], list(outs))
+
+
+def fp_cmp_fill(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], params: FpParamsStruct, op: int, values_dev,
+                values_len: int, results_dev, results_len: int, units, count: Optional[int] = None) -> None:
+    """h2hip_fp_cmp_fill_dev: the own cells of FpChip's comparisons for every unit — by the mask `op`, enforce_less_than_p(a) (FP_CMP_REDUCE_A),
+    enforce_less_than_p(b) (FP_CMP_REDUCE_B), big_is_equal(a, b) (FP_CMP_EQUAL), in this order — written down the device columns from each
+    unit's (column, row) across the break points; the cells of the k range checks per enforced operand are left as gaps.  units: (column, row,
+    a_offset, b_offset) tuples or a table from fp_mul_table().  results_dev (or None): per unit, for each enforced operand s_0 .. s_{k-1} and
+    the final borrow, then for EQUAL the equality cell's value.  Stream-ordered on the context's stream."""
+    arr = _as_table(units, fp_mul_table)
+    ctx._chk(ctx.lib.h2hip_fp_cmp_fill_dev(ctx.handle, _col_array(columns), len(columns), usable_rows, _bp_array(break_points, len(columns)),
+                                           C.cast(C.pointer(params), _vp), op, _dev_ptr(values_dev), values_len, _dev_ptr(results_dev), results_len,
+                                           C.cast(arr, _vp), len(units) if count is None else count))
+
+
+def fp_cmp_range_tables(break_points: Optional[Sequence[int]], num_columns: int, params: FpParamsStruct, op: int, units, lookup_slots: Sequence[int],
+                        lib=None) -> list:
+    """h2hip_fp_cmp_range_checks: [(width, range_check_table)] of the range checks of `units`: one table (they share the width pad + lb), unit
+    by unit (rows and lookup slots ascend); none for a mask that enforces no operand.  Build it once for a layout used in every proof."""
+    lib = lib or load_library()
+    lay = fp_cmp_layout(params, op, lib)
+    count, ngaps = len(lookup_slots), len(lay.ranges)
+    if not count or not ngaps:
+        return []
+    arr = _as_table(units, fp_mul_table)
+    checks = (RangeCheckStruct * (ngaps * count))()
+    code = lib.h2hip_fp_cmp_range_checks(_bp_array(break_points, num_columns), num_columns, C.cast(C.pointer(params), _vp), op, C.cast(arr, _vp),
+                                         (C.c_uint64 * count)(*lookup_slots), count, C.cast(checks, _vp))
+    _raise_on(code, lib)
+    return [(lay.ranges[0][2], checks)]
+
+
+def fp_cmp_fill_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], lookup_columns: Sequence[int],
+                            params: FpParamsStruct, op: int, values_dev, values_len: int, results_dev, results_len: int, units,
+                            lookup_slots: Sequence[int] = (), range_tables: Optional[list] = None) -> None:
+    """fp_cmp_fill, then the one range_fill_checks call from results_dev: the whole run of every unit and its lookup cells."""
+    assert results_dev, "the range checks read results_dev"
+    arr = _as_table(units, fp_mul_table)
+    tables = range_tables if range_tables is not None else fp_cmp_range_tables(break_points, len(columns), params, op, arr, lookup_slots, ctx.lib)
+    fp_cmp_fill(ctx, columns, usable_rows, break_points, params, op, values_dev, values_len, results_dev, results_len, arr, len(units))
+    for bits, table in tables:
+        range_fill_checks(ctx, columns, usable_rows, break_points, lookup_columns, results_dev, results_len, bits, params.lookup_bits, table)
+
+
+def ec_fill_strict_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], lookup_columns: Sequence[int],
+                               params: FpParamsStruct, op: int, cmp_mask: int, values_dev, values_len: int, results_dev, results_len: int,
+                               cmp_results_dev, cmp_results_len: int, units, lookup_slots: Sequence[int], tables: Optional[tuple] = None):
+    """ec_add_unequal / ec_sub_unequal with is_strict = true (op = EC_ADD_UNEQUAL or EC_SUB_UNEQUAL): for each unit the comparison of
+    check_points_are_unequal over (P.x, Q.x) at the unit's (column, row) — cmp_mask = FP_CMP_EQUAL, plus FP_CMP_REDUCE_A for a non-strict P
+    and FP_CMP_REDUCE_B for a non-strict Q — and the curve operation directly behind it (its position by trace_seek, its lookup slots
+    continuing the comparison's): the reference's context order, in two fused calls and the range calls.  units: (column, row, p_offset,
+    q_offset) tuples; lookup_slots[u]: the queue position of unit u's first lookup cell.  cmp_results_dev takes the comparison's results
+    (fp_cmp_layout's results_per_unit per unit), results_dev the curve operation's.  tables: the third item of an earlier call's return
+    value for the same layout (units and lookup_slots are then not walked again).
+    -> ([(column, row)] of each unit's equality cell, which the circuit pins to 0; [(column, row)] of each curve operation's first cell;
+    the tables)"""
+    assert op in (EC_ADD_UNEQUAL, EC_SUB_UNEQUAL) and cmp_mask & FP_CMP_EQUAL and 0 < cmp_mask <= 7
+    assert results_dev and cmp_results_dev, "the range checks read the results"
+    if tables is None:
+        lib, ncols = ctx.lib, len(columns)
+        cl = fp_cmp_layout(params, cmp_mask, lib)
+        ec_units = [trace_seek(break_points, ncols, c, r, cl.num_cells, lib) + (p, q) for c, r, p, q in units]
+        eq_cells = [trace_seek(break_points, ncols, c, r, cl.out_cell_offsets[2], lib) for c, r, _p, _q in units]
+        cmp_table, ec_table = fp_mul_table(list(units)), ec_op_table(ec_units)   # (P.x and Q.x lead their points: the comparison's operands)
+        tables = (eq_cells, [(c, r) for c, r, _p, _q in ec_units],
+                  (cmp_table, fp_cmp_range_tables(break_points, ncols, params, cmp_mask, cmp_table, lookup_slots, lib),
+                   ec_table, ec_range_tables(break_points, ncols, params, op, ec_table, [s + cl.num_lookup_cells for s in lookup_slots], lib)))
+    eq_cells, ec_cells, (cmp_table, cmp_ranges, ec_table, ec_ranges) = tables
+    fp_cmp_fill_with_ranges(ctx, columns, usable_rows, break_points, lookup_columns, params, cmp_mask, values_dev, values_len, cmp_results_dev, cmp_results_len,
+                            cmp_table, range_tables=cmp_ranges)
+    ec_fill_with_ranges(ctx, columns, usable_rows, break_points, lookup_columns, params, op, values_dev, values_len, results_dev, results_len, ec_table,
+                        range_tables=ec_ranges)
+    return eq_cells, ec_cells, tables

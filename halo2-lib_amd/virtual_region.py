@@ -433,6 +433,27 @@ class GateChip:
         return ctx.assign_region_last([c, a, b, Witness((a.value * b.value + c.value) % R_MOD)], [0])
 
     @staticmethod
+    def and_(ctx: Context, a, b) -> AssignedValue:
+        """gate.and = mul (flex_gate/mod.rs:555-562)"""
+        return GateChip.mul(ctx, a, b)
+
+    @staticmethod
+    def is_zero(ctx: Context, a: AssignedValue) -> AssignedValue:
+        """| out | a | inv | 1 | 0 | a | out | 0 | with gates on cells 0 and 4 and cell 0 constrained equal to cell 6 (flex_gate/mod.rs:789-809):
+        out = [a == 0], inv = a^-1, 1 for a = 0 -> the second out cell"""
+        x = a.value % R_MOD
+        out, inv = (1, 1) if x == 0 else (0, pow(x, -1, R_MOD))
+        row_offset = len(ctx.advice)
+        ctx.assign_region([Witness(out), Existing(a), Witness(inv), Constant(1), Constant(0), Existing(a), Witness(out), Constant(0)], [0, 4])
+        ctx.constrain_equal(ctx.get(row_offset), ctx.get(row_offset + 6))
+        return ctx.get(-2)
+
+    @staticmethod
+    def is_equal(ctx: Context, a, b) -> AssignedValue:
+        """is_zero(sub(a, b)) (flex_gate/mod.rs:815-823)"""
+        return GateChip.is_zero(ctx, GateChip.sub(ctx, a, b))
+
+    @staticmethod
     def inner_product(ctx: Context, a: Sequence, b: Sequence) -> AssignedValue:
         """inner_product_simple: | 0 | a0 | b0 | s1 | a1 | b1 | s2 | ... with a gate every three rows — consecutive gates OVERLAP in the
         running-sum cell, the case the break-point copy exists for"""
@@ -522,6 +543,14 @@ class RangeChip:
         """range/mod.rs:604-635"""
         assert num_bits < FR_CAPACITY, "num_bits must leave one native-field bit of headroom for check_less_than"
         self.range_check(ctx, self._shifted_difference(ctx, a, b, num_bits), num_bits)
+
+    def is_less_than(self, ctx: Context, a, b, num_bits: int) -> AssignedValue:
+        """range/mod.rs:646-687: the seven cells over padded_bits = ceil(num_bits / lookup_bits) lookup_bits, the range check of the first of
+        them at padded_bits + lookup_bits, is_zero of that check's last limb -> 1 when a < b, else 0"""
+        padded_bits = -(-num_bits // self.lookup_bits) * self.lookup_bits
+        assert padded_bits + self.lookup_bits <= FR_CAPACITY, "num_bits is too large for this is_less_than implementation"
+        last_limb = self._range_check(ctx, self._shifted_difference(ctx, a, b, padded_bits), padded_bits + self.lookup_bits)
+        return GateChip.is_zero(ctx, last_limb)
 
 
 def _q(v):

@@ -756,12 +756,15 @@ int h2hip_trace_seek(const uint32_t *break_points_host, size_t num_columns, uint
                      uint32_t *column_out, uint32_t *row_out);
 int h2hip_fp_mul_range_checks(const uint32_t *break_points_host, size_t num_columns, const h2hip_fp_params *params, const h2hip_fp_mul *units_host,
                               const uint64_t *lookup_slots_host, size_t count, h2hip_range_check *checks_out);
-/* EccChip's ec_add_unequal (is_strict = false) and ec_double written on the device [halo2-ecc/src/ecc/mod.rs:153-179, :302-327] for `count`
+/* EccChip's ec_add_unequal, ec_sub_unequal (both is_strict = false) and ec_double written on the device [halo2-ecc/src/ecc/mod.rs:153-179,
+ * :219-246, :302-327] for `count`
  * units over the limb layout of h2hip_fp_params, k = 3 or 4.  A point is 2 (k + 1) consecutive Fr of values_dev: x's k limbs and native
  * residue, then y's; P lies at p_offset, Q at q_offset (ignored for DOUBLE).  One unit's run is the reference's, cell for cell, every cell a
  * canonical Montgomery Fr; a CRT value below is its k limb cells followed by its native cell, ip(x; y) as for h2hip_fp_mul_fill_dev:
  *   sub(a, b)     per cell j <= k of the two values: a_j - b_j, b_j, 1, a_j     (4 (k + 1) cells) [bigint/sub_no_carry.rs:14-33, gate.sub
  *                 halo2-base/src/gates/flex_gate/mod.rs:184-196]
+ *   add(a, b)     per cell j <= k of the two values: a_j, b_j, 1, a_j + b_j     (4 (k + 1) cells; the result is the LAST cell of each four)
+ *                 [bigint/add_no_carry.rs:12-39, gate.add flex_gate/mod.rs:158-168]
  *   smul(a, c)    per cell: 0, a_j, c, c a_j                                     (4 (k + 1) cells) [bigint/scalar_mul_no_carry.rs:16-35]
  *   mul(a, b)     S1_i (i < k) and S2 of h2hip_fp_mul_fill_dev over the cells of a and b          [bigint/mul_no_carry.rs:24-32, :45]
  *   load(l)       l_0 .. l_{k-1}; l_0, l_1, 2^n, s_1, ..., s_{k-1} (evaluate_native, the last cell the native); then k gaps: the range
@@ -772,15 +775,19 @@ int h2hip_fp_mul_range_checks(const uint32_t *break_points_host, size_t num_colu
  *   carry(a)      S3 .. S9 of h2hip_fp_mul_fill_dev with the cell a_i in place of P_i and a_nat in place of N [bigint/carry_mod.rs:100-184]
  * ADD_UNEQUAL: dx = sub(Q.x, P.x); dy = sub(Q.y, P.y); load(lambda); ld = mul(lambda, dx); zero(sub(ld, dy)) [divide_unsafe,
  *   fields/mod.rs:217-238]; x3 = carry(sub(sub(mul(lambda, lambda), P.x), Q.x)); y3 = carry(sub(mul(lambda, sub(P.x, x3)), P.y)).
+ * SUB_UNEQUAL (P - Q): dx = sub(Q.x, P.x); sy = add(Q.y, P.y); load(lambda); ld = mul(lambda, dx); zero(add(ld, sy)) [neg_divide_unsafe,
+ *   fields/mod.rs:256-277]; x3 and y3 exactly as for ADD_UNEQUAL.
  * DOUBLE: y2 = smul(P.y, 2); x3_ = smul(P.x, 3); num = mul(x3_, P.x); load(lambda); zero(sub(mul(lambda, y2), num)); l2 = mul(lambda, lambda);
  *   x2 = smul(P.x, 2); x3 = carry(sub(l2, x2)); y3 = carry(sub(mul(lambda, sub(P.x, x3)), P.y)).
- * At k = 3 a unit has 458 (ADD_UNEQUAL) or 483 (DOUBLE) own cells and 9 k gaps.  max_limb_bits is threaded as the reference threads it (+1
- * per sub, + ceil(log2 c) per smul, ceil(log2 k) + a + b per mul) and gives each reduction its own rb: from max(a, 2 n + bit_length(k)) for
+ * At k = 3 a unit has 458 (ADD_UNEQUAL, SUB_UNEQUAL) or 483 (DOUBLE) own cells and 9 k gaps; an add has the cells and the max_limb_bits of a
+ * sub, so h2hip_ec_layout gives SUB_UNEQUAL every number it gives ADD_UNEQUAL.  max_limb_bits is threaded as the reference threads it (+1
+ * per sub or add, + ceil(log2 c) per smul, ceil(log2 k) + a + b per mul) and gives each reduction its own rb: from max(a, 2 n + bit_length(k)) for
  * zero, max(max(n, a) + 1, 2 n + bit_length(k)) for carry, rb = floor((that - n + 1 + lb) / lb) lb - 1.  Fp::NUM_BITS in load is bits(p): for
  * a prime field the two are the same number by definition, so no accepted modulus differs.
  * The integers, defined for every input (nothing is asserted; a bad witness is the witness checker's business): an operand integer is X =
  * sum (canon(x_i) mod 2^n) 2^(n i); no-carry values are exact signed integers over those; limb and native cells are Fr arithmetic over the
- * operand cells themselves.  lambda = (num mod p) (den mod p)^-1 mod p with den = X2 - X1, num = Y2 - Y1 (DOUBLE: 2 Y, 3 X^2), 0 where den has
+ * operand cells themselves.  lambda = (num mod p) (den mod p)^-1 mod p with den = X2 - X1, num = Y2 - Y1 (DOUBLE: 2 Y, 3 X^2; SUB_UNEQUAL: num =
+ * -(Y2 + Y1), so lambda is 0 where Y2 + Y1 = 0 mod p too, and zero's value is lambda (X2 - X1) + (Y2 + Y1)), 0 where den has
  * no inverse.  (Q, O) = FLOOR divmod of the signed value by p; q_i = the low k limbs of |Q|, negated in Fr when Q < 0 (decompose_bigint); o_i
  * the low k limbs of O; c_i as for h2hip_fp_mul_fill_dev.  x3's integer in y3 is the O of x3's reduction.
  * results_dev (may be NULL): unit u gets 9 k + 3 Fr at index u (9 k + 3): x3 and y3 (k + 1 each: a point in operand form, a later call may read
@@ -802,6 +809,7 @@ int h2hip_fp_mul_range_checks(const uint32_t *break_points_host, size_t num_colu
  * pointers, the break points, the constants and the segment table are the only uploads. */
 #define H2HIP_EC_ADD_UNEQUAL 0   /* ecc/mod.rs ec_add_unequal, is_strict = false */
 #define H2HIP_EC_DOUBLE 1        /* ecc/mod.rs ec_double */
+#define H2HIP_EC_SUB_UNEQUAL 3   /* ecc/mod.rs ec_sub_unequal, is_strict = false: P - Q (2 is no operation: it stays refused as an unknown op) */
 typedef struct h2hip_ec_op {
     uint32_t column, row;        /* first cell of the unit's run */
     uint64_t p_offset, q_offset; /* values_dev indices of the two points; q_offset is ignored for H2HIP_EC_DOUBLE */
@@ -813,6 +821,51 @@ int h2hip_ec_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_colum
                       const h2hip_ec_op *units_host, size_t count);
 int h2hip_ec_range_checks(const uint32_t *break_points_host, size_t num_columns, const h2hip_fp_params *params, uint32_t op,
                           const h2hip_ec_op *units_host, const uint64_t *lookup_slots_host, size_t count, h2hip_range_check *checks_out);
+/* FpChip's comparisons written on the device for `count` pairs of CRT integers lying on the device (operands as for h2hip_fp_mul_fill_dev: k
+ * limb cells, then the native cell, from a_offset / b_offset of values_dev; only the limb cells are read).  op is a non-empty mask; one unit's
+ * run is, in this order and in the reference's cell order, every cell a canonical Montgomery Fr:
+ *   H2HIP_FP_CMP_REDUCE_A (1)  enforce_less_than_p(a)                                   [halo2-ecc/src/fields/fp.rs:123-142]
+ *   H2HIP_FP_CMP_REDUCE_B (2)  enforce_less_than_p(b)
+ *   H2HIP_FP_CMP_EQUAL    (4)  big_is_equal::assign(a, b)                                [bigint/big_is_equal.rs]
+ * so 1 is enforce_less_than / into_strict_point, 4 is is_equal_unenforced, 7 is FieldChip::is_equal, and 4, 5, 6, 7 are the cells of
+ * check_points_are_unequal for a strict / non-strict P.x and Q.x [ecc/mod.rs:183-202] (assert_is_const writes no cell: it is a constant
+ * equality the circuit puts on the cell out_cell_offsets names).  a_offset is not read for op = 2, b_offset not for op = 1.
+ * enforce_less_than_p(x), with pad = ceil(n / lb) lb, t_0 = p_0 and borrow_i the outcome of limb i, per limb i < k:
+ *   i >= 1:     p_i, borrow_{i-1}, 1, t_i = p_i + borrow_{i-1}                           [gate.add, flex_gate/mod.rs:158-168]
+ *   is_less_than: s_i = x_i + 2^pad - t_i, t_i, 1, x_i + 2^pad, -2^pad, 1, x_i           [range/mod.rs:646-687]
+ *   a gap:      the range check of s_i at pad + lb bits: pad / lb + 1 limbs, no tail gate (3 (pad / lb + 1) - 2 cells), flags 0
+ *   is_zero:    z, l_i, inv, 1, 0, l_i, z, 0; the second z is borrow_i                   [flex_gate/mod.rs:789-809]
+ * 19 k - 4 own cells and k gaps per enforced operand.  big_is_equal(a, b), per limb i < k:
+ *   a_i - b_i, b_i, 1, a_i [gate.sub]; is_zero of that difference (8 cells), its second z is eq_i; for i >= 1: 0, eq_i, partial_{i-1},
+ *   partial_i = eq_i partial_{i-1} [gate.and = mul], partial_0 = eq_0
+ * 16 k - 4 cells, no gap.  The values, defined for every input (nothing is asserted): s_i and a_i - b_i in Fr over the cell values themselves;
+ * l_i = (canon(s_i) >> pad) mod 2^lb, the last limb cell h2hip_range_fill_checks_dev writes for s_i (one decomposition serves both); z = [x = 0]
+ * and inv = x^-1 in Fr, 1 for x = 0, for the cell x an is_zero is given.  For limbs below 2^n the final borrow is [X < p] and partial_{k-1} is
+ * [A = B].
+ * results_dev (may be NULL): unit u gets h2hip_fp_cmp_layout's results_per_unit Fr at index u results_per_unit: for each enforced operand, in
+ * order, s_0 .. s_{k-1} and the final borrow; for EQUAL the equality cell's value.
+ * h2hip_fp_cmp_layout (host only, pure): the unit's cells, own cells, lookup cells and results; ranges[k per enforced operand]: each gap's
+ * offset, cells, width pad + lb and the results entry it checks, in context order (the lookup queue order); out_cell_offsets[3]: the final
+ * borrow cell of a's check, of b's, and the equality cell (partial_{k-1}), UINT32_MAX where the mask has none.
+ * h2hip_fp_cmp_range_checks (host only, pure): the range units of `count` units, unit by unit, a unit's gaps in context order (rows and
+ * lookup slots ascend): a_offset = u results_per_unit + the gap's results index, lookup_slot = lookup_slots_host[u] + the lookup cells of
+ * the unit's gaps before it.  All have one width: one h2hip_range_fill_checks_dev call over results_dev fills them (none for op = 4).
+ * H2HIP_ERR_INVALID with a message, before anything is launched or uploaded (all columns and results_dev are then untouched): the refusals of
+ * h2hip_fp_mul_fill_dev applied to this unit (its parameters, its run, its operands, results_len < count results_per_unit, count times the
+ * unit's segments > 2^32: 2 k segments per enforced operand, k for EQUAL), and: op = 0 or op > 7; pad + lb > 253.  count == 0 is H2HIP_OK
+ * without device work.  Stream-ordered on the context's stream: two kernels (one lane per unit; one lane per (unit, segment), an is_zero
+ * segment's lane doing its own inversion); the unit table, the column pointers, the break points, the constants and the segment table are
+ * the only uploads. */
+#define H2HIP_FP_CMP_REDUCE_A 1
+#define H2HIP_FP_CMP_REDUCE_B 2
+#define H2HIP_FP_CMP_EQUAL 4
+int h2hip_fp_cmp_layout(const h2hip_fp_params *params, uint32_t op, size_t *num_cells, size_t *num_own_cells, size_t *num_lookup_cells,
+                        size_t *results_per_unit, h2hip_fp_mul_range *ranges, uint32_t *out_cell_offsets);
+int h2hip_fp_cmp_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const uint32_t *break_points_host,
+                          const h2hip_fp_params *params, uint32_t op, const void *values_dev, size_t values_len, void *results_dev, size_t results_len,
+                          const h2hip_fp_mul *units_host, size_t count);
+int h2hip_fp_cmp_range_checks(const uint32_t *break_points_host, size_t num_columns, const h2hip_fp_params *params, uint32_t op,
+                              const h2hip_fp_mul *units_host, const uint64_t *lookup_slots_host, size_t count, h2hip_range_check *checks_out);
 /* The RLC gates' terms of the quotient numerator on the extended domain, folded in order for j < count:
  *      acc[i] = acc[i]*y + q_j[i]*(a_j[i]*gamma + a_j[i+s] - a_j[i+2s]),  s = 2^(ext_k-k), indices mod 2^ext_k.
  * q_dev / a_dev: HOST arrays of device pointers; 64 columns per launch. */

@@ -1,0 +1,889 @@
+"""The curve arithmetic of a strict MSM trace filled on the device: EccChip's ec_sub_unequal (h2hip_ec_fill_dev with H2HIP_EC_SUB_UNEQUAL),
+FpChip's comparisons (h2hip_fp_cmp_fill_dev: enforce_less_than_p of one or both operands, big_is_equal of the pair) and the two together as
+ec_add_unequal / ec_sub_unequal with is_strict = true (plonk.ec_fill_strict_with_ranges), shared by tests/test_ec_strict.py (the CPU-emulated
+build) and tests/test_ec_strict_gpu.py: every check takes a ctx.  Every comparison is bit-exact.
+
+The definition is a Python-integer restatement over virtual_region.Context, GateChip and RangeChip of ec_sub_unequal (ecc/mod.rs:219-246, with
+neg_divide_unsafe, fields/mod.rs:256-277, and add_no_carry::crt), enforce_less_than_p (fields/fp.rs:123-142), big_is_equal::assign
+(bigint/big_is_equal.rs) and check_points_are_unequal (ecc/mod.rs:183-202), the range checks included, so one thread holds the whole run and
+the lookup queue.  tests/ec_fill_checks.py supplies load_private, check_carry_mod_to_zero and carry_mod.
+
+  A  the definition itself: P - Q against integer curve arithmetic, the final borrow = [A < p], the equality cell = [A == B];
+  B  the fill against the definition over sentinel-filled columns: the bare call, the *_with_ranges call, layout and range tables, for every
+     mask 1 .. 7 and for SUB_UNEQUAL; ec_layout(SUB) == ec_layout(ADD);
+  C  column breaks as assign_witnesses makes them, through ec_fill_strict_with_ranges;  D  chaining;  E  the refusals;
+  F  a BaseConfig proof of the MSM fragment S = A2 - A0 (strict), T = S + P (strict), D = 2 T, and the same circuit with P.x = S.x.
+"""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+
+import halo2_lib_amd as H
+from halo2_lib_amd import plonk as PL
+from halo2_lib_amd import virtual_region as VR
+from oracle import plonk as P
+from tests import ec_fill_checks as K
+from tests import fp_mul_checks as F
+from tests.dyn_lookup_util import rng_budget, srs, vk_from_gpu
+from tests.ec_fill_checks import CURVES, PARAMS, Crt, Unit, aff_add, aff_double, multiples, operand, point
+from tests.fp_mul_checks import MODULI, SECP_P, Spec, _operand, _thread, own_mask
+from tests.poseidon_trace_checks import _compare, _ints, place
+from tests.range_fill_checks import lookup_positions
+from tests.rlc_checks import SENTINEL
+from tests.util import PreDrawnRng, R, fr
+
+_vp = C.c_void_p
+ERR_INVALID = -1
+ADD, DOUBLE, SUB = PL.EC_ADD_UNEQUAL, PL.EC_DOUBLE, PL.EC_SUB_UNEQUAL
+RA, RB, EQ = PL.FP_CMP_REDUCE_A, PL.FP_CMP_REDUCE_B, PL.FP_CMP_EQUAL
+MASKS = list(range(1, 8))
+SOLVE_BLOCK, PLACE_BLOCK = 64, 256   # ec_fill.hip and fp_cmp.hip: lanes per workgroup of the per-unit and of the per-(unit, segment) kernel
+ROOT = F.ROOT
+NO_CELL = 0xFFFFFFFF
+
+
+def cmp_segments(k, mask):
+    """lanes per unit of the comparison's placing kernel: 2 k per enforced operand, k for EQUAL"""
+    return 2 * k * (bool(mask & RA) + bool(mask & RB)) + (k if mask & EQ else 0)
+
+
+def cmp_results(k, mask):
+    return (k + 1) * (bool(mask & RA) + bool(mask & RB)) + (1 if mask & EQ else 0)
+
+
+def _queue_len(ctx, chip):
+    return len(chip.lookup_manager.cells_to_lookup.get(ctx.tag(), []))
+
+
+# ------------------------------------------------------------------------------------------------ the definition: ec_sub_unequal
+def add_no_carry(ctx, a, b):
+    """add_no_carry::crt (bigint/add_no_carry.rs:12-39): gate.add per limb and on the natives"""
+    limbs = [VR.GateChip.add(ctx, x, y) for x, y in zip(a.limbs, b.limbs)]
+    return Crt(limbs, VR.GateChip.add(ctx, a.native, b.native), a.value + b.value, max(a.mlb, b.mlb) + 1)
+
+
+def neg_divide_unsafe(ctx, chip, sp, a, b, u):
+    """FieldChip::neg_divide_unsafe (fields/mod.rs:256-277): quot = -a / b, 0 for a b with no inverse; quot b + a carries to zero"""
+    k = sp.k
+    a_val, b_val = a.value % sp.p, b.value % sp.p
+    quot_val = -a_val * pow(b_val, -1, sp.p) % sp.p if math.gcd(b_val, sp.p) == 1 else 0
+    lam_offsets = [len(ctx.advice) - u.start + i for i in range(k)]
+    quot = K.load_private(ctx, chip, sp, quot_val, u, 2 * (k + 1))
+    u.lam_offsets = lam_offsets + [u.gaps[0][0] - 1]
+    quot_b = K.mul_no_carry(ctx, sp, quot, b)
+    K.check_carry_mod_to_zero(ctx, chip, sp, add_no_carry(ctx, quot_b, a), u, 3 * k + 3)
+    return quot
+
+
+def ec_sub(ctx, chip, sp, pt, qt):
+    """ec_sub_unequal(P, Q, is_strict = false) of points given as 2 (k + 1) cells -> a Unit as ec_fill_checks.ec_op's"""
+    k = sp.k
+    u = Unit()
+    u.start, u.queue = len(ctx.advice), _queue_len(ctx, chip)
+    u.gaps, u.results, u.quots, u.rb, u.out_offsets = [], [None] * (9 * k + 3), [], [], []
+    px, py = operand(sp, pt[:k + 1]), operand(sp, pt[k + 1:])
+    qx, qy = operand(sp, qt[:k + 1]), operand(sp, qt[k + 1:])
+    dx = K.sub_no_carry(ctx, qx, px)                                          # ecc/mod.rs:228-246
+    sy = add_no_carry(ctx, qy, py)
+    lam = neg_divide_unsafe(ctx, chip, sp, sy, dx, u)
+    lam_sq = K.mul_no_carry(ctx, sp, lam, lam)
+    x3nc = K.sub_no_carry(ctx, K.sub_no_carry(ctx, lam_sq, px), qx)
+    x3 = K.carry_mod(ctx, chip, sp, x3nc, u, 0, 5 * k + 3)
+    dx13 = K.sub_no_carry(ctx, px, x3)
+    y3nc = K.sub_no_carry(ctx, K.mul_no_carry(ctx, sp, lam, dx13), py)
+    y3 = K.carry_mod(ctx, chip, sp, y3nc, u, k + 1, 7 * k + 3)
+    u.lam, u.x3, u.y3 = lam.value, x3.value, y3.value
+    u.out_offsets += u.lam_offsets
+    u.out_cells = x3.cells() + y3.cells()
+    u.end = len(ctx.advice)
+    u.lookups = _queue_len(ctx, chip) - u.queue
+    return u
+
+
+def curve_op(ctx, chip, sp, op, pt, qt=None):
+    return ec_sub(ctx, chip, sp, pt, qt) if op == SUB else K.ec_op(ctx, chip, sp, op, pt, qt)
+
+
+# ------------------------------------------------------------------------------------------------ the definition: the comparisons
+def enforce_less_than_p(ctx, chip, sp, limbs, u, res):
+    """FpChip::enforce_less_than_p (fields/fp.rs:123-142) without its closing assert_is_const (no cell) -> the final borrow cell"""
+    lb = sp.lb
+    pad = -(-sp.n // lb) * lb
+    borrow = None
+    for i, (p_limb, a_limb) in enumerate(zip(sp.mod_vec, limbs)):
+        b = VR.Constant(p_limb) if borrow is None else VR.Existing(VR.GateChip.add(ctx, VR.Constant(p_limb), borrow))
+        at = len(ctx.advice)
+        borrow = chip.is_less_than(ctx, VR.Existing(a_limb), b, sp.n)
+        u.gaps.append((at + 7 - u.start, len(ctx.advice) - 8 - (at + 7), pad + lb, res + i))
+        u.results[res + i] = ctx.advice[at]
+    u.results[res + sp.k] = borrow.value
+    return borrow
+
+
+def big_is_equal(ctx, a_limbs, b_limbs):
+    """big_is_equal::assign (bigint/big_is_equal.rs)"""
+    partial = VR.GateChip.is_equal(ctx, a_limbs[0], b_limbs[0])
+    for a_limb, b_limb in zip(a_limbs[1:], b_limbs[1:]):
+        eq_limb = VR.GateChip.is_equal(ctx, a_limb, b_limb)
+        partial = VR.GateChip.and_(ctx, eq_limb, partial)
+    return partial
+
+
+def cmp_op(ctx, chip, sp, mask, a, b, pin=False):
+    """the comparison unit of mask `mask` over the CRT operands a, b (k + 1 cells each): enforce_less_than_p(a), enforce_less_than_p(b),
+    big_is_equal(a, b), those the mask names.  Masks 4 .. 7 are check_points_are_unequal's cells for a strict / non-strict P.x and Q.x; pin
+    adds its assert_is_const(x_is_equal, 0), a constant equality and no cell.  -> a Unit"""
+    k = sp.k
+    u = Unit()
+    u.start, u.queue = len(ctx.advice), _queue_len(ctx, chip)
+    u.gaps, u.results, u.out_offsets = [], [None] * cmp_results(k, mask), [NO_CELL] * 3
+    res = 0
+    for e, x in enumerate((a, b)):
+        if mask & (RA, RB)[e]:
+            borrow = enforce_less_than_p(ctx, chip, sp, x[:k], u, res)
+            u.out_offsets[e] = len(ctx.advice) - 2 - u.start
+            assert ctx.advice[-2] == borrow.value
+            res += k + 1
+    u.eq = None
+    if mask & EQ:
+        eq = big_is_equal(ctx, a[:k], b[:k])
+        u.out_offsets[2] = len(ctx.advice) - 1 - u.start
+        u.results[res] = eq.value
+        u.eq = eq
+        if pin and not ctx.witness_gen_only:
+            ctx.copy_manager.constant_equalities.append((0, eq.cell))       # gate.assert_is_const(x_is_equal, 0)
+    u.end = len(ctx.advice)
+    u.lookups = _queue_len(ctx, chip) - u.queue
+    return u
+
+
+def strict_op(ctx, chip, sp, op, mask, pt, qt):
+    """ec_add_unequal / ec_sub_unequal with is_strict = true: check_points_are_unequal over (P.x, Q.x), then the operation
+    -> (the comparison's Unit, the operation's)"""
+    k = sp.k
+    c = cmp_op(ctx, chip, sp, mask, pt[:k + 1], qt[:k + 1], pin=True)
+    return c, curve_op(ctx, chip, sp, op, pt, qt)
+
+
+class Sub:
+    """what check_fill needs to know of a kind of unit: SUB_UNEQUAL"""
+    name = "sub_unequal"
+
+    def __init__(self, sp, op=SUB):
+        self.sp, self.op, self.nres, self.oplen = sp, op, 9 * sp.k + 3, 2 * (sp.k + 1)
+
+    def unit_def(self, a_vals, b_vals):
+        ctx, chip, _ = _thread(self.sp.lb)
+        u = curve_op(ctx, chip, self.sp, self.op, _operand(a_vals, 0), _operand(b_vals, 1))
+        return u, list(ctx.advice), [c.value for c in chip.lookup_manager.cells_to_lookup.get(ctx.tag(), [])]
+
+    def layout(self, lib=None):
+        return PL.ec_layout(self.sp.params(), self.op, lib)
+
+    def fill(self, ctx, cols, usable, bps, d_vals, nvals, d_res, nres, units):
+        PL.ec_fill(ctx, cols, usable, bps, self.sp.params(), self.op, d_vals, nvals, d_res, nres, units)
+
+    def fill_ranges(self, ctx, cols, usable, bps, lks, d_vals, nvals, d_res, nres, units, slots_):
+        PL.ec_fill_with_ranges(ctx, cols, usable, bps, lks, self.sp.params(), self.op, d_vals, nvals, d_res, nres, units, slots_)
+
+    def range_tables(self, bps, ncols, units, slots_):
+        return PL.ec_range_tables(bps, ncols, self.sp.params(), self.op, units, slots_)
+
+
+class Cmp:
+    """... and the comparison unit of one mask"""
+
+    def __init__(self, sp, mask):
+        self.sp, self.mask, self.nres, self.oplen = sp, mask, cmp_results(sp.k, mask), sp.k + 1
+        self.name = "cmp mask %d" % mask
+
+    def unit_def(self, a_vals, b_vals):
+        ctx, chip, _ = _thread(self.sp.lb)
+        u = cmp_op(ctx, chip, self.sp, self.mask, _operand(a_vals, 0), _operand(b_vals, 1))
+        return u, list(ctx.advice), [c.value for c in chip.lookup_manager.cells_to_lookup.get(ctx.tag(), [])]
+
+    def layout(self, lib=None):
+        return PL.fp_cmp_layout(self.sp.params(), self.mask, lib)
+
+    def fill(self, ctx, cols, usable, bps, d_vals, nvals, d_res, nres, units):
+        PL.fp_cmp_fill(ctx, cols, usable, bps, self.sp.params(), self.mask, d_vals, nvals, d_res, nres, units)
+
+    def fill_ranges(self, ctx, cols, usable, bps, lks, d_vals, nvals, d_res, nres, units, slots_):
+        PL.fp_cmp_fill_with_ranges(ctx, cols, usable, bps, lks, self.sp.params(), self.mask, d_vals, nvals, d_res, nres, units, slots_)
+
+    def range_tables(self, bps, ncols, units, slots_):
+        return PL.fp_cmp_range_tables(bps, ncols, self.sp.params(), self.mask, units, slots_)
+
+
+# ------------------------------------------------------------------------------------------------ the pools
+def _limbs_int(sp, limbs):
+    return sum(v << (sp.n * i) for i, v in enumerate(limbs))
+
+
+def cmp_proper_pool(sp):
+    """[(a's k + 1 values, b's)] over proper integers: 0, 1, p - 1, p, p + 1, 2^bits(p) - 1; p with one limb one unit below / above (the
+    step where a_i < p_i + borrow turns the borrow on, for each i); pairs equal everywhere and pairs differing in exactly limb i"""
+    p, n, k = sp.p, sp.n, sp.k
+    top = (1 << (n * k)) - 1
+    ints = [0, 1, p - 1, p, min(p + 1, top), (1 << p.bit_length()) - 1]
+    for i in range(k):
+        for d in (-1, 1):
+            limbs = list(sp.mod_vec)
+            if 0 <= limbs[i] + d < (1 << n):
+                limbs[i] += d
+                ints.append(_limbs_int(sp, limbs))
+    g = np.random.default_rng([0xC3, n, k, p % (1 << 32)])
+    rnd = [int.from_bytes(g.bytes(40), "little") % p for _ in range(2)]
+    ints += rnd
+    pairs = [(x, x) for x in ints] + [(x, ints[(j + 1) % len(ints)]) for j, x in enumerate(ints)] + [(p, x) for x in ints[:3]] + [(ints[5], p - 1)]
+    for i in range(k):                                                          # differing in exactly limb i
+        for x in (rnd[0], p):
+            limbs = sp.crt(x)[:k]
+            limbs[i] ^= 1
+            pairs.append((x, _limbs_int(sp, limbs)))
+            pairs.append((_limbs_int(sp, limbs), x))
+    return [(sp.crt(x), sp.crt(y)) for x, y in pairs]
+
+
+def cmp_improper_pool(sp):
+    """operands with one limb cell that is no limb: 2^n, 2^pad, 2^(pad + lb) - 1 and r - 1, in a, in b, in both (equal and unequal)"""
+    n, k, lb = sp.n, sp.k, sp.lb
+    pad = -(-n // lb) * lb
+    out = []
+    for j, bad in enumerate((1 << n, 1 << pad, (1 << (pad + lb)) - 1, R - 1)):
+        i = j % k
+        a, b = sp.crt(sp.p - 1 - j), sp.crt(sp.p - 1 - j)
+        a[i] = bad
+        out += [(a, b), (b, a)]
+        b2 = list(a)
+        out.append((a, b2))
+        b3 = list(a)
+        b3[(i + 1) % k] ^= 2
+        out.append((a, b3))
+    return out
+
+
+def cmp_pool(sp):
+    return cmp_proper_pool(sp) + cmp_improper_pool(sp)
+
+
+def sub_pool(sp, modulus, seed=0xEC):
+    """ec_fill_checks.operand_pool, and pairs with y2 = -y1 mod p (sy = 0 mod p: lambda = 0, an exact zero check whatever dx is), with
+    x2 < x1 and x2 > x1 for small and large lambda: the zero check's quotient is negative, positive and exact at least once"""
+    p = sp.p
+    pool = K.operand_pool(sp, modulus, seed)
+    g = np.random.default_rng([seed + 1, sp.n, sp.k, p % (1 << 32)])
+    rnd = [int.from_bytes(g.bytes(40), "little") % p for _ in range(4)]
+    extra = [((rnd[0], rnd[1]), (rnd[2], p - rnd[1])), ((5, 9), (3, 2)), ((3, 2), (5, 9)), ((rnd[0], 1), (rnd[0] + 1, p - 2))]
+    if modulus in CURVES:
+        m = multiples(modulus, 6)
+        extra += [(m[4], m[1]), (m[0], m[5])]
+    return pool + [(point(sp, *a), point(sp, *b)) for a, b in extra]
+
+
+# ------------------------------------------------------------------------------------------------ A: the definition itself
+def check_definition():
+    """P - Q of the restatement equals P + (-Q) in integer curve arithmetic on secp256k1 and BN254 G1, every flex gate of its thread holds,
+    the zero check is exact; for proper operands the final borrow is [A < p] and the equality cell [A == B], every gate of the comparison's
+    thread holds and is_zero's two outputs agree; the cell counts are the formulas' (19 k - 4 per enforced operand with k gaps, 16 k - 4)"""
+    for n, k, lb in PARAMS:
+        for curve, (p, _b, _g) in CURVES.items():
+            sp = Spec(n, k, lb, p)
+            m = multiples(curve, 7)
+            for a, b in ((m[0], m[1]), (m[2], m[6]), (m[5], m[3])):
+                ctx, chip, _ = _thread(lb)
+                u = ec_sub(ctx, chip, sp, _operand(point(sp, *a), 0), _operand(point(sp, *b), 1))
+                cells = list(ctx.advice)
+                assert (u.x3, u.y3) == aff_add(p, a, (b[0], -b[1] % p)), (curve, n)
+                assert u.lam == -(a[1] + b[1]) * pow(b[0] - a[0], -1, p) % p and u.quots[0][1] == 0
+                got = [sum(cells[off] << (n * i) for i, off in enumerate(u.out_offsets[j * (k + 1):j * (k + 1) + k])) for j in range(3)]
+                assert got == [u.x3, u.y3, u.lam]
+                assert not any(abs(q) >> (n * k) for q, _rem in u.quots)
+                bad = [s for s, q in enumerate(ctx.selector) if q and (cells[s] + cells[s + 1] * cells[s + 2] - cells[s + 3]) % R]
+                assert not bad, (curve, n, k, lb, bad)
+                assert int(own_mask(u).sum()) == int(own_mask(K.unit_def(sp, ADD, point(sp, *a), point(sp, *b))[0]).sum())
+                if k == 3:
+                    assert int(own_mask(u).sum()) == 458
+        for modulus, p in MODULI.items():
+            sp = Spec(n, k, lb, p)
+            for a_vals, b_vals in cmp_proper_pool(sp):
+                A, B = _limbs_int(sp, a_vals[:k]), _limbs_int(sp, b_vals[:k])
+                ctx, chip, _ = _thread(lb)
+                u = cmp_op(ctx, chip, sp, 7, _operand(a_vals, 0), _operand(b_vals, 1))
+                cells = list(ctx.advice)
+                assert cells[u.out_offsets[0]] == int(A < p) and cells[u.out_offsets[1]] == int(B < p) and cells[u.out_offsets[2]] == int(A == B), (modulus, n, A, B)
+                assert u.results[k] == int(A < p) and u.results[2 * k + 1] == int(B < p) and u.results[2 * k + 2] == int(A == B)
+                bad = [s for s, q in enumerate(ctx.selector) if q and (cells[s] + cells[s + 1] * cells[s + 2] - cells[s + 3]) % R]
+                assert not bad, (modulus, n, k, lb, bad)
+                assert all(cells[x.offset] == cells[y.offset] for x, y in ctx.copy_manager.advice_equalities if x.type_id == y.type_id == "fp")
+                assert all(v < (1 << lb) for v in (c.value for c in chip.lookup_manager.cells_to_lookup[ctx.tag()]))
+                assert int(own_mask(u).sum()) == 2 * (19 * k - 4) + 16 * k - 4 and len(u.gaps) == 2 * k
+    sp = Spec(88, 3, 18, SECP_P)
+    for mask in MASKS:
+        u, cells, lookups = Cmp(sp, mask).unit_def(sp.crt(5), sp.crt(7))
+        enforced = bool(mask & RA) + bool(mask & RB)
+        assert int(own_mask(u).sum()) == enforced * 53 + (44 if mask & EQ else 0) and len(u.gaps) == 3 * enforced
+        assert all(g[1] == 16 and g[2] == 108 for g in u.gaps) and len(lookups) == 6 * 3 * enforced     # pad = 90: six limbs of 18 bits
+
+
+def check_pool_signs():
+    """SUB_UNEQUAL's pools contain a negative and a positive quotient in each of the three reductions, a zero check that is exact and one with
+    a remainder (the denominator 0, the numerator not); the comparison's pools turn every borrow on and off and every eq_i"""
+    for n, k, lb in PARAMS[:1] + PARAMS[-1:]:
+        for modulus, p in MODULI.items():
+            sp = Spec(n, k, lb, p)
+            quots = [Sub(sp).unit_def(a, b)[0].quots for a, b in sub_pool(sp, modulus)]
+            for r in range(3):
+                assert any(q[r][0] < 0 for q in quots) and any(q[r][0] > 0 for q in quots), (modulus, r)
+            assert any(q[0][1] == 0 for q in quots) and any(q[0][1] != 0 for q in quots), modulus
+            seen = set()
+            for a_vals, b_vals in cmp_pool(sp):
+                u, cells, _l = Cmp(sp, 7).unit_def(a_vals, b_vals)
+                for e in range(2):
+                    for i in range(k):
+                        seen.add(("borrow", i, cells[u.gaps[e * k + i][0] + u.gaps[e * k + i][1] + 6]))
+                seen.add(("eq", cells[u.out_offsets[2]]))
+            assert seen >= {("borrow", i, v) for i in range(k) for v in (0, 1)} | {("eq", 0), ("eq", 1)}, (modulus, n, sorted(seen))
+
+
+# ------------------------------------------------------------------------------------------------ B: the fill against its definition
+def _queue_before(sp, u, j):
+    return sum(-(-g[2] // sp.lb) + (1 if g[2] % sp.lb > 1 else 0) for g in u.gaps[:j])
+
+
+def check_layout_and_ranges():
+    """ec_layout(SUB) equals ec_layout(ADD) in every number and the definition's counts, gaps and offsets; fp_cmp_layout equals the
+    definition's for every mask; both range tables give the definition's positions and lookup queue order unit by unit, rows and slots
+    ascending inside a width"""
+    for n, k, lb in PARAMS + [K.CARRY_WIDTHS]:
+        for modulus, p in MODULI.items():
+            sp = Spec(n, k, lb, p)
+            u, cells, lookups = Sub(sp).unit_def(point(sp, 3, 5), point(sp, p - 2, 11))
+            lay = PL.ec_layout(sp.params(), SUB)
+            assert lay == PL.ec_layout(sp.params(), ADD), (n, k, lb, modulus)
+            assert (lay.num_cells, lay.num_own_cells, lay.num_lookup_cells) == (len(cells), int(own_mask(u).sum()), len(lookups)), (n, k, lb)
+            assert lay.ranges == u.gaps and lay.out_cell_offsets == u.out_offsets, (n, k, lb, lay, u.gaps, u.out_offsets)
+            for mask in MASKS:
+                u, cells, lookups = Cmp(sp, mask).unit_def(sp.crt(3), sp.crt(p - 2))
+                lay = PL.fp_cmp_layout(sp.params(), mask)
+                assert (lay.num_cells, lay.num_own_cells, lay.num_lookup_cells, lay.results_per_unit) == (
+                    len(cells), int(own_mask(u).sum()), len(lookups), cmp_results(k, mask)), (n, k, lb, mask)
+                assert lay.ranges == u.gaps and lay.out_cell_offsets == u.out_offsets, (n, k, lb, mask, lay, u.gaps, u.out_offsets)
+                assert len(cells) - len(u.gaps) * (u.gaps[0][1] if u.gaps else 0) == (bool(mask & RA) + bool(mask & RB)) * (19 * k - 4) + (16 * k - 4 if mask & EQ else 0)
+    sp = Spec(88, 3, 8, SECP_P)
+    for kind in [Sub(sp)] + [Cmp(sp, mask) for mask in MASKS]:
+        thread, chip, _ = _thread(sp.lb)
+        bps, ncols, units, slots_, defs = [700, 650], 3, [], [], []
+        pos = (0, 5)
+        thread.advice += [0] * 5
+        for j in range(4):
+            a, b = (point(sp, 3 + j, 5), point(sp, 9, 11 + j)) if isinstance(kind, Sub) else (sp.crt(SECP_P - 2 + j), sp.crt(SECP_P))
+            if isinstance(kind, Sub):
+                u = ec_sub(thread, chip, sp, _operand(a, 2 * j), _operand(b, 2 * j + 1))
+            else:
+                u = cmp_op(thread, chip, sp, kind.mask, _operand(a, 2 * j), _operand(b, 2 * j + 1))
+            units.append(pos + (0, 0))
+            slots_.append(u.queue + 3)
+            defs.append(u)
+            pos = place(pos[0], pos[1], u.end - u.start, bps, ncols)[1]
+        tables = kind.range_tables(bps, ncols, units, slots_)
+        groups = K.width_groups(defs[0].gaps)
+        assert [w for w, _t in tables] == list(groups), kind.name
+        for (width, table), idx in zip(tables, groups.values()):
+            want = []
+            for ui, u in enumerate(defs):
+                first = {}
+                for i, c, r in place(units[ui][0], units[ui][1], u.end - u.start, bps, ncols)[0]:
+                    first.setdefault(i, (c, r))
+                want += [first[u.gaps[j][0]] + (ui * kind.nres + u.gaps[j][3], slots_[ui] + _queue_before(sp, u, j)) for j in idx]
+            got = [(t.column, t.row, t.a_offset, t.lookup_slot) for t in table]
+            assert got == want, (kind.name, width)
+            assert all(a[3] < b[3] and (a[0], a[1]) < (b[0], b[1]) for a, b in zip(got, got[1:])), "slots and rows ascend inside a width"
+
+
+def check_fill(ctx, kind, pool, count, nl=1):
+    """`count` units per call over three gate columns (no breaks), until every operand pair was a unit; each call once bare (own cells equal
+    the definition's, the gaps and every other cell keep the sentinel, results_dev equals the named cells) and once through the kind's
+    *_with_ranges call over nl lookup columns (the whole run and the lookup columns equal the definition's, the queue starting at a position
+    that is no multiple of nl)"""
+    sp = kind.sp
+    lay = kind.layout(ctx.lib)
+    vals = [v for a, b in pool for v in a + b]
+    nres, ol = kind.nres, kind.oplen
+    cache = {}
+    done = 0
+    while done < len(pool):
+        units, defs, slots_, rows, slot = [], [], [], [1, 3, 0], nl + 1 if nl > 1 else 1
+        for j in range(count):
+            at = (done + j) % len(pool)
+            if at not in cache:
+                cache[at] = kind.unit_def(*pool[at])
+            u, cells, lookups = cache[at]
+            assert len(cells) == lay.num_cells
+            col = j % 3
+            units.append((col, rows[col], 2 * ol * at, 2 * ol * at + ol))
+            defs.append((u, cells, lookups))
+            slots_.append(slot)
+            rows[col] += len(cells) + (j % 2)
+            slot += len(lookups) + (j % 2)
+        done += count
+        rows_n = max(max(rows), -(-slot // nl)) + 9
+        where = lookup_positions(slot, nl)
+        d_vals = ctx.to_device(fr(vals))
+        try:
+            for with_ranges in (False, True):
+                want = [np.tile(SENTINEL, (rows_n, 1)) for _ in range(3)]
+                want_lk = [np.tile(SENTINEL, (rows_n, 1)) for _ in range(nl)]
+                want_res = np.tile(SENTINEL, (count * nres + 2, 1))
+                d_cols = [ctx.to_device(c) for c in want]
+                d_lk = [ctx.to_device(c) for c in want_lk]
+                d_res = ctx.to_device(want_res)
+                for j, ((col, row, _a, _b), (u, cells, lookups), s) in enumerate(zip(units, defs, slots_)):
+                    keep = np.ones(len(cells), dtype=bool) if with_ranges else own_mask(u)
+                    want[col][row:row + len(cells)][keep] = fr(cells)[keep]
+                    want_res[j * nres:(j + 1) * nres] = fr(u.results)
+                    if with_ranges:
+                        for i, v in enumerate(fr(lookups) if lookups else []):
+                            c, r = where[s + i]
+                            want_lk[c][r] = v
+                try:
+                    if with_ranges:
+                        kind.fill_ranges(ctx, d_cols, rows_n - 2, None, d_lk, d_vals, len(vals), d_res, count * nres, units, slots_)
+                    else:
+                        kind.fill(ctx, d_cols, rows_n - 2, None, d_vals, len(vals), d_res, count * nres, units)
+                    ctx.sync()
+                    what = "(n, k, lb) = (%d, %d, %d), %s, count = %d, nl = %d, ranges = %s" % (sp.n, sp.k, sp.lb, kind.name, count, nl, with_ranges)
+                    _compare(ctx, d_cols, want, what + " (gate columns)")
+                    _compare(ctx, d_lk, want_lk, what + " (lookup columns)")
+                    _compare(ctx, [d_res], [want_res], what + " (results)")
+                finally:
+                    for ptr in d_cols + d_lk + [d_res]:
+                        ctx.free(ptr)
+        finally:
+            ctx.free(d_vals)
+
+
+def check_sub_fill(ctx, n, k, lb, modulus, count, nl=1, pool=None):
+    sp = Spec(n, k, lb, MODULI[modulus])
+    check_fill(ctx, Sub(sp), sub_pool(sp, modulus) if pool is None else pool, count, nl)
+
+
+def check_cmp_fill(ctx, n, k, lb, modulus, mask, count, nl=1, pool=None):
+    sp = Spec(n, k, lb, MODULI[modulus])
+    check_fill(ctx, Cmp(sp, mask), cmp_pool(sp) if pool is None else pool, count, nl)
+
+
+# ------------------------------------------------------------------------------------------------ the strict operation: two fused calls
+def _strict_thread(sp, op, mask, pairs, filler=0):
+    """one thread: `filler` plain cells, then strict operations back to back, each over witnesses of its own
+    -> (thread, chip, [(comparison Unit, operation Unit)])"""
+    thread, chip, _ = _thread(sp.lb)
+    thread.advice += list(range(100, 100 + filler))
+    thread.selector += [False] * filler
+    defs = [strict_op(thread, chip, sp, op, mask, _operand(a, 2 * j), _operand(b, 2 * j + 1)) for j, (a, b) in enumerate(pairs)]
+    return thread, chip, defs
+
+
+def _run_strict(ctx, sp, op, mask, thread, chip, defs, vals, bps, ncols, usable, filler, what):
+    """the thread laid into ncols columns by virtual_region.assign_witnesses, its lookup queue by assign_raw, against one
+    ec_fill_strict_with_ranges call from each unit's first cell and queue position; the equality cells and the operations' first cells it
+    returns are where the definition has them"""
+    k = sp.k
+    pt, nres, cres = 2 * (k + 1), 9 * k + 3, cmp_results(k, mask)
+    nunits = len(defs)
+    total = len(thread.advice)
+    first = {}
+    for i, c, r in place(0, 0, total, bps, ncols)[0]:
+        first.setdefault(i, (c, r))
+    units = [first[c.start] + (2 * pt * j, 2 * pt * j + pt) for j, (c, _o) in enumerate(defs)]
+    slots_ = [c.queue for c, _o in defs]
+    rows_n = usable + 9
+    region = VR.Region(rows_n, ncols + 1)
+    VR.assign_witnesses([thread], list(range(ncols)), region, bps if bps is not None else [])
+    chip.lookup_manager.witness_gen_only = True
+    chip.lookup_manager.assign_raw([ncols], region)
+    want = [np.tile(SENTINEL, (rows_n, 1)) for _ in range(ncols + 1)]
+    for c in range(ncols + 1):
+        rows = sorted(region.advice[c])
+        want[c][rows] = fr([region.advice[c][r] for r in rows])
+    start = [np.tile(SENTINEL, (rows_n, 1)) for _ in range(ncols + 1)]
+    start[0][:filler] = want[0][:filler]
+    d_cols = [ctx.to_device(c) for c in start]
+    d_vals = ctx.to_device(fr(vals))
+    d_res = ctx.to_device(np.tile(SENTINEL, (nunits * nres, 1)))
+    d_cres = ctx.to_device(np.tile(SENTINEL, (nunits * cres, 1)))
+    try:
+        eq_cells, op_cells, _t = PL.ec_fill_strict_with_ranges(ctx, d_cols[:ncols], usable, bps, d_cols[ncols:], sp.params(), op, mask, d_vals, len(vals),
+                                                               d_res, nunits * nres, d_cres, nunits * cres, units, slots_)
+        ctx.sync()
+        assert eq_cells == [first[c.start + c.out_offsets[2]] for c, _o in defs], what
+        assert op_cells == [first[o.start] for _c, o in defs], what
+        _compare(ctx, d_cols, want, what)
+        want_res = np.concatenate([fr(o.results) for _c, o in defs])
+        want_cres = np.concatenate([fr(c.results) for c, _o in defs])
+        _compare(ctx, [d_res, d_cres], [want_res, want_cres], what + " (results)")
+    finally:
+        for ptr in d_cols + [d_vals, d_res, d_cres]:
+            ctx.free(ptr)
+
+
+def check_strict(ctx, n, k, lb, op, mask, count=5):
+    """`count` strict operations back to back in one column, no breaks: the comparison in front of each operation, lookup slots continued"""
+    sp = Spec(n, k, lb, SECP_P)
+    pool = sub_pool(sp, "secp256k1_p")
+    pairs = [pool[(3 * j) % len(pool)] for j in range(count)]
+    thread, chip, defs = _strict_thread(sp, op, mask, pairs, 7)
+    vals = [v for a, b in pairs for v in a + b]
+    usable = max(len(thread.advice), _queue_len(thread, chip)) + 5
+    _run_strict(ctx, sp, op, mask, thread, chip, defs, vals, None, 1, usable, 7, "strict op %d mask %d (%d, %d, %d)" % (op, mask, n, k, lb))
+
+
+# ------------------------------------------------------------------------------------------------ C: column breaks
+BREAK_CASES = ["borrow_add", "less_than_overlapped_gate", "cmp_gap", "is_zero", "and", "cmp_last", "sub_add"]
+
+
+def _break_cells(sp):
+    """the cell of a strict SUB_UNEQUAL unit (mask 7) each case's break falls on, from the definition's own offsets"""
+    thread, chip, defs = _strict_thread(sp, SUB, 7, [(point(sp, 3, 5), point(sp, 7, 11))])
+    c, o = defs[0]
+    k = sp.k
+    second = c.gaps[0][0] + c.gaps[0][1] + 8            # behind limb 0's is_zero: the gate.add of limb 1's borrow
+    return {
+        "borrow_add": second + 1,                        # p_1 [borrow_0] 1 t_1
+        "less_than_overlapped_gate": 3,                  # s_0 t_0 1 [a_0 + 2^pad] -2^pad 1 a_0: the cell both gates hold
+        "cmp_gap": c.gaps[1][0] + 2,                     # inside the range check of s_1 (the range fill writes the copy)
+        "is_zero": c.gaps[0][0] + c.gaps[0][1] + 4,      # z l inv 1 [0] l z 0: the cell its second gate starts on
+        "and": c.out_offsets[2] - 2,                     # the last and: 0 [eq_2] partial_1 partial_2
+        "cmp_last": c.end - 1,                           # the operation right behind, in the next column
+        "sub_add": c.end + 4 * (k + 1) + 5,              # sy = add(Q.y, P.y), its second gate: a [b] 1 out
+    }, c.end + (o.end - o.start)
+
+
+def check_breaks(ctx, case, ncols):
+    """one thread (plain cells, then strict SUB_UNEQUAL units at (88, 3, 8), mask 7, back to back) laid into ncols columns by
+    virtual_region.assign_witnesses and by ec_fill_strict_with_ranges, from the same break points.  Every break falls on the cell the case names."""
+    sp = Spec(88, 3, 8, SECP_P)
+    cells_of, ncells = _break_cells(sp)
+    cell = cells_of[case]
+    filler = 50
+    targets = [(1 + 2 * b, cell) for b in range(ncols - 1)]
+    idx = [filler + unit * ncells + c for unit, c in targets]
+    bps = [idx[0]] + [b - a for a, b in zip(idx, idx[1:])]
+    nunits = targets[-1][0] + 2
+    usable = max(bps + [filler + nunits * ncells - idx[-1]]) + 100   # (the last column takes what lies behind the last break)
+    pool = sub_pool(sp, "secp256k1_p", 0xB7)
+    pairs = [pool[(5 * j) % len(pool)] for j in range(nunits)]
+    thread, chip, defs = _strict_thread(sp, SUB, 7, pairs, filler)
+    assert all(o.end - c.start == ncells for c, o in defs)
+    at = place(0, 0, len(thread.advice), bps, ncols)[0]
+    for (unit, c), b, col in zip(targets, bps, range(ncols)):   # the break cell is the cell the case names
+        i = filler + unit * ncells + c
+        assert (i, col, b) in at and (i, col + 1, 0) in at, (case, unit, c)
+    assert usable >= _queue_len(thread, chip)
+    if case == "and":
+        c0 = defs[0][0]
+        assert thread.advice[c0.start + cell] in (0, 1) and thread.advice[c0.start + cell - 1] == 0 and thread.selector[c0.start + cell - 1]
+    vals = [v for a, b in pairs for v in a + b]
+    _run_strict(ctx, sp, SUB, 7, thread, chip, defs, vals, bps, ncols, usable, filler, "breaks (%s, %d columns)" % (case, ncols))
+
+
+# ------------------------------------------------------------------------------------------------ D: chaining
+def check_chained(ctx, n, k, lb, count=3):
+    """S = A - B by a bare SUB_UNEQUAL call; then ec_fill_strict_with_ranges(ADD_UNEQUAL, mask 7) adds to S, read from the first call's
+    results, the S of the next unit.  Columns, the lookup column and the results equal the definition's over sentinels; with curve points the
+    final point is (A - B) + (A' - B') computed in integers."""
+    p = SECP_P
+    sp = Spec(n, k, lb, p)
+    nres, pt, cres = 9 * k + 3, 2 * (k + 1), cmp_results(k, 7)
+    m = multiples("secp256k1_p", 3 * count + 5)
+    ab = [(m[3 * j + 4], m[j]) for j in range(count)]                       # A - B = (2 j + 4) G
+    firsts = [(point(sp, *a), point(sp, *b)) for a, b in ab]
+    vals = [v for a, b in firsts for v in a + b]
+    defs1 = [Sub(sp).unit_def(a, b) for a, b in firsts]
+    ncells = len(defs1[0][1])
+    units1 = [(0, 2 + j * (ncells + 1), 2 * pt * j, 2 * pt * j + pt) for j in range(count)]
+    ops2 = [(defs1[j][0].results[:pt], defs1[(j + 1) % count][0].results[:pt]) for j in range(count)]
+    thread, chip, defs2 = _strict_thread(sp, ADD, 7, ops2)
+    neg = lambda a: (a[0], -a[1] % p)
+    for j, (_c, o) in enumerate(defs2):
+        j2 = (j + 1) % count
+        want = aff_add(p, aff_add(p, ab[j][0], neg(ab[j][1])), aff_add(p, ab[j2][0], neg(ab[j2][1])))
+        assert (o.x3, o.y3) == want
+    total = len(thread.advice)
+    units2 = [(1, 1 + c.start, nres * j, nres * ((j + 1) % count)) for j, (c, _o) in enumerate(defs2)]
+    slots_ = [3 + c.queue for c, _o in defs2]
+    queue = _queue_len(thread, chip)
+    rows_n = max(2 + count * (ncells + 1), total + 1, queue + 3) + 9
+    sent, sent_res, sent_cres = np.tile(SENTINEL, (rows_n, 1)), np.tile(SENTINEL, (count * nres + 2, 1)), np.tile(SENTINEL, (count * cres + 1, 1))
+    d_cols = [ctx.to_device(sent) for _ in range(2)]
+    d_lk = ctx.to_device(sent)
+    d_vals = ctx.to_device(fr(vals))
+    d_res = [ctx.to_device(sent_res) for _ in range(2)]
+    d_cres = ctx.to_device(sent_cres)
+    try:
+        PL.ec_fill(ctx, d_cols, rows_n - 2, None, sp.params(), SUB, d_vals, len(vals), d_res[0], count * nres, units1)
+        PL.ec_fill_strict_with_ranges(ctx, d_cols, rows_n - 2, None, [d_lk], sp.params(), ADD, 7, d_res[0], count * nres, d_res[1], count * nres,
+                                      d_cres, count * cres, units2, slots_)
+        ctx.sync()
+        want = [sent.copy() for _ in range(2)]
+        want_lk, want_res, want_cres = sent.copy(), [sent_res.copy() for _ in range(2)], sent_cres.copy()
+        for j, ((col, row, _a, _b), (u, cells, _l)) in enumerate(zip(units1, defs1)):
+            keep = own_mask(u)
+            want[col][row:row + len(cells)][keep] = fr(cells)[keep]
+            want_res[0][j * nres:(j + 1) * nres] = fr(u.results)
+        want[1][1:1 + total] = fr(list(thread.advice))
+        lookups = [c.value for c in chip.lookup_manager.cells_to_lookup[thread.tag()]]
+        want_lk[3:3 + queue] = fr(lookups)
+        for j, (c, o) in enumerate(defs2):
+            want_res[1][j * nres:(j + 1) * nres] = fr(o.results)
+            want_cres[j * cres:(j + 1) * cres] = fr(c.results)
+        _compare(ctx, d_cols + [d_lk] + d_res + [d_cres], want + [want_lk] + want_res + [want_cres], "chained calls, (n, k, lb) = (%d, %d, %d)" % (n, k, lb))
+    finally:
+        for ptr in d_cols + [d_lk, d_vals, d_cres] + d_res:
+            ctx.free(ptr)
+
+
+# ------------------------------------------------------------------------------------------------ E: the refusals
+def check_rejections(ctx):
+    """one case per reachable refusal of h2hip_fp_cmp_fill_dev, and the unknown op of h2hip_ec_fill_dev: H2HIP_ERR_INVALID, the reason in
+    h2hip_last_error, the sentinel everywhere (columns and results); then count == 0 and good calls from the same context.  Not reachable:
+    pad + lb > 253 (limb_bits <= 125 and lookup_bits <= 63 give pad + lb <= n + 2 lb - 1 <= 250)."""
+    sp = Spec(88, 3, 8, SECP_P)
+    k, mask = sp.k, 7
+    nres, ol = cmp_results(k, mask), k + 1
+    lay = PL.fp_cmp_layout(sp.params(), mask, ctx.lib)
+    ncells = lay.num_cells
+    n_rows, usable = 2 * ncells + 60, 2 * ncells + 50
+    ints = [SECP_P - 1, SECP_P, 5, SECP_P - 1]
+    vals = [v for x in ints for v in sp.crt(x)]
+    nv = len(vals)
+    sent, sent_res = np.tile(SENTINEL, (n_rows, 1)), np.tile(SENTINEL, (4 * nres, 1))
+    d_cols = [ctx.to_device(sent) for _ in range(3)]
+    d_vals = ctx.to_device(fr(vals))
+    d_res = ctx.to_device(sent_res)
+    good = sp.params()
+    ok = (0, 0, 0, ol)
+    try:
+        def refused(what, reason, call):
+            try:
+                call()
+            except H.H2HipError as e:
+                assert e.code == ERR_INVALID, (what, e.code)
+                msg = ctx.lib.h2hip_last_error().decode()
+                assert reason in msg, (what, msg)
+            else:
+                raise AssertionError("%s was accepted" % what)
+            ctx.sync()
+            for ptr in d_cols:
+                assert np.array_equal(ctx.download(ptr, (n_rows, 4)), sent), "%s: a cell was written" % what
+            assert np.array_equal(ctx.download(d_res, (4 * nres, 4)), sent_res), "%s: a result was written" % what
+
+        def fill(units, cols=None, usable_rows=usable, bps=None, params=good, op=mask, vdev=None, vlen=nv, rdev=None, rlen=4 * nres):
+            return lambda: PL.fp_cmp_fill(ctx, d_cols if cols is None else cols, usable_rows, bps, params, op, d_vals if vdev is None else vdev, vlen,
+                                          d_res if rdev is None else rdev, rlen, units)
+
+        par = lambda n=88, k_=3, lb=8, p=SECP_P, flags=0: PL.fp_params(n, k_, lb, p, flags)
+        cols = (_vp * 3)(*[_vp(int(ptr)) for ptr in d_cols])
+        tab = C.cast(PL.fp_mul_table([ok]), _vp)
+        pp = C.cast(C.pointer(good), _vp)
+        raw = lambda c, p_, v, t, cnt=1, op=mask: (lambda: ctx._chk(ctx.lib.h2hip_fp_cmp_fill_dev(ctx.handle, c, 3, usable, None, p_, op, v, nv, _vp(int(d_res)), 4 * nres, t, cnt)))
+        refused("columns NULL", "NULL argument", raw(None, pp, _vp(int(d_vals)), tab))
+        refused("params NULL", "NULL argument", raw(cols, None, _vp(int(d_vals)), tab))
+        refused("values NULL", "NULL argument", raw(cols, pp, None, tab))
+        refused("units NULL", "NULL argument", raw(cols, pp, _vp(int(d_vals)), None))
+        refused("op 0", "mask", fill([ok], op=0))
+        refused("op 8", "mask", fill([ok], op=8))
+        refused("flags != 0", "flags", fill([ok], params=par(flags=1)))
+        refused("limb_bits 63", "limb_bits outside", fill([ok], params=par(n=63, k_=4, p=(1 << 252) - 1)))
+        refused("limb_bits 128", "limb_bits outside", fill([ok], params=par(n=128, k_=2)))
+        refused("num_limbs 1", "num_limbs outside", fill([ok], params=par(k_=1)))
+        refused("num_limbs 5", "num_limbs outside", fill([ok], params=par(n=64, k_=5)))
+        refused("n k > 320", "> 320", fill([ok], params=par(n=107, k_=3, p=(1 << 320) - 1)))
+        refused("p == 0", "zero", fill([ok], params=par(p=0)))
+        refused("p < 2^(n (k - 1))", "exactly num_limbs", fill([ok], params=par(p=(1 << 176) - 1)))
+        refused("p >= 2^(n k)", "exactly num_limbs", fill([ok], params=par(p=1 << 264)))
+        refused("quot_max_bits >= n k", "quot_max_bits", fill([ok], params=par(p=(1 << 252) - 1)))
+        refused("a limb of p equal to 1", "equals 1", fill([ok], params=par(p=(1 << 255) + (1 << 88) + 12345)))
+        refused("lookup_bits 0", "lookup_bits", fill([ok], params=par(lb=0)))
+        refused("lookup_bits 64", "lookup_bits", fill([ok], params=par(lb=64)))
+        refused("column index out of range", "column index", fill([ok, (3, 0, ol, 2 * ol)]))
+        refused("a NULL column", "column index", fill([ok, (1, 0, ol, 2 * ol)], cols=[d_cols[0], 0, d_cols[2]]))
+        refused("a run that leaves the usable rows", "usable rows", fill([ok, (1, usable - ncells + 1, ol, 2 * ol)]))
+        refused("a run that leaves the last column", "last column", fill([ok, (2, usable - ncells + 1, ol, 2 * ol)], bps=[usable - 1, usable - 1]))
+        refused("a break point >= usable_rows", "break point", fill([ok], bps=[10, usable]))
+        refused("a past values_len", "outside values_len", fill([ok, (1, 0, nv - ol + 1, 0)]))
+        refused("b past values_len", "outside values_len", fill([(1, 0, 0, (1 << 64) - 2)]))
+        refused("results_len too small", "results_len", fill([ok, (1, 0, ol, 2 * ol)], rlen=2 * nres - 1))
+        refused("count times the segments > 2^32", "2^32", raw(cols, pp, _vp(int(d_vals)), tab, cnt=(1 << 32) // cmp_segments(3, mask) + 1))
+        refused("two units' cells overlap", "cells overlap", fill([ok, (0, ncells - 1, ol, 2 * ol)]))
+        refused("a unit inside another's gap", "cells overlap", fill([ok, (0, lay.ranges[0][0], ol, 2 * ol)]))
+        refused("a break copy inside another unit", "cells overlap", fill([(1, 0, 0, ol), (0, 20, ol, 2 * ol)], bps=[25, usable - 1]))
+        refused("an operand inside cells this call writes", "operand range", fill([(1, 0, 5, 300)], vdev=d_cols[1], vlen=usable))
+        refused("the results inside cells this call writes", "results overlap", fill([(1, 0, 0, ol)], rdev=d_cols[1] + 32 * 10, rlen=nres))
+        refused("the results over operands of the call", "operand range", fill([ok], rdev=d_vals, rlen=nv))
+        refused("ec_fill: an unknown op", "unknown op", lambda: PL.ec_fill(ctx, d_cols, usable, None, good, 4, d_vals, nv, d_res, 4 * nres, [(0, 0, 0, 0)]))
+        for what, prm, op in (("layout: flags", par(flags=2), 7), ("layout: p", par(p=0), 1), ("layout: op", good, 0), ("layout: op", good, 8)):
+            try:
+                PL.fp_cmp_layout(prm, op, ctx.lib)
+            except H.H2HipError as e:
+                assert e.code == ERR_INVALID, what
+            else:
+                raise AssertionError(what + " was accepted")
+        # count == 0 needs nothing
+        ctx._chk(ctx.lib.h2hip_fp_cmp_fill_dev(ctx.handle, None, 0, 0, None, None, 9, None, 0, None, 0, None, 0))
+        # the largest run that still fits (its last cell on row usable - 1), an operand that ends with values_len, a mask 1 unit whose b_offset
+        # and a mask 2 unit whose a_offset is past everything (ignored), a unit that ends on its break point
+        units = [(0, usable - ncells, nv - ol, 0), (1, 30, ol, 2 * ol)]
+        bps = [usable - 1, 30 + ncells - 1]
+        fill(units, bps=bps, rlen=2 * nres)()
+        one = [(2, 3, 2 * ol, (1 << 64) - 1)]
+        fill(one, op=RA, rdev=d_res + 32 * 2 * nres, rlen=k + 1)()
+        two = [(2, 3 + ncells, (1 << 64) - 1, 3 * ol)]
+        fill(two, op=RB, rdev=d_res + 32 * (2 * nres + k + 1), rlen=k + 1)()
+        ctx.sync()
+        want = [np.tile(SENTINEL, (n_rows, 1)) for _ in range(3)]
+        want_res = np.tile(SENTINEL, (4 * nres, 1))
+        at = 0
+        for m_, (col, row, a, b) in [(7, units[0]), (7, units[1]), (RA, one[0]), (RB, two[0])]:
+            av = vals[a:a + ol] if m_ != RB else [0] * ol
+            bv = vals[b:b + ol] if m_ != RA else [0] * ol
+            u, cells, _ = Cmp(sp, m_).unit_def(av, bv)
+            own = own_mask(u)
+            for i, c, r in place(col, row, len(cells), bps if m_ == 7 else None, 3)[0]:
+                if own[i]:
+                    want[c][r] = fr([cells[i]])[0]
+            want_res[at:at + len(u.results)] = fr(u.results)
+            at += len(u.results)
+        _compare(ctx, d_cols + [d_res], want + [want_res], "after the refusals")
+    finally:
+        for ptr in d_cols + [d_vals, d_res]:
+            ctx.free(ptr)
+
+
+def check_names_in_every_layer():
+    """the op constant and the three new symbols in the header, the Rust sys crate and ctypes"""
+    hdr = open(os.path.join(ROOT, "include", "h2hip.h")).read()
+    rs = open(os.path.join(ROOT, "ffi", "rust", "h2hip-sys", "src", "lib.rs")).read()
+    for name, py in (("H2HIP_EC_SUB_UNEQUAL", SUB), ("H2HIP_FP_CMP_REDUCE_A", RA), ("H2HIP_FP_CMP_REDUCE_B", RB), ("H2HIP_FP_CMP_EQUAL", EQ)):
+        assert int(re.search(r"#define %s (\d+)" % name, hdr).group(1)) == py == int(re.search(r"pub const %s: u32 = (\d+);" % name, rs).group(1))
+    lib = H.load_library()
+    for fn in ("h2hip_fp_cmp_layout", "h2hip_fp_cmp_fill_dev", "h2hip_fp_cmp_range_checks"):
+        assert ("int %s(" % fn) in hdr and ("pub fn %s(" % fn) in rs and hasattr(lib, fn), fn
+
+
+# ------------------------------------------------------------------------------------------------ F: inside a proof
+def _msm_program(builder, sp, a2, a0, pv):
+    """loads A2, A0 and P as witnesses (2 (k + 1) cells each), then S = A2 - A0 (strict, mask 7), T = S + P (strict, mask 7), D = 2 T: the
+    start point, one addition and one doubling of multi_scalar_multiply's loop.  The first limb of A2.x is the instance.
+    -> [(thread offset of the unit's first cell, queue position, the Unit)] of S's comparison, S, T's comparison, T, D"""
+    ctx = builder.main()
+    chip = VR.RangeChip(sp.lb, builder.lookup_manager)
+    k = sp.k
+    a2t, a0t, ptt = ([ctx.load_witness(v) for v in vals] for vals in (a2, a0, pv))
+    cs = cmp_op(ctx, chip, sp, 7, a2t[:k + 1], a0t[:k + 1], pin=True)
+    s = ec_sub(ctx, chip, sp, a2t, a0t)
+    ct = cmp_op(ctx, chip, sp, 7, s.out_cells[:k + 1], ptt[:k + 1], pin=True)
+    t = K.ec_op(ctx, chip, sp, ADD, s.out_cells, ptt)
+    d = K.ec_op(ctx, chip, sp, DOUBLE, t.out_cells)
+    builder.assigned_instances = [[a2t[0]]]
+    return [(u.start, u.queue, u) for u in (cs, s, ct, t, d)]
+
+
+def check_proof(ctx, kk, seed, nl, mode="proof"):
+    """F: a BaseConfig circuit built through the Context mirror (the MSM fragment on secp256k1 at (88, 3)), both equality cells pinned to 0
+    through constant_equalities; keygen from the mirror's selectors and copies; the device advice starts with the loaded witnesses only; two
+    ec_fill_strict_with_ranges calls and one ec_fill_with_ranges call (each reads the results of the one before) write every other gate cell
+    and the whole lookup columns.  mode "proof": the columns equal the Python-computed advice, the proof has the bytes of the oracle prover's
+    proof over the host-laid trace, both verifiers accept it, check_witness finds nothing.  mode "equal_x": P = (S.x, another y): the fill
+    still equals the definition; of the second comparison's cells check_witness reports the pinned equality cell's copy and nothing else."""
+    lb = kk - 1
+    sp = Spec(88, 3, lb, SECP_P)
+    k, nres, pt, cres = sp.k, 9 * sp.k + 3, 2 * (sp.k + 1), cmp_results(sp.k, 7)
+    m = multiples("secp256k1_p", 6)
+    a2, a0 = point(sp, *m[4]), point(sp, *m[1])
+    s_int = aff_add(SECP_P, m[4], (m[1][0], -m[1][1] % SECP_P))
+    pv = point(sp, *m[5]) if mode == "proof" else point(sp, s_int[0], m[5][1])
+    n = 1 << kk
+    na = 12
+    while True:                                        # the number of gate columns the layout fills (an empty one would have a disjoint selector)
+        sh = P.Shape(kk, na, nl, 1, 1, lb)
+        kb = VR.BaseCircuitBuilder(False)
+        _msm_program(kb, sp, a2, a0, pv)
+        advice_k, fixed, copies, instances, bps = kb.synthesize(sh)
+        if len(bps) == na - 1:
+            break
+        na = len(bps) + 1
+    assert na >= 2 and len(bps) >= 1
+    pb = VR.BaseCircuitBuilder(True)
+    pb.break_points = bps
+    calls = _msm_program(pb, sp, a2, a0, pv)
+    advice, _, _, _, _ = pb.synthesize(sh)
+    assert all(np.array_equal(a, b) for a, b in zip(advice, advice_k))
+    assert (calls[1][2].x3, calls[1][2].y3) == s_int
+    total = sum(len(t.advice) for t in pb.threads)
+    first = {}
+    for i, c, r in place(0, 0, total, bps, na)[0]:
+        first.setdefault(i, (c, r))
+    assert all(first[i] == (0, i) for i in range(3 * pt))           # the witnesses: flat index i of the gate allocation
+    kzg, srs_params = srs(ctx, kk, seed)
+    gpk = PL.keygen(kzg, PL.BaseCircuitParams.new(kk, na, nl, 1, 1, lb), fixed, copies)
+    budget = rng_budget(sh)
+    # one device buffer: [gate columns][results of S][of T][of D][the comparisons' results]
+    host = np.zeros((na * n + 3 * nres + 2 * cres, 4), dtype=np.uint64)
+    host[:3 * pt] = advice[0][:3 * pt]
+    d_gate = ctx.to_device(host)
+    d_lookup = ctx.to_device(np.zeros((nl * n, 4), dtype=np.uint64))
+    d_cols = [d_gate + 32 * n * c for c in range(na)]
+    d_lks = [d_lookup + 32 * n * c for c in range(nl)]
+    res_at = [na * n + j * nres for j in range(3)]
+    cres_at = [na * n + 3 * nres + j * cres for j in range(2)]
+    eq_want = [first[calls[j][0] + calls[j][2].out_offsets[2]] for j in (0, 2)]
+    try:
+        eq0, op0, _ = PL.ec_fill_strict_with_ranges(ctx, d_cols, sh.usable_rows, bps, d_lks, sp.params(), SUB, 7, d_gate, len(host), d_gate + 32 * res_at[0], nres,
+                                                    d_gate + 32 * cres_at[0], cres, [first[calls[0][0]] + (0, pt)], [calls[0][1]])
+        eq1, op1, _ = PL.ec_fill_strict_with_ranges(ctx, d_cols, sh.usable_rows, bps, d_lks, sp.params(), ADD, 7, d_gate, len(host), d_gate + 32 * res_at[1], nres,
+                                                    d_gate + 32 * cres_at[1], cres, [first[calls[2][0]] + (res_at[0], 2 * pt)], [calls[2][1]])
+        PL.ec_fill_with_ranges(ctx, d_cols, sh.usable_rows, bps, d_lks, sp.params(), DOUBLE, d_gate, len(host), d_gate + 32 * res_at[2], nres,
+                               [first[calls[4][0]] + (res_at[1], 0)], [calls[4][1]])
+        ctx.sync()
+        assert eq0 + eq1 == eq_want and op0 + op1 == [first[calls[1][0]], first[calls[3][0]]]
+        # both equality cells are pinned to the constant 0 by the key's copies
+        pinned = {r for l, r in copies if l[0][0] == "fixed"} | {l for l, r in copies if r[0][0] == "fixed"}
+        assert all((("advice", c), r) in pinned for c, r in eq_want)
+        got_cols = np.concatenate([ctx.download(d_gate, (na, n, 4)), ctx.download(d_lookup, (nl, n, 4))])
+        for c in range(na + nl):
+            assert np.array_equal(got_cols[c], advice[c]), "advice column %d differs from the Python-computed advice" % c
+        if mode == "equal_x":
+            ct = calls[2][2]
+            assert ct.results[-1] == 1 and calls[3][2].lam == 0
+            total_f, fails = PL.check_witness(gpk, d_cols + d_lks, instances, max_failures=4096, advice_on_device=True)
+            cmp_cells = {first[calls[2][0] + i] for i in range(ct.end - ct.start)}
+            perm_col = lambda c: 1 + c                                  # one constants column, then the gate advice
+            eq_c, eq_r = eq_want[1]
+            inside = [f for f in fails if (f.kind == "gate" and (f.column, f.row) in cmp_cells) or
+                      (f.kind == "copy" and ((f.column - 1, f.row) in cmp_cells or (f.peer_column - 1, f.peer_row) in cmp_cells))]
+            assert total_f == len(fails) and inside, fails[:8]
+            assert all(f.kind == "copy" and ((f.column, f.row) == (perm_col(eq_c), eq_r) or (f.peer_column, f.peer_row) == (perm_col(eq_c), eq_r)) for f in inside), inside
+            assert not any(f.kind == "lookup" for f in fails)
+            return
+        want = PL.create_proof(gpk, advice, instances, PreDrawnRng(budget, 2000 + seed))
+        got = PL.create_proof(gpk, d_cols + d_lks, instances, PreDrawnRng(budget, 2000 + seed), advice_on_device=True)
+        assert got == want, "the proof over the device-filled trace differs from the one over the host-laid trace"
+        asm = P.PermutationAssembly(sh)
+        for l, r in copies:
+            asm.copy(l, r)
+        opk = P.keygen(srs_params, sh, fixed, asm, 2)
+        oracle = P.create_proof(srs_params, opk, advice, [_ints(v) for v in instances], PreDrawnRng(budget, 2000 + seed), 2)
+        assert got == oracle, "the proof differs from the oracle prover's over the host-laid trace"
+        assert PL.verify_proof(gpk, instances, got), "h2hip_plonk_verify_proof rejects the proof"
+        assert P.verify_proof(srs_params, vk_from_gpu(sh, gpk), [_ints(v) for v in instances], got), "the test verifier rejects the proof"
+        total_f, fails = PL.check_witness(gpk, d_cols + d_lks, instances, advice_on_device=True)
+        assert total_f == 0, fails
+    finally:
+        ctx.free(d_gate)
+        ctx.free(d_lookup)
+        gpk.free()
+        kzg.free()

@@ -1,5 +1,5 @@
 """EccChip curve operations filled on the device against the same cells computed on the host.
-Usage: python tools/ec_time.py [k] [limb_bits] [num_limbs] [lookup_bits] [reps] [runs] [op]     (defaults 19 88 3 18 7 3 0)
+Usage: python tools/ec_time.py [k] [limb_bits] [num_limbs] [lookup_bits] [reps] [runs] [op]     (defaults 19 88 3 18 7 3 0; op: 0 ec_add_unequal, 1 ec_double, 3 ec_sub_unequal)
 
 The layout is the headline's shape: one gate column of 2^k rows filled down to the usable rows with ec_add_unequal units over secp256k1's p
 ((88, 3, 18): 908 cells and 162 lookup cells per unit, about 577 units) and one lookup-advice column that takes their lookup cells; the
@@ -83,7 +83,7 @@ for _ in range(4 * count):                    # arbitrary reduced coordinates: x
     ops += [(x >> (nbits * i)) & mask for i in range(nlimbs)] + [x % R]
 vals = fr(ops)
 print("k=%d: %d %s units (%d, %d, %d): %d gate cells (%d own) and %d lookup cells, %d range calls per fill" % (
-    k, count, "ec_double" if op else "ec_add_unequal", nbits, nlimbs, lb, count * lay.num_cells, count * lay.num_own_cells,
+    k, count, {0: "ec_add_unequal", 1: "ec_double", 3: "ec_sub_unequal"}[op], nbits, nlimbs, lb, count * lay.num_cells, count * lay.num_own_cells,
     count * lay.num_lookup_cells, len(range_tables)), flush=True)
 
 d_vals = ctx.to_device(vals)
