@@ -12,7 +12,7 @@ namespace h2 {
 
 #define H2_INL __attribute__((always_inline))
 
-constexpr uint32_t EC_MAX_SEGS = 80, EC_MAX_GAPS = 9 * FP_MAX_K, EC_CONSTS = 2 * FP_MAX_K + 8, EC_REC_REGS = 14;
+constexpr uint32_t EC_MAX_SEGS = 80, EC_MAX_GAPS = UNIT_MAX_GAPS, EC_CONSTS = 2 * FP_MAX_K + 8, EC_REC_REGS = 14;
 constexpr int EC_WA = 10;   // words of an operand integer (n k <= 318 bits) and of lambda; a no-carry value has 2 EC_WA
 
 // a CRT value is a "register" of k + 1 Fr (k limb cells, the native cell): registers 0 .. 3 are P.x, P.y, Q.x, Q.y in values_dev, register
@@ -56,16 +56,16 @@ struct EcSeg {
 };
 
 // what one call's lanes share
-struct EcCall {
-    TraceCols tc;
-    const Fr *values, *consts;
-    Fr *results, *rec;
+struct EcCall : TraceCall {
     const EcSeg *segs;
     uint32_t n, k;
     uint32_t p[FP_P_WORDS], mu[FP_MU_WORDS];   // wave-uniform: the modulus and its Barrett constant, 32-bit words
     int32_t p30[9];                            // the modulus in 30-bit limbs and -p^-1 mod 2^30, for the division steps
     uint32_t neg_pinv30;
 };
+H2_CALL_LEADS(EcCall) H2_OFFSET_IS(EcCall, segs, 56) H2_OFFSET_IS(EcCall, n, 64) H2_OFFSET_IS(EcCall, k, 68) H2_OFFSET_IS(EcCall, p, 72)
+H2_OFFSET_IS(EcCall, mu, 116) H2_OFFSET_IS(EcCall, p30, 168) H2_OFFSET_IS(EcCall, neg_pinv30, 204)
+static_assert(sizeof(EcCall) == 208, "EcCall grew or shrank");
 
 // ---- integers
 template <int N>
@@ -574,13 +574,11 @@ H2_HD void ec_place_slot(const EcCall &ec, const h2hip_ec_op &unit, uint32_t u, 
 }
 
 // ---- what the host derives from the parameters and the operation, once per call (host only)
-struct EcShape {
+struct EcShape : UnitShape {
     FpShape fp;
-    uint32_t op, k, nsegs, ngaps, total, own, num_lookups;
+    uint32_t op, k, nsegs;
     uint32_t rb[3], limb_bits_max[3];
     EcSeg segs[EC_MAX_SEGS];
-    h2hip_fp_mul_range gaps[EC_MAX_GAPS];
-    uint32_t gap_lookups[EC_MAX_GAPS];
     uint32_t out_offsets[3 * (FP_MAX_K + 1)];
 };
 struct EcBuilder {

@@ -44,10 +44,7 @@ int h2hip_ec_layout(const h2hip_fp_params *params, uint32_t op, size_t *num_cell
     EcShape sh;
     const char *bad = ec_prepare(*params, op, sh, nullptr, nullptr);
     H2_REQUIRE(!bad, bad);
-    *num_cells = sh.total;
-    *num_own_cells = sh.own;
-    *num_lookup_cells = sh.num_lookups;
-    for (uint32_t j = 0; j < sh.ngaps; ++j) ranges[j] = sh.gaps[j];
+    unit_layout_out(sh, num_cells, num_own_cells, num_lookup_cells, ranges);
     for (uint32_t j = 0; j < 3 * (sh.k + 1); ++j) out_cell_offsets[j] = sh.out_offsets[j];
     return H2HIP_OK;
 }
@@ -65,7 +62,7 @@ int h2hip_ec_range_checks(const uint32_t *break_points_host, size_t num_columns,
     size_t start[EC_MAX_GAPS];
     for (uint32_t g = 0; g < ng; ++g) start[g] = g ? start[g - 1] + (size_t)gaps_in[g - 1] * count : 0;
     for (uint32_t j = 0; j < sh.ngaps; ++j) rank[j] = seen[group_of[j]]++;
-    return fp_gap_checks(break_points_host, num_columns, sh.gaps, sh.gap_lookups, sh.ngaps, ec_result_len(sh.k), units_host, lookup_slots_host, count, checks_out,
+    return fp_gap_checks(break_points_host, num_columns, sh, ec_result_len(sh.k), units_host, lookup_slots_host, count, checks_out,
                          [&](size_t u, uint32_t j) { return start[group_of[j]] + u * gaps_in[group_of[j]] + rank[j]; });
 }
 
@@ -82,66 +79,30 @@ int h2hip_ec_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_colum
     Fr consts[EC_CONSTS];
     const char *bad = ec_prepare(*params, op, sh, &ec, consts);
     H2_REQUIRE(!bad, bad);
-    const uint32_t k = sh.k, slots = sh.nsegs, cells = sh.total, point = 2 * (k + 1);
+    const uint32_t k = sh.k, point = 2 * (k + 1);
     const bool two = op != H2HIP_EC_DOUBLE, sub = op == H2HIP_EC_SUB_UNEQUAL;
-    H2_REQUIRE(count <= ((uint64_t)1 << 32) / slots, "more than 2^32 slots (count * the unit's segments) in one call");
-    TraceRuns runs{columns_dev, num_columns, usable_rows, break_points_host};
-    bad = runs.args_bad();
-    H2_REQUIRE(!bad, bad);
-    H2_REQUIRE(values_len <= SIZE_MAX / sizeof(Fr) && results_len <= SIZE_MAX / sizeof(Fr), "values_len / results_len is no count of field elements");
-    H2_REQUIRE(!results_dev || results_len / ec_result_len(k) >= count, "results_len < count * (9 num_limbs + 3)");
-    std::vector<ByteRange> reads;
-    runs.written.reserve(count + 9);
-    reads.reserve(2 * count);
-    for (size_t j = 0; j < count; ++j) {
-        const h2hip_ec_op &u = units_host[j];
-        bad = runs.run(u.column, u.row, cells);   // the unit's whole run, gaps included
-        H2_REQUIRE(!bad, bad);
-        H2_REQUIRE(operand_range(values_dev, values_len, u.p_offset, point - 1, reads) && (!two || operand_range(values_dev, values_len, u.q_offset, point - 1, reads)),
-                   "a unit's operand lies outside values_len");
-    }
-    // two units' cells are disjoint; the results lie in none of them; no operand lies in anything written.  Address intervals, sorted and swept.
-    bad = byte_ranges_clash(runs.written, {}, "two units' cells overlap (break copies and the range checks' gaps included)");
-    H2_REQUIRE(!bad, bad);
-    if (results_dev) runs.written.push_back(ByteRange{(uintptr_t)results_dev, (uintptr_t)results_dev + sizeof(Fr) * ec_result_len(k) * count});
-    bad = byte_ranges_clash(runs.written, {&reads}, "the results overlap cells this call writes");
-    H2_REQUIRE(!bad, bad);
-    // ---- tables: [unit table][column pointers][break points][constants][segments], and the records
-    DevTables t;
-    Fr *rec = nullptr;
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_TMP2, sizeof(Fr) * ec_record_len(k) * count, (void **)&rec));
-    H2_CHK(pack_tables(ctx, {{units_host, sizeof(h2hip_ec_op) * count}, columns_table(runs), breaks_table(runs), {consts, sizeof(Fr) * EC_CONSTS},
-                             {sh.segs, sizeof(EcSeg) * slots}}, t));
-    ec.tc = t.tc;
-    ec.values = (const Fr *)values_dev;
-    ec.consts = (const Fr *)t.at[3];
-    ec.segs = (const EcSeg *)t.at[4];
-    ec.results = (Fr *)results_dev;
-    ec.rec = rec;
-    const h2hip_ec_op *units = (const h2hip_ec_op *)t.at[0];
-    const dim3 solve_grid((uint32_t)((count + EC_SOLVE_BLOCK - 1) / EC_SOLVE_BLOCK)), solve_block(EC_SOLVE_BLOCK);
-    prof_begin(ctx, "ec_solve_kernel");
-    if (k == 3 && sub)
-        hipLaunchKernelGGL((ec_solve_kernel<3, H2HIP_EC_SUB_UNEQUAL>), solve_grid, solve_block, 0, ctx->stream, ec, units, (uint32_t)count);
-    else if (sub)
-        hipLaunchKernelGGL((ec_solve_kernel<4, H2HIP_EC_SUB_UNEQUAL>), solve_grid, solve_block, 0, ctx->stream, ec, units, (uint32_t)count);
-    else if (k == 3 && two)
-        hipLaunchKernelGGL((ec_solve_kernel<3, H2HIP_EC_ADD_UNEQUAL>), solve_grid, solve_block, 0, ctx->stream, ec, units, (uint32_t)count);
-    else if (k == 3)
-        hipLaunchKernelGGL((ec_solve_kernel<3, H2HIP_EC_DOUBLE>), solve_grid, solve_block, 0, ctx->stream, ec, units, (uint32_t)count);
-    else if (two)
-        hipLaunchKernelGGL((ec_solve_kernel<4, H2HIP_EC_ADD_UNEQUAL>), solve_grid, solve_block, 0, ctx->stream, ec, units, (uint32_t)count);
-    else
-        hipLaunchKernelGGL((ec_solve_kernel<4, H2HIP_EC_DOUBLE>), solve_grid, solve_block, 0, ctx->stream, ec, units, (uint32_t)count);
-    prof_end(ctx);
-    H2_HIPCHK(hipGetLastError());
-    const uint64_t lanes = (uint64_t)count * slots;
-    prof_begin(ctx, "ec_place_kernel");
-    hipLaunchKernelGGL(ec_place_kernel, dim3((uint32_t)((lanes + EC_PLACE_BLOCK - 1) / EC_PLACE_BLOCK)), dim3(EC_PLACE_BLOCK), 0, ctx->stream, ec,
-                       units, slots, lanes);
-    prof_end(ctx);
-    H2_HIPCHK(hipGetLastError());
-    return H2HIP_OK;
+    const FusedKind kind{__func__, sh.total, sh.nsegs, ec_result_len(k), ec_record_len(k), {{true, point - 1}, {two, point - 1}}, {consts, sizeof(Fr) * EC_CONSTS},
+                         {sh.segs, sizeof(EcSeg) * sh.nsegs}, "ec_solve_kernel", "ec_place_kernel", EC_SOLVE_BLOCK, EC_PLACE_BLOCK};
+    return fused_fill(
+        ctx, columns_dev, num_columns, usable_rows, break_points_host, values_dev, values_len, results_dev, results_len, units_host, count, kind, ec,
+        [&](dim3 grid, const h2hip_ec_op *units, const void *segs) {
+            ec.segs = (const EcSeg *)segs;
+            if (k == 3 && sub)
+                hipLaunchKernelGGL((ec_solve_kernel<3, H2HIP_EC_SUB_UNEQUAL>), grid, dim3(EC_SOLVE_BLOCK), 0, ctx->stream, ec, units, (uint32_t)count);
+            else if (sub)
+                hipLaunchKernelGGL((ec_solve_kernel<4, H2HIP_EC_SUB_UNEQUAL>), grid, dim3(EC_SOLVE_BLOCK), 0, ctx->stream, ec, units, (uint32_t)count);
+            else if (k == 3 && two)
+                hipLaunchKernelGGL((ec_solve_kernel<3, H2HIP_EC_ADD_UNEQUAL>), grid, dim3(EC_SOLVE_BLOCK), 0, ctx->stream, ec, units, (uint32_t)count);
+            else if (k == 3)
+                hipLaunchKernelGGL((ec_solve_kernel<3, H2HIP_EC_DOUBLE>), grid, dim3(EC_SOLVE_BLOCK), 0, ctx->stream, ec, units, (uint32_t)count);
+            else if (two)
+                hipLaunchKernelGGL((ec_solve_kernel<4, H2HIP_EC_ADD_UNEQUAL>), grid, dim3(EC_SOLVE_BLOCK), 0, ctx->stream, ec, units, (uint32_t)count);
+            else
+                hipLaunchKernelGGL((ec_solve_kernel<4, H2HIP_EC_DOUBLE>), grid, dim3(EC_SOLVE_BLOCK), 0, ctx->stream, ec, units, (uint32_t)count);
+        },
+        [&](dim3 grid, const h2hip_ec_op *units, uint32_t slots, uint64_t lanes) {
+            hipLaunchKernelGGL(ec_place_kernel, grid, dim3(EC_PLACE_BLOCK), 0, ctx->stream, ec, units, slots, lanes);
+        });
 }
 
 }  // extern "C"

@@ -28,13 +28,13 @@ H2_HD uint32_t cmp_result_len(uint32_t k, uint32_t op) {
 }
 
 // what one call's lanes share.  consts (canonical Montgomery Fr): [m_i, i < k][2^pad][-2^pad]
-struct CmpCall {
-    TraceCols tc;
-    const Fr *values, *consts;
-    Fr *results, *rec;
+struct CmpCall : TraceCall {
     const CmpSeg *segs;
     uint32_t k, op, pad, lb;
 };
+H2_CALL_LEADS(CmpCall) H2_OFFSET_IS(CmpCall, segs, 56) H2_OFFSET_IS(CmpCall, k, 64) H2_OFFSET_IS(CmpCall, op, 68) H2_OFFSET_IS(CmpCall, pad, 72)
+H2_OFFSET_IS(CmpCall, lb, 76)
+static_assert(sizeof(CmpCall) == 80, "CmpCall grew or shrank");
 
 // c ? a : b word by word (a ?: over two Fr objects selects between their addresses and sends both to scratch)
 H2_HD Fr cmp_select(bool c, const Fr &a, const Fr &b) {
@@ -141,12 +141,10 @@ H2_HD void cmp_place_slot(const CmpCall &cc, const h2hip_fp_mul &unit, uint32_t 
 }
 
 // ---- what the host derives from the parameters and the mask, once per call (host only)
-struct CmpShape {
+struct CmpShape : UnitShape {
     FpShape fp;
-    uint32_t op, k, pad, width, nsegs, ngaps, total, own, num_lookups, gap_cells, gap_lookups_each;
+    uint32_t op, k, pad, width, nsegs, gap_cells, gap_lookups_each;
     CmpSeg segs[CMP_MAX_SEGS];
-    h2hip_fp_mul_range gaps[CMP_MAX_GAPS];
-    uint32_t gap_lookups[CMP_MAX_GAPS];
     uint32_t out_offsets[3];
 };
 // nullptr when the parameters and the mask are served, else the reason.  cc, consts (CMP_CONSTS entries): optional

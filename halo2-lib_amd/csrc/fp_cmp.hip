@@ -44,11 +44,8 @@ int h2hip_fp_cmp_layout(const h2hip_fp_params *params, uint32_t op, size_t *num_
     CmpShape sh;
     const char *bad = cmp_prepare(*params, op, sh, nullptr, nullptr);
     H2_REQUIRE(!bad, bad);
-    *num_cells = sh.total;
-    *num_own_cells = sh.own;
-    *num_lookup_cells = sh.num_lookups;
+    unit_layout_out(sh, num_cells, num_own_cells, num_lookup_cells, ranges);
     *results_per_unit = cmp_result_len(sh.k, op);
-    for (uint32_t j = 0; j < sh.ngaps; ++j) ranges[j] = sh.gaps[j];
     for (uint32_t j = 0; j < 3; ++j) out_cell_offsets[j] = sh.out_offsets[j];
     return H2HIP_OK;
 }
@@ -62,7 +59,7 @@ int h2hip_fp_cmp_range_checks(const uint32_t *break_points_host, size_t num_colu
     H2_REQUIRE(!bad, bad);
     // one width; unit-major: rows and lookup slots ascend with the units
     const uint32_t ngaps = sh.ngaps;
-    return fp_gap_checks(break_points_host, num_columns, sh.gaps, sh.gap_lookups, ngaps, cmp_result_len(sh.k, op), units_host, lookup_slots_host, count, checks_out,
+    return fp_gap_checks(break_points_host, num_columns, sh, cmp_result_len(sh.k, op), units_host, lookup_slots_host, count, checks_out,
                          [ngaps](size_t u, uint32_t j) { return u * ngaps + j; });
 }
 
@@ -79,55 +76,19 @@ int h2hip_fp_cmp_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_c
     Fr consts[CMP_CONSTS];
     const char *bad = cmp_prepare(*params, op, sh, &cc, consts);
     H2_REQUIRE(!bad, bad);
-    const uint32_t k = sh.k, slots = sh.nsegs, cells = sh.total, nres = cmp_result_len(k, op);
+    const uint32_t k = sh.k;
     const bool reads_a = op & (H2HIP_FP_CMP_REDUCE_A | H2HIP_FP_CMP_EQUAL), reads_b = op & (H2HIP_FP_CMP_REDUCE_B | H2HIP_FP_CMP_EQUAL);
-    H2_REQUIRE(count <= ((uint64_t)1 << 32) / slots, "more than 2^32 lanes (count * the unit's segments) in one call");
-    TraceRuns runs{columns_dev, num_columns, usable_rows, break_points_host};
-    bad = runs.args_bad();
-    H2_REQUIRE(!bad, bad);
-    H2_REQUIRE(values_len <= SIZE_MAX / sizeof(Fr) && results_len <= SIZE_MAX / sizeof(Fr), "values_len / results_len is no count of field elements");
-    H2_REQUIRE(!results_dev || results_len / nres >= count, "results_len < count * the results of a unit (h2hip_fp_cmp_layout)");
-    std::vector<ByteRange> reads;
-    runs.written.reserve(count + 9);
-    reads.reserve(2 * count);
-    for (size_t j = 0; j < count; ++j) {
-        const h2hip_fp_mul &u = units_host[j];
-        bad = runs.run(u.column, u.row, cells);   // the unit's whole run, gaps included
-        H2_REQUIRE(!bad, bad);
-        H2_REQUIRE((!reads_a || operand_range(values_dev, values_len, u.a_offset, k, reads)) && (!reads_b || operand_range(values_dev, values_len, u.b_offset, k, reads)),
-                   "a unit's operand lies outside values_len");
-    }
-    // two units' cells are disjoint; the results lie in none of them; no operand lies in anything written.  Address intervals, sorted and swept.
-    bad = byte_ranges_clash(runs.written, {}, "two units' cells overlap (break copies and the range checks' gaps included)");
-    H2_REQUIRE(!bad, bad);
-    if (results_dev) runs.written.push_back(ByteRange{(uintptr_t)results_dev, (uintptr_t)results_dev + sizeof(Fr) * nres * count});
-    bad = byte_ranges_clash(runs.written, {&reads}, "the results overlap cells this call writes");
-    H2_REQUIRE(!bad, bad);
-    // ---- tables: [unit table][column pointers][break points][constants][segments], and the records
-    DevTables t;
-    Fr *rec = nullptr;
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_TMP2, sizeof(Fr) * cmp_record_len(k) * count, (void **)&rec));
-    H2_CHK(pack_tables(ctx, {{units_host, sizeof(h2hip_fp_mul) * count}, columns_table(runs), breaks_table(runs), {consts, sizeof(Fr) * CMP_CONSTS},
-                             {sh.segs, sizeof(CmpSeg) * slots}}, t));
-    cc.tc = t.tc;
-    cc.values = (const Fr *)values_dev;
-    cc.consts = (const Fr *)t.at[3];
-    cc.segs = (const CmpSeg *)t.at[4];
-    cc.results = (Fr *)results_dev;
-    cc.rec = rec;
-    const h2hip_fp_mul *units = (const h2hip_fp_mul *)t.at[0];
-    prof_begin(ctx, "fp_cmp_solve_kernel");
-    hipLaunchKernelGGL(fp_cmp_solve_kernel, dim3((uint32_t)((count + CMP_SOLVE_BLOCK - 1) / CMP_SOLVE_BLOCK)), dim3(CMP_SOLVE_BLOCK), 0, ctx->stream, cc, units,
-                       (uint32_t)count);
-    prof_end(ctx);
-    H2_HIPCHK(hipGetLastError());
-    const uint64_t lanes = (uint64_t)count * slots;
-    prof_begin(ctx, "fp_cmp_place_kernel");
-    hipLaunchKernelGGL(fp_cmp_place_kernel, dim3((uint32_t)((lanes + CMP_PLACE_BLOCK - 1) / CMP_PLACE_BLOCK)), dim3(CMP_PLACE_BLOCK), 0, ctx->stream, cc,
-                       units, slots, lanes);
-    prof_end(ctx);
-    H2_HIPCHK(hipGetLastError());
-    return H2HIP_OK;
+    const FusedKind kind{__func__, sh.total, sh.nsegs, cmp_result_len(k, op), cmp_record_len(k), {{reads_a, k}, {reads_b, k}}, {consts, sizeof(Fr) * CMP_CONSTS},
+                         {sh.segs, sizeof(CmpSeg) * sh.nsegs}, "fp_cmp_solve_kernel", "fp_cmp_place_kernel", CMP_SOLVE_BLOCK, CMP_PLACE_BLOCK};
+    return fused_fill(
+        ctx, columns_dev, num_columns, usable_rows, break_points_host, values_dev, values_len, results_dev, results_len, units_host, count, kind, cc,
+        [&](dim3 grid, const h2hip_fp_mul *units, const void *segs) {
+            cc.segs = (const CmpSeg *)segs;
+            hipLaunchKernelGGL(fp_cmp_solve_kernel, grid, dim3(CMP_SOLVE_BLOCK), 0, ctx->stream, cc, units, (uint32_t)count);
+        },
+        [&](dim3 grid, const h2hip_fp_mul *units, uint32_t slots, uint64_t lanes) {
+            hipLaunchKernelGGL(fp_cmp_place_kernel, grid, dim3(CMP_PLACE_BLOCK), 0, ctx->stream, cc, units, slots, lanes);
+        });
 }
 
 }  // extern "C"

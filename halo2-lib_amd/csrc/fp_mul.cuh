@@ -20,14 +20,14 @@ constexpr uint32_t FP_CONSTS = 2 * FP_MAX_K + 4;
 constexpr uint32_t FP_NUM_BITS = 254, FP_CAPACITY = 253;   // F::NUM_BITS, F::CAPACITY
 
 // what one call's lanes share.  consts (canonical Montgomery Fr): [m_i, i < k][2^(n i), i < k][2^quot_last_limb_bits][2^rb][m_nat][-1]
-struct FpCall {
-    TraceCols tc;
-    const Fr *values, *consts;
-    Fr *results, *rec;
+struct FpCall : TraceCall {
     uint32_t n, k;
     uint32_t gap_o, gap_ol, gap_q, gap_ql, gap_c;   // cells of the range checks of o_i (the last), q_i + B (the last), -c_i + 2^rb
     uint32_t p[FP_P_WORDS], mu[FP_MU_WORDS];        // wave-uniform: the modulus and its Barrett constant, 32-bit words
 };
+H2_CALL_LEADS(FpCall) H2_OFFSET_IS(FpCall, n, 56) H2_OFFSET_IS(FpCall, k, 60) H2_OFFSET_IS(FpCall, gap_o, 64) H2_OFFSET_IS(FpCall, gap_ol, 68)
+H2_OFFSET_IS(FpCall, gap_q, 72) H2_OFFSET_IS(FpCall, gap_ql, 76) H2_OFFSET_IS(FpCall, gap_c, 80) H2_OFFSET_IS(FpCall, p, 84) H2_OFFSET_IS(FpCall, mu, 128)
+static_assert(sizeof(FpCall) == 184, "FpCall grew or shrank");
 H2_HD uint32_t fp_record_len(uint32_t k) { return 5 * k + 3; }    // [q_i][o_i][-c_i][P_i][check_i] N quot_native out_native
 H2_HD uint32_t fp_result_len(uint32_t k) { return 3 * k + 1; }    // [o_i] out_native [q_i + B][-c_i + 2^rb]
 H2_HD uint32_t fp_unit_slots(uint32_t k) { return 4 * k + 3; }
@@ -374,14 +374,19 @@ H2_HD void fp_place_slot(const FpCall &fc, const h2hip_fp_mul &unit, uint32_t u,
 }
 
 // ---- what the host derives from the parameters, once per call (host only)
-struct FpShape {
+// what the shape of every fused unit (FpShape, EcShape, CmpShape) states of its run: the cells, those the unit writes itself, the lookup
+// cells of its range checks, and the gaps those checks fill, in context order (the lookup queue order)
+constexpr uint32_t UNIT_MAX_GAPS = 9 * FP_MAX_K;
+struct UnitShape {
+    uint32_t total, own, num_lookups, ngaps;
+    h2hip_fp_mul_range gaps[UNIT_MAX_GAPS];
+    uint32_t gap_lookups[UNIT_MAX_GAPS];
+};
+// the gaps: o_i (behind S3), q_i + B (behind its four cells), -c_i + 2^rb (behind its eight)
+struct FpShape : UnitShape {
     uint32_t n, k, lb, rb, out_last_bits, quot_last_bits;
     uint32_t gap[5];       // cells of a range check of n, out_last_bits, n + 1, quot_last_bits + 1, rb + 1 bits
     FpLayout lay;
-    // the 3 k gaps in context order (the lookup queue order): o_i (behind S3), q_i + B (behind its four cells), -c_i + 2^rb (behind its eight)
-    h2hip_fp_mul_range gaps[3 * FP_MAX_K];
-    uint32_t gap_lookups[3 * FP_MAX_K];
-    size_t own, num_lookups;
 };
 inline uint32_t fp_words_bits(const uint32_t *w, int nw) {
     for (int j = nw - 1; j >= 0; --j)
@@ -440,8 +445,10 @@ inline const char *fp_prepare(const h2hip_fp_params &pr, FpShape &sh, FpCall *fc
         lookups[j] = range_unit_lookups(L, rem);
     }
     sh.lay = fp_layout(k, sh.gap[0], sh.gap[1], sh.gap[2], sh.gap[3], sh.gap[4]);
+    sh.total = sh.lay.total;
     sh.own = 3 * k * k + 29 * k + 3;
     sh.num_lookups = 0;
+    sh.ngaps = 3 * k;
     for (uint32_t j = 0; j < 3 * k; ++j) {
         const uint32_t i = j % k, grp = j / k, w = 2 * grp + (grp < 2 && i == k - 1 ? 1 : 0);   // (the last o and the last q have a width of their own)
         const uint32_t off = grp == 0 ? sh.lay.base4 + i * sh.gap[0] : grp == 1 ? sh.lay.base5 + i * (4 + sh.gap[2]) + 4 : sh.lay.base6 + i * (8 + sh.gap[4]) + 8;
@@ -497,21 +504,28 @@ inline const char *fp_prepare(const h2hip_fp_params &pr, FpShape &sh, FpCall *fc
 // out[index(u, j)]: its first cell by h2hip_trace_seek's walk from the unit's first cell, its value at results entry u result_len +
 // result_index, its lookup cells behind those of the unit's gaps before it.  -> H2HIP_OK, or h2hip_trace_seek's refusal
 template <class Unit, class Index>
-inline int fp_gap_checks(const uint32_t *break_points, size_t num_columns, const h2hip_fp_mul_range *gaps, const uint32_t *gap_lookups, uint32_t ngaps,
-                         uint32_t result_len, const Unit *units, const uint64_t *lookup_slots, size_t count, h2hip_range_check *out, Index index) {
+inline int fp_gap_checks(const uint32_t *break_points, size_t num_columns, const UnitShape &sh, uint32_t result_len, const Unit *units,
+                         const uint64_t *lookup_slots, size_t count, h2hip_range_check *out, Index index) {
     for (size_t u = 0; u < count; ++u) {
         uint64_t slot = lookup_slots[u];
-        for (uint32_t j = 0; j < ngaps; ++j) {
+        for (uint32_t j = 0; j < sh.ngaps; ++j) {
             h2hip_range_check &c = out[index(u, j)];
-            const int r = h2hip_trace_seek(break_points, num_columns, units[u].column, units[u].row, gaps[j].cell_offset, &c.column, &c.row);
+            const int r = h2hip_trace_seek(break_points, num_columns, units[u].column, units[u].row, sh.gaps[j].cell_offset, &c.column, &c.row);
             if (r != H2HIP_OK) return r;
-            c.a_offset = (uint64_t)u * result_len + gaps[j].result_index;
+            c.a_offset = (uint64_t)u * result_len + sh.gaps[j].result_index;
             c.b_offset = 0;
             c.lookup_slot = slot;
-            slot += gap_lookups[j];
+            slot += sh.gap_lookups[j];
         }
     }
     return H2HIP_OK;
+}
+// the *_layout functions' common out-parameters
+inline void unit_layout_out(const UnitShape &sh, size_t *num_cells, size_t *num_own_cells, size_t *num_lookup_cells, h2hip_fp_mul_range *ranges) {
+    *num_cells = sh.total;
+    *num_own_cells = sh.own;
+    *num_lookup_cells = sh.num_lookups;
+    for (uint32_t j = 0; j < sh.ngaps; ++j) ranges[j] = sh.gaps[j];
 }
 
 }  // namespace h2

@@ -47,10 +47,7 @@ int h2hip_fp_mul_layout(const h2hip_fp_params *params, size_t *num_cells, size_t
     const char *bad = fp_prepare(*params, sh, nullptr, nullptr);
     H2_REQUIRE(!bad, bad);
     const uint32_t k = sh.k;
-    *num_cells = sh.lay.total;
-    *num_own_cells = sh.own;
-    *num_lookup_cells = sh.num_lookups;
-    for (uint32_t j = 0; j < 3 * k; ++j) ranges[j] = sh.gaps[j];
+    unit_layout_out(sh, num_cells, num_own_cells, num_lookup_cells, ranges);
     for (uint32_t i = 0; i < k; ++i) out_cell_offsets[i] = sh.lay.base3 + fp_tri(i) + 10 * i + 3 * (i + 1) + 1 + 4;   // o_i: the fifth cell behind prod_i
     out_cell_offsets[k] = sh.lay.off9 - 1;   // out_native: the last cell of S8
     return H2HIP_OK;
@@ -64,7 +61,7 @@ int h2hip_fp_mul_range_checks(const uint32_t *break_points_host, size_t num_colu
     const char *bad = fp_prepare(*params, sh, nullptr, nullptr);
     H2_REQUIRE(!bad, bad);
     // gap-major: the gaps of one width are consecutive
-    return fp_gap_checks(break_points_host, num_columns, sh.gaps, sh.gap_lookups, 3 * sh.k, fp_result_len(sh.k), units_host, lookup_slots_host, count, checks_out,
+    return fp_gap_checks(break_points_host, num_columns, sh, fp_result_len(sh.k), units_host, lookup_slots_host, count, checks_out,
                          [count](size_t u, uint32_t j) { return (size_t)j * count + u; });
 }
 
@@ -81,57 +78,22 @@ int h2hip_fp_mul_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_c
     Fr consts[FP_CONSTS];
     const char *bad = fp_prepare(*params, sh, &fc, consts);
     H2_REQUIRE(!bad, bad);
-    const uint32_t k = sh.k, slots = fp_unit_slots(k), cells = sh.lay.total;
-    H2_REQUIRE(count <= ((uint64_t)1 << 32) / slots, "more than 2^32 slots (count * (4 num_limbs + 3)) in one call");
-    TraceRuns runs{columns_dev, num_columns, usable_rows, break_points_host};
-    bad = runs.args_bad();
-    H2_REQUIRE(!bad, bad);
-    H2_REQUIRE(values_len <= SIZE_MAX / sizeof(Fr) && results_len <= SIZE_MAX / sizeof(Fr), "values_len / results_len is no count of field elements");
-    H2_REQUIRE(!results_dev || results_len / fp_result_len(k) >= count, "results_len < count * (3 num_limbs + 1)");
-    std::vector<ByteRange> reads;
-    runs.written.reserve(count + 9);
-    reads.reserve(2 * count);
-    for (size_t j = 0; j < count; ++j) {
-        const h2hip_fp_mul &u = units_host[j];
-        bad = runs.run(u.column, u.row, cells);   // the unit's whole run, gaps included
-        H2_REQUIRE(!bad, bad);
-        H2_REQUIRE(operand_range(values_dev, values_len, u.a_offset, k, reads) && operand_range(values_dev, values_len, u.b_offset, k, reads),
-                   "a unit's operand lies outside values_len");
-    }
-    // two units' cells are disjoint; the results lie in none of them; no operand lies in anything written.  Address intervals, sorted and swept.
-    bad = byte_ranges_clash(runs.written, {}, "two units' cells overlap (break copies and the range checks' gaps included)");
-    H2_REQUIRE(!bad, bad);
-    if (results_dev) runs.written.push_back(ByteRange{(uintptr_t)results_dev, (uintptr_t)results_dev + sizeof(Fr) * fp_result_len(k) * count});
-    bad = byte_ranges_clash(runs.written, {&reads}, "the results overlap cells this call writes");
-    H2_REQUIRE(!bad, bad);
-    // ---- tables: [unit table][column pointers][break points][constants], and the records
-    DevTables t;
-    Fr *rec = nullptr;
-    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_TMP2, sizeof(Fr) * fp_record_len(k) * count, (void **)&rec));
-    H2_CHK(pack_tables(ctx, {{units_host, sizeof(h2hip_fp_mul) * count}, columns_table(runs), breaks_table(runs), {consts, sizeof(Fr) * FP_CONSTS}}, t));
-    fc.tc = t.tc;
-    fc.values = (const Fr *)values_dev;
-    fc.consts = (const Fr *)t.at[3];
-    fc.results = (Fr *)results_dev;
-    fc.rec = rec;
-    const h2hip_fp_mul *units = (const h2hip_fp_mul *)t.at[0];
-    const dim3 solve_grid((uint32_t)((count + FP_SOLVE_BLOCK - 1) / FP_SOLVE_BLOCK)), solve_block(FP_SOLVE_BLOCK);
-    prof_begin(ctx, "fp_mul_solve_kernel");
-    if (k == 2)
-        hipLaunchKernelGGL(fp_mul_solve_kernel<2>, solve_grid, solve_block, 0, ctx->stream, fc, units, (uint32_t)count);
-    else if (k == 3)
-        hipLaunchKernelGGL(fp_mul_solve_kernel<3>, solve_grid, solve_block, 0, ctx->stream, fc, units, (uint32_t)count);
-    else
-        hipLaunchKernelGGL(fp_mul_solve_kernel<4>, solve_grid, solve_block, 0, ctx->stream, fc, units, (uint32_t)count);
-    prof_end(ctx);
-    H2_HIPCHK(hipGetLastError());
-    const uint64_t lanes = (uint64_t)count * slots;
-    prof_begin(ctx, "fp_mul_place_kernel");
-    hipLaunchKernelGGL(fp_mul_place_kernel, dim3((uint32_t)((lanes + FP_PLACE_BLOCK - 1) / FP_PLACE_BLOCK)), dim3(FP_PLACE_BLOCK), 0, ctx->stream, fc,
-                       units, slots, lanes);
-    prof_end(ctx);
-    H2_HIPCHK(hipGetLastError());
-    return H2HIP_OK;
+    const uint32_t k = sh.k;
+    const FusedKind kind{__func__, sh.total, fp_unit_slots(k), fp_result_len(k), fp_record_len(k), {{true, k}, {true, k}}, {consts, sizeof(Fr) * FP_CONSTS}, {nullptr, 0},
+                         "fp_mul_solve_kernel", "fp_mul_place_kernel", FP_SOLVE_BLOCK, FP_PLACE_BLOCK};
+    return fused_fill(
+        ctx, columns_dev, num_columns, usable_rows, break_points_host, values_dev, values_len, results_dev, results_len, units_host, count, kind, fc,
+        [&](dim3 grid, const h2hip_fp_mul *units, const void *) {
+            if (k == 2)
+                hipLaunchKernelGGL(fp_mul_solve_kernel<2>, grid, dim3(FP_SOLVE_BLOCK), 0, ctx->stream, fc, units, (uint32_t)count);
+            else if (k == 3)
+                hipLaunchKernelGGL(fp_mul_solve_kernel<3>, grid, dim3(FP_SOLVE_BLOCK), 0, ctx->stream, fc, units, (uint32_t)count);
+            else
+                hipLaunchKernelGGL(fp_mul_solve_kernel<4>, grid, dim3(FP_SOLVE_BLOCK), 0, ctx->stream, fc, units, (uint32_t)count);
+        },
+        [&](dim3 grid, const h2hip_fp_mul *units, uint32_t slots, uint64_t lanes) {
+            hipLaunchKernelGGL(fp_mul_place_kernel, grid, dim3(FP_PLACE_BLOCK), 0, ctx->stream, fc, units, slots, lanes);
+        });
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // The host prologue the device trace fills share (poseidon_trace.hip, range_fill.hip, fp_mul.hip, ec_fill.hip; gate_chains.hip takes the
 // table packer alone): the checks of the column arguments, the address intervals a unit's run and its operands cover, the sweep that finds two
 // of them at one address, and the upload of a call's small tables.  Host only.  An entry point reads: its parameters, a loop over the units
-// (TraceRuns::run, operand_range), the clash checks, then pack_tables and the launches.
+// (TraceRuns::run, operand_range), the clash checks, then pack_tables and the launches.  The fused fills (fp_mul.hip, ec_fill.hip,
+// fp_cmp.hip) have all of that in one place, fused_fill at the end of this file.
 #pragma once
 #include "internal.h"
 #include "trace_place.cuh"
@@ -99,7 +100,8 @@ struct DevTables {
 };
 inline int pack_tables(h2hip_ctx *ctx, std::initializer_list<HostTable> tables, DevTables &out) {
     size_t end = 0, n = 0;
-    for (const HostTable &t : tables) end = (end + 255) / 256 * 256 + t.bytes;
+    for (const HostTable &t : tables)
+        if (t.bytes) end = (end + 255) / 256 * 256 + t.bytes;
     char *base = nullptr;
     H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_TMP1, end, (void **)&base));
     out.tc = TraceCols{nullptr, nullptr, 0};
@@ -120,6 +122,76 @@ inline int pack_tables(h2hip_ctx *ctx, std::initializer_list<HostTable> tables, 
 inline HostTable columns_table(const TraceRuns &r) { return HostTable{r.columns_dev, sizeof(void *) * r.num_columns, HostTable::COLUMNS}; }
 inline HostTable breaks_table(const TraceRuns &r) {
     return HostTable{r.break_points, r.break_points ? sizeof(uint32_t) * (r.num_columns - 1) : 0, HostTable::BREAKS};
+}
+
+// ---- the fused fills (fp_mul.hip, ec_fill.hip, fp_cmp.hip): a solve kernel, one lane per unit, leaves a record per unit; a place kernel, one
+// lane per (unit, slot), writes the cells.  What a kind states of itself; fused_fill is everything between its *_prepare and its kernels.
+struct FusedKind {
+    const char *func;                            // the entry point, for the messages
+    uint32_t cells, slots, results, record;      // per unit: the run with its gaps, the place kernel's lanes, results entries, Fr of the record
+    struct {
+        bool read;
+        uint32_t span;                           // elements offset .. offset + span of values_dev
+    } operand[2];
+    HostTable consts, segs;                      // segs: of no bytes for a kind without a segment table
+    const char *solve_name, *place_name;         // for prof_begin
+    uint32_t solve_block, place_block;
+};
+inline uint64_t unit_operand(const h2hip_fp_mul &u, int i) { return i ? u.b_offset : u.a_offset; }
+inline uint64_t unit_operand(const h2hip_ec_op &u, int i) { return i ? u.q_offset : u.p_offset; }
+
+// Every check of the column arguments, the operands and the results, before anything is uploaded or launched; the records in WS_TMP2; the
+// tables [units][column pointers][break points][constants]([segments]) in WS_TMP1; call's five leading members; then solve(grid, units,
+// segs) and, behind it, place(grid, units, slots, lanes) launch on ctx->stream, each between prof_begin and prof_end.  units, segs: the
+// tables' device addresses (solve stores segs in its call struct where the kind has a segment table: place's launch finds it there).
+// count >= 1.
+template <class Unit, class Solve, class Place>
+int fused_fill(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const uint32_t *break_points_host, const void *values_dev,
+               size_t values_len, void *results_dev, size_t results_len, const Unit *units_host, size_t count, const FusedKind &kind, TraceCall &call,
+               Solve solve, Place place) {
+    H2_REQUIRE_AS(kind.func, count <= ((uint64_t)1 << 32) / kind.slots, "more than 2^32 lanes of the place kernel (count * the unit's slots) in one call");
+    TraceRuns runs{columns_dev, num_columns, usable_rows, break_points_host};
+    const char *bad = runs.args_bad();
+    H2_REQUIRE_AS(kind.func, !bad, bad);
+    H2_REQUIRE_AS(kind.func, values_len <= SIZE_MAX / sizeof(Fr) && results_len <= SIZE_MAX / sizeof(Fr), "values_len / results_len is no count of field elements");
+    H2_REQUIRE_AS(kind.func, !results_dev || results_len / kind.results >= count, "results_len < count * the results of a unit");
+    std::vector<ByteRange> reads;
+    runs.written.reserve(count + 9);
+    reads.reserve(2 * count);
+    for (size_t j = 0; j < count; ++j) {
+        const Unit &u = units_host[j];
+        bad = runs.run(u.column, u.row, kind.cells);   // the unit's whole run, gaps included
+        H2_REQUIRE_AS(kind.func, !bad, bad);
+        for (int i = 0; i < 2; ++i)
+            H2_REQUIRE_AS(kind.func, !kind.operand[i].read || operand_range(values_dev, values_len, unit_operand(u, i), kind.operand[i].span, reads),
+                          "a unit's operand lies outside values_len");
+    }
+    // two units' cells are disjoint; the results lie in none of them; no operand lies in anything written.  Address intervals, sorted and swept.
+    bad = byte_ranges_clash(runs.written, {}, "two units' cells overlap (break copies and the range checks' gaps included)");
+    H2_REQUIRE_AS(kind.func, !bad, bad);
+    if (results_dev) runs.written.push_back(ByteRange{(uintptr_t)results_dev, (uintptr_t)results_dev + sizeof(Fr) * kind.results * count});
+    bad = byte_ranges_clash(runs.written, {&reads}, "the results overlap cells this call writes");
+    H2_REQUIRE_AS(kind.func, !bad, bad);
+    DevTables t;
+    Fr *rec = nullptr;
+    H2_CHK(ws_reserve(ctx, h2hip_ctx::WS_TMP2, sizeof(Fr) * kind.record * count, (void **)&rec));
+    H2_CHK(pack_tables(ctx, {{units_host, sizeof(Unit) * count}, columns_table(runs), breaks_table(runs), kind.consts, kind.segs}, t));
+    call.tc = t.tc;
+    call.values = (const Fr *)values_dev;
+    call.consts = (const Fr *)t.at[3];
+    call.results = (Fr *)results_dev;
+    call.rec = rec;
+    const Unit *units = (const Unit *)t.at[0];
+    const uint64_t lanes = (uint64_t)count * kind.slots;
+    prof_begin(ctx, kind.solve_name);
+    solve(dim3((uint32_t)((count + kind.solve_block - 1) / kind.solve_block)), units, (const void *)t.at[4]);
+    prof_end(ctx);
+    H2_HIPCHK(hipGetLastError());
+    prof_begin(ctx, kind.place_name);
+    place(dim3((uint32_t)((lanes + kind.place_block - 1) / kind.place_block)), units, kind.slots, lanes);
+    prof_end(ctx);
+    H2_HIPCHK(hipGetLastError());
+    return H2HIP_OK;
 }
 
 }  // namespace h2

@@ -13,6 +13,24 @@ struct TraceCols {
     const uint32_t *bps;
     uint32_t last_col;
 };
+// what the call structs of the fused fills (FpCall, EcCall, CmpCall) begin with, as their base: trace_host.h's fused_fill sets these five
+struct TraceCall {
+    TraceCols tc;
+    const Fr *values, *consts;
+    Fr *results, *rec;
+};
+// A kernel argument's words stay where they are (one moved word has cost SGPRs and the alignment of the modulus words): each call struct
+// states the offset of every member.  (offsetof through a base is conditionally supported; the compilers this builds with support it)
+#define H2_OFFSET_IS(Call, member, at)                                                          \
+    _Pragma("clang diagnostic push") _Pragma("clang diagnostic ignored \"-Winvalid-offsetof\"") \
+    static_assert(offsetof(Call, member) == (at), #Call "." #member " moved");                  \
+    _Pragma("clang diagnostic pop")
+#define H2_CALL_LEADS(Call)        \
+    H2_OFFSET_IS(Call, tc, 0)      \
+    H2_OFFSET_IS(Call, values, 24) \
+    H2_OFFSET_IS(Call, consts, 32) \
+    H2_OFFSET_IS(Call, results, 40) \
+    H2_OFFSET_IS(Call, rec, 48)
 
 constexpr uint32_t TRACE_NO_BREAK = 0xFFFFFFFFu;
 // the cells from `row` up to and including the break cell of column `col` (a unit has fewer than 2^31 cells: without a break ahead the

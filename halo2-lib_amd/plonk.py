@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import hashlib
-from typing import NamedTuple, Optional, Sequence
+from typing import Callable, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -869,6 +869,78 @@ def fp_mul_table(units: Sequence) -> C.Array:
     return _struct_table(FpMulStruct, units)
 
 
+class _FusedKind(NamedTuple):
+    """one kind of fused unit (a library call of a solve and a place kernel, with its layout and range-check functions)"""
+    table: Callable          # the builder of its unit table
+    layout: str              # the three library functions
+    fill: str
+    range_checks: str
+    has_op: bool             # they take an op behind params
+    max_ranges: int          # the layout function's ranges / out_cell_offsets buffers,
+    max_outs: int
+    valid: Callable          # (k, op) -> how many entries of each are valid
+    results_per_unit: bool   # the layout function reports it
+    groups: Callable         # (k, ranges) -> [(width, gaps)]: how the flat check array is cut into tables, in its order
+
+
+def _by_width(_k: int, ranges: list) -> list:
+    widths: dict = {}
+    for r in ranges:
+        widths[r[2]] = widths.get(r[2], 0) + 1             # (a dict keeps the order of first appearance)
+    return list(widths.items())
+
+
+def _fused_layout(kind: _FusedKind, params, op: int, lib) -> list:
+    """the fields of the kind's layout tuple"""
+    lib = lib or load_library()
+    sizes = [C.c_size_t(0) for _ in range(4 if kind.results_per_unit else 3)]
+    ranges, outs = (FpMulRangeStruct * kind.max_ranges)(), (C.c_uint32 * kind.max_outs)()
+    code = getattr(lib, kind.layout)(C.cast(C.pointer(params), _vp), *([op] if kind.has_op else []), *[C.byref(x) for x in sizes], C.cast(ranges, _vp), outs)
+    _raise_on(code, lib)
+    nranges, nouts = kind.valid(params.num_limbs, op)
+    return [x.value for x in sizes] + [[(r.cell_offset, r.num_cells, r.range_bits, r.result_index) for r in ranges[:nranges]], list(outs[:nouts])]
+
+
+def _fused_fill(kind: _FusedKind, ctx: Context, columns, usable_rows, break_points, params, op, values_dev, values_len, results_dev, results_len, units, count) -> None:
+    arr = _as_table(units, kind.table)
+    ctx._chk(getattr(ctx.lib, kind.fill)(ctx.handle, _col_array(columns), len(columns), usable_rows, _bp_array(break_points, len(columns)),
+                                         C.cast(C.pointer(params), _vp), *([op] if kind.has_op else []), _dev_ptr(values_dev), values_len,
+                                         _dev_ptr(results_dev), results_len, C.cast(arr, _vp), len(units) if count is None else count))
+
+
+def _fused_range_tables(kind: _FusedKind, break_points, num_columns, params, op, units, lookup_slots, lib) -> list:
+    lib = lib or load_library()
+    ranges = _fused_layout(kind, params, op, lib)[-2]
+    count = len(lookup_slots)
+    if not count or not ranges:
+        return []
+    arr = _as_table(units, kind.table)
+    checks = (RangeCheckStruct * (len(ranges) * count))()
+    code = getattr(lib, kind.range_checks)(_bp_array(break_points, num_columns), num_columns, C.cast(C.pointer(params), _vp), *([op] if kind.has_op else []),
+                                           C.cast(arr, _vp), (C.c_uint64 * count)(*lookup_slots), count, C.cast(checks, _vp))
+    _raise_on(code, lib)
+    tables, at = [], 0
+    for bits, gaps in kind.groups(params.num_limbs, ranges):
+        tables.append((bits, (RangeCheckStruct * (gaps * count)).from_buffer(checks, C.sizeof(RangeCheckStruct) * at)))
+        at += gaps * count
+    return tables
+
+
+def _fused_fill_with_ranges(kind: _FusedKind, ctx: Context, columns, usable_rows, break_points, lookup_columns, params, op, values_dev, values_len, results_dev,
+                            results_len, units, lookup_slots, range_tables) -> None:
+    assert results_dev, "the range checks read results_dev"
+    arr = _as_table(units, kind.table)
+    tables = range_tables if range_tables is not None else _fused_range_tables(kind, break_points, len(columns), params, op, arr, lookup_slots, ctx.lib)
+    _fused_fill(kind, ctx, columns, usable_rows, break_points, params, op, values_dev, values_len, results_dev, results_len, arr, len(units))
+    for bits, table in tables:
+        range_fill_checks(ctx, columns, usable_rows, break_points, lookup_columns, results_dev, results_len, bits, params.lookup_bits, table)
+
+
+# gap-major: the gaps of one width are consecutive (o_i, the last o, q_i + B, the last q, -c_i + 2^rb)
+_FP_MUL = _FusedKind(fp_mul_table, "h2hip_fp_mul_layout", "h2hip_fp_mul_fill_dev", "h2hip_fp_mul_range_checks", False, 12, 5, lambda k, _op: (3 * k, k + 1), False,
+                     lambda k, ranges: [(ranges[j0][2], j1 - j0) for j0, j1 in ((0, k - 1), (k - 1, k), (k, 2 * k - 1), (2 * k - 1, 2 * k), (2 * k, 3 * k))])
+
+
 class FpMulLayout(NamedTuple):
     """h2hip_fp_mul_layout: the cells of one FpChip::mul unit, its own cells (the rest are the gaps of its range checks), the lookup cells of
     those checks, ranges = [(cell_offset, num_cells, range_bits, result_index)] of the 3 k gaps in context order (o, q, c: the lookup queue
@@ -881,14 +953,7 @@ class FpMulLayout(NamedTuple):
 
 
 def fp_mul_layout(params: FpParamsStruct, lib=None) -> FpMulLayout:
-    lib = lib or load_library()
-    cells, own, lookups = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-    ranges, outs = (FpMulRangeStruct * 12)(), (C.c_uint32 * 5)()
-    code = lib.h2hip_fp_mul_layout(C.cast(C.pointer(params), _vp), C.byref(cells), C.byref(own), C.byref(lookups), C.cast(ranges, _vp), outs)
-    _raise_on(code, lib)
-    k = params.num_limbs
-    return FpMulLayout(cells.value, own.value, lookups.value, [(r.cell_offset, r.num_cells, r.range_bits, r.result_index) for r in ranges[:3 * k]],
-                       list(outs[:k + 1]))
+    return FpMulLayout(*_fused_layout(_FP_MUL, params, 0, lib))
 
 
 def trace_seek(break_points: Optional[Sequence[int]], num_columns: int, column: int, row: int, offset: int, lib=None):
@@ -908,10 +973,7 @@ def fp_mul_fill(ctx: Context, columns: Sequence[int], usable_rows: int, break_po
     a_offset, b_offset) tuples or a table from fp_mul_table(); an operand is the k + 1 Fr of values_dev from its offset (k limbs, then the
     native residue).  results_dev (or None): 3 k + 1 Fr per unit — o_i, out_native, q_i + B, -c_i + 2^rb.  count: the units of a table
     to fill (default: all).  Stream-ordered on the context's stream."""
-    arr = _as_table(units, fp_mul_table)
-    ctx._chk(ctx.lib.h2hip_fp_mul_fill_dev(ctx.handle, _col_array(columns), len(columns), usable_rows, _bp_array(break_points, len(columns)),
-                                           C.cast(C.pointer(params), _vp), _dev_ptr(values_dev), values_len, _dev_ptr(results_dev), results_len,
-                                           C.cast(arr, _vp), len(units) if count is None else count))
+    _fused_fill(_FP_MUL, ctx, columns, usable_rows, break_points, params, 0, values_dev, values_len, results_dev, results_len, units, count)
 
 
 def fp_mul_range_tables(break_points: Optional[Sequence[int]], num_columns: int, params: FpParamsStruct, units, lookup_slots: Sequence[int], lib=None) -> list:
@@ -919,19 +981,7 @@ def fp_mul_range_tables(break_points: Optional[Sequence[int]], num_columns: int,
     table from fp_mul_table()), five tables of one width each in context order (the checks of o_i, of the last o, of q_i + B, of the last q,
     of -c_i + 2^rb), all made by one library call: each check's (column, row) by trace_seek's walk from its unit's first cell, its value at
     results index u (3 k + 1) + result_index, its lookup_slot from lookup_slots[u].  Build it once for a layout used in every proof."""
-    lib = lib or load_library()
-    k, count = params.num_limbs, len(lookup_slots)
-    arr = _as_table(units, fp_mul_table)
-    checks = (RangeCheckStruct * max(3 * k * count, 1))()
-    code = lib.h2hip_fp_mul_range_checks(_bp_array(break_points, num_columns), num_columns, C.cast(C.pointer(params), _vp), C.cast(arr, _vp), (C.c_uint64 * max(count, 1))(*lookup_slots), count,
-                                         C.cast(checks, _vp))
-    _raise_on(code, lib)
-    widths = [r[2] for r in fp_mul_layout(params, lib).ranges]
-    tables = []
-    for j0, j1 in ((0, k - 1), (k - 1, k), (k, 2 * k - 1), (2 * k - 1, 2 * k), (2 * k, 3 * k)):   # gap-major: the gaps of one width are consecutive
-        if count:
-            tables.append((widths[j0], (RangeCheckStruct * ((j1 - j0) * count)).from_buffer(checks, C.sizeof(RangeCheckStruct) * j0 * count)))
-    return tables
+    return _fused_range_tables(_FP_MUL, break_points, num_columns, params, 0, units, lookup_slots, lib)
 
 
 def fp_mul_fill_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], lookup_columns: Sequence[int],
@@ -940,12 +990,8 @@ def fp_mul_fill_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: i
     """fp_mul_fill, then five range_fill_checks calls (one per group of gaps of one width) from results_dev: the whole run of every unit and
     its lookup cells.  units: (column, row, a_offset, b_offset) tuples or a table from fp_mul_table(); lookup_slots[u]: the queue position of
     unit u's first lookup cell (not read with range_tables, the result of fp_mul_range_tables() built once for the layout)."""
-    assert results_dev, "the range checks read results_dev"
-    arr = _as_table(units, fp_mul_table)
-    tables = range_tables if range_tables is not None else fp_mul_range_tables(break_points, len(columns), params, arr, lookup_slots, ctx.lib)
-    fp_mul_fill(ctx, columns, usable_rows, break_points, params, values_dev, values_len, results_dev, results_len, arr, len(units))
-    for bits, table in tables:
-        range_fill_checks(ctx, columns, usable_rows, break_points, lookup_columns, results_dev, results_len, bits, params.lookup_bits, table)
+    _fused_fill_with_ranges(_FP_MUL, ctx, columns, usable_rows, break_points, lookup_columns, params, 0, values_dev, values_len, results_dev, results_len, units,
+                            lookup_slots, range_tables)
 
 
 class EcOpStruct(C.Structure):   # h2hip_ec_op
@@ -960,6 +1006,9 @@ def ec_op_table(units: Sequence) -> C.Array:
     return _struct_table(EcOpStruct, units)
 
 
+_EC = _FusedKind(ec_op_table, "h2hip_ec_layout", "h2hip_ec_fill_dev", "h2hip_ec_range_checks", True, 36, 15, lambda k, _op: (9 * k, 3 * (k + 1)), False, _by_width)
+
+
 class EcLayout(NamedTuple):
     """h2hip_ec_layout: the cells of one ec_add_unequal / ec_double unit, its own cells (the rest are the gaps of its range checks), the lookup
     cells of those checks, ranges = [(cell_offset, num_cells, range_bits, result_index)] of the 9 k gaps in context order (the lookup queue
@@ -972,14 +1021,7 @@ class EcLayout(NamedTuple):
 
 
 def ec_layout(params: FpParamsStruct, op: int, lib=None) -> EcLayout:
-    lib = lib or load_library()
-    cells, own, lookups = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-    ranges, outs = (FpMulRangeStruct * 36)(), (C.c_uint32 * 15)()
-    code = lib.h2hip_ec_layout(C.cast(C.pointer(params), _vp), op, C.byref(cells), C.byref(own), C.byref(lookups), C.cast(ranges, _vp), outs)
-    _raise_on(code, lib)
-    k = params.num_limbs
-    return EcLayout(cells.value, own.value, lookups.value, [(r.cell_offset, r.num_cells, r.range_bits, r.result_index) for r in ranges[:9 * k]],
-                    list(outs[:3 * (k + 1)]))
+    return EcLayout(*_fused_layout(_EC, params, op, lib))
 
 
 def ec_fill(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], params: FpParamsStruct, op: int, values_dev,
@@ -990,10 +1032,7 @@ def ec_fill(ctx: Context, columns: Sequence[int], usable_rows: int, break_points
     (column, row, p_offset, q_offset) tuples or a table from ec_op_table(); a point is the 2 (k + 1) Fr of values_dev from its offset (x's k
     limbs and native residue, then y's).  results_dev (or None): 9 k + 3 Fr per unit — x3, y3 (a point a later call may read), lambda, then
     per reduction q_i + B and -c_i + 2^rb.  count: the units of a table to fill (default: all).  Stream-ordered on the context's stream."""
-    arr = _as_table(units, ec_op_table)
-    ctx._chk(ctx.lib.h2hip_ec_fill_dev(ctx.handle, _col_array(columns), len(columns), usable_rows, _bp_array(break_points, len(columns)),
-                                       C.cast(C.pointer(params), _vp), op, _dev_ptr(values_dev), values_len, _dev_ptr(results_dev), results_len,
-                                       C.cast(arr, _vp), len(units) if count is None else count))
+    _fused_fill(_EC, ctx, columns, usable_rows, break_points, params, op, values_dev, values_len, results_dev, results_len, units, count)
 
 
 def ec_range_tables(break_points: Optional[Sequence[int]], num_columns: int, params: FpParamsStruct, op: int, units, lookup_slots: Sequence[int],
@@ -1002,22 +1041,7 @@ def ec_range_tables(break_points: Optional[Sequence[int]], num_columns: int, par
     from ec_op_table()), one table per distinct width in the order of first appearance among ec_layout's ranges, all made by one library call;
     inside a table the checks run unit by unit (rows and lookup slots ascend).  lookup_slots[u]: the queue position of unit u's first lookup
     cell.  Build it once for a layout used in every proof."""
-    lib = lib or load_library()
-    k, count = params.num_limbs, len(lookup_slots)
-    arr = _as_table(units, ec_op_table)
-    checks = (RangeCheckStruct * max(9 * k * count, 1))()
-    code = lib.h2hip_ec_range_checks(_bp_array(break_points, num_columns), num_columns, C.cast(C.pointer(params), _vp), op, C.cast(arr, _vp), (C.c_uint64 * max(count, 1))(*lookup_slots),
-                                     count, C.cast(checks, _vp))
-    _raise_on(code, lib)
-    widths: dict = {}
-    for r in ec_layout(params, op, lib).ranges:
-        widths[r[2]] = widths.get(r[2], 0) + 1             # (a dict keeps the order of first appearance)
-    tables, at = [], 0
-    for bits, gaps in widths.items():
-        if count:
-            tables.append((bits, (RangeCheckStruct * (gaps * count)).from_buffer(checks, C.sizeof(RangeCheckStruct) * at)))
-        at += gaps * count
-    return tables
+    return _fused_range_tables(_EC, break_points, num_columns, params, op, units, lookup_slots, lib)
 
 
 def ec_fill_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], lookup_columns: Sequence[int],
@@ -1026,16 +1050,14 @@ def ec_fill_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: int, 
     """ec_fill, then one range_fill_checks call per width group from results_dev: the whole run of every unit and its lookup cells.
     lookup_slots[u]: the queue position of unit u's first lookup cell (not read with range_tables, the result of ec_range_tables() built once
     for the layout)."""
-    assert results_dev, "the range checks read results_dev"
-    arr = _as_table(units, ec_op_table)
-    tables = range_tables if range_tables is not None else ec_range_tables(break_points, len(columns), params, op, arr, lookup_slots, ctx.lib)
-    ec_fill(ctx, columns, usable_rows, break_points, params, op, values_dev, values_len, results_dev, results_len, arr, len(units))
-    for bits, table in tables:
-        range_fill_checks(ctx, columns, usable_rows, break_points, lookup_columns, results_dev, results_len, bits, params.lookup_bits, table)
+    _fused_fill_with_ranges(_EC, ctx, columns, usable_rows, break_points, lookup_columns, params, op, values_dev, values_len, results_dev, results_len, units,
+                            lookup_slots, range_tables)
 
 
 FP_CMP_REDUCE_A, FP_CMP_REDUCE_B, FP_CMP_EQUAL = 1, 2, 4
 NO_CELL = 0xFFFFFFFF
+_FP_CMP = _FusedKind(fp_mul_table, "h2hip_fp_cmp_layout", "h2hip_fp_cmp_fill_dev", "h2hip_fp_cmp_range_checks", True, 8, 3,
+                     lambda k, op: (k * (bool(op & FP_CMP_REDUCE_A) + bool(op & FP_CMP_REDUCE_B)), 3), True, _by_width)
 
 
 class FpCmpLayout(NamedTuple):
@@ -1052,14 +1074,7 @@ class FpCmpLayout(NamedTuple):
 
 
 def fp_cmp_layout(params: FpParamsStruct, op: int, lib=None) -> FpCmpLayout:
-    lib = lib or load_library()
-    cells, own, lookups, nres = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-    ranges, outs = (FpMulRangeStruct * 8)(), (C.c_uint32 * 3)()
-    code = lib.h2hip_fp_cmp_layout(C.cast(C.pointer(params), _vp), op, C.byref(cells), C.byref(own), C.byref(lookups), C.byref(nres), C.cast(ranges, _vp), outs)
-    _raise_on(code, lib)
-    ngaps = params.num_limbs * (bool(op & FP_CMP_REDUCE_A) + bool(op & FP_CMP_REDUCE_B))
-    return FpCmpLayout(cells.value, own.value, lookups.value, nres.value,
-                       [(r.cell_offset, r.num_cells, r.range_bits, r.result_index) for r in ranges[:ngaps]], list(outs))
+    return FpCmpLayout(*_fused_layout(_FP_CMP, params, op, lib))
 
 
 def fp_cmp_fill(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], params: FpParamsStruct, op: int, values_dev,
@@ -1069,39 +1084,22 @@ def fp_cmp_fill(ctx: Context, columns: Sequence[int], usable_rows: int, break_po
     unit's (column, row) across the break points; the cells of the k range checks per enforced operand are left as gaps.  units: (column, row,
     a_offset, b_offset) tuples or a table from fp_mul_table().  results_dev (or None): per unit, for each enforced operand s_0 .. s_{k-1} and
     the final borrow, then for EQUAL the equality cell's value.  Stream-ordered on the context's stream."""
-    arr = _as_table(units, fp_mul_table)
-    ctx._chk(ctx.lib.h2hip_fp_cmp_fill_dev(ctx.handle, _col_array(columns), len(columns), usable_rows, _bp_array(break_points, len(columns)),
-                                           C.cast(C.pointer(params), _vp), op, _dev_ptr(values_dev), values_len, _dev_ptr(results_dev), results_len,
-                                           C.cast(arr, _vp), len(units) if count is None else count))
+    _fused_fill(_FP_CMP, ctx, columns, usable_rows, break_points, params, op, values_dev, values_len, results_dev, results_len, units, count)
 
 
 def fp_cmp_range_tables(break_points: Optional[Sequence[int]], num_columns: int, params: FpParamsStruct, op: int, units, lookup_slots: Sequence[int],
                         lib=None) -> list:
     """h2hip_fp_cmp_range_checks: [(width, range_check_table)] of the range checks of `units`: one table (they share the width pad + lb), unit
     by unit (rows and lookup slots ascend); none for a mask that enforces no operand.  Build it once for a layout used in every proof."""
-    lib = lib or load_library()
-    lay = fp_cmp_layout(params, op, lib)
-    count, ngaps = len(lookup_slots), len(lay.ranges)
-    if not count or not ngaps:
-        return []
-    arr = _as_table(units, fp_mul_table)
-    checks = (RangeCheckStruct * (ngaps * count))()
-    code = lib.h2hip_fp_cmp_range_checks(_bp_array(break_points, num_columns), num_columns, C.cast(C.pointer(params), _vp), op, C.cast(arr, _vp),
-                                         (C.c_uint64 * count)(*lookup_slots), count, C.cast(checks, _vp))
-    _raise_on(code, lib)
-    return [(lay.ranges[0][2], checks)]
+    return _fused_range_tables(_FP_CMP, break_points, num_columns, params, op, units, lookup_slots, lib)
 
 
 def fp_cmp_fill_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], lookup_columns: Sequence[int],
                             params: FpParamsStruct, op: int, values_dev, values_len: int, results_dev, results_len: int, units,
                             lookup_slots: Sequence[int] = (), range_tables: Optional[list] = None) -> None:
     """fp_cmp_fill, then the one range_fill_checks call from results_dev: the whole run of every unit and its lookup cells."""
-    assert results_dev, "the range checks read results_dev"
-    arr = _as_table(units, fp_mul_table)
-    tables = range_tables if range_tables is not None else fp_cmp_range_tables(break_points, len(columns), params, op, arr, lookup_slots, ctx.lib)
-    fp_cmp_fill(ctx, columns, usable_rows, break_points, params, op, values_dev, values_len, results_dev, results_len, arr, len(units))
-    for bits, table in tables:
-        range_fill_checks(ctx, columns, usable_rows, break_points, lookup_columns, results_dev, results_len, bits, params.lookup_bits, table)
+    _fused_fill_with_ranges(_FP_CMP, ctx, columns, usable_rows, break_points, lookup_columns, params, op, values_dev, values_len, results_dev, results_len, units,
+                            lookup_slots, range_tables)
 
 
 def ec_fill_strict_with_ranges(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], lookup_columns: Sequence[int],
