@@ -169,6 +169,27 @@ pub const H2HIP_EC_SUB_UNEQUAL: u32 = 3;
 pub const H2HIP_FP_CMP_REDUCE_A: u32 = 1;
 pub const H2HIP_FP_CMP_REDUCE_B: u32 = 2;
 pub const H2HIP_FP_CMP_EQUAL: u32 = 4;
+/// one unit of h2hip_ec_select_fill_dev: ec_select of the points at values_dev[p_offset ..] and values_dev[q_offset ..] by the cell at sel_offset, or
+/// ec_select_from_bits over the packed table at p_offset by the little-endian bits from sel_offset; its run of cells from (column, row) downwards
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct h2hip_ec_select {
+    pub column: u32,
+    pub row: u32,
+    pub p_offset: u64,
+    pub q_offset: u64,
+    pub sel_offset: u64,
+}
+pub const H2HIP_EC_SELECT: u32 = 0;
+pub const H2HIP_EC_SELECT_FROM_BITS: u32 = 1;
+/// one unit of h2hip_num_to_bits_fill_dev: GateChip::num_to_bits of the value at values_dev[a_offset], its run of cells from (column, row) downwards
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct h2hip_bits_unit {
+    pub column: u32,
+    pub row: u32,
+    pub a_offset: u64,
+}
 pub const H2HIP_POSEIDON_ABSORB_ONLY: u32 = 1;
 pub const H2HIP_POSEIDON_WITH_CONSTS: u32 = 2;
 /// a later phase's witness: `fill(user, phase, challenges, num_challenges, columns_dev, num_columns)` (include/h2hip.h states the contract)
@@ -457,6 +478,14 @@ extern "C" {
                                  results_dev: *mut c_void, results_len: usize, units_host: *const h2hip_fp_mul, count: usize) -> c_int;
     pub fn h2hip_fp_cmp_range_checks(break_points_host: *const u32, num_columns: usize, params: *const h2hip_fp_params, op: u32,
                                      units_host: *const h2hip_fp_mul, lookup_slots_host: *const u64, count: usize, checks_out: *mut h2hip_range_check) -> c_int;
+    pub fn h2hip_ec_select_layout(params: *const h2hip_fp_params, op: u32, window_bits: u32, num_cells: *mut usize, out_cell_offsets: *mut u32) -> c_int;
+    pub fn h2hip_ec_select_fill_dev(ctx: *mut h2hip_ctx, columns_dev: *const *mut c_void, num_columns: usize, usable_rows: usize,
+                                    break_points_host: *const u32, params: *const h2hip_fp_params, op: u32, window_bits: u32, values_dev: *const c_void,
+                                    values_len: usize, results_dev: *mut c_void, results_len: usize, units_host: *const h2hip_ec_select, count: usize) -> c_int;
+    pub fn h2hip_num_to_bits_layout(num_bits: u32, num_cells: *mut usize, sum_cell_offset: *mut u32) -> c_int;
+    pub fn h2hip_num_to_bits_fill_dev(ctx: *mut h2hip_ctx, columns_dev: *const *mut c_void, num_columns: usize, usable_rows: usize,
+                                      break_points_host: *const u32, values_dev: *const c_void, values_len: usize, results_dev: *mut c_void,
+                                      results_len: usize, num_bits: u32, units_host: *const h2hip_bits_unit, count: usize) -> c_int;
     pub fn h2hip_quotient_rlc_gate_batch_dev(ctx: *mut h2hip_ctx, acc_dev: *mut c_void, q_dev: *const *const c_void, a_dev: *const *const c_void,
                                              count: usize, ext_k: u32, k: u32, gamma: *const c_void, y: *const c_void) -> c_int;
     pub fn h2hip_plonk_pk_free(ctx: *mut h2hip_ctx, pk: *mut h2hip_plonk_pk);

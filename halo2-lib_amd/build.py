@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libh2hip.so")
-SOURCES = ["capi.hip", "ntt.hip", "msm.hip", "msm_batch.hip", "msm_tables.hip", "fr_ops.hip", "poly_eval.hip", "quotient.hip", "poseidon.hip", "probes.hip", "srs.hip", "lookup.hip", "prover_ops.hip", "plonk.hip", "plonk_prove.hip", "verifier.hip", "verify_batch.hip", "g2.hip", "comm.hip", "rng.hip", "witness_check.hip", "rlc.hip", "gate_chains.hip", "poseidon_trace.hip", "range_fill.hip", "fp_mul.hip", "ec_fill.hip", "fp_cmp.hip", "trace_place.hip"]
+SOURCES = ["capi.hip", "ntt.hip", "msm.hip", "msm_batch.hip", "msm_tables.hip", "fr_ops.hip", "poly_eval.hip", "quotient.hip", "poseidon.hip", "probes.hip", "srs.hip", "lookup.hip", "prover_ops.hip", "plonk.hip", "plonk_prove.hip", "verifier.hip", "verify_batch.hip", "g2.hip", "comm.hip", "rng.hip", "witness_check.hip", "rlc.hip", "gate_chains.hip", "poseidon_trace.hip", "range_fill.hip", "fp_mul.hip", "ec_fill.hip", "fp_cmp.hip", "ec_select.hip", "trace_place.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".cuh", ".h", ".inc"))) + [os.path.join("..", "..", "include", "h2hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 

@@ -2,7 +2,7 @@
 // table packer alone): the checks of the column arguments, the address intervals a unit's run and its operands cover, the sweep that finds two
 // of them at one address, and the upload of a call's small tables.  Host only.  An entry point reads: its parameters, a loop over the units
 // (TraceRuns::run, operand_range), the clash checks, then pack_tables and the launches.  The fused fills (fp_mul.hip, ec_fill.hip,
-// fp_cmp.hip) have all of that in one place, fused_fill at the end of this file.
+// fp_cmp.hip, ec_select.hip) have all of that in one place, fused_fill at the end of this file.
 #pragma once
 #include "internal.h"
 #include "trace_place.cuh"
@@ -124,7 +124,7 @@ inline HostTable breaks_table(const TraceRuns &r) {
     return HostTable{r.break_points, r.break_points ? sizeof(uint32_t) * (r.num_columns - 1) : 0, HostTable::BREAKS};
 }
 
-// ---- the fused fills (fp_mul.hip, ec_fill.hip, fp_cmp.hip): a solve kernel, one lane per unit, leaves a record per unit; a place kernel, one
+// ---- the fused fills (fp_mul.hip, ec_fill.hip, fp_cmp.hip, ec_select.hip): a solve kernel, one lane per unit, leaves a record per unit; a place kernel, one
 // lane per (unit, slot), writes the cells.  What a kind states of itself; fused_fill is everything between its *_prepare and its kernels.
 struct FusedKind {
     const char *func;                            // the entry point, for the messages
@@ -132,13 +132,14 @@ struct FusedKind {
     struct {
         bool read;
         uint32_t span;                           // elements offset .. offset + span of values_dev
-    } operand[2];
+    } operand[3];                                // (a kind of two operands leaves the third unread)
     HostTable consts, segs;                      // segs: of no bytes for a kind without a segment table
     const char *solve_name, *place_name;         // for prof_begin
     uint32_t solve_block, place_block;
 };
-inline uint64_t unit_operand(const h2hip_fp_mul &u, int i) { return i ? u.b_offset : u.a_offset; }
-inline uint64_t unit_operand(const h2hip_ec_op &u, int i) { return i ? u.q_offset : u.p_offset; }
+inline uint64_t unit_operand(const h2hip_fp_mul &u, int i) { return i == 0 ? u.a_offset : i == 1 ? u.b_offset : 0; }
+inline uint64_t unit_operand(const h2hip_ec_op &u, int i) { return i == 0 ? u.p_offset : i == 1 ? u.q_offset : 0; }
+inline uint64_t unit_operand(const h2hip_ec_select &u, int i) { return i == 0 ? u.p_offset : i == 1 ? u.q_offset : u.sel_offset; }
 
 // Every check of the column arguments, the operands and the results, before anything is uploaded or launched; the records in WS_TMP2; the
 // tables [units][column pointers][break points][constants]([segments]) in WS_TMP1; call's five leading members; then solve(grid, units,
@@ -157,12 +158,12 @@ int fused_fill(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, siz
     H2_REQUIRE_AS(kind.func, !results_dev || results_len / kind.results >= count, "results_len < count * the results of a unit");
     std::vector<ByteRange> reads;
     runs.written.reserve(count + 9);
-    reads.reserve(2 * count);
+    reads.reserve(((size_t)kind.operand[0].read + kind.operand[1].read + kind.operand[2].read) * count);
     for (size_t j = 0; j < count; ++j) {
         const Unit &u = units_host[j];
         bad = runs.run(u.column, u.row, kind.cells);   // the unit's whole run, gaps included
         H2_REQUIRE_AS(kind.func, !bad, bad);
-        for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 3; ++i)
             H2_REQUIRE_AS(kind.func, !kind.operand[i].read || operand_range(values_dev, values_len, unit_operand(u, i), kind.operand[i].span, reads),
                           "a unit's operand lies outside values_len");
     }

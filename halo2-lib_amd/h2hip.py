@@ -133,6 +133,10 @@ _PROTOS = {
     "h2hip_fp_cmp_layout": (_int, [_vp, _u32, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), _vp, C.POINTER(_u32)]),
     "h2hip_fp_cmp_fill_dev": (_int, [_vp, C.POINTER(_vp), _sz, _sz, C.POINTER(_u32), _vp, _u32, _vp, _sz, _vp, _sz, _vp, _sz]),
     "h2hip_fp_cmp_range_checks": (_int, [C.POINTER(_u32), _sz, _vp, _u32, _vp, C.POINTER(C.c_uint64), _sz, _vp]),
+    "h2hip_ec_select_layout": (_int, [_vp, _u32, _u32, C.POINTER(_sz), C.POINTER(_u32)]),
+    "h2hip_ec_select_fill_dev": (_int, [_vp, C.POINTER(_vp), _sz, _sz, C.POINTER(_u32), _vp, _u32, _u32, _vp, _sz, _vp, _sz, _vp, _sz]),
+    "h2hip_num_to_bits_layout": (_int, [_u32, C.POINTER(_sz), C.POINTER(_u32)]),
+    "h2hip_num_to_bits_fill_dev": (_int, [_vp, C.POINTER(_vp), _sz, _sz, C.POINTER(_u32), _vp, _sz, _vp, _sz, _u32, _vp, _sz]),
     "h2hip_quotient_rlc_gate_batch_dev": (_int, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _sz, _u32, _u32, _vp, _vp]),
     "h2hip_plonk_pk_free": (None, [_vp, _vp]),
     "h2hip_plonk_pk_commitments": (_int, [_vp, _vp, _vp]),

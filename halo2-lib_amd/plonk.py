@@ -1131,3 +1131,81 @@ def ec_fill_strict_with_ranges(ctx: Context, columns: Sequence[int], usable_rows
     ec_fill_with_ranges(ctx, columns, usable_rows, break_points, lookup_columns, params, op, values_dev, values_len, results_dev, results_len, ec_table,
                         range_tables=ec_ranges)
     return eq_cells, ec_cells, tables
+
+
+class EcSelectStruct(C.Structure):   # h2hip_ec_select
+    _fields_ = [("column", C.c_uint32), ("row", C.c_uint32), ("p_offset", C.c_uint64), ("q_offset", C.c_uint64), ("sel_offset", C.c_uint64)]
+
+
+class BitsUnitStruct(C.Structure):   # h2hip_bits_unit
+    _fields_ = [("column", C.c_uint32), ("row", C.c_uint32), ("a_offset", C.c_uint64)]
+
+
+EC_SELECT, EC_SELECT_FROM_BITS = 0, 1
+
+
+def ec_select_table(units: Sequence) -> C.Array:
+    """a ctypes table of h2hip_ec_select from (column, row, p_offset, q_offset, sel_offset) tuples: build it once for a layout used in every proof"""
+    return _struct_table(EcSelectStruct, units)
+
+
+def bits_unit_table(units: Sequence) -> C.Array:
+    """a ctypes table of h2hip_bits_unit from (column, row, a_offset) tuples"""
+    return _struct_table(BitsUnitStruct, units)
+
+
+# no gaps, no range checks: of the record, the table builder, the two library functions and the out_cell_offsets buffer are read
+_EC_SELECT = _FusedKind(ec_select_table, "h2hip_ec_select_layout", "h2hip_ec_select_fill_dev", "", True, 0, 10, lambda k, _op: (0, 2 * (k + 1)), False,
+                        lambda _k, _ranges: [])
+
+
+class EcSelectLayout(NamedTuple):
+    """h2hip_ec_select_layout: the cells of one selection unit and the offsets of the cells of the selected point (x's k limb cells and native
+    cell, then y's)"""
+    num_cells: int
+    out_cell_offsets: list
+
+
+def ec_select_layout(params: FpParamsStruct, op: int, window_bits: int = 0, lib=None) -> EcSelectLayout:
+    lib = lib or load_library()
+    kind = _EC_SELECT
+    cells, outs = C.c_size_t(0), (C.c_uint32 * kind.max_outs)()
+    code = getattr(lib, kind.layout)(C.cast(C.pointer(params), _vp), op, window_bits, C.byref(cells), outs)
+    _raise_on(code, lib)
+    return EcSelectLayout(cells.value, list(outs[:kind.valid(params.num_limbs, op)[1]]))
+
+
+def ec_select_fill(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], params: FpParamsStruct, op: int,
+                   window_bits: int, values_dev, values_len: int, results_dev, results_len: int, units, count: Optional[int] = None) -> None:
+    """h2hip_ec_select_fill_dev: every cell of ec_select (op = EC_SELECT, window_bits = 0: sel ? P : Q, one GateChip::select per limb and
+    native cell of x and y) or of ec_select_from_bits (EC_SELECT_FROM_BITS: bits_to_indicator over the window_bits little-endian bits from
+    sel_offset, then select_by_indicator::crt over the 2^window_bits points packed from p_offset) for every unit, written down the device
+    columns from each unit's (column, row) across the break points.  units: (column, row, p_offset, q_offset, sel_offset) tuples or a table
+    from ec_select_table(); a point is the 2 (k + 1) Fr of values_dev from its offset.  results_dev (or None): 2 (k + 1) Fr per unit, the
+    selected point as the operand ec_fill, fp_cmp_fill or a later selection reads.  Stream-ordered on the context's stream."""
+    kind = _EC_SELECT
+    arr = _as_table(units, kind.table)
+    ctx._chk(getattr(ctx.lib, kind.fill)(ctx.handle, _col_array(columns), len(columns), usable_rows, _bp_array(break_points, len(columns)),
+                                         C.cast(C.pointer(params), _vp), op, window_bits, _dev_ptr(values_dev), values_len, _dev_ptr(results_dev), results_len,
+                                         C.cast(arr, _vp), len(units) if count is None else count))
+
+
+def num_to_bits_layout(num_bits: int, lib=None):
+    """h2hip_num_to_bits_layout -> (cells of one unit, the offset of the recomposed sum's cell); bit 0 sits at offset 0, bit i at 1 + 3 (i - 1)"""
+    lib = lib or load_library()
+    cells, at = C.c_size_t(0), C.c_uint32(0)
+    code = lib.h2hip_num_to_bits_layout(num_bits, C.byref(cells), C.byref(at))
+    _raise_on(code, lib)
+    return cells.value, at.value
+
+
+def num_to_bits_fill(ctx: Context, columns: Sequence[int], usable_rows: int, break_points: Optional[Sequence[int]], values_dev, values_len: int,
+                     results_dev, results_len: int, num_bits: int, units, count: Optional[int] = None) -> None:
+    """h2hip_num_to_bits_fill_dev: every cell of GateChip::num_to_bits at `num_bits` for every unit, written down the device columns from each
+    unit's (column, row) across the break points.  units: (column, row, a_offset) tuples or a table from bits_unit_table(); the value is
+    values_dev[a_offset].  results_dev (or None): num_bits Fr per unit, the bits little-endian (consecutive units leave one bit string, which
+    ec_select_fill reads).  Stream-ordered on the context's stream."""
+    arr = _as_table(units, bits_unit_table)
+    ctx._chk(ctx.lib.h2hip_num_to_bits_fill_dev(ctx.handle, _col_array(columns), len(columns), usable_rows, _bp_array(break_points, len(columns)),
+                                                _dev_ptr(values_dev), values_len, _dev_ptr(results_dev), results_len, num_bits, C.cast(arr, _vp),
+                                                len(units) if count is None else count))

@@ -466,8 +466,77 @@ class GateChip:
         ctx.assign_region(cells, [3 * i for i in range(len(a))])
         return ctx.last()
 
+    @staticmethod
+    def select(ctx: Context, a, b, sel) -> AssignedValue:
+        """sel ? a : b as | a - b | 1 | b | a | b | sel | a - b | out | with gates on cells 0 and 4, cell 0 constrained equal to cell 6 and cell 2
+        to cell 4 (flex_gate/mod.rs:1144-1170): out = (a - b) sel + b -> the last cell"""
+        a, b, sel = _q(a), _q(b), _q(sel)
+        diff = (a.value - b.value) % R_MOD
+        row_offset = len(ctx.advice)
+        ctx.assign_region([Witness(diff), Constant(1), b, a, b, sel, Witness(diff), Witness((diff * sel.value + b.value) % R_MOD)], [0, 4])
+        ctx.constrain_equal(ctx.get(row_offset), ctx.get(row_offset + 6))
+        ctx.constrain_equal(ctx.get(row_offset + 2), ctx.get(row_offset + 4))
+        return ctx.last()
 
-FR_CAPACITY = 253                                                         # F::CAPACITY of bn256's Fr: 2^253 < r
+    @staticmethod
+    def assert_bit(ctx: Context, x: AssignedValue):
+        """| 0 | x | x | x | (flex_gate/mod.rs:303-305)"""
+        ctx.assign_region([Constant(0), Existing(x), Existing(x), Existing(x)], [0])
+
+    @staticmethod
+    def bits_to_indicator(ctx: Context, bits: Sequence[AssignedValue]) -> List[AssignedValue]:
+        """the indicator of the number the little-endian `bits` spell (flex_gate/mod.rs:609-656): | 1 - b | b | 1 | 1 | for the last bit, then
+        bit by bit downwards, per entry ind of the level before, | (1 - bit) ind | ind | bit | ind | and mul(ind, bit) -> the 2^len(bits)
+        entries of the last level.  The products are defined for bits that are none."""
+        k = len(bits)
+        assert k > 0, "bits_to_indicator: bits must be non-empty"
+        ctx.assign_region([Witness((1 - bits[k - 1].value) % R_MOD), Existing(bits[k - 1]), Constant(1), Constant(1)], [0])
+        indicator = [ctx.get(-4), ctx.get(-3)]
+        offset = 0
+        for idx in range(1, k):
+            bit = bits[k - 1 - idx]
+            for old_idx in range(1 << idx):
+                ind = indicator[offset + old_idx]
+                ctx.assign_region([Witness((1 - bit.value) * ind.value % R_MOD), Existing(ind), Existing(bit), Existing(ind)], [0])
+                indicator.append(ctx.get(-4))
+                indicator.append(GateChip.mul(ctx, Existing(ind), Existing(bit)))
+            offset += 1 << idx
+        return indicator[(1 << k) - 2:]
+
+    @staticmethod
+    def select_by_indicator(ctx: Context, a: Sequence, indicator: Sequence[AssignedValue]) -> AssignedValue:
+        """| 0 | a_0 | ind_0 | s_0 | a_1 | ind_1 | s_1 | ... with a gate every three rows (flex_gate/mod.rs:709-730), the sums in the arithmetic
+        form s_i = s_{i-1} + a_i ind_i: the reference's "a where ind != 0" for a one-hot indicator, and a satisfied gate for any other"""
+        a = [_q(v) for v in a]
+        assert len(a) == len(indicator) and a
+        cells, s = [Constant(0)], 0
+        for x, ind in zip(a, indicator):
+            s = (s + x.value * ind.value) % R_MOD
+            cells += [x, Existing(ind), Witness(s)]
+        ctx.assign_region(cells, [3 * i for i in range(len(a))])
+        return ctx.last()
+
+    @staticmethod
+    def num_to_bits(ctx: Context, a: AssignedValue, range_bits: int) -> List[AssignedValue]:
+        """the little-endian bits of a (flex_gate/mod.rs:1215-1241): the inner product of the bits against the powers of two in the "b starts
+        with Constant(1)" form, constrained equal to a, then assert_bit per bit.  to_u64_limbs truncates: a value that does not fit gets the
+        bits of its low range_bits bits, and the copy constraint between a and the sum then fails."""
+        assert range_bits > 0
+        bits = [Witness((a.value >> i) & 1) for i in range(range_bits)]
+        row_offset = len(ctx.advice)
+        if range_bits == 1:
+            ctx.assign_region(bits)
+            acc = ctx.last()
+        else:
+            acc = RangeChip._inner_product_from_one(ctx, bits, [Constant(1 << i) for i in range(range_bits)])
+        ctx.constrain_equal(a, acc)
+        bit_cells = [ctx.get(row_offset)] + [ctx.get(row_offset + 1 + 3 * (i - 1)) for i in range(1, range_bits)]
+        for cell in bit_cells:
+            GateChip.assert_bit(ctx, cell)
+        return bit_cells
+
+
+FR_CAPACITY = 253                                                        # F::CAPACITY of bn256's Fr: 2^253 < r
 
 
 class RangeChip:

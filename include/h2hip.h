@@ -866,6 +866,70 @@ int h2hip_fp_cmp_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_c
                           const h2hip_fp_mul *units_host, size_t count);
 int h2hip_fp_cmp_range_checks(const uint32_t *break_points_host, size_t num_columns, const h2hip_fp_params *params, uint32_t op,
                               const h2hip_fp_mul *units_host, const uint64_t *lookup_slots_host, size_t count, h2hip_range_check *checks_out);
+/* EccChip's point selections written on the device for `count` units over the limb layout of h2hip_fp_params, k = 3 or 4 (only n, k and the
+ * parameter checks of h2hip_fp_mul_fill_dev matter: no big integer is computed).  Points are in the operand form of h2hip_ec_fill_dev: 2 (k + 1)
+ * consecutive Fr of values_dev, x's k limbs and native residue, then y's.  One unit's run is the reference's, cell for cell, every cell a
+ * canonical Montgomery Fr (a Constant(c) cell holds c, a copy of an earlier cell its value); all products and sums are Fr arithmetic over the
+ * cell values themselves and are defined for every input (nothing is asserted):
+ *   H2HIP_EC_SELECT (0), window_bits = 0: ec_select(P, Q, sel) = sel ? P : Q [halo2-ecc/src/ecc/mod.rs:402-415, bigint/select.rs:26-50].  P lies
+ *     at p_offset, Q at q_offset, sel is the one Fr at sel_offset.  For x, then y, per limb j < k, then the native cell, one GateChip::select
+ *     [halo2-base/src/gates/flex_gate/mod.rs:1144-1170]:  a - b, 1, b, a, b, sel, a - b, out  with out = (a - b) sel + b.  16 (k + 1) cells.
+ *   H2HIP_EC_SELECT_FROM_BITS (1), window_bits = w in 1 .. 8, m = 2^w: ec_select_from_bits [ecc/mod.rs:442-456]; strict_ec_select_from_bits
+ *     and ec_select_by_indicator behind bits_to_indicator write the same cells.  The m table points lie packed at p_offset + j 2 (k + 1), the w
+ *     bits little-endian at sel_offset .. sel_offset + w; q_offset is not read.
+ *       bits_to_indicator [flex_gate/mod.rs:609-656], 2^(w+3) - 12 cells:  1 - b_{w-1}, b_{w-1}, 1, 1;  then for idx = 1 .. w - 1 with bit =
+ *         b_{w-1-idx}, for each of the 2^idx entries ind of the level before, in order:  (1 - bit) ind, ind, bit, ind;  0, ind, bit, ind bit.
+ *         Entry v of the last level is the indicator of v = sum b_i 2^i.
+ *       for x, then y [bigint/select_by_indicator.rs:29-69]: per limb j < k a chain  0, a_0, ind_0, s_0, ..., a_{m-1}, ind_{m-1}, s_{m-1}
+ *         (3 m + 1 cells) with s_i = s_{i-1} + a_i ind_i, the arithmetic form of h2hip_gate_fill_chains_dev (the reference's "sum = a where
+ *         ind != 0" equals it for the one-hot indicator boolean bits give; this form satisfies the gate for any input); then the native
+ *         cell: for m > k evaluate_native over the k output limbs, o_0, o_1, 2^n, s_1, ... (3 k - 2 cells), else one more chain over the
+ *         table's native cells.
+ *     2^(w+3) - 12 + 2 (k (3 m + 1) + (m > k ? 3 k - 2 : 3 m + 1)) cells: 424 at k = 3, w = 4.
+ * There are no gaps and no lookup cells.  results_dev (may be NULL): unit u gets 2 (k + 1) Fr at index u 2 (k + 1), the selected point in
+ * operand form (the out cells, or the chains' last sums and the native): consecutive units leave a packed table that h2hip_ec_fill_dev,
+ * h2hip_fp_cmp_fill_dev and a later select read directly.
+ * h2hip_ec_select_layout (host only, pure): the run's length and out_cell_offsets[2 (k + 1)], the offsets of the result cells.
+ * H2HIP_ERR_INVALID with a message, before anything is launched or uploaded (all columns and results_dev are then untouched): the refusals of
+ * h2hip_fp_mul_fill_dev applied to this unit (its parameters, its run, results_len < count 2 (k + 1), count times the unit's segments > 2^32),
+ * and: an unknown op; window_bits outside 1 .. 8 for op 1 or non-zero for op 0; k < 3; a point, a table, sel or the bits outside values_len.
+ * count == 0 is H2HIP_OK without device work.  Stream-ordered on the context's stream: two kernels (one lane per unit; one lane per (unit,
+ * segment): an 8-cell select, an indicator node, two entries of a chain, or evaluate_native); the unit table, the column pointers, the break
+ * points and the constants are the only uploads. */
+#define H2HIP_EC_SELECT 0
+#define H2HIP_EC_SELECT_FROM_BITS 1
+typedef struct h2hip_ec_select {
+    uint32_t column, row;                    /* first cell of the unit's run */
+    uint64_t p_offset, q_offset, sel_offset; /* values_dev indices: P or the table; Q (op 0 only); sel or the first bit */
+} h2hip_ec_select;                           /* 32 bytes */
+int h2hip_ec_select_layout(const h2hip_fp_params *params, uint32_t op, uint32_t window_bits, size_t *num_cells, uint32_t *out_cell_offsets);
+int h2hip_ec_select_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const uint32_t *break_points_host,
+                             const h2hip_fp_params *params, uint32_t op, uint32_t window_bits, const void *values_dev, size_t values_len,
+                             void *results_dev, size_t results_len, const h2hip_ec_select *units_host, size_t count);
+/* GateChip::num_to_bits written on the device [flex_gate/mod.rs:1215-1241] for `count` values of one width nb = num_bits, the value of unit u
+ * the Fr at a_offset of values_dev.  One unit's run, 7 nb - 2 cells, every cell a canonical Montgomery Fr:
+ *   l_0, l_1, 2, s_1, l_2, 4, s_2, ..., s_{nb-1}   the inner product against the powers of two in inner_product_simple's "b starts with
+ *                                                   Constant(1)" form, 3 nb - 2 cells (one cell for nb = 1)
+ *   0, l_i, l_i, l_i for i < nb                     assert_bit per bit, in order [flex_gate/mod.rs:303-305]
+ * l_i is bit i of the canonical integer of the value, s_i its low i + 1 bits.  A value that does not fit gets the bits of its low nb bits (as
+ * to_u64_limbs truncates) and s_{nb-1} differs from it: no refusal, the copy between the value and the sum is keygen's and the witness
+ * check reports it.  results_dev (may be NULL): unit u gets nb Fr at index u nb, the bits little-endian, so scalar chunks in consecutive
+ * units leave the consecutive bit string H2HIP_EC_SELECT_FROM_BITS reads.
+ * h2hip_num_to_bits_layout (host only, pure): the run's length and the offset of s_{nb-1} (of l_0 for nb = 1); bit 0 sits at offset 0, bit i at
+ * 1 + 3 (i - 1).
+ * H2HIP_ERR_INVALID with a message, before anything is launched or uploaded: a NULL mandatory argument; num_bits outside 1 .. 254; count
+ * num_bits > 2^32; and what h2hip_range_fill_checks_dev refuses of gate cells, operands and results (a column index >= num_columns or a NULL
+ * column; a run that leaves the usable rows or the last column; a break point >= usable_rows; a_offset >= values_len; results_len < count
+ * num_bits; two units' cells overlapping; a value or the results overlapping anything the call writes).  count == 0 is H2HIP_OK without
+ * device work.  Stream-ordered on the context's stream: one kernel, one lane per (unit, bit). */
+typedef struct h2hip_bits_unit {
+    uint32_t column, row; /* first cell of the unit's run */
+    uint64_t a_offset;    /* values_dev index of the value */
+} h2hip_bits_unit;        /* 16 bytes */
+int h2hip_num_to_bits_layout(uint32_t num_bits, size_t *num_cells, uint32_t *sum_cell_offset);
+int h2hip_num_to_bits_fill_dev(h2hip_ctx *ctx, void *const *columns_dev, size_t num_columns, size_t usable_rows, const uint32_t *break_points_host,
+                               const void *values_dev, size_t values_len, void *results_dev, size_t results_len, uint32_t num_bits,
+                               const h2hip_bits_unit *units_host, size_t count);
 /* The RLC gates' terms of the quotient numerator on the extended domain, folded in order for j < count:
  *      acc[i] = acc[i]*y + q_j[i]*(a_j[i]*gamma + a_j[i+s] - a_j[i+2s]),  s = 2^(ext_k-k), indices mod 2^ext_k.
  * q_dev / a_dev: HOST arrays of device pointers; 64 columns per launch. */
