@@ -14,31 +14,21 @@ so one thread holds the full run and the lookup queue.
   D  every reachable refusal; E  the structs in the header, the Rust sys crate and ctypes;
   F  a BaseConfig proof of R = P + Q, D = 2 R, S = D + P whose trace three fill calls write.
 """
-import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 
-import halo2_lib_amd as H
 from halo2_lib_amd import plonk as PL
 from halo2_lib_amd import virtual_region as VR
-from oracle import plonk as P
 from tests import fp_mul_checks as F
-from tests.dyn_lookup_util import rng_budget, srs, vk_from_gpu
-from tests.fp_mul_checks import BN254_Q, MODULI, SECP_N, SECP_P, Spec, _signed, _tdiv
-from tests.poseidon_trace_checks import _compare, _ints, place
-from tests.range_fill_checks import lookup_positions
-from tests.rlc_checks import SENTINEL
-from tests.util import PreDrawnRng, R, fr
+from tests import fused_fill_harness as FH
+from tests.fp_mul_checks import BN254_Q, MODULI, SECP_N, SECP_P, Spec
+from tests.fused_fill_harness import SENTINEL, EcOp, compare, lookup_positions, own_mask, place, signed, tdiv
+from tests.util import R, fr
 
-_vp = C.c_void_p
-ERR_INVALID = -1
 ADD, DOUBLE = PL.EC_ADD_UNEQUAL, PL.EC_DOUBLE
 OPS = {"add_unequal": ADD, "double": DOUBLE}
 SOLVE_BLOCK, PLACE_BLOCK = 64, 256   # ec_fill.hip: lanes per workgroup of the per-unit and of the per-(unit, segment) kernel
-ROOT = F.ROOT
 PARAMS = [(88, 3, 8), (88, 3, 18), (90, 3, 15), (64, 4, 8)]   # (limb_bits, num_limbs, lookup_bits)
 CURVES = {"secp256k1_p": (SECP_P, 7, (0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798,
                                        0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8)),
@@ -150,7 +140,7 @@ def _carry_to_zero(u, ctx, chip, sp, check_assigned, mlb, res):
     rb = (mlb - n + 1 + lb) // lb * lb - 1
     carries, previous = [], None
     for cell in check_assigned:
-        carries.append(_tdiv(_signed(cell.value) + (carries[-1] if carries else 0), 1 << n))
+        carries.append(tdiv(signed(cell.value) + (carries[-1] if carries else 0), 1 << n))
     for i, (cell, carry) in enumerate(zip(check_assigned, carries)):
         ctx.assign_region([VR.Existing(cell), VR.Witness(-carry % R), VR.Constant(sp.limb_bases[1]),
                            VR.Existing(previous) if previous is not None else VR.Constant(0)], [0])
@@ -265,13 +255,10 @@ def ec_op(ctx, chip, sp, op, pt, qt=None):
     return u
 
 
-_thread, _operand, own_mask = F._thread, F._operand, F.own_mask
-
-
 def unit_def(sp, op, p_vals, q_vals=None):
     """one unit on a thread of its own -> (the Unit, its cells, the lookup values in queue order, the thread)"""
-    ctx, chip, _ = _thread(sp.lb)
-    u = ec_op(ctx, chip, sp, op, _operand(p_vals, 0), _operand(q_vals, 1) if op == ADD else None)
+    ctx, chip, _ = FH.thread(sp.lb)
+    u = ec_op(ctx, chip, sp, op, FH.operand(p_vals, 0), FH.operand(q_vals, 1) if op == ADD else None)
     return u, list(ctx.advice), [c.value for c in chip.lookup_manager.cells_to_lookup.get(ctx.tag(), [])], ctx
 
 
@@ -342,10 +329,10 @@ def check_definition():
         sp = Spec(n, k, lb, SECP_N)
         for a_vals, b_vals in F.operand_pairs(sp, 7)[:12]:
             want = F.unit_def(sp, a_vals, b_vals)
-            ctx, chip, _ = _thread(lb)
+            ctx, chip, _ = FH.thread(lb)
             u = Unit()
             u.start, u.gaps, u.results, u.quots, u.rb, u.out_offsets = 0, [], [None] * (3 * k + 1), [], [], []
-            a, b = operand(sp, _operand(a_vals, 0)), operand(sp, _operand(b_vals, 1))
+            a, b = operand(sp, FH.operand(a_vals, 0)), operand(sp, FH.operand(b_vals, 1))
             carry_mod(ctx, chip, sp, mul_no_carry(ctx, sp, a, b), u, 0, k + 1)
             assert list(ctx.advice) == want[1] and [c.value for c in chip.lookup_manager.cells_to_lookup[ctx.tag()]] == want[2], (n, k, lb)
             assert u.gaps == want[0].gaps and u.results == want[0].results
@@ -364,7 +351,7 @@ def check_three_carry_widths(ctx):
     assert unit_def(sp, DOUBLE, point(sp, *m[0]))[0].rb == [140, 93, 140]
     pool = operand_pool(sp, "secp256k1_p")
     for op in (ADD, DOUBLE):
-        check_fill(ctx, n, k, lb, "secp256k1_p", op, 5, pool=pool[:10])
+        check_op_fill(ctx, n, k, lb, "secp256k1_p", op, 5, pool=pool[:10])
 
 
 def check_pool_signs():
@@ -403,12 +390,12 @@ def check_layout_and_ranges():
                 assert len(width_groups(u.gaps)) <= 7
     sp = Spec(88, 3, 8, SECP_P)
     for op in (ADD, DOUBLE):
-        thread, chip, _ = _thread(sp.lb)
+        thread, chip, _ = FH.thread(sp.lb)
         bps, ncols, units, slots_, defs = [700, 650], 3, [], [], []
         pos = (0, 5)
         thread.advice += [0] * 5
         for j in range(4):
-            u = ec_op(thread, chip, sp, op, _operand(point(sp, 3 + j, 5), 2 * j), _operand(point(sp, 9, 11 + j), 2 * j + 1))
+            u = ec_op(thread, chip, sp, op, FH.operand(point(sp, 3 + j, 5), 2 * j), FH.operand(point(sp, 9, 11 + j), 2 * j + 1))
             units.append(pos + (0, 0))
             slots_.append(u.queue + 3)
             defs.append(u)
@@ -429,64 +416,10 @@ def check_layout_and_ranges():
             assert all(a[3] < b[3] and (a[0], a[1]) < (b[0], b[1]) for a, b in zip(got, got[1:])), "slots and rows ascend inside a width"
 
 
-def check_fill(ctx, n, k, lb, modulus, op, count, nl=1, pool=None):
-    """`count` units per call over three gate columns (no breaks), until every operand pair was a unit; each call once bare (own cells equal
-    the definition's, the gaps and every other cell keep the sentinel, results_dev equals the named cells) and once through
-    ec_fill_with_ranges over nl lookup columns (the whole run and the lookup columns equal the definition's, the queue starting at a position
-    that is no multiple of nl)"""
+def check_op_fill(ctx, n, k, lb, modulus, op, count, nl=1, pool=None):
+    """the harness's check_fill over the operand pool: the bare call and ec_fill_with_ranges over nl lookup columns"""
     sp = Spec(n, k, lb, MODULI[modulus])
-    pool = operand_pool(sp, modulus) if pool is None else pool
-    lay = PL.ec_layout(sp.params(), op, ctx.lib)
-    vals = [v for a, b in pool for v in a + b]
-    nres, pt = 9 * k + 3, 2 * (k + 1)
-    done = 0
-    while done < len(pool):
-        units, defs, slots_, rows, slot = [], [], [], [1, 3, 0], nl + 1 if nl > 1 else 1
-        for j in range(count):
-            at = (done + j) % len(pool)
-            u, cells, lookups, _ = unit_def(sp, op, *pool[at])
-            assert len(cells) == lay.num_cells
-            col = j % 3
-            units.append((col, rows[col], 2 * pt * at, 2 * pt * at + pt))
-            defs.append((u, cells, lookups))
-            slots_.append(slot)
-            rows[col] += len(cells) + (j % 2)
-            slot += len(lookups) + (j % 2)
-        done += count
-        rows_n = max(max(rows), -(-slot // nl)) + 9
-        where = lookup_positions(slot, nl)
-        d_vals = ctx.to_device(fr(vals))
-        try:
-            for with_ranges in (False, True):
-                want = [np.tile(SENTINEL, (rows_n, 1)) for _ in range(3)]
-                want_lk = [np.tile(SENTINEL, (rows_n, 1)) for _ in range(nl)]
-                want_res = np.tile(SENTINEL, (count * nres + 2, 1))
-                d_cols = [ctx.to_device(c) for c in want]
-                d_lk = [ctx.to_device(c) for c in want_lk]
-                d_res = ctx.to_device(want_res)
-                for j, ((col, row, _a, _b), (u, cells, lookups), s) in enumerate(zip(units, defs, slots_)):
-                    keep = np.ones(len(cells), dtype=bool) if with_ranges else own_mask(u)
-                    want[col][row:row + len(cells)][keep] = fr(cells)[keep]
-                    want_res[j * nres:(j + 1) * nres] = fr(u.results)
-                    if with_ranges:
-                        for i, v in enumerate(fr(lookups)):
-                            c, r = where[s + i]
-                            want_lk[c][r] = v
-                try:
-                    if with_ranges:
-                        PL.ec_fill_with_ranges(ctx, d_cols, rows_n - 2, None, d_lk, sp.params(), op, d_vals, len(vals), d_res, count * nres, units, slots_)
-                    else:
-                        PL.ec_fill(ctx, d_cols, rows_n - 2, None, sp.params(), op, d_vals, len(vals), d_res, count * nres, units)
-                    ctx.sync()
-                    what = "(n, k, lb) = (%d, %d, %d), %s, op = %d, count = %d, nl = %d, ranges = %s" % (n, k, lb, modulus, op, count, nl, with_ranges)
-                    _compare(ctx, d_cols, want, what + " (gate columns)")
-                    _compare(ctx, d_lk, want_lk, what + " (lookup columns)")
-                    _compare(ctx, [d_res], [want_res], what + " (results)")
-                finally:
-                    for ptr in d_cols + d_lk + [d_res]:
-                        ctx.free(ptr)
-        finally:
-            ctx.free(d_vals)
+    FH.check_fill(ctx, EcOp(sp, op), operand_pool(sp, modulus) if pool is None else pool, count, nl)
 
 
 # ------------------------------------------------------------------------------------------------ B: chaining
@@ -540,7 +473,7 @@ def check_chained(ctx, n, k, lb, count=3):
                 if which:
                     for i, v in enumerate(fr(lookups)):
                         want_lk[where[slots_[which - 1][j] + i][1]] = v
-        _compare(ctx, d_cols + [d_lk] + d_res, want + [want_lk] + want_res, "chained calls, (n, k, lb) = (%d, %d, %d)" % (n, k, lb))
+        compare(ctx, d_cols + [d_lk] + d_res, want + [want_lk] + want_res, "chained calls, (n, k, lb) = (%d, %d, %d)" % (n, k, lb))
     finally:
         for ptr in d_cols + [d_lk, d_vals] + d_res:
             ctx.free(ptr)
@@ -564,57 +497,16 @@ def _break_cells(sp):
 BREAK_CASES = ["a_subtraction", "load_witness_cells", "zero_check_overlapped_gate", "a_gap", "out_native", "unit_last"]
 
 
-def check_breaks(ctx, case, ncols, op=ADD):
-    """one thread (plain cells, then (88, 3, 8) units back to back, each reading witnesses of its own) laid into ncols columns by virtual_region.assign_witnesses and by ec_fill_with_ranges from each unit's first cell, from the same break points; the
-    lookup column by LookupAnyManager.assign_raw and by the fill.  Every break falls on the cell the case names."""
+def check_op_breaks(ctx, case, ncols, op=ADD):
+    """the harness's check_breaks over (88, 3, 8) units through ec_fill_with_ranges: the first break inside the third unit, every later one
+    3 units further down the thread, each on the cell the case names"""
     sp = Spec(88, 3, 8, SECP_P)
-    k = sp.k
-    u0, cells0, _, _ = unit_def(sp, op, point(sp, 3, 5), point(sp, 7, 11))
-    cell = _break_cells(sp)[case]
-    ncells = len(cells0)
-    filler = 50                                        # the first break inside the third unit, every later one 3 units further down the thread
-    targets = [(2 + 3 * b, cell) for b in range(ncols - 1)]
-    idx = [filler + unit * ncells + c for unit, c in targets]
-    bps = [idx[0]] + [b - a for a, b in zip(idx, idx[1:])]
-    usable = max(bps) + 100
-    nunits = targets[-1][0] + 2
+    kind = EcOp(sp, op)
+    ncells, filler = kind.layout(ctx.lib).num_cells, 50
+    targets = [(2 + 3 * b, _break_cells(sp)[case]) for b in range(ncols - 1)]
+    usable = max(FH.break_points(filler, ncells, targets)) + 100
     pool = operand_pool(sp, "secp256k1_p", 0xB7)
-    pt, nres = 2 * (k + 1), 9 * k + 3
-    vals = [v for j in range(nunits) for x in pool[(5 * j) % len(pool)] for v in x]
-    thread, chip, _ = _thread()
-    thread.advice += list(range(100, 100 + filler))
-    thread.selector += [False] * filler
-    pos, units, slots_ = place(0, 0, filler, bps, ncols)[1], [], []
-    for j in range(nunits):
-        a_vals, b_vals = pool[(5 * j) % len(pool)]
-        u = ec_op(thread, chip, sp, op, _operand(a_vals, 2 * j), _operand(b_vals, 2 * j + 1))
-        assert u.end - u.start == ncells
-        units.append((pos[0], pos[1], 2 * pt * j, 2 * pt * j + pt))
-        slots_.append(u.queue)
-        pos = place(pos[0], pos[1], ncells, bps, ncols)[1]
-    for (unit, c), b, col in zip(targets, bps, range(ncols)):   # the break cell is the cell the case names
-        cells_at = place(units[unit][0], units[unit][1], ncells, bps, ncols)[0]
-        assert (c, col, b) in cells_at and (c, col + 1, 0) in cells_at, (case, unit, c)
-    region = VR.Region(usable + 9, ncols + 1)
-    VR.assign_witnesses([thread], list(range(ncols)), region, bps)
-    chip.lookup_manager.witness_gen_only = True
-    chip.lookup_manager.assign_raw([ncols], region)
-    want = [np.tile(SENTINEL, (usable + 9, 1)) for _ in range(ncols + 1)]
-    for c in range(ncols + 1):
-        rows = sorted(region.advice[c])
-        want[c][rows] = fr([region.advice[c][r] for r in rows])
-    start = [np.tile(SENTINEL, (usable + 9, 1)) for _ in range(ncols + 1)]
-    start[0][:filler] = want[0][:filler]
-    d_cols = [ctx.to_device(c) for c in start]
-    d_vals = ctx.to_device(fr(vals))
-    d_res = ctx.to_device(np.tile(SENTINEL, (nunits * nres, 1)))
-    try:
-        PL.ec_fill_with_ranges(ctx, d_cols[:ncols], usable, bps, d_cols[ncols:], sp.params(), op, d_vals, len(vals), d_res, nunits * nres, units, slots_)
-        ctx.sync()
-        _compare(ctx, d_cols, want, "breaks (%s, %d columns)" % (case, ncols))
-    finally:
-        for ptr in d_cols + [d_vals, d_res]:
-            ctx.free(ptr)
+    FH.check_breaks(ctx, kind, [pool[(5 * j) % len(pool)] for j in range(targets[-1][0] + 2)], targets, filler, usable, ncols)
 
 
 # ------------------------------------------------------------------------------------------------ D: the refusals
@@ -623,86 +515,28 @@ def check_rejections(ctx):
     count == 0 and a good call from the same context.  Not reachable: a product with ceil(log2 k) + a + b > 252 (n k <= 318 and k >= 3 give
     n <= 106, and the largest product, DOUBLE's 3 x * x, has 2 + (n + 2) + n <= 216 bits) and a width whose limbs take more than 253 bits."""
     sp = Spec(88, 3, 8, SECP_P)
-    k, nres, pt = sp.k, 30, 8
-    lay = PL.ec_layout(sp.params(), ADD, ctx.lib)
+    nres, pt = 30, 8
+    kind = EcOp(sp, ADD)
+    lay = kind.layout(ctx.lib)
     ncells = lay.num_cells
-    n_rows, usable = 2 * ncells + 60, 2 * ncells + 50
     m = multiples("secp256k1_p", 4)
     vals = [v for a in m for v in point(sp, *a)]
-    nv = len(vals)
-    sent, sent_res = np.tile(SENTINEL, (n_rows, 1)), np.tile(SENTINEL, (4 * nres, 1))
-    d_cols = [ctx.to_device(sent) for _ in range(3)]
-    d_vals = ctx.to_device(fr(vals))
-    d_res = ctx.to_device(sent_res)
-    good = sp.params()
-    ok = (0, 0, 0, pt)
-    try:
-        def refused(what, reason, call):
-            try:
-                call()
-            except H.H2HipError as e:
-                assert e.code == ERR_INVALID, (what, e.code)
-                msg = ctx.lib.h2hip_last_error().decode()
-                assert reason in msg, (what, msg)
-            else:
-                raise AssertionError("%s was accepted" % what)
-            ctx.sync()
-            for ptr in d_cols:
-                assert np.array_equal(ctx.download(ptr, (n_rows, 4)), sent), "%s: a cell was written" % what
-            assert np.array_equal(ctx.download(d_res, (4 * nres, 4)), sent_res), "%s: a result was written" % what
-
-        def fill(units, cols=None, usable_rows=usable, bps=None, params=good, op=ADD, vdev=None, vlen=nv, rdev=None, rlen=4 * nres):
-            return lambda: PL.ec_fill(ctx, d_cols if cols is None else cols, usable_rows, bps, params, op, d_vals if vdev is None else vdev, vlen,
-                                      d_res if rdev is None else rdev, rlen, units)
-
-        par = lambda n=88, k_=3, lb=8, p=SECP_P, flags=0: PL.fp_params(n, k_, lb, p, flags)
-        cols = (_vp * 3)(*[_vp(int(ptr)) for ptr in d_cols])
-        tab = C.cast(PL.ec_op_table([ok]), _vp)
-        pp = C.cast(C.pointer(good), _vp)
-        raw = lambda c, p_, v, t, cnt=1: (lambda: ctx._chk(ctx.lib.h2hip_ec_fill_dev(ctx.handle, c, 3, usable, None, p_, ADD, v, nv, _vp(int(d_res)), 4 * nres, t, cnt)))
-        refused("columns NULL", "NULL argument", raw(None, pp, _vp(int(d_vals)), tab))
-        refused("params NULL", "NULL argument", raw(cols, None, _vp(int(d_vals)), tab))
-        refused("values NULL", "NULL argument", raw(cols, pp, None, tab))
-        refused("units NULL", "NULL argument", raw(cols, pp, _vp(int(d_vals)), None))
-        refused("an unknown op", "unknown op", fill([ok], op=2))
-        refused("flags != 0", "flags", fill([ok], params=par(flags=1)))
-        refused("limb_bits 63", "limb_bits outside", fill([ok], params=par(n=63, k_=4, p=(1 << 252) - 1)))
-        refused("limb_bits 128", "limb_bits outside", fill([ok], params=par(n=128, k_=2)))
-        refused("num_limbs 1", "num_limbs outside", fill([ok], params=par(k_=1)))
-        refused("num_limbs 5", "num_limbs outside", fill([ok], params=par(n=64, k_=5)))
-        refused("n k > 320", "> 320", fill([ok], params=par(n=107, k_=3, p=(1 << 320) - 1)))
-        refused("p == 0", "zero", fill([ok], params=par(p=0)))
-        refused("p < 2^(n (k - 1))", "exactly num_limbs", fill([ok], params=par(p=(1 << 176) - 1)))
-        refused("p >= 2^(n k)", "exactly num_limbs", fill([ok], params=par(p=1 << 264)))
-        refused("quot_max_bits >= n k", "quot_max_bits", fill([ok], params=par(p=(1 << 252) - 1)))
-        refused("a limb of p equal to 1", "equals 1", fill([ok], params=par(p=(1 << 255) + (1 << 88) + 12345)))
-        refused("bits(p) > 256", "more than 256 bits", fill([ok], params=par(p=(1 << 260) + 12345)))
-        refused("p even", "even", fill([ok], params=par(p=(1 << 255) + 12346)))
-        refused("n k > 318", "> 318", fill([ok], params=par(n=80, k_=4, p=SECP_P)))
-        refused("lookup_bits 0", "lookup_bits", fill([ok], params=par(lb=0)))
-        refused("lookup_bits 64", "lookup_bits", fill([ok], params=par(lb=64)))
-        refused("column index out of range", "column index", fill([ok, (3, 0, pt, 2 * pt)]))
-        refused("a NULL column", "column index", fill([ok, (1, 0, pt, 2 * pt)], cols=[d_cols[0], 0, d_cols[2]]))
-        refused("a run that leaves the usable rows", "usable rows", fill([ok, (1, usable - ncells + 1, pt, 2 * pt)]))
-        refused("a run that leaves the last column", "last column", fill([ok, (2, usable - ncells + 1, pt, 2 * pt)], bps=[usable - 1, usable - 1]))
-        refused("a break point >= usable_rows", "break point", fill([ok], bps=[10, usable]))
-        refused("P past values_len", "outside values_len", fill([ok, (1, 0, nv - pt + 1, 0)]))
+    with FH.RefusalBench(ctx, kind, vals, (0, pt), (pt, 2 * pt), ncells, segments(3, ADD), 4 * nres) as b:
+        usable, nv, fill, refused = b.usable, b.nv, b.fill, b.refused
+        b.refuse_nulls()
+        refused("an unknown op", "unknown op", fill([b.ok], op=2))
+        b.refuse_params(behind={"a limb of p equal to 1": [("bits(p) > 256", "more than 256 bits", dict(p=(1 << 260) + 12345)),
+                                                           ("p even", "even", dict(p=(1 << 255) + 12346)),
+                                                           ("n k > 318", "> 318", dict(n=80, k_=4, p=SECP_P))]})
+        b.refuse_placement()
+        refused("P past values_len", "outside values_len", fill([b.ok, (1, 0, nv - pt + 1, 0)]))
         refused("Q past values_len", "outside values_len", fill([(1, 0, 0, (1 << 64) - 2)]))
-        refused("results_len too small", "results_len", fill([ok, (1, 0, pt, 2 * pt)], rlen=2 * nres - 1))
-        refused("count times the segments > 2^32", "2^32", raw(cols, pp, _vp(int(d_vals)), tab, cnt=(1 << 32) // segments(3, ADD) + 1))
-        refused("two units' cells overlap", "cells overlap", fill([ok, (0, ncells - 1, pt, 2 * pt)]))
-        refused("a unit inside another's gap", "cells overlap", fill([ok, (0, lay.ranges[0][0], pt, 2 * pt)]))
-        refused("a break copy inside another unit", "cells overlap", fill([(1, 0, 0, pt), (0, 20, pt, 2 * pt)], bps=[25, usable - 1]))
-        refused("an operand inside cells this call writes", "operand range", fill([(1, 0, 5, 300)], vdev=d_cols[1], vlen=usable))
-        refused("the results inside cells this call writes", "results overlap", fill([(1, 0, 0, pt)], rdev=d_cols[1] + 32 * 10, rlen=nres))
-        refused("the results over operands of the call", "operand range", fill([ok], rdev=d_vals, rlen=nv))
-        for what, prm, op in (("layout: flags", par(flags=2), ADD), ("layout: p", par(p=0), DOUBLE), ("layout: op", good, 7)):
-            try:
-                PL.ec_layout(prm, op, ctx.lib)
-            except H.H2HipError as e:
-                assert e.code == ERR_INVALID, what
-            else:
-                raise AssertionError(what + " was accepted")
+        b.refuse_results_len()
+        b.refuse_count()
+        b.refuse_overlaps(lay.ranges[0][0])
+        b.refuse_aliasing((5, 300))
+        for what, prm, op in (("layout: flags", FH.par(flags=2), ADD), ("layout: p", FH.par(p=0), DOUBLE), ("layout: op", kind.params, 7)):
+            FH.layout_refused(what, lambda: PL.ec_layout(prm, op, ctx.lib))
         # count == 0 needs nothing
         ctx._chk(ctx.lib.h2hip_ec_fill_dev(ctx.handle, None, 0, 0, None, None, 9, None, 0, None, 0, None, 0))
         # the largest run that still fits (its last cell on row usable - 1), a point that ends with values_len, a DOUBLE whose q_offset is
@@ -712,45 +546,29 @@ def check_rejections(ctx):
         fill(units, bps=bps, rlen=2 * nres)()
         lay2 = PL.ec_layout(sp.params(), DOUBLE, ctx.lib)
         dbl = [(2, 3, 2 * pt, (1 << 64) - 1)]
-        fill(dbl, op=DOUBLE, rdev=d_res + 32 * 2 * nres, rlen=nres)()
+        fill(dbl, op=DOUBLE, rdev=b.d_res + 32 * 2 * nres, rlen=nres)()
         ctx.sync()
-        want = [np.tile(SENTINEL, (n_rows, 1)) for _ in range(3)]
+        want = [np.tile(SENTINEL, (b.n_rows, 1)) for _ in range(3)]
         want_res = np.tile(SENTINEL, (4 * nres, 1))
-        for j, (op, (col, row, a, b)) in enumerate([(ADD, units[0]), (ADD, units[1]), (DOUBLE, dbl[0])]):
-            u, cells, _, _ = unit_def(sp, op, vals[a:a + pt], vals[b:b + pt] if op == ADD else None)
+        for j, (op, (col, row, a, b_)) in enumerate([(ADD, units[0]), (ADD, units[1]), (DOUBLE, dbl[0])]):
+            u, cells, _, _ = unit_def(sp, op, vals[a:a + pt], vals[b_:b_ + pt] if op == ADD else None)
             own = own_mask(u)
             for i, c, r in place(col, row, len(cells), bps if op == ADD else None, 3)[0]:
                 if own[i]:
                     want[c][r] = fr([cells[i]])[0]
             want_res[j * nres:(j + 1) * nres] = fr(u.results)
-        assert lay2.num_cells + 3 < n_rows
-        _compare(ctx, d_cols + [d_res], want + [want_res], "after the refusals")
-    finally:
-        for ptr in d_cols + [d_vals, d_res]:
-            ctx.free(ptr)
+        assert lay2.num_cells + 3 < b.n_rows
+        compare(ctx, b.d_cols + [b.d_res], want + [want_res], "after the refusals")
 
 
 # ------------------------------------------------------------------------------------------------ E: the structs in every layer
 def check_struct_layout():
     """h2hip_ec_op: the same fields in the header, the Rust sys crate and ctypes, 24 bytes; the two op constants alike; every function named
     in the C++ mirror and the safe Rust wrapper"""
-    hdr = open(os.path.join(ROOT, "include", "h2hip.h")).read()
-    rs = open(os.path.join(ROOT, "ffi", "rust", "h2hip-sys", "src", "lib.rs")).read()
-    body = re.search(r"typedef struct h2hip_ec_op\s*\{(.*?)\}\s*h2hip_ec_op\s*;", hdr, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    cmap = {"uint32_t": "u32", "uint64_t": "u64"}
-    c_fields = [(nm.strip(), cmap[decl.split(None, 1)[0]]) for decl in body.split(";") if decl.strip() for nm in decl.strip().split(None, 1)[1].split(",")]
-    rs_body = re.search(r"pub struct h2hip_ec_op\s*\{(.*?)\}", rs, flags=re.S).group(1)
-    rs_fields = re.findall(r"pub ([a-z_]+): ([a-z0-9]+)", rs_body)
-    py_fields = [(nm, {C.c_uint32: "u32", C.c_uint64: "u64"}[ty]) for nm, ty in PL.EcOpStruct._fields_]
-    assert c_fields == rs_fields == py_fields == [("column", "u32"), ("row", "u32"), ("p_offset", "u64"), ("q_offset", "u64")], (c_fields, rs_fields, py_fields)
-    assert C.sizeof(PL.EcOpStruct) == 24 and PL.EcOpStruct.p_offset.offset == 8 and PL.EcOpStruct.q_offset.offset == 16
-    for name, py in (("H2HIP_EC_ADD_UNEQUAL", ADD), ("H2HIP_EC_DOUBLE", DOUBLE)):
-        assert int(re.search(r"#define %s (\d+)" % name, hdr).group(1)) == py == int(re.search(r"pub const %s: u32 = (\d+);" % name, rs).group(1))
-    for layer in ("halo2-lib_amd/host/halo2_proofs.hpp", "ffi/rust/h2hip-sys/src/safe.rs"):
-        src = open(os.path.join(ROOT, layer)).read()
-        for fn in ("h2hip_ec_fill_dev", "h2hip_ec_layout", "h2hip_ec_range_checks"):
-            assert fn in src, (layer, fn)
+    FH.check_names(constants=[("H2HIP_EC_ADD_UNEQUAL", ADD), ("H2HIP_EC_DOUBLE", DOUBLE)], structs=[("h2hip_ec_op", PL.EcOpStruct, 24)],
+                   mirrored=("h2hip_ec_fill_dev", "h2hip_ec_layout", "h2hip_ec_range_checks"))
+    assert [nm for nm, _ty in PL.EcOpStruct._fields_] == ["column", "row", "p_offset", "q_offset"]
+    assert PL.EcOpStruct.p_offset.offset == 8 and PL.EcOpStruct.q_offset.offset == 16
 
 
 # ------------------------------------------------------------------------------------------------ F: inside a proof
@@ -782,90 +600,34 @@ def check_proof(ctx, kk, seed, nl, mode="proof"):
     m = multiples("secp256k1_p", 5)
     p_vals = point(sp, *m[1])
     q_vals = point(sp, *m[4]) if mode == "proof" else point(sp, m[1][0], m[4][1])
-    n = 1 << kk
-    na = 12
-    while True:                                        # the number of gate columns the layout fills (an empty one would have a disjoint selector)
-        sh = P.Shape(kk, na, nl, 1, 1, lb)
-        kb = VR.BaseCircuitBuilder(False)
-        _ec_program(kb, sp, p_vals, q_vals)
-        advice_k, fixed, copies, instances, bps = kb.synthesize(sh)
-        if len(bps) == na - 1:
-            break
-        na = len(bps) + 1
-    assert na >= 2 and len(bps) >= 1
-    pb = VR.BaseCircuitBuilder(True)
-    pb.break_points = bps
-    calls = _ec_program(pb, sp, p_vals, q_vals)
-    advice, _, _, _, _ = pb.synthesize(sh)
-    assert all(np.array_equal(a, b) for a, b in zip(advice, advice_k))
-    total = sum(len(t.advice) for t in pb.threads)
-    cells_at, _ = place(0, 0, total, bps, na)
-    first = {}
-    for i, c, r in cells_at:
-        first.setdefault(i, (c, r))
-    assert all(first[i] == (0, i) for i in range(2 * pt))           # the witnesses: flat index i of the gate allocation
-    kzg, srs_params = srs(ctx, kk, seed)
-    gpk = PL.keygen(kzg, PL.BaseCircuitParams.new(kk, na, nl, 1, 1, lb), fixed, copies)
-    budget = rng_budget(sh)
-    # one device buffer: [gate columns][results of R][of D][of S]: a unit finds one point in the results of the call before it, P among the witnesses
-    host = np.zeros((na * n + 3 * nres, 4), dtype=np.uint64)
-    host[:2 * pt] = advice[0][:2 * pt]
-    d_gate = ctx.to_device(host)
-    d_lookup = ctx.to_device(np.zeros((nl * n, 4), dtype=np.uint64))
-    d_cols = [d_gate + 32 * n * c for c in range(na)]
-    d_lks = [d_lookup + 32 * n * c for c in range(nl)]
-    res_at = [na * n + j * nres for j in range(3)]
-    tables = [first[calls[0][0]] + (0, pt), first[calls[1][0]] + (res_at[0], 0), first[calls[2][0]] + (res_at[1], 0)]
-
-    def fill_all():
+    with FH.ProofBench(ctx, kk, nl, lb, seed, lambda builder: _ec_program(builder, sp, p_vals, q_vals)) as pb:
+        calls, first = pb.calls, pb.first
+        # one device buffer: [gate columns][results of R][of D][of S]: a unit finds one point in the results of the call before it, P among the witnesses
+        res_at = pb.buffers(3 * nres, [range(2 * pt)])
+        res_at = [res_at + j * nres for j in range(3)]
+        tables = [first[calls[0][0]] + (0, pt), first[calls[1][0]] + (res_at[0], 0), first[calls[2][0]] + (res_at[1], 0)]
         for j, op in enumerate((ADD, DOUBLE, ADD)):
-            PL.ec_fill_with_ranges(ctx, d_cols, sh.usable_rows, bps, d_lks, sp.params(), op, d_gate, len(host), d_gate + 32 * res_at[j], nres,
+            PL.ec_fill_with_ranges(ctx, pb.d_cols, pb.sh.usable_rows, pb.bps, pb.d_lks, sp.params(), op, pb.d_gate, len(pb.host), pb.d_gate + 32 * res_at[j], nres,
                                    [tables[j]], [calls[j][1]])
         ctx.sync()
-
-    try:
-        fill_all()
-        got_cols = np.concatenate([ctx.download(d_gate, (na, n, 4)), ctx.download(d_lookup, (nl, n, 4))])
-        for c in range(na + nl):
-            assert np.array_equal(got_cols[c], advice[c]), "advice column %d differs from the Python-computed advice" % c
+        pb.check_columns()
         s0, _q, u0 = calls[0]
         if mode == "equal_x":
             assert u0.lam == 0 and u0.quots[0][1] != 0
-            total_f, fails = PL.check_witness(gpk, d_cols + d_lks, instances, max_failures=4096, advice_on_device=True)
+            total_f, fails = pb.check_witness(max_failures=4096)
             # the zero check's native identity 0 + m_nat * quot_native = qc_nat is the gate four cells before x3's first reduction segment
             native_gate = first[s0 + u0.gaps[3 * k - 1][0] + u0.gaps[3 * k - 1][1] + 3 * k - 2]
             assert total_f >= 1 and any(f.kind == "gate" and (f.column, f.row) == native_gate for f in fails), (native_gate, fails[:8])
             return
-        want = PL.create_proof(gpk, advice, instances, PreDrawnRng(budget, 2000 + seed))
-        got = PL.create_proof(gpk, d_cols + d_lks, instances, PreDrawnRng(budget, 2000 + seed), advice_on_device=True)
-        assert got == want, "the proof over device-filled curve operations differs from the one over the Python-computed advice"
-        assert PL.verify_proof(gpk, instances, got), "h2hip_plonk_verify_proof rejects the proof"
-        assert P.verify_proof(srs_params, vk_from_gpu(sh, gpk), [_ints(v) for v in instances], got), "the test verifier rejects the proof"
-        total_f, fails = PL.check_witness(gpk, d_cols + d_lks, instances, advice_on_device=True)
-        assert total_f == 0, fails
+        pb.check_proof()
         # ---- the lambda_1 witness cell itself changed by one: its copies no longer equal it, no gate sees it
-        c, r = first[s0 + u0.lam_offsets[1]]
-        ctx.upload(d_cols[c] + 32 * r, fr([(_ints(advice[c][r:r + 1])[0] + 1) % R]))
-        total_f, fails = PL.check_witness(gpk, d_cols + d_lks, instances, max_failures=64, advice_on_device=True)
+        total_f, fails = pb.changed(s0 + u0.lam_offsets[1])
         assert total_f >= 1 and fails and all(f.kind == "copy" for f in fails), fails
-        ctx.upload(d_cols[c] + 32 * r, advice[c][r:r + 1])
         # ---- lambda_1 changed by one on the device, where the zero check reads it: its copy inside ip(lambda_0, lambda_1; dx_1, dx_0), the
         # second limb of lambda * dx (0 l_0 dx_1 s_0 [l_1] dx_0 s_1).  The gate on s_0 no longer holds: a row of divide_unsafe's constraint
         off = u0.gaps[k - 1][0] + u0.gaps[k - 1][1] + 4 + 4             # behind lambda's last gap: ip_0 (4 cells), then 0 l_0 dx_1 s_0 [l_1]
-        assert advice_cell(advice, first, s0 + off) == advice_cell(advice, first, s0 + u0.lam_offsets[1])
+        assert pb.cell(s0 + off) == pb.cell(s0 + u0.lam_offsets[1])
         gate_row = first[s0 + off - 1]
         assert first[s0 + off + 2] == (gate_row[0], gate_row[1] + 3), "a break cuts the gate"
-        c, r = first[s0 + off]
-        ctx.upload(d_cols[c] + 32 * r, fr([(_ints(advice[c][r:r + 1])[0] + 1) % R]))
-        total_f, fails = PL.check_witness(gpk, d_cols + d_lks, instances, max_failures=64, advice_on_device=True)
+        total_f, fails = pb.changed(s0 + off)
         assert total_f >= 1 and any(f.kind == "gate" and (f.column, f.row) == gate_row for f in fails), fails
-    finally:
-        ctx.free(d_gate)
-        ctx.free(d_lookup)
-        gpk.free()
-        kzg.free()
-
-
-def advice_cell(advice, first, i):
-    c, r = first[i]
-    return _ints(advice[c][r:r + 1])[0]

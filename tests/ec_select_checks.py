@@ -12,24 +12,17 @@ select_by_indicator::crt (bigint/select_by_indicator.rs:29-69) behind bits_to_in
   D  column breaks as assign_witnesses makes them;  E  chaining: bits -> selection -> addition -> selection with no host copy in between;
   F  the refusals;  G  a BaseConfig proof whose selections and bits the device calls write.
 """
-import ctypes as C
-
 import numpy as np
 
-import halo2_lib_amd as H
 from halo2_lib_amd import plonk as PL
 from halo2_lib_amd import virtual_region as VR
-from oracle import plonk as P
 from tests import ec_fill_checks as K
-from tests.dyn_lookup_util import rng_budget, srs, vk_from_gpu
+from tests import fused_fill_harness as FH
 from tests.ec_fill_checks import CURVES, PARAMS, aff_add, multiples, point
-from tests.fp_mul_checks import MODULI, SECP_P, Spec, _operand, _thread, own_mask
-from tests.poseidon_trace_checks import _compare, _ints, place
-from tests.rlc_checks import SENTINEL
-from tests.util import PreDrawnRng, R, fr
+from tests.fp_mul_checks import MODULI, SECP_P, Spec
+from tests.fused_fill_harness import SENTINEL, Bits, FromBits, Select, compare, own_mask, place
+from tests.util import R, fr
 
-_vp = C.c_void_p
-ERR_INVALID = -1
 SELECT, FROM_BITS, ADD = PL.EC_SELECT, PL.EC_SELECT_FROM_BITS, PL.EC_ADD_UNEQUAL
 SOLVE_BLOCK, PLACE_BLOCK, BITS_BLOCK = 64, 256, 256   # ec_select.hip: lanes per workgroup of the per-unit, the per-(unit, segment) and the per-(unit, bit) kernel
 PIECE = 2                                              # ec_select.cuh: entries of a chain per lane of the placing kernel
@@ -67,7 +60,7 @@ class Unit:
 
 def _begin(ctx):
     u = Unit()
-    u.start = len(ctx.advice)
+    u.start, u.queue, u.gaps = len(ctx.advice), 0, []   # (no range checks: no lookup cells, no gaps)
     return u
 
 
@@ -133,73 +126,9 @@ def gates_hold(ctx, cells=None):
     return [s for s, q in enumerate(ctx.selector) if q and (cells[s] + cells[s + 1] * cells[s + 2] - cells[s + 3]) % R]
 
 
-class Select:
-    """what the checks need to know of a kind of unit.  A case is the unit's operand values: (P's 2 (k + 1), Q's, [sel])"""
-
-    def __init__(self, sp):
-        self.sp, self.nres, self.name = sp, 2 * (sp.k + 1), "select"
-
-    def define(self, ctx, case, tag=0):
-        p, q, s = case
-        return ec_select(ctx, self.sp, _operand(p, 3 * tag), _operand(q, 3 * tag + 1), _operand(s, 3 * tag + 2)[0])
-
-    def unit(self, col, row, at, case):
-        """the unit whose operands lie at `at` of the values, in the case's order"""
-        return (col, row, at, at + len(case[0]), at + len(case[0]) + len(case[1]))
-
-    def layout(self, lib=None):
-        return PL.ec_select_layout(self.sp.params(), SELECT, 0, lib)
-
-    def fill(self, ctx, cols, usable, bps, d_vals, nvals, d_res, nres, units):
-        PL.ec_select_fill(ctx, cols, usable, bps, self.sp.params(), SELECT, 0, d_vals, nvals, d_res, nres, units)
-
-
-class FromBits:
-    """... (the table's m points flat, the w bits)"""
-
-    def __init__(self, sp, w):
-        self.sp, self.w, self.nres, self.name = sp, w, 2 * (sp.k + 1), "from_bits w = %d" % w
-
-    def define(self, ctx, case, tag=0):
-        table, bits = case
-        pt = self.nres
-        cells = _operand(table, 2 * tag)
-        return ec_select_from_bits(ctx, self.sp, [cells[j * pt:(j + 1) * pt] for j in range(1 << self.w)], _operand(bits, 2 * tag + 1))
-
-    def unit(self, col, row, at, case):
-        return (col, row, at, 0, at + len(case[0]))
-
-    def layout(self, lib=None):
-        return PL.ec_select_layout(self.sp.params(), FROM_BITS, self.w, lib)
-
-    def fill(self, ctx, cols, usable, bps, d_vals, nvals, d_res, nres, units):
-        PL.ec_select_fill(ctx, cols, usable, bps, self.sp.params(), FROM_BITS, self.w, d_vals, nvals, d_res, nres, units)
-
-
-class Bits:
-    """... ([the value],)"""
-
-    def __init__(self, nb):
-        self.nb, self.nres, self.name = nb, nb, "num_to_bits %d" % nb
-
-    def define(self, ctx, case, tag=0):
-        return num_to_bits(ctx, _operand(case[0], tag)[0], self.nb)
-
-    def unit(self, col, row, at, case):
-        return (col, row, at)
-
-    def layout(self, lib=None):
-        return PL.num_to_bits_layout(self.nb, lib)
-
-    def fill(self, ctx, cols, usable, bps, d_vals, nvals, d_res, nres, units):
-        PL.num_to_bits_fill(ctx, cols, usable, bps, d_vals, nvals, d_res, nres, self.nb, units)
-
-
 def unit_def(kind, case):
     """one unit on a thread of its own -> (the Unit, its cells)"""
-    ctx, _chip, _ = _thread()
-    u = kind.define(ctx, case)
-    return u, list(ctx.advice)
+    return kind.unit_def(case)[:2]
 
 
 # ------------------------------------------------------------------------------------------------ the pools
@@ -288,8 +217,8 @@ def check_definition():
                 m = 1 << w
                 kind = FromBits(sp, w)
                 for table, pat in from_bits_pool(sp, w, modulus):
-                    ctx, _chip, _ = _thread()
-                    u = kind.define(ctx, (table, pat))
+                    ctx, _chip, _ = FH.thread()
+                    u = kind.define(ctx, _chip, (table, pat))
                     assert not gates_hold(ctx), (n, k, w, pat)
                     assert u.end - u.start == from_bits_cells(k, w) and ((k, w) not in CELLS or CELLS[(k, w)] == u.end - u.start)
                     if all(b in (0, 1) for b in pat):
@@ -303,16 +232,16 @@ def check_definition():
                     assert all(ctx.advice[x.offset] == ctx.advice[y.offset] for x, y in ctx.copy_manager.advice_equalities if x.type_id == y.type_id == "fp")
             kind = Select(sp)
             for p, q, s in select_pool(sp, modulus):
-                ctx, _chip, _ = _thread()
-                u = kind.define(ctx, (p, q, s))
+                ctx, _chip, _ = FH.thread()
+                u = kind.define(ctx, _chip, (p, q, s))
                 assert not gates_hold(ctx) and u.end - u.start == 16 * (k + 1)
                 if s[0] in (0, 1):
                     assert u.results == [x % R for x in (p if s[0] else q)]
                 assert u.out_offsets == [8 * j + 7 for j in range(pt)]
     for nb in NUM_BITS + [5]:
         for (vals,) in bits_pool(nb):
-            ctx, _chip, _ = _thread()
-            u = Bits(nb).define(ctx, (vals,))
+            ctx, _chip, _ = FH.thread()
+            u = Bits(nb).define(ctx, _chip, (vals,))
             v = vals[0]
             assert not gates_hold(ctx) and u.end - u.start == 7 * nb - 2
             assert all(b in (0, 1) for b in u.results) and sum(b << i for i, b in enumerate(u.results)) == v % (1 << nb)
@@ -345,91 +274,28 @@ def check_layouts(ctx):
         assert PL.num_to_bits_layout(nb, ctx.lib) == (len(cells), u.sum_offset) == (7 * nb - 2, 3 * nb - 3)
 
 
-def check_fill(ctx, kind, pool, count):
-    """`count` units per call over three gate columns (no breaks), until every case of the pool was a unit: every cell of every run equals
-    the definition's, every other cell keeps the sentinel, results_dev holds the definition's result cells unit by unit"""
-    lay = kind.layout(ctx.lib)
-    vals, at = [], []
-    for case in pool:
-        at.append(len(vals))
-        vals += [v % R for part in case for v in part]
-    nres = kind.nres
-    cache = {}
-    done = 0
-    d_vals = ctx.to_device(fr(vals))
-    try:
-        while done < len(pool):
-            units, defs, rows = [], [], [1, 3, 0]
-            for j in range(count):
-                i = (done + j) % len(pool)
-                if i not in cache:
-                    cache[i] = unit_def(kind, pool[i])
-                u, cells = cache[i]
-                assert len(cells) == lay[0]
-                col = j % 3
-                units.append(kind.unit(col, rows[col], at[i], pool[i]))
-                defs.append((u, cells))
-                rows[col] += len(cells) + (j % 2)
-            done += count
-            rows_n = max(rows) + 9
-            want = [np.tile(SENTINEL, (rows_n, 1)) for _ in range(3)]
-            want_res = np.tile(SENTINEL, (count * nres + 2, 1))
-            d_cols = [ctx.to_device(c) for c in want]
-            d_res = ctx.to_device(want_res)
-            for j, (unit, (u, cells)) in enumerate(zip(units, defs)):
-                want[unit[0]][unit[1]:unit[1] + len(cells)] = fr(cells)
-                want_res[j * nres:(j + 1) * nres] = fr(u.results)
-            try:
-                kind.fill(ctx, d_cols, rows_n - 2, None, d_vals, len(vals), d_res, count * nres, units)
-                ctx.sync()
-                what = "%s, count = %d" % (kind.name, count)
-                _compare(ctx, d_cols, want, what + " (gate columns)")
-                _compare(ctx, [d_res], [want_res], what + " (results)")
-            finally:
-                for ptr in d_cols + [d_res]:
-                    ctx.free(ptr)
-    finally:
-        ctx.free(d_vals)
-
-
 def check_select_fill(ctx, n, k, lb, modulus, count=5, pool=None):
     sp = Spec(n, k, lb, MODULI[modulus])
-    check_fill(ctx, Select(sp), select_pool(sp, modulus) if pool is None else pool, count)
+    FH.check_fill(ctx, Select(sp), select_pool(sp, modulus) if pool is None else pool, count)
 
 
 def check_from_bits_fill(ctx, n, k, lb, modulus, w, count=5, pool=None):
     sp = Spec(n, k, lb, MODULI[modulus])
-    check_fill(ctx, FromBits(sp, w), from_bits_pool(sp, w, modulus) if pool is None else pool, count)
+    FH.check_fill(ctx, FromBits(sp, w), from_bits_pool(sp, w, modulus) if pool is None else pool, count)
 
 
 def check_bits_fill(ctx, nb, count=4, pool=None):
     pool = bits_pool(nb) if pool is None else pool
     if nb < 254:
         assert any(v[0][0] >= (1 << nb) for v in pool), "the pool holds a value that does not fit"
-    check_fill(ctx, Bits(nb), pool, count)
+    FH.check_fill(ctx, Bits(nb), pool, count)
 
 
 def check_no_results(ctx):
     """results_dev = NULL: the cells are written all the same"""
     sp = Spec(88, 3, 8, SECP_P)
     for kind, pool in ((Select(sp), select_pool(sp, "secp256k1_p")[:2]), (FromBits(sp, 2), from_bits_pool(sp, 2, "secp256k1_p")[:2]), (Bits(5), bits_pool(5)[:2])):
-        vals = [v % R for case in pool for part in case for v in part]
-        u0, cells0 = unit_def(kind, pool[0])
-        u1, cells1 = unit_def(kind, pool[1])
-        per = len(vals) // 2
-        units = [kind.unit(0, 2, 0, pool[0]), kind.unit(0, 3 + len(cells0), per, pool[1])]
-        rows_n = 2 * len(cells0) + 12
-        want = np.tile(SENTINEL, (rows_n, 1))
-        want[2:2 + len(cells0)] = fr(cells0)
-        want[3 + len(cells0):3 + 2 * len(cells0)] = fr(cells1)
-        d_col, d_vals = ctx.to_device(np.tile(SENTINEL, (rows_n, 1))), ctx.to_device(fr(vals))
-        try:
-            kind.fill(ctx, [d_col], rows_n - 2, None, d_vals, len(vals), None, 0, units)
-            ctx.sync()
-            _compare(ctx, [d_col], [want], kind.name + " without results")
-        finally:
-            ctx.free(d_col)
-            ctx.free(d_vals)
+        FH.check_no_results(ctx, kind, pool, 12, 2)
 
 
 # ------------------------------------------------------------------------------------------------ D: column breaks
@@ -461,10 +327,9 @@ def break_cells(name):
 BREAK_CASES = [(name, case) for name in ("select", "from_bits", "bits") for case in break_cells(name)]
 
 
-def check_breaks(ctx, name, case, ncols):
-    """one thread (plain cells, then units of one kind back to back, each reading operands of its own) laid into ncols columns by
-    virtual_region.assign_witnesses and by the fill from each unit's first cell, from the same break points.  Every break falls on the cell
-    the case names (case "two": both breaks inside one unit, three columns)."""
+def check_select_breaks(ctx, name, case, ncols):
+    """the harness's check_breaks over units of one kind behind 50 plain cells: every break on the cell the case names (case "two": both
+    breaks inside one unit, three columns)"""
     kind, pool = _break_kind(name)
     cells_at = break_cells(name)[case]
     if len(cells_at) == 2:
@@ -474,51 +339,10 @@ def check_breaks(ctx, name, case, ncols):
         targets = [(1 + 2 * b, cells_at[0]) for b in range(ncols - 1)]
     filler = 50
     nunits = targets[-1][0] + 2
-    thread, _chip, _ = _thread()
-    thread.advice += list(range(100, 100 + filler))
-    thread.selector += [False] * filler
-    cases = [pool[(3 * j + 1) % len(pool)] for j in range(nunits)]
-    defs = [kind.define(thread, case_, j) for j, case_ in enumerate(cases)]
-    ncells = defs[0].end - defs[0].start
-    assert all(u.end - u.start == ncells for u in defs)
-    idx = [filler + unit * ncells + c for unit, c in targets]
-    bps = [idx[0]] + [b - a for a, b in zip(idx, idx[1:])]
-    total = len(thread.advice)
-    usable = max(bps + [total - idx[-1]]) + 20
-    at = place(0, 0, total, bps, ncols)[0]
-    first = {}
-    for i, c, r in at:
-        first.setdefault(i, (c, r))
-    for i, b, col in zip(idx, bps, range(ncols)):   # the break cell is the cell the case names
-        assert (i, col, b) in at and (i, col + 1, 0) in at, (name, case, i)
-    vals, offs = [], []
-    for case_ in cases:
-        offs.append(len(vals))
-        vals += [v % R for part in case_ for v in part]
-    units = [kind.unit(*first[u.start], offs[j], cases[j]) for j, u in enumerate(defs)]
-    rows_n = usable + 9
-    region = VR.Region(rows_n, ncols)
-    VR.assign_witnesses([thread], list(range(ncols)), region, bps)
-    want = [np.tile(SENTINEL, (rows_n, 1)) for _ in range(ncols)]
-    for c in range(ncols):
-        rows = sorted(region.advice[c])
-        want[c][rows] = fr([region.advice[c][r] for r in rows])
-    start = [np.tile(SENTINEL, (rows_n, 1)) for _ in range(ncols)]
-    start[0][:filler] = want[0][:filler]
-    nres = kind.nres
-    want_res = np.concatenate([fr(u.results) for u in defs] + [np.tile(SENTINEL, (1, 1))])
-    d_cols = [ctx.to_device(c) for c in start]
-    d_vals = ctx.to_device(fr(vals))
-    d_res = ctx.to_device(np.tile(SENTINEL, (nunits * nres + 1, 1)))
-    try:
-        kind.fill(ctx, d_cols, usable, bps, d_vals, len(vals), d_res, nunits * nres, units)
-        ctx.sync()
-        what = "breaks (%s, %s, %d columns)" % (name, case, ncols)
-        _compare(ctx, d_cols, want, what)
-        _compare(ctx, [d_res], [want_res], what + " (results)")
-    finally:
-        for ptr in d_cols + [d_vals, d_res]:
-            ctx.free(ptr)
+    ncells = kind.layout(ctx.lib)[0]
+    bps = FH.break_points(filler, ncells, targets)
+    usable = max(bps + [filler + nunits * ncells - sum(bps)]) + 20   # (the last column takes what lies behind the last break)
+    FH.check_breaks(ctx, kind, [pool[(3 * j + 1) % len(pool)] for j in range(nunits)], targets, filler, usable, ncols)
 
 
 # ------------------------------------------------------------------------------------------------ E: chaining
@@ -587,7 +411,7 @@ def check_chained(ctx, curve, n=88, k=3, lb=8, count=3):
         PL.ec_fill(ctx, d_cols, rows_n - 2, None, sp.params(), ADD, d_buf, total, d_buf + 32 * at_s3, count * nres, units[2])
         PL.ec_select_fill(ctx, d_cols, rows_n - 2, None, sp.params(), SELECT, 0, d_buf, total, d_buf + 32 * at_z, count * pt, units[3])
         ctx.sync()
-        _compare(ctx, d_cols + [d_buf], want + [want_buf], "chained calls on %s" % curve)
+        compare(ctx, d_cols + [d_buf], want + [want_buf], "chained calls on %s" % curve)
     finally:
         for ptr in d_cols + [d_buf]:
             ctx.free(ptr)
@@ -600,113 +424,48 @@ def check_rejections(ctx):
     sp = Spec(88, 3, 8, SECP_P)
     k, pt, w = sp.k, 2 * (sp.k + 1), 2
     ncells = from_bits_cells(k, w)
-    n_rows, usable = 2 * ncells + 60, 2 * ncells + 50
     table, pat = from_bits_pool(sp, w, "secp256k1_p")[2]
     vals = [v % R for v in table] + pat + [1]                                # the table, two bits, a selector
-    nv, at_bits = len(vals), 4 * pt
-    sent, sent_res = np.tile(SENTINEL, (n_rows, 1)), np.tile(SENTINEL, (4 * pt, 1))
-    d_cols = [ctx.to_device(sent) for _ in range(3)]
-    d_vals = ctx.to_device(fr(vals))
-    d_res = ctx.to_device(sent_res)
-    good = sp.params()
-    ok = (0, 0, 0, 0, at_bits)
-    try:
-        def refused(what, reason, call):
-            try:
-                call()
-            except H.H2HipError as e:
-                assert e.code == ERR_INVALID, (what, e.code)
-                msg = ctx.lib.h2hip_last_error().decode()
-                assert reason in msg, (what, msg)
-            else:
-                raise AssertionError("%s was accepted" % what)
-            ctx.sync()
-            for ptr in d_cols:
-                assert np.array_equal(ctx.download(ptr, (n_rows, 4)), sent), "%s: a cell was written" % what
-            assert np.array_equal(ctx.download(d_res, (4 * pt, 4)), sent_res), "%s: a result was written" % what
-
-        def fill(units, cols=None, usable_rows=usable, bps=None, params=good, op=FROM_BITS, wb=w, vdev=None, vlen=nv, rdev=None, rlen=4 * pt):
-            return lambda: PL.ec_select_fill(ctx, d_cols if cols is None else cols, usable_rows, bps, params, op, wb, d_vals if vdev is None else vdev, vlen,
-                                             d_res if rdev is None else rdev, rlen, units)
-
-        par = lambda n=88, k_=3, lb=8, p=SECP_P, flags=0: PL.fp_params(n, k_, lb, p, flags)
-        cols = (_vp * 3)(*[_vp(int(ptr)) for ptr in d_cols])
-        tab = C.cast(PL.ec_select_table([ok]), _vp)
-        pp = C.cast(C.pointer(good), _vp)
-        raw = lambda c, p_, v, t, cnt=1: (lambda: ctx._chk(ctx.lib.h2hip_ec_select_fill_dev(ctx.handle, c, 3, usable, None, p_, FROM_BITS, w, v, nv, _vp(int(d_res)), 4 * pt, t, cnt)))
-        refused("columns NULL", "NULL argument", raw(None, pp, _vp(int(d_vals)), tab))
-        refused("params NULL", "NULL argument", raw(cols, None, _vp(int(d_vals)), tab))
-        refused("values NULL", "NULL argument", raw(cols, pp, None, tab))
-        refused("units NULL", "NULL argument", raw(cols, pp, _vp(int(d_vals)), None))
+    at_bits = 4 * pt
+    kind = FromBits(sp, w)
+    with FH.RefusalBench(ctx, kind, vals, (0, at_bits), (0, at_bits), ncells, from_bits_segments(k, w), 4 * pt) as b:
+        usable, nv, fill, refused, ok = b.usable, b.nv, b.fill, b.refused, b.ok
+        b.refuse_nulls()
         refused("op 2", "unknown op", fill([ok], op=2))
-        refused("window_bits 0 for op 1", "window_bits outside", fill([ok], wb=0))
-        refused("window_bits 9 for op 1", "window_bits outside", fill([ok], wb=9))
-        refused("window_bits 1 for op 0", "window_bits must be 0", fill([ok], op=SELECT, wb=1))
-        refused("num_limbs 2", "num_limbs < 3", fill([ok], params=par(n=125, k_=2, p=(1 << 250) - 1)))
-        refused("flags != 0", "flags", fill([ok], params=par(flags=1)))
-        refused("limb_bits 63", "limb_bits outside", fill([ok], params=par(n=63, k_=4, p=(1 << 252) - 1)))
-        refused("num_limbs 5", "num_limbs outside", fill([ok], params=par(n=64, k_=5)))
-        refused("p == 0", "zero", fill([ok], params=par(p=0)))
-        refused("p >= 2^(n k)", "exactly num_limbs", fill([ok], params=par(p=1 << 264)))
-        refused("lookup_bits 0", "lookup_bits", fill([ok], params=par(lb=0)))
-        refused("column index out of range", "column index", fill([ok, (3, 0, 0, 0, at_bits)]))
-        refused("a NULL column", "column index", fill([ok, (1, 0, 0, 0, at_bits)], cols=[d_cols[0], 0, d_cols[2]]))
-        refused("a run that leaves the usable rows", "usable rows", fill([ok, (1, usable - ncells + 1, 0, 0, at_bits)]))
-        refused("a run that leaves the last column", "last column", fill([ok, (2, usable - ncells + 1, 0, 0, at_bits)], bps=[usable - 1, usable - 1]))
-        refused("a break point >= usable_rows", "break point", fill([ok], bps=[10, usable]))
+        refused("window_bits 0 for op 1", "window_bits outside", fill([ok], w=0))
+        refused("window_bits 9 for op 1", "window_bits outside", fill([ok], w=9))
+        refused("window_bits 1 for op 0", "window_bits must be 0", fill([ok], op=SELECT, w=1))
+        refused("num_limbs 2", "num_limbs < 3", fill([ok], params=FH.par(n=125, k_=2, p=(1 << 250) - 1)))
+        b.refuse_params(only=("flags != 0", "limb_bits 63", "num_limbs 5", "p == 0", "p >= 2^(n k)", "lookup_bits 0"))
+        b.refuse_placement()
         refused("a table past values_len", "outside values_len", fill([ok, (1, 0, nv - 4 * pt + 1, 0, at_bits)]))
         refused("the bits past values_len", "outside values_len", fill([ok, (1, 0, 0, 0, nv - 1)]))
         refused("the bits far past values_len", "outside values_len", fill([(1, 0, 0, 0, (1 << 64) - 2)]))
-        refused("sel past values_len", "outside values_len", fill([(1, 0, 0, pt, nv)], op=SELECT, wb=0))
-        refused("Q past values_len", "outside values_len", fill([(1, 0, 0, nv - pt + 1, 0)], op=SELECT, wb=0))
-        refused("results_len too small", "results_len", fill([ok, (1, 0, 0, 0, at_bits)], rlen=2 * pt - 1))
-        refused("count times the segments > 2^32", "2^32", raw(cols, pp, _vp(int(d_vals)), tab, cnt=(1 << 32) // from_bits_segments(k, w) + 1))
-        refused("two units' cells overlap", "cells overlap", fill([ok, (0, ncells - 1, 0, 0, at_bits)]))
-        refused("a break copy inside another unit", "cells overlap", fill([(1, 0, 0, 0, at_bits), (0, 20, 0, 0, at_bits)], bps=[25, usable - 1]))
-        refused("the bits inside cells this call writes", "operand range", fill([(1, 0, 150, 0, 5)], vdev=d_cols[1], vlen=usable))
-        refused("the results inside cells this call writes", "results overlap", fill([(1, 0, 0, 0, at_bits)], rdev=d_cols[1] + 32 * 10, rlen=pt))
-        refused("the results over operands of the call", "operand range", fill([ok], rdev=d_vals, rlen=nv))
-        for what, prm, op, wb in (("layout: flags", par(flags=2), FROM_BITS, 2), ("layout: op", good, 3, 0), ("layout: window", good, FROM_BITS, 0),
-                                  ("layout: window of op 0", good, SELECT, 2), ("layout: k", par(n=125, k_=2, p=(1 << 250) - 1), SELECT, 0)):
-            try:
-                PL.ec_select_layout(prm, op, wb, ctx.lib)
-            except H.H2HipError as e:
-                assert e.code == ERR_INVALID, what
-            else:
-                raise AssertionError(what + " was accepted")
+        refused("sel past values_len", "outside values_len", fill([(1, 0, 0, pt, nv)], op=SELECT, w=0))
+        refused("Q past values_len", "outside values_len", fill([(1, 0, 0, nv - pt + 1, 0)], op=SELECT, w=0))
+        b.refuse_results_len()
+        b.refuse_count()
+        b.refuse_overlaps()
+        b.refuse_aliasing((150, 5))
+        for what, prm, op, wb in (("layout: flags", FH.par(flags=2), FROM_BITS, 2), ("layout: op", kind.params, 3, 0), ("layout: window", kind.params, FROM_BITS, 0),
+                                  ("layout: window of op 0", kind.params, SELECT, 2), ("layout: k", FH.par(n=125, k_=2, p=(1 << 250) - 1), SELECT, 0)):
+            FH.layout_refused(what, lambda: PL.ec_select_layout(prm, op, wb, ctx.lib))
         # ---- h2hip_num_to_bits_fill_dev: the scalar is vals[nv - 1]
         nb, bcells = 5, 33
-        bok = (0, 0, nv - 1)
-
-        def bfill(units, cols=None, usable_rows=usable, bps=None, vdev=None, vlen=nv, rdev=None, rlen=4 * pt, num_bits=nb):
-            return lambda: PL.num_to_bits_fill(ctx, d_cols if cols is None else cols, usable_rows, bps, d_vals if vdev is None else vdev, vlen,
-                                               d_res if rdev is None else rdev, rlen, num_bits, units)
-
-        btab = C.cast(PL.bits_unit_table([bok]), _vp)
-        braw = lambda c, v, t, cnt=1, num_bits=nb: (lambda: ctx._chk(ctx.lib.h2hip_num_to_bits_fill_dev(ctx.handle, c, 3, usable, None, v, nv, _vp(int(d_res)), 4 * pt, num_bits, t, cnt)))
-        refused("bits: columns NULL", "NULL argument", braw(None, _vp(int(d_vals)), btab))
-        refused("bits: values NULL", "NULL argument", braw(cols, None, btab))
-        refused("bits: units NULL", "NULL argument", braw(cols, _vp(int(d_vals)), None))
-        refused("bits: num_bits 0", "num_bits outside", bfill([bok], num_bits=0))
-        refused("bits: num_bits 255", "num_bits outside", bfill([bok], num_bits=255))
-        refused("bits: count times num_bits > 2^32", "2^32", braw(cols, _vp(int(d_vals)), btab, cnt=(1 << 32) // nb + 1))
-        refused("bits: column index out of range", "column index", bfill([bok, (3, 0, 0)]))
-        refused("bits: a NULL column", "column index", bfill([bok, (1, 0, 0)], cols=[d_cols[0], 0, d_cols[2]]))
-        refused("bits: a run that leaves the usable rows", "usable rows", bfill([bok, (1, usable - bcells + 1, 0)]))
-        refused("bits: a run that leaves the last column", "last column", bfill([bok, (2, usable - bcells + 1, 0)], bps=[usable - 1, usable - 1]))
-        refused("bits: a break point >= usable_rows", "break point", bfill([bok], bps=[10, usable]))
-        refused("bits: the value past values_len", "outside values_len", bfill([bok, (1, 0, nv)]))
-        refused("bits: results_len too small", "results_len", bfill([bok, (1, 0, 0)], rlen=2 * nb - 1))
-        refused("bits: two units' cells overlap", "cells overlap", bfill([bok, (0, bcells - 1, 0)]))
-        refused("bits: the value inside cells this call writes", "operand range", bfill([(1, 0, 7)], vdev=d_cols[1], vlen=usable))
-        refused("bits: the results inside cells this call writes", "results overlap", bfill([(1, 0, 0)], rdev=d_cols[1] + 32 * 10, rlen=nb))
-        refused("bits: the results over the value", "operand range", bfill([bok], rdev=d_vals + 32 * (nv - 3), rlen=nb))
-        try:
-            PL.num_to_bits_layout(0, ctx.lib)
-        except H.H2HipError as e:
-            assert e.code == ERR_INVALID
-        else:
-            raise AssertionError("num_to_bits_layout(0) was accepted")
+        bb = b.over(Bits(nb), (nv - 1,), (0,), bcells, nb, "bits: ")
+        brefused, bfill, bok = bb.refused, bb.fill, bb.ok
+        bb.refuse_nulls()
+        brefused("num_bits 0", "num_bits outside", bfill([bok], nb=0))
+        brefused("num_bits 255", "num_bits outside", bfill([bok], nb=255))
+        bb.refuse_count()
+        bb.refuse_placement()
+        brefused("the value past values_len", "outside values_len", bfill([bok, (1, 0, nv)]))
+        bb.refuse_results_len()
+        bb.refuse_overlaps(break_copy=False)
+        brefused("the value inside cells this call writes", "operand range", bfill([(1, 0, 7)], vdev=b.d_cols[1], vlen=usable))
+        brefused("the results inside cells this call writes", "results overlap", bfill([(1, 0, 0)], rdev=b.d_cols[1] + 32 * 10, rlen=nb))
+        brefused("the results over the value", "operand range", bfill([bok], rdev=b.d_vals + 32 * (nv - 3), rlen=nb))
+        FH.layout_refused("num_to_bits_layout(0)", lambda: PL.num_to_bits_layout(0, ctx.lib))
         # count == 0 needs nothing
         ctx._chk(ctx.lib.h2hip_ec_select_fill_dev(ctx.handle, None, 0, 0, None, None, 9, 99, None, 0, None, 0, None, 0))
         ctx._chk(ctx.lib.h2hip_num_to_bits_fill_dev(ctx.handle, None, 0, 0, None, None, 0, None, 0, 0, None, 0))
@@ -716,11 +475,11 @@ def check_rejections(ctx):
         bps = [usable - 1, 30 + ncells - 1]
         fill(units, bps=bps, rlen=2 * pt)()
         one = [(2, 3, 0, pt, nv - 1)]
-        fill(one, op=SELECT, wb=0, rdev=d_res + 32 * 2 * pt, rlen=pt)()
+        fill(one, op=SELECT, w=0, rdev=b.d_res + 32 * 2 * pt, rlen=pt)()
         bit = [(2, 3 + 16 * (k + 1), nv - 1)]
-        bfill(bit, rdev=d_res + 32 * 3 * pt, rlen=nb)()
+        bfill(bit, rdev=b.d_res + 32 * 3 * pt, rlen=nb)()
         ctx.sync()
-        want = [np.tile(SENTINEL, (n_rows, 1)) for _ in range(3)]
+        want = [np.tile(SENTINEL, (b.n_rows, 1)) for _ in range(3)]
         want_res = np.tile(SENTINEL, (4 * pt, 1))
         uf, cf = unit_def(FromBits(sp, w), (table, pat))
         for col, row, *_ in units:
@@ -733,28 +492,14 @@ def check_rejections(ctx):
         ub, cb = unit_def(Bits(nb), ([vals[nv - 1]],))
         want[2][bit[0][1]:bit[0][1] + len(cb)] = fr(cb)
         want_res[3 * pt:3 * pt + nb] = fr(ub.results)
-        _compare(ctx, d_cols + [d_res], want + [want_res], "after the refusals")
-    finally:
-        for ptr in d_cols + [d_vals, d_res]:
-            ctx.free(ptr)
+        compare(ctx, b.d_cols + [b.d_res], want + [want_res], "after the refusals")
 
 
 def check_names_in_every_layer():
     """the two constants, the four symbols and the two structs in the header, the Rust sys crate and ctypes"""
-    import os
-    import re
-
-    hdr = open(os.path.join(K.ROOT, "include", "h2hip.h")).read()
-    rs = open(os.path.join(K.ROOT, "ffi", "rust", "h2hip-sys", "src", "lib.rs")).read()
-    for name, py in (("H2HIP_EC_SELECT", SELECT), ("H2HIP_EC_SELECT_FROM_BITS", FROM_BITS)):
-        assert int(re.search(r"#define %s (\d+)" % name, hdr).group(1)) == py == int(re.search(r"pub const %s: u32 = (\d+);" % name, rs).group(1))
-    lib = H.load_library()
-    for fn in ("h2hip_ec_select_layout", "h2hip_ec_select_fill_dev", "h2hip_num_to_bits_layout", "h2hip_num_to_bits_fill_dev"):
-        assert ("int %s(" % fn) in hdr and ("pub fn %s(" % fn) in rs and hasattr(lib, fn), fn
-    for name, struct, size in (("h2hip_ec_select", PL.EcSelectStruct, 32), ("h2hip_bits_unit", PL.BitsUnitStruct, 16)):
-        c_fields = re.findall(r"(\w+)[,;]", re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, re.S).group(1), flags=re.S))
-        rs_fields = re.findall(r"pub (\w+):", re.search(r"pub struct %s \{(.*?)\}" % name, rs, re.S).group(1))
-        assert c_fields == rs_fields == [f for f, _t in struct._fields_] and C.sizeof(struct) == size, (name, c_fields, rs_fields)
+    FH.check_names(constants=[("H2HIP_EC_SELECT", SELECT), ("H2HIP_EC_SELECT_FROM_BITS", FROM_BITS)],
+                   functions=("h2hip_ec_select_layout", "h2hip_ec_select_fill_dev", "h2hip_num_to_bits_layout", "h2hip_num_to_bits_fill_dev"),
+                   structs=[("h2hip_ec_select", PL.EcSelectStruct, 32), ("h2hip_bits_unit", PL.BitsUnitStruct, 16)])
 
 
 # ------------------------------------------------------------------------------------------------ G: inside a proof
@@ -796,66 +541,33 @@ def check_proof(ctx, kk, seed, nl, s=2):
     copy between s and the recomposed sum and nothing else."""
     lb = kk - 1
     sp = Spec(88, 3, lb, SECP_P)
-    k, nres, pt = sp.k, 9 * sp.k + 3, 2 * (sp.k + 1)
+    nres, pt = 9 * sp.k + 3, 2 * (sp.k + 1)
     m = multiples("secp256k1_p", 7)
     table_vals = [v for q in m[:4] for v in point(sp, *q)]
     a_vals = point(sp, *m[6])
-    n = 1 << kk
-    filler = max(0, n - 1100)                          # plain witness cells in front of the addition: the step crosses a column break at k = 11 as at k = 10
-    na = 12
-    while True:                                        # the number of gate columns the layout fills (an empty one would have a disjoint selector)
-        sh = P.Shape(kk, na, nl, 1, 1, lb)
-        kb = VR.BaseCircuitBuilder(False)
-        _msm_program(kb, sp, s, table_vals, a_vals, filler)
-        advice_k, fixed, copies, instances, bps = kb.synthesize(sh)
-        if len(bps) == na - 1:
-            break
-        na = len(bps) + 1
-    assert na >= 2 and len(bps) >= 1
-    pb = VR.BaseCircuitBuilder(True)
-    pb.break_points = bps
-    calls, fill_at = _msm_program(pb, sp, s, table_vals, a_vals, filler)
-    advice, _, _, _, _ = pb.synthesize(sh)
-    assert all(np.array_equal(a, b) for a, b in zip(advice, advice_k))
-    ub, uf, ua, uz = (c[2] for c in calls)
-    if s < 4:
-        t_int = m[s]
-        s_int = aff_add(SECP_P, m[6], t_int)
-        assert (ua.x3, ua.y3) == s_int and uz.results == [v % R for v in (point(sp, *s_int) if s & 1 else a_vals)]
-    total = sum(len(t.advice) for t in pb.threads)
-    first = {}
-    for i, c, r in place(0, 0, total, bps, na)[0]:
-        first.setdefault(i, (c, r))
-    nw = 1 + 5 * pt
-    assert first[ua.start][0] < first[ua.end - 1][0], "a column break falls inside the addition"
-    assert all(first[i] == (0, i) for i in list(range(nw)) + list(range(fill_at, fill_at + filler)))   # the witnesses: flat index i of the gate allocation
-    kzg, srs_params = srs(ctx, kk, seed)
-    gpk = PL.keygen(kzg, PL.BaseCircuitParams.new(kk, na, nl, 1, 1, lb), fixed, copies)
-    budget = rng_budget(sh)
-    # one device buffer: [gate columns][the bits][T][the addition's results][Z]
-    at_bits = na * n
-    at_t, at_s, at_z = at_bits + 2, at_bits + 2 + pt, at_bits + 2 + pt + nres
-    host = np.zeros((at_z + pt, 4), dtype=np.uint64)
-    host[:nw] = advice[0][:nw]
-    host[fill_at:fill_at + filler] = advice[0][fill_at:fill_at + filler]
-    d_gate = ctx.to_device(host)
-    d_lookup = ctx.to_device(np.zeros((nl * n, 4), dtype=np.uint64))
-    d_cols = [d_gate + 32 * n * c for c in range(na)]
-    d_lks = [d_lookup + 32 * n * c for c in range(nl)]
-    try:
-        PL.num_to_bits_fill(ctx, d_cols, sh.usable_rows, bps, d_gate, len(host), d_gate + 32 * at_bits, 2, 2, [first[calls[0][0]] + (0,)])
-        PL.ec_select_fill(ctx, d_cols, sh.usable_rows, bps, sp.params(), FROM_BITS, 2, d_gate, len(host), d_gate + 32 * at_t, pt,
-                          [first[calls[1][0]] + (1, 0, at_bits)])
-        PL.ec_fill_with_ranges(ctx, d_cols, sh.usable_rows, bps, d_lks, sp.params(), ADD, d_gate, len(host), d_gate + 32 * at_s, nres,
+    filler = max(0, (1 << kk) - 1100)                  # plain witness cells in front of the addition: the step crosses a column break at k = 11 as at k = 10
+    with FH.ProofBench(ctx, kk, nl, lb, seed, lambda builder: _msm_program(builder, sp, s, table_vals, a_vals, filler)) as pb:
+        (calls, fill_at), first = pb.calls, pb.first
+        ub, uf, ua, uz = (c[2] for c in calls)
+        if s < 4:
+            t_int = m[s]
+            s_int = aff_add(SECP_P, m[6], t_int)
+            assert (ua.x3, ua.y3) == s_int and uz.results == [v % R for v in (point(sp, *s_int) if s & 1 else a_vals)]
+        nw = 1 + 5 * pt
+        assert first[ua.start][0] < first[ua.end - 1][0], "a column break falls inside the addition"
+        # one device buffer: [gate columns][the bits][T][the addition's results][Z]
+        at_bits = pb.buffers(2 + pt + nres + pt, [range(nw), range(fill_at, fill_at + filler)])
+        at_t, at_s, at_z = at_bits + 2, at_bits + 2 + pt, at_bits + 2 + pt + nres
+        d_cols, d_gate, usable, bps, nhost = pb.d_cols, pb.d_gate, pb.sh.usable_rows, pb.bps, len(pb.host)
+        PL.num_to_bits_fill(ctx, d_cols, usable, bps, d_gate, nhost, d_gate + 32 * at_bits, 2, 2, [first[calls[0][0]] + (0,)])
+        PL.ec_select_fill(ctx, d_cols, usable, bps, sp.params(), FROM_BITS, 2, d_gate, nhost, d_gate + 32 * at_t, pt, [first[calls[1][0]] + (1, 0, at_bits)])
+        PL.ec_fill_with_ranges(ctx, d_cols, usable, bps, pb.d_lks, sp.params(), ADD, d_gate, nhost, d_gate + 32 * at_s, nres,
                                [first[calls[2][0]] + (1 + 4 * pt, at_t)], [calls[2][1]])
-        PL.ec_select_fill(ctx, d_cols, sh.usable_rows, bps, sp.params(), SELECT, 0, d_gate, len(host), d_gate + 32 * at_z, pt,
-                          [first[calls[3][0]] + (at_s, 1 + 4 * pt, at_bits)])
+        PL.ec_select_fill(ctx, d_cols, usable, bps, sp.params(), SELECT, 0, d_gate, nhost, d_gate + 32 * at_z, pt, [first[calls[3][0]] + (at_s, 1 + 4 * pt, at_bits)])
         ctx.sync()
-        got_cols = np.concatenate([ctx.download(d_gate, (na, n, 4)), ctx.download(d_lookup, (nl, n, 4))])
-        for c in range(na + nl):
-            assert np.array_equal(got_cols[c], advice[c]), "advice column %d differs from the Python-computed advice" % c
+        pb.check_columns()
         if s >= 4:
-            total_f, fails = PL.check_witness(gpk, d_cols + d_lks, instances, max_failures=4096, advice_on_device=True)
+            total_f, fails = pb.check_witness(max_failures=4096)
             perm = lambda cell: (1 + cell[0], cell[1])                      # one constants column, then the gate advice
             s_cell, sum_cell = perm(first[0]), perm(first[ub.start + ub.sum_offset])
             assert total_f == len(fails) and fails, fails[:8]
@@ -866,19 +578,4 @@ def check_proof(ctx, kk, seed, nl, s=2):
                 assert f.kind == "copy" and sum_cell in ends and all(e == sum_cell or e[1] == 0 for e in ends), fails[:8]
             assert any(s_cell in [(f.column, f.row), (f.peer_column, f.peer_row)] for f in fails), fails[:8]
             return
-        got = PL.create_proof(gpk, d_cols + d_lks, instances, PreDrawnRng(budget, 2000 + seed), advice_on_device=True)
-        asm = P.PermutationAssembly(sh)
-        for l, r in copies:
-            asm.copy(l, r)
-        opk = P.keygen(srs_params, sh, fixed, asm, 2)
-        oracle = P.create_proof(srs_params, opk, advice, [_ints(v) for v in instances], PreDrawnRng(budget, 2000 + seed), 2)
-        assert got == oracle, "the proof differs from the oracle prover's over the host-synthesized trace"
-        assert PL.verify_proof(gpk, instances, got), "h2hip_plonk_verify_proof rejects the proof"
-        assert P.verify_proof(srs_params, vk_from_gpu(sh, gpk), [_ints(v) for v in instances], got), "the test verifier rejects the proof"
-        total_f, fails = PL.check_witness(gpk, d_cols + d_lks, instances, advice_on_device=True)
-        assert total_f == 0, fails
-    finally:
-        ctx.free(d_gate)
-        ctx.free(d_lookup)
-        gpk.free()
-        kzg.free()
+        pb.check_proof(host=False, oracle=True)

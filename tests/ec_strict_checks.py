@@ -14,34 +14,23 @@ the lookup queue.  tests/ec_fill_checks.py supplies load_private, check_carry_mo
   C  column breaks as assign_witnesses makes them, through ec_fill_strict_with_ranges;  D  chaining;  E  the refusals;
   F  a BaseConfig proof of the MSM fragment S = A2 - A0 (strict), T = S + P (strict), D = 2 T, and the same circuit with P.x = S.x.
 """
-import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 
-import halo2_lib_amd as H
 from halo2_lib_amd import plonk as PL
 from halo2_lib_amd import virtual_region as VR
-from oracle import plonk as P
 from tests import ec_fill_checks as K
-from tests import fp_mul_checks as F
-from tests.dyn_lookup_util import rng_budget, srs, vk_from_gpu
+from tests import fused_fill_harness as FH
 from tests.ec_fill_checks import CURVES, PARAMS, Crt, Unit, aff_add, aff_double, multiples, operand, point
-from tests.fp_mul_checks import MODULI, SECP_P, Spec, _operand, _thread, own_mask
-from tests.poseidon_trace_checks import _compare, _ints, place
-from tests.range_fill_checks import lookup_positions
-from tests.rlc_checks import SENTINEL
-from tests.util import PreDrawnRng, R, fr
+from tests.fp_mul_checks import MODULI, SECP_P, Spec
+from tests.fused_fill_harness import SENTINEL, Cmp, EcOp, compare, own_mask, place
+from tests.util import R, fr
 
-_vp = C.c_void_p
-ERR_INVALID = -1
 ADD, DOUBLE, SUB = PL.EC_ADD_UNEQUAL, PL.EC_DOUBLE, PL.EC_SUB_UNEQUAL
 RA, RB, EQ = PL.FP_CMP_REDUCE_A, PL.FP_CMP_REDUCE_B, PL.FP_CMP_EQUAL
 MASKS = list(range(1, 8))
 SOLVE_BLOCK, PLACE_BLOCK = 64, 256   # ec_fill.hip and fp_cmp.hip: lanes per workgroup of the per-unit and of the per-(unit, segment) kernel
-ROOT = F.ROOT
 NO_CELL = 0xFFFFFFFF
 
 
@@ -52,10 +41,6 @@ def cmp_segments(k, mask):
 
 def cmp_results(k, mask):
     return (k + 1) * (bool(mask & RA) + bool(mask & RB)) + (1 if mask & EQ else 0)
-
-
-def _queue_len(ctx, chip):
-    return len(chip.lookup_manager.cells_to_lookup.get(ctx.tag(), []))
 
 
 # ------------------------------------------------------------------------------------------------ the definition: ec_sub_unequal
@@ -82,7 +67,7 @@ def ec_sub(ctx, chip, sp, pt, qt):
     """ec_sub_unequal(P, Q, is_strict = false) of points given as 2 (k + 1) cells -> a Unit as ec_fill_checks.ec_op's"""
     k = sp.k
     u = Unit()
-    u.start, u.queue = len(ctx.advice), _queue_len(ctx, chip)
+    u.start, u.queue = len(ctx.advice), FH.queue_len(ctx, chip)
     u.gaps, u.results, u.quots, u.rb, u.out_offsets = [], [None] * (9 * k + 3), [], [], []
     px, py = operand(sp, pt[:k + 1]), operand(sp, pt[k + 1:])
     qx, qy = operand(sp, qt[:k + 1]), operand(sp, qt[k + 1:])
@@ -99,7 +84,7 @@ def ec_sub(ctx, chip, sp, pt, qt):
     u.out_offsets += u.lam_offsets
     u.out_cells = x3.cells() + y3.cells()
     u.end = len(ctx.advice)
-    u.lookups = _queue_len(ctx, chip) - u.queue
+    u.lookups = FH.queue_len(ctx, chip) - u.queue
     return u
 
 
@@ -138,7 +123,7 @@ def cmp_op(ctx, chip, sp, mask, a, b, pin=False):
     adds its assert_is_const(x_is_equal, 0), a constant equality and no cell.  -> a Unit"""
     k = sp.k
     u = Unit()
-    u.start, u.queue = len(ctx.advice), _queue_len(ctx, chip)
+    u.start, u.queue = len(ctx.advice), FH.queue_len(ctx, chip)
     u.gaps, u.results, u.out_offsets = [], [None] * cmp_results(k, mask), [NO_CELL] * 3
     res = 0
     for e, x in enumerate((a, b)):
@@ -156,7 +141,7 @@ def cmp_op(ctx, chip, sp, mask, a, b, pin=False):
         if pin and not ctx.witness_gen_only:
             ctx.copy_manager.constant_equalities.append((0, eq.cell))       # gate.assert_is_const(x_is_equal, 0)
     u.end = len(ctx.advice)
-    u.lookups = _queue_len(ctx, chip) - u.queue
+    u.lookups = FH.queue_len(ctx, chip) - u.queue
     return u
 
 
@@ -166,56 +151,6 @@ def strict_op(ctx, chip, sp, op, mask, pt, qt):
     k = sp.k
     c = cmp_op(ctx, chip, sp, mask, pt[:k + 1], qt[:k + 1], pin=True)
     return c, curve_op(ctx, chip, sp, op, pt, qt)
-
-
-class Sub:
-    """what check_fill needs to know of a kind of unit: SUB_UNEQUAL"""
-    name = "sub_unequal"
-
-    def __init__(self, sp, op=SUB):
-        self.sp, self.op, self.nres, self.oplen = sp, op, 9 * sp.k + 3, 2 * (sp.k + 1)
-
-    def unit_def(self, a_vals, b_vals):
-        ctx, chip, _ = _thread(self.sp.lb)
-        u = curve_op(ctx, chip, self.sp, self.op, _operand(a_vals, 0), _operand(b_vals, 1))
-        return u, list(ctx.advice), [c.value for c in chip.lookup_manager.cells_to_lookup.get(ctx.tag(), [])]
-
-    def layout(self, lib=None):
-        return PL.ec_layout(self.sp.params(), self.op, lib)
-
-    def fill(self, ctx, cols, usable, bps, d_vals, nvals, d_res, nres, units):
-        PL.ec_fill(ctx, cols, usable, bps, self.sp.params(), self.op, d_vals, nvals, d_res, nres, units)
-
-    def fill_ranges(self, ctx, cols, usable, bps, lks, d_vals, nvals, d_res, nres, units, slots_):
-        PL.ec_fill_with_ranges(ctx, cols, usable, bps, lks, self.sp.params(), self.op, d_vals, nvals, d_res, nres, units, slots_)
-
-    def range_tables(self, bps, ncols, units, slots_):
-        return PL.ec_range_tables(bps, ncols, self.sp.params(), self.op, units, slots_)
-
-
-class Cmp:
-    """... and the comparison unit of one mask"""
-
-    def __init__(self, sp, mask):
-        self.sp, self.mask, self.nres, self.oplen = sp, mask, cmp_results(sp.k, mask), sp.k + 1
-        self.name = "cmp mask %d" % mask
-
-    def unit_def(self, a_vals, b_vals):
-        ctx, chip, _ = _thread(self.sp.lb)
-        u = cmp_op(ctx, chip, self.sp, self.mask, _operand(a_vals, 0), _operand(b_vals, 1))
-        return u, list(ctx.advice), [c.value for c in chip.lookup_manager.cells_to_lookup.get(ctx.tag(), [])]
-
-    def layout(self, lib=None):
-        return PL.fp_cmp_layout(self.sp.params(), self.mask, lib)
-
-    def fill(self, ctx, cols, usable, bps, d_vals, nvals, d_res, nres, units):
-        PL.fp_cmp_fill(ctx, cols, usable, bps, self.sp.params(), self.mask, d_vals, nvals, d_res, nres, units)
-
-    def fill_ranges(self, ctx, cols, usable, bps, lks, d_vals, nvals, d_res, nres, units, slots_):
-        PL.fp_cmp_fill_with_ranges(ctx, cols, usable, bps, lks, self.sp.params(), self.mask, d_vals, nvals, d_res, nres, units, slots_)
-
-    def range_tables(self, bps, ncols, units, slots_):
-        return PL.fp_cmp_range_tables(bps, ncols, self.sp.params(), self.mask, units, slots_)
 
 
 # ------------------------------------------------------------------------------------------------ the pools
@@ -294,8 +229,8 @@ def check_definition():
             sp = Spec(n, k, lb, p)
             m = multiples(curve, 7)
             for a, b in ((m[0], m[1]), (m[2], m[6]), (m[5], m[3])):
-                ctx, chip, _ = _thread(lb)
-                u = ec_sub(ctx, chip, sp, _operand(point(sp, *a), 0), _operand(point(sp, *b), 1))
+                ctx, chip, _ = FH.thread(lb)
+                u = ec_sub(ctx, chip, sp, FH.operand(point(sp, *a), 0), FH.operand(point(sp, *b), 1))
                 cells = list(ctx.advice)
                 assert (u.x3, u.y3) == aff_add(p, a, (b[0], -b[1] % p)), (curve, n)
                 assert u.lam == -(a[1] + b[1]) * pow(b[0] - a[0], -1, p) % p and u.quots[0][1] == 0
@@ -311,8 +246,8 @@ def check_definition():
             sp = Spec(n, k, lb, p)
             for a_vals, b_vals in cmp_proper_pool(sp):
                 A, B = _limbs_int(sp, a_vals[:k]), _limbs_int(sp, b_vals[:k])
-                ctx, chip, _ = _thread(lb)
-                u = cmp_op(ctx, chip, sp, 7, _operand(a_vals, 0), _operand(b_vals, 1))
+                ctx, chip, _ = FH.thread(lb)
+                u = cmp_op(ctx, chip, sp, 7, FH.operand(a_vals, 0), FH.operand(b_vals, 1))
                 cells = list(ctx.advice)
                 assert cells[u.out_offsets[0]] == int(A < p) and cells[u.out_offsets[1]] == int(B < p) and cells[u.out_offsets[2]] == int(A == B), (modulus, n, A, B)
                 assert u.results[k] == int(A < p) and u.results[2 * k + 1] == int(B < p) and u.results[2 * k + 2] == int(A == B)
@@ -323,7 +258,7 @@ def check_definition():
                 assert int(own_mask(u).sum()) == 2 * (19 * k - 4) + 16 * k - 4 and len(u.gaps) == 2 * k
     sp = Spec(88, 3, 18, SECP_P)
     for mask in MASKS:
-        u, cells, lookups = Cmp(sp, mask).unit_def(sp.crt(5), sp.crt(7))
+        u, cells, lookups = Cmp(sp, mask).unit_def((sp.crt(5), sp.crt(7)))
         enforced = bool(mask & RA) + bool(mask & RB)
         assert int(own_mask(u).sum()) == enforced * 53 + (44 if mask & EQ else 0) and len(u.gaps) == 3 * enforced
         assert all(g[1] == 16 and g[2] == 108 for g in u.gaps) and len(lookups) == 6 * 3 * enforced     # pad = 90: six limbs of 18 bits
@@ -335,13 +270,13 @@ def check_pool_signs():
     for n, k, lb in PARAMS[:1] + PARAMS[-1:]:
         for modulus, p in MODULI.items():
             sp = Spec(n, k, lb, p)
-            quots = [Sub(sp).unit_def(a, b)[0].quots for a, b in sub_pool(sp, modulus)]
+            quots = [EcOp(sp, SUB).unit_def((a, b))[0].quots for a, b in sub_pool(sp, modulus)]
             for r in range(3):
                 assert any(q[r][0] < 0 for q in quots) and any(q[r][0] > 0 for q in quots), (modulus, r)
             assert any(q[0][1] == 0 for q in quots) and any(q[0][1] != 0 for q in quots), modulus
             seen = set()
             for a_vals, b_vals in cmp_pool(sp):
-                u, cells, _l = Cmp(sp, 7).unit_def(a_vals, b_vals)
+                u, cells, _l = Cmp(sp, 7).unit_def((a_vals, b_vals))
                 for e in range(2):
                     for i in range(k):
                         seen.add(("borrow", i, cells[u.gaps[e * k + i][0] + u.gaps[e * k + i][1] + 6]))
@@ -361,30 +296,27 @@ def check_layout_and_ranges():
     for n, k, lb in PARAMS + [K.CARRY_WIDTHS]:
         for modulus, p in MODULI.items():
             sp = Spec(n, k, lb, p)
-            u, cells, lookups = Sub(sp).unit_def(point(sp, 3, 5), point(sp, p - 2, 11))
+            u, cells, lookups = EcOp(sp, SUB).unit_def((point(sp, 3, 5), point(sp, p - 2, 11)))
             lay = PL.ec_layout(sp.params(), SUB)
             assert lay == PL.ec_layout(sp.params(), ADD), (n, k, lb, modulus)
             assert (lay.num_cells, lay.num_own_cells, lay.num_lookup_cells) == (len(cells), int(own_mask(u).sum()), len(lookups)), (n, k, lb)
             assert lay.ranges == u.gaps and lay.out_cell_offsets == u.out_offsets, (n, k, lb, lay, u.gaps, u.out_offsets)
             for mask in MASKS:
-                u, cells, lookups = Cmp(sp, mask).unit_def(sp.crt(3), sp.crt(p - 2))
+                u, cells, lookups = Cmp(sp, mask).unit_def((sp.crt(3), sp.crt(p - 2)))
                 lay = PL.fp_cmp_layout(sp.params(), mask)
                 assert (lay.num_cells, lay.num_own_cells, lay.num_lookup_cells, lay.results_per_unit) == (
                     len(cells), int(own_mask(u).sum()), len(lookups), cmp_results(k, mask)), (n, k, lb, mask)
                 assert lay.ranges == u.gaps and lay.out_cell_offsets == u.out_offsets, (n, k, lb, mask, lay, u.gaps, u.out_offsets)
                 assert len(cells) - len(u.gaps) * (u.gaps[0][1] if u.gaps else 0) == (bool(mask & RA) + bool(mask & RB)) * (19 * k - 4) + (16 * k - 4 if mask & EQ else 0)
     sp = Spec(88, 3, 8, SECP_P)
-    for kind in [Sub(sp)] + [Cmp(sp, mask) for mask in MASKS]:
-        thread, chip, _ = _thread(sp.lb)
+    for kind in [EcOp(sp, SUB)] + [Cmp(sp, mask) for mask in MASKS]:
+        thread, chip, _ = FH.thread(sp.lb)
         bps, ncols, units, slots_, defs = [700, 650], 3, [], [], []
         pos = (0, 5)
         thread.advice += [0] * 5
         for j in range(4):
-            a, b = (point(sp, 3 + j, 5), point(sp, 9, 11 + j)) if isinstance(kind, Sub) else (sp.crt(SECP_P - 2 + j), sp.crt(SECP_P))
-            if isinstance(kind, Sub):
-                u = ec_sub(thread, chip, sp, _operand(a, 2 * j), _operand(b, 2 * j + 1))
-            else:
-                u = cmp_op(thread, chip, sp, kind.mask, _operand(a, 2 * j), _operand(b, 2 * j + 1))
+            a, b = (point(sp, 3 + j, 5), point(sp, 9, 11 + j)) if isinstance(kind, EcOp) else (sp.crt(SECP_P - 2 + j), sp.crt(SECP_P))
+            u = kind.define(thread, chip, (a, b), j)
             units.append(pos + (0, 0))
             slots_.append(u.queue + 3)
             defs.append(u)
@@ -404,86 +336,24 @@ def check_layout_and_ranges():
             assert all(a[3] < b[3] and (a[0], a[1]) < (b[0], b[1]) for a, b in zip(got, got[1:])), "slots and rows ascend inside a width"
 
 
-def check_fill(ctx, kind, pool, count, nl=1):
-    """`count` units per call over three gate columns (no breaks), until every operand pair was a unit; each call once bare (own cells equal
-    the definition's, the gaps and every other cell keep the sentinel, results_dev equals the named cells) and once through the kind's
-    *_with_ranges call over nl lookup columns (the whole run and the lookup columns equal the definition's, the queue starting at a position
-    that is no multiple of nl)"""
-    sp = kind.sp
-    lay = kind.layout(ctx.lib)
-    vals = [v for a, b in pool for v in a + b]
-    nres, ol = kind.nres, kind.oplen
-    cache = {}
-    done = 0
-    while done < len(pool):
-        units, defs, slots_, rows, slot = [], [], [], [1, 3, 0], nl + 1 if nl > 1 else 1
-        for j in range(count):
-            at = (done + j) % len(pool)
-            if at not in cache:
-                cache[at] = kind.unit_def(*pool[at])
-            u, cells, lookups = cache[at]
-            assert len(cells) == lay.num_cells
-            col = j % 3
-            units.append((col, rows[col], 2 * ol * at, 2 * ol * at + ol))
-            defs.append((u, cells, lookups))
-            slots_.append(slot)
-            rows[col] += len(cells) + (j % 2)
-            slot += len(lookups) + (j % 2)
-        done += count
-        rows_n = max(max(rows), -(-slot // nl)) + 9
-        where = lookup_positions(slot, nl)
-        d_vals = ctx.to_device(fr(vals))
-        try:
-            for with_ranges in (False, True):
-                want = [np.tile(SENTINEL, (rows_n, 1)) for _ in range(3)]
-                want_lk = [np.tile(SENTINEL, (rows_n, 1)) for _ in range(nl)]
-                want_res = np.tile(SENTINEL, (count * nres + 2, 1))
-                d_cols = [ctx.to_device(c) for c in want]
-                d_lk = [ctx.to_device(c) for c in want_lk]
-                d_res = ctx.to_device(want_res)
-                for j, ((col, row, _a, _b), (u, cells, lookups), s) in enumerate(zip(units, defs, slots_)):
-                    keep = np.ones(len(cells), dtype=bool) if with_ranges else own_mask(u)
-                    want[col][row:row + len(cells)][keep] = fr(cells)[keep]
-                    want_res[j * nres:(j + 1) * nres] = fr(u.results)
-                    if with_ranges:
-                        for i, v in enumerate(fr(lookups) if lookups else []):
-                            c, r = where[s + i]
-                            want_lk[c][r] = v
-                try:
-                    if with_ranges:
-                        kind.fill_ranges(ctx, d_cols, rows_n - 2, None, d_lk, d_vals, len(vals), d_res, count * nres, units, slots_)
-                    else:
-                        kind.fill(ctx, d_cols, rows_n - 2, None, d_vals, len(vals), d_res, count * nres, units)
-                    ctx.sync()
-                    what = "(n, k, lb) = (%d, %d, %d), %s, count = %d, nl = %d, ranges = %s" % (sp.n, sp.k, sp.lb, kind.name, count, nl, with_ranges)
-                    _compare(ctx, d_cols, want, what + " (gate columns)")
-                    _compare(ctx, d_lk, want_lk, what + " (lookup columns)")
-                    _compare(ctx, [d_res], [want_res], what + " (results)")
-                finally:
-                    for ptr in d_cols + d_lk + [d_res]:
-                        ctx.free(ptr)
-        finally:
-            ctx.free(d_vals)
-
-
 def check_sub_fill(ctx, n, k, lb, modulus, count, nl=1, pool=None):
     sp = Spec(n, k, lb, MODULI[modulus])
-    check_fill(ctx, Sub(sp), sub_pool(sp, modulus) if pool is None else pool, count, nl)
+    FH.check_fill(ctx, EcOp(sp, SUB), sub_pool(sp, modulus) if pool is None else pool, count, nl)
 
 
 def check_cmp_fill(ctx, n, k, lb, modulus, mask, count, nl=1, pool=None):
     sp = Spec(n, k, lb, MODULI[modulus])
-    check_fill(ctx, Cmp(sp, mask), cmp_pool(sp) if pool is None else pool, count, nl)
+    FH.check_fill(ctx, Cmp(sp, mask), cmp_pool(sp) if pool is None else pool, count, nl)
 
 
 # ------------------------------------------------------------------------------------------------ the strict operation: two fused calls
 def _strict_thread(sp, op, mask, pairs, filler=0):
     """one thread: `filler` plain cells, then strict operations back to back, each over witnesses of its own
     -> (thread, chip, [(comparison Unit, operation Unit)])"""
-    thread, chip, _ = _thread(sp.lb)
+    thread, chip, _ = FH.thread(sp.lb)
     thread.advice += list(range(100, 100 + filler))
     thread.selector += [False] * filler
-    defs = [strict_op(thread, chip, sp, op, mask, _operand(a, 2 * j), _operand(b, 2 * j + 1)) for j, (a, b) in enumerate(pairs)]
+    defs = [strict_op(thread, chip, sp, op, mask, FH.operand(a, 2 * j), FH.operand(b, 2 * j + 1)) for j, (a, b) in enumerate(pairs)]
     return thread, chip, defs
 
 
@@ -521,10 +391,10 @@ def _run_strict(ctx, sp, op, mask, thread, chip, defs, vals, bps, ncols, usable,
         ctx.sync()
         assert eq_cells == [first[c.start + c.out_offsets[2]] for c, _o in defs], what
         assert op_cells == [first[o.start] for _c, o in defs], what
-        _compare(ctx, d_cols, want, what)
+        compare(ctx, d_cols, want, what)
         want_res = np.concatenate([fr(o.results) for _c, o in defs])
         want_cres = np.concatenate([fr(c.results) for c, _o in defs])
-        _compare(ctx, [d_res, d_cres], [want_res, want_cres], what + " (results)")
+        compare(ctx, [d_res, d_cres], [want_res, want_cres], what + " (results)")
     finally:
         for ptr in d_cols + [d_vals, d_res, d_cres]:
             ctx.free(ptr)
@@ -537,7 +407,7 @@ def check_strict(ctx, n, k, lb, op, mask, count=5):
     pairs = [pool[(3 * j) % len(pool)] for j in range(count)]
     thread, chip, defs = _strict_thread(sp, op, mask, pairs, 7)
     vals = [v for a, b in pairs for v in a + b]
-    usable = max(len(thread.advice), _queue_len(thread, chip)) + 5
+    usable = max(len(thread.advice), FH.queue_len(thread, chip)) + 5
     _run_strict(ctx, sp, op, mask, thread, chip, defs, vals, None, 1, usable, 7, "strict op %d mask %d (%d, %d, %d)" % (op, mask, n, k, lb))
 
 
@@ -562,7 +432,7 @@ def _break_cells(sp):
     }, c.end + (o.end - o.start)
 
 
-def check_breaks(ctx, case, ncols):
+def check_strict_breaks(ctx, case, ncols):
     """one thread (plain cells, then strict SUB_UNEQUAL units at (88, 3, 8), mask 7, back to back) laid into ncols columns by
     virtual_region.assign_witnesses and by ec_fill_strict_with_ranges, from the same break points.  Every break falls on the cell the case names."""
     sp = Spec(88, 3, 8, SECP_P)
@@ -582,7 +452,7 @@ def check_breaks(ctx, case, ncols):
     for (unit, c), b, col in zip(targets, bps, range(ncols)):   # the break cell is the cell the case names
         i = filler + unit * ncells + c
         assert (i, col, b) in at and (i, col + 1, 0) in at, (case, unit, c)
-    assert usable >= _queue_len(thread, chip)
+    assert usable >= FH.queue_len(thread, chip)
     if case == "and":
         c0 = defs[0][0]
         assert thread.advice[c0.start + cell] in (0, 1) and thread.advice[c0.start + cell - 1] == 0 and thread.selector[c0.start + cell - 1]
@@ -602,7 +472,7 @@ def check_chained(ctx, n, k, lb, count=3):
     ab = [(m[3 * j + 4], m[j]) for j in range(count)]                       # A - B = (2 j + 4) G
     firsts = [(point(sp, *a), point(sp, *b)) for a, b in ab]
     vals = [v for a, b in firsts for v in a + b]
-    defs1 = [Sub(sp).unit_def(a, b) for a, b in firsts]
+    defs1 = [EcOp(sp, SUB).unit_def((a, b)) for a, b in firsts]
     ncells = len(defs1[0][1])
     units1 = [(0, 2 + j * (ncells + 1), 2 * pt * j, 2 * pt * j + pt) for j in range(count)]
     ops2 = [(defs1[j][0].results[:pt], defs1[(j + 1) % count][0].results[:pt]) for j in range(count)]
@@ -615,7 +485,7 @@ def check_chained(ctx, n, k, lb, count=3):
     total = len(thread.advice)
     units2 = [(1, 1 + c.start, nres * j, nres * ((j + 1) % count)) for j, (c, _o) in enumerate(defs2)]
     slots_ = [3 + c.queue for c, _o in defs2]
-    queue = _queue_len(thread, chip)
+    queue = FH.queue_len(thread, chip)
     rows_n = max(2 + count * (ncells + 1), total + 1, queue + 3) + 9
     sent, sent_res, sent_cres = np.tile(SENTINEL, (rows_n, 1)), np.tile(SENTINEL, (count * nres + 2, 1)), np.tile(SENTINEL, (count * cres + 1, 1))
     d_cols = [ctx.to_device(sent) for _ in range(2)]
@@ -640,7 +510,7 @@ def check_chained(ctx, n, k, lb, count=3):
         for j, (c, o) in enumerate(defs2):
             want_res[1][j * nres:(j + 1) * nres] = fr(o.results)
             want_cres[j * cres:(j + 1) * cres] = fr(c.results)
-        _compare(ctx, d_cols + [d_lk] + d_res + [d_cres], want + [want_lk] + want_res + [want_cres], "chained calls, (n, k, lb) = (%d, %d, %d)" % (n, k, lb))
+        compare(ctx, d_cols + [d_lk] + d_res + [d_cres], want + [want_lk] + want_res + [want_cres], "chained calls, (n, k, lb) = (%d, %d, %d)" % (n, k, lb))
     finally:
         for ptr in d_cols + [d_lk, d_vals, d_cres] + d_res:
             ctx.free(ptr)
@@ -653,85 +523,28 @@ def check_rejections(ctx):
     pad + lb > 253 (limb_bits <= 125 and lookup_bits <= 63 give pad + lb <= n + 2 lb - 1 <= 250)."""
     sp = Spec(88, 3, 8, SECP_P)
     k, mask = sp.k, 7
-    nres, ol = cmp_results(k, mask), k + 1
-    lay = PL.fp_cmp_layout(sp.params(), mask, ctx.lib)
+    kind = Cmp(sp, mask)
+    nres, ol = kind.nres, k + 1
+    lay = kind.layout(ctx.lib)
     ncells = lay.num_cells
-    n_rows, usable = 2 * ncells + 60, 2 * ncells + 50
     ints = [SECP_P - 1, SECP_P, 5, SECP_P - 1]
     vals = [v for x in ints for v in sp.crt(x)]
-    nv = len(vals)
-    sent, sent_res = np.tile(SENTINEL, (n_rows, 1)), np.tile(SENTINEL, (4 * nres, 1))
-    d_cols = [ctx.to_device(sent) for _ in range(3)]
-    d_vals = ctx.to_device(fr(vals))
-    d_res = ctx.to_device(sent_res)
-    good = sp.params()
-    ok = (0, 0, 0, ol)
-    try:
-        def refused(what, reason, call):
-            try:
-                call()
-            except H.H2HipError as e:
-                assert e.code == ERR_INVALID, (what, e.code)
-                msg = ctx.lib.h2hip_last_error().decode()
-                assert reason in msg, (what, msg)
-            else:
-                raise AssertionError("%s was accepted" % what)
-            ctx.sync()
-            for ptr in d_cols:
-                assert np.array_equal(ctx.download(ptr, (n_rows, 4)), sent), "%s: a cell was written" % what
-            assert np.array_equal(ctx.download(d_res, (4 * nres, 4)), sent_res), "%s: a result was written" % what
-
-        def fill(units, cols=None, usable_rows=usable, bps=None, params=good, op=mask, vdev=None, vlen=nv, rdev=None, rlen=4 * nres):
-            return lambda: PL.fp_cmp_fill(ctx, d_cols if cols is None else cols, usable_rows, bps, params, op, d_vals if vdev is None else vdev, vlen,
-                                          d_res if rdev is None else rdev, rlen, units)
-
-        par = lambda n=88, k_=3, lb=8, p=SECP_P, flags=0: PL.fp_params(n, k_, lb, p, flags)
-        cols = (_vp * 3)(*[_vp(int(ptr)) for ptr in d_cols])
-        tab = C.cast(PL.fp_mul_table([ok]), _vp)
-        pp = C.cast(C.pointer(good), _vp)
-        raw = lambda c, p_, v, t, cnt=1, op=mask: (lambda: ctx._chk(ctx.lib.h2hip_fp_cmp_fill_dev(ctx.handle, c, 3, usable, None, p_, op, v, nv, _vp(int(d_res)), 4 * nres, t, cnt)))
-        refused("columns NULL", "NULL argument", raw(None, pp, _vp(int(d_vals)), tab))
-        refused("params NULL", "NULL argument", raw(cols, None, _vp(int(d_vals)), tab))
-        refused("values NULL", "NULL argument", raw(cols, pp, None, tab))
-        refused("units NULL", "NULL argument", raw(cols, pp, _vp(int(d_vals)), None))
-        refused("op 0", "mask", fill([ok], op=0))
-        refused("op 8", "mask", fill([ok], op=8))
-        refused("flags != 0", "flags", fill([ok], params=par(flags=1)))
-        refused("limb_bits 63", "limb_bits outside", fill([ok], params=par(n=63, k_=4, p=(1 << 252) - 1)))
-        refused("limb_bits 128", "limb_bits outside", fill([ok], params=par(n=128, k_=2)))
-        refused("num_limbs 1", "num_limbs outside", fill([ok], params=par(k_=1)))
-        refused("num_limbs 5", "num_limbs outside", fill([ok], params=par(n=64, k_=5)))
-        refused("n k > 320", "> 320", fill([ok], params=par(n=107, k_=3, p=(1 << 320) - 1)))
-        refused("p == 0", "zero", fill([ok], params=par(p=0)))
-        refused("p < 2^(n (k - 1))", "exactly num_limbs", fill([ok], params=par(p=(1 << 176) - 1)))
-        refused("p >= 2^(n k)", "exactly num_limbs", fill([ok], params=par(p=1 << 264)))
-        refused("quot_max_bits >= n k", "quot_max_bits", fill([ok], params=par(p=(1 << 252) - 1)))
-        refused("a limb of p equal to 1", "equals 1", fill([ok], params=par(p=(1 << 255) + (1 << 88) + 12345)))
-        refused("lookup_bits 0", "lookup_bits", fill([ok], params=par(lb=0)))
-        refused("lookup_bits 64", "lookup_bits", fill([ok], params=par(lb=64)))
-        refused("column index out of range", "column index", fill([ok, (3, 0, ol, 2 * ol)]))
-        refused("a NULL column", "column index", fill([ok, (1, 0, ol, 2 * ol)], cols=[d_cols[0], 0, d_cols[2]]))
-        refused("a run that leaves the usable rows", "usable rows", fill([ok, (1, usable - ncells + 1, ol, 2 * ol)]))
-        refused("a run that leaves the last column", "last column", fill([ok, (2, usable - ncells + 1, ol, 2 * ol)], bps=[usable - 1, usable - 1]))
-        refused("a break point >= usable_rows", "break point", fill([ok], bps=[10, usable]))
-        refused("a past values_len", "outside values_len", fill([ok, (1, 0, nv - ol + 1, 0)]))
+    with FH.RefusalBench(ctx, kind, vals, (0, ol), (ol, 2 * ol), ncells, cmp_segments(3, mask), 4 * nres) as b:
+        usable, nv, fill, refused = b.usable, b.nv, b.fill, b.refused
+        b.refuse_nulls()
+        refused("op 0", "mask", fill([b.ok], op=0))
+        refused("op 8", "mask", fill([b.ok], op=8))
+        b.refuse_params()
+        b.refuse_placement()
+        refused("a past values_len", "outside values_len", fill([b.ok, (1, 0, nv - ol + 1, 0)]))
         refused("b past values_len", "outside values_len", fill([(1, 0, 0, (1 << 64) - 2)]))
-        refused("results_len too small", "results_len", fill([ok, (1, 0, ol, 2 * ol)], rlen=2 * nres - 1))
-        refused("count times the segments > 2^32", "2^32", raw(cols, pp, _vp(int(d_vals)), tab, cnt=(1 << 32) // cmp_segments(3, mask) + 1))
-        refused("two units' cells overlap", "cells overlap", fill([ok, (0, ncells - 1, ol, 2 * ol)]))
-        refused("a unit inside another's gap", "cells overlap", fill([ok, (0, lay.ranges[0][0], ol, 2 * ol)]))
-        refused("a break copy inside another unit", "cells overlap", fill([(1, 0, 0, ol), (0, 20, ol, 2 * ol)], bps=[25, usable - 1]))
-        refused("an operand inside cells this call writes", "operand range", fill([(1, 0, 5, 300)], vdev=d_cols[1], vlen=usable))
-        refused("the results inside cells this call writes", "results overlap", fill([(1, 0, 0, ol)], rdev=d_cols[1] + 32 * 10, rlen=nres))
-        refused("the results over operands of the call", "operand range", fill([ok], rdev=d_vals, rlen=nv))
-        refused("ec_fill: an unknown op", "unknown op", lambda: PL.ec_fill(ctx, d_cols, usable, None, good, 4, d_vals, nv, d_res, 4 * nres, [(0, 0, 0, 0)]))
-        for what, prm, op in (("layout: flags", par(flags=2), 7), ("layout: p", par(p=0), 1), ("layout: op", good, 0), ("layout: op", good, 8)):
-            try:
-                PL.fp_cmp_layout(prm, op, ctx.lib)
-            except H.H2HipError as e:
-                assert e.code == ERR_INVALID, what
-            else:
-                raise AssertionError(what + " was accepted")
+        b.refuse_results_len()
+        b.refuse_count()
+        b.refuse_overlaps(lay.ranges[0][0])
+        b.refuse_aliasing((5, 300))
+        refused("ec_fill: an unknown op", "unknown op", lambda: PL.ec_fill(ctx, b.d_cols, usable, None, kind.params, 4, b.d_vals, nv, b.d_res, 4 * nres, [(0, 0, 0, 0)]))
+        for what, prm, op in (("layout: flags", FH.par(flags=2), 7), ("layout: p", FH.par(p=0), 1), ("layout: op", kind.params, 0), ("layout: op", kind.params, 8)):
+            FH.layout_refused(what, lambda: PL.fp_cmp_layout(prm, op, ctx.lib))
         # count == 0 needs nothing
         ctx._chk(ctx.lib.h2hip_fp_cmp_fill_dev(ctx.handle, None, 0, 0, None, None, 9, None, 0, None, 0, None, 0))
         # the largest run that still fits (its last cell on row usable - 1), an operand that ends with values_len, a mask 1 unit whose b_offset
@@ -740,38 +553,30 @@ def check_rejections(ctx):
         bps = [usable - 1, 30 + ncells - 1]
         fill(units, bps=bps, rlen=2 * nres)()
         one = [(2, 3, 2 * ol, (1 << 64) - 1)]
-        fill(one, op=RA, rdev=d_res + 32 * 2 * nres, rlen=k + 1)()
+        fill(one, op=RA, rdev=b.d_res + 32 * 2 * nres, rlen=k + 1)()
         two = [(2, 3 + ncells, (1 << 64) - 1, 3 * ol)]
-        fill(two, op=RB, rdev=d_res + 32 * (2 * nres + k + 1), rlen=k + 1)()
+        fill(two, op=RB, rdev=b.d_res + 32 * (2 * nres + k + 1), rlen=k + 1)()
         ctx.sync()
-        want = [np.tile(SENTINEL, (n_rows, 1)) for _ in range(3)]
+        want = [np.tile(SENTINEL, (b.n_rows, 1)) for _ in range(3)]
         want_res = np.tile(SENTINEL, (4 * nres, 1))
         at = 0
-        for m_, (col, row, a, b) in [(7, units[0]), (7, units[1]), (RA, one[0]), (RB, two[0])]:
+        for m_, (col, row, a, b_) in [(7, units[0]), (7, units[1]), (RA, one[0]), (RB, two[0])]:
             av = vals[a:a + ol] if m_ != RB else [0] * ol
-            bv = vals[b:b + ol] if m_ != RA else [0] * ol
-            u, cells, _ = Cmp(sp, m_).unit_def(av, bv)
+            bv = vals[b_:b_ + ol] if m_ != RA else [0] * ol
+            u, cells, _ = Cmp(sp, m_).unit_def((av, bv))
             own = own_mask(u)
             for i, c, r in place(col, row, len(cells), bps if m_ == 7 else None, 3)[0]:
                 if own[i]:
                     want[c][r] = fr([cells[i]])[0]
             want_res[at:at + len(u.results)] = fr(u.results)
             at += len(u.results)
-        _compare(ctx, d_cols + [d_res], want + [want_res], "after the refusals")
-    finally:
-        for ptr in d_cols + [d_vals, d_res]:
-            ctx.free(ptr)
+        compare(ctx, b.d_cols + [b.d_res], want + [want_res], "after the refusals")
 
 
 def check_names_in_every_layer():
     """the op constant and the three new symbols in the header, the Rust sys crate and ctypes"""
-    hdr = open(os.path.join(ROOT, "include", "h2hip.h")).read()
-    rs = open(os.path.join(ROOT, "ffi", "rust", "h2hip-sys", "src", "lib.rs")).read()
-    for name, py in (("H2HIP_EC_SUB_UNEQUAL", SUB), ("H2HIP_FP_CMP_REDUCE_A", RA), ("H2HIP_FP_CMP_REDUCE_B", RB), ("H2HIP_FP_CMP_EQUAL", EQ)):
-        assert int(re.search(r"#define %s (\d+)" % name, hdr).group(1)) == py == int(re.search(r"pub const %s: u32 = (\d+);" % name, rs).group(1))
-    lib = H.load_library()
-    for fn in ("h2hip_fp_cmp_layout", "h2hip_fp_cmp_fill_dev", "h2hip_fp_cmp_range_checks"):
-        assert ("int %s(" % fn) in hdr and ("pub fn %s(" % fn) in rs and hasattr(lib, fn), fn
+    FH.check_names(constants=[("H2HIP_EC_SUB_UNEQUAL", SUB), ("H2HIP_FP_CMP_REDUCE_A", RA), ("H2HIP_FP_CMP_REDUCE_B", RB), ("H2HIP_FP_CMP_EQUAL", EQ)],
+                   functions=("h2hip_fp_cmp_layout", "h2hip_fp_cmp_fill_dev", "h2hip_fp_cmp_range_checks"))
 
 
 # ------------------------------------------------------------------------------------------------ F: inside a proof
@@ -806,60 +611,31 @@ def check_proof(ctx, kk, seed, nl, mode="proof"):
     a2, a0 = point(sp, *m[4]), point(sp, *m[1])
     s_int = aff_add(SECP_P, m[4], (m[1][0], -m[1][1] % SECP_P))
     pv = point(sp, *m[5]) if mode == "proof" else point(sp, s_int[0], m[5][1])
-    n = 1 << kk
-    na = 12
-    while True:                                        # the number of gate columns the layout fills (an empty one would have a disjoint selector)
-        sh = P.Shape(kk, na, nl, 1, 1, lb)
-        kb = VR.BaseCircuitBuilder(False)
-        _msm_program(kb, sp, a2, a0, pv)
-        advice_k, fixed, copies, instances, bps = kb.synthesize(sh)
-        if len(bps) == na - 1:
-            break
-        na = len(bps) + 1
-    assert na >= 2 and len(bps) >= 1
-    pb = VR.BaseCircuitBuilder(True)
-    pb.break_points = bps
-    calls = _msm_program(pb, sp, a2, a0, pv)
-    advice, _, _, _, _ = pb.synthesize(sh)
-    assert all(np.array_equal(a, b) for a, b in zip(advice, advice_k))
-    assert (calls[1][2].x3, calls[1][2].y3) == s_int
-    total = sum(len(t.advice) for t in pb.threads)
-    first = {}
-    for i, c, r in place(0, 0, total, bps, na)[0]:
-        first.setdefault(i, (c, r))
-    assert all(first[i] == (0, i) for i in range(3 * pt))           # the witnesses: flat index i of the gate allocation
-    kzg, srs_params = srs(ctx, kk, seed)
-    gpk = PL.keygen(kzg, PL.BaseCircuitParams.new(kk, na, nl, 1, 1, lb), fixed, copies)
-    budget = rng_budget(sh)
-    # one device buffer: [gate columns][results of S][of T][of D][the comparisons' results]
-    host = np.zeros((na * n + 3 * nres + 2 * cres, 4), dtype=np.uint64)
-    host[:3 * pt] = advice[0][:3 * pt]
-    d_gate = ctx.to_device(host)
-    d_lookup = ctx.to_device(np.zeros((nl * n, 4), dtype=np.uint64))
-    d_cols = [d_gate + 32 * n * c for c in range(na)]
-    d_lks = [d_lookup + 32 * n * c for c in range(nl)]
-    res_at = [na * n + j * nres for j in range(3)]
-    cres_at = [na * n + 3 * nres + j * cres for j in range(2)]
-    eq_want = [first[calls[j][0] + calls[j][2].out_offsets[2]] for j in (0, 2)]
-    try:
-        eq0, op0, _ = PL.ec_fill_strict_with_ranges(ctx, d_cols, sh.usable_rows, bps, d_lks, sp.params(), SUB, 7, d_gate, len(host), d_gate + 32 * res_at[0], nres,
+    with FH.ProofBench(ctx, kk, nl, lb, seed, lambda builder: _msm_program(builder, sp, a2, a0, pv)) as pb:
+        calls, first, copies = pb.calls, pb.first, pb.copies
+        assert (calls[1][2].x3, calls[1][2].y3) == s_int
+        # one device buffer: [gate columns][results of S][of T][of D][the comparisons' results]
+        res_at = pb.buffers(3 * nres + 2 * cres, [range(3 * pt)])
+        cres_at = [res_at + 3 * nres + j * cres for j in range(2)]
+        res_at = [res_at + j * nres for j in range(3)]
+        eq_want = [first[calls[j][0] + calls[j][2].out_offsets[2]] for j in (0, 2)]
+        d_cols, d_lks, d_gate, usable, bps, nhost = pb.d_cols, pb.d_lks, pb.d_gate, pb.sh.usable_rows, pb.bps, len(pb.host)
+        eq0, op0, _ = PL.ec_fill_strict_with_ranges(ctx, d_cols, usable, bps, d_lks, sp.params(), SUB, 7, d_gate, nhost, d_gate + 32 * res_at[0], nres,
                                                     d_gate + 32 * cres_at[0], cres, [first[calls[0][0]] + (0, pt)], [calls[0][1]])
-        eq1, op1, _ = PL.ec_fill_strict_with_ranges(ctx, d_cols, sh.usable_rows, bps, d_lks, sp.params(), ADD, 7, d_gate, len(host), d_gate + 32 * res_at[1], nres,
+        eq1, op1, _ = PL.ec_fill_strict_with_ranges(ctx, d_cols, usable, bps, d_lks, sp.params(), ADD, 7, d_gate, nhost, d_gate + 32 * res_at[1], nres,
                                                     d_gate + 32 * cres_at[1], cres, [first[calls[2][0]] + (res_at[0], 2 * pt)], [calls[2][1]])
-        PL.ec_fill_with_ranges(ctx, d_cols, sh.usable_rows, bps, d_lks, sp.params(), DOUBLE, d_gate, len(host), d_gate + 32 * res_at[2], nres,
+        PL.ec_fill_with_ranges(ctx, d_cols, usable, bps, d_lks, sp.params(), DOUBLE, d_gate, nhost, d_gate + 32 * res_at[2], nres,
                                [first[calls[4][0]] + (res_at[1], 0)], [calls[4][1]])
         ctx.sync()
         assert eq0 + eq1 == eq_want and op0 + op1 == [first[calls[1][0]], first[calls[3][0]]]
         # both equality cells are pinned to the constant 0 by the key's copies
         pinned = {r for l, r in copies if l[0][0] == "fixed"} | {l for l, r in copies if r[0][0] == "fixed"}
         assert all((("advice", c), r) in pinned for c, r in eq_want)
-        got_cols = np.concatenate([ctx.download(d_gate, (na, n, 4)), ctx.download(d_lookup, (nl, n, 4))])
-        for c in range(na + nl):
-            assert np.array_equal(got_cols[c], advice[c]), "advice column %d differs from the Python-computed advice" % c
+        pb.check_columns()
         if mode == "equal_x":
             ct = calls[2][2]
             assert ct.results[-1] == 1 and calls[3][2].lam == 0
-            total_f, fails = PL.check_witness(gpk, d_cols + d_lks, instances, max_failures=4096, advice_on_device=True)
+            total_f, fails = pb.check_witness(max_failures=4096)
             cmp_cells = {first[calls[2][0] + i] for i in range(ct.end - ct.start)}
             perm_col = lambda c: 1 + c                                  # one constants column, then the gate advice
             eq_c, eq_r = eq_want[1]
@@ -869,21 +645,4 @@ def check_proof(ctx, kk, seed, nl, mode="proof"):
             assert all(f.kind == "copy" and ((f.column, f.row) == (perm_col(eq_c), eq_r) or (f.peer_column, f.peer_row) == (perm_col(eq_c), eq_r)) for f in inside), inside
             assert not any(f.kind == "lookup" for f in fails)
             return
-        want = PL.create_proof(gpk, advice, instances, PreDrawnRng(budget, 2000 + seed))
-        got = PL.create_proof(gpk, d_cols + d_lks, instances, PreDrawnRng(budget, 2000 + seed), advice_on_device=True)
-        assert got == want, "the proof over the device-filled trace differs from the one over the host-laid trace"
-        asm = P.PermutationAssembly(sh)
-        for l, r in copies:
-            asm.copy(l, r)
-        opk = P.keygen(srs_params, sh, fixed, asm, 2)
-        oracle = P.create_proof(srs_params, opk, advice, [_ints(v) for v in instances], PreDrawnRng(budget, 2000 + seed), 2)
-        assert got == oracle, "the proof differs from the oracle prover's over the host-laid trace"
-        assert PL.verify_proof(gpk, instances, got), "h2hip_plonk_verify_proof rejects the proof"
-        assert P.verify_proof(srs_params, vk_from_gpu(sh, gpk), [_ints(v) for v in instances], got), "the test verifier rejects the proof"
-        total_f, fails = PL.check_witness(gpk, d_cols + d_lks, instances, advice_on_device=True)
-        assert total_f == 0, fails
-    finally:
-        ctx.free(d_gate)
-        ctx.free(d_lookup)
-        gpk.free()
-        kzg.free()
+        pb.check_proof(oracle=True)

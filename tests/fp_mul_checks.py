@@ -14,27 +14,18 @@ range_check calls included, so one thread holds the full run and the lookup queu
   D  the structs in the header, the Rust sys crate and ctypes;
   E  a BaseConfig proof whose field multiplications two fill calls write, the second reading the first's results.
 """
-import ctypes as C
 import itertools
-import os
-import re
 
 import numpy as np
 
 import halo2_lib_amd as H
 from halo2_lib_amd import plonk as PL
 from halo2_lib_amd import virtual_region as VR
-from oracle import plonk as P
-from tests.dyn_lookup_util import rng_budget, srs, vk_from_gpu
-from tests.poseidon_trace_checks import _compare, _ints, place
-from tests.range_fill_checks import lookup_positions
-from tests.rlc_checks import SENTINEL
-from tests.util import PreDrawnRng, R, fr
+from tests import fused_fill_harness as FH
+from tests.fused_fill_harness import ERR_INVALID, SENTINEL, FpMul, compare, lookup_positions, operand, own_mask, place, signed, tdiv, thread
+from tests.util import R, fr
 
-_vp = C.c_void_p
-ERR_INVALID = -1
 SOLVE_BLOCK, PLACE_BLOCK = 64, 256   # fp_mul.hip: lanes per workgroup of the per-unit and of the per-(unit, slot) kernel
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SECP_P = (1 << 256) - (1 << 32) - 977
 SECP_N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
 BN254_Q = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
@@ -71,16 +62,6 @@ class Spec:
     def crt(self, x):
         """the k limbs and the native residue of the integer x < 2^(n k)"""
         return [(x >> (self.n * i)) & ((1 << self.n) - 1) for i in range(self.k)] + [x % R]
-
-
-def _signed(v):
-    """fe_to_bigint (halo2-base/src/utils/mod.rs:199-208)"""
-    return v if v <= R // 2 else v - R
-
-
-def _tdiv(a, b):
-    """BigInt's `/`: toward zero"""
-    return abs(a) // b if a >= 0 else -(abs(a) // b)
 
 
 class Unit:
@@ -134,7 +115,7 @@ def fp_mul(ctx, chip, sp, a, b):
         ranged(VR.GateChip.add(ctx, cell, VR.Constant(pow(2, bits, R))), bits + 1, k + 1 + i)
     carries, previous = [], None                                              # check_carry_to_zero.rs:38-49
     for cell in check_assigned:
-        carries.append(_tdiv(_signed(cell.value) + (carries[-1] if carries else 0), 1 << n))
+        carries.append(tdiv(signed(cell.value) + (carries[-1] if carries else 0), 1 << n))
     u.carries, u.checks = carries, [c.value for c in check_assigned]
     for i, (cell, carry) in enumerate(zip(check_assigned, carries)):          # :64-85
         ctx.assign_region([VR.Existing(cell), VR.Witness(-carry % R), VR.Constant(sp.limb_bases[1]),
@@ -155,28 +136,11 @@ def fp_mul(ctx, chip, sp, a, b):
     return u
 
 
-def _thread(lb=8):
-    cm = VR.CopyConstraintManager()
-    ctx = VR.Context(False, "fp", 0, cm)
-    return ctx, VR.RangeChip(lb, VR.LookupAnyManager(False, cm)), cm
-
-
-def _operand(vals, tag):
-    return [VR.AssignedValue(v % R, VR.ContextCell("operand", tag, i)) for i, v in enumerate(vals)]
-
-
 def unit_def(sp, a_vals, b_vals):
     """one unit on a thread of its own -> (the Unit, its cells, the lookup values in queue order, the thread)"""
-    ctx, chip, _ = _thread(sp.lb)
-    u = fp_mul(ctx, chip, sp, _operand(a_vals, 0), _operand(b_vals, 1))
+    ctx, chip, _ = thread(sp.lb)
+    u = fp_mul(ctx, chip, sp, operand(a_vals, 0), operand(b_vals, 1))
     return u, list(ctx.advice), [c.value for c in chip.lookup_manager.cells_to_lookup.get(ctx.tag(), [])], ctx
-
-
-def own_mask(u):
-    own = np.ones(u.end - u.start, dtype=bool)
-    for at, cells, _bits, _res in u.gaps:
-        own[at:at + cells] = False
-    return own
 
 
 def integer_pool(sp, seed):
@@ -230,7 +194,7 @@ def check_definition():
                 if (n, k) == (88, 3) and proper:
                     acc = 0
                     for chk, c in zip(u.checks, u.carries):
-                        acc += _signed(chk)
+                        acc += signed(chk)
                         assert acc % (1 << n) == 0 and acc >> n == c and abs(c) < 1 << 90, (name, c.bit_length())
                         acc = c
     sp = Spec(88, 3, 18, SECP_P)
@@ -300,64 +264,10 @@ def check_seek_grid():
     assert seen == {"starts on a break cell", "one cell between two breaks", "break on the last cell", "in the last column"}, seen
 
 
-def check_fill(ctx, n, k, lb, modulus, count, nl=1, pairs=None, seed=0xF9):
-    """`count` units per call over three gate columns (no breaks), until every operand pair was a unit; each call once bare (own cells equal
-    the definition's, the gaps and every other cell keep the sentinel, results_dev equals the named cells) and once through
-    fp_mul_fill_with_ranges over nl lookup columns (the whole run and the lookup columns equal the definition's, the queue starting at a
-    position that is no multiple of nl)"""
+def check_mul_fill(ctx, n, k, lb, modulus, count, nl=1, pairs=None, seed=0xF9):
+    """the harness's check_fill over every operand pair: the bare call and fp_mul_fill_with_ranges over nl lookup columns"""
     sp = Spec(n, k, lb, MODULI[modulus])
-    pairs = operand_pairs(sp, seed) if pairs is None else pairs
-    lay = PL.fp_mul_layout(sp.params(), ctx.lib)
-    vals = [v for a, b in pairs for v in a + b]
-    nres = 3 * k + 1
-    done = 0
-    while done < len(pairs):
-        units, defs, slots_, rows, slot = [], [], [], [1, 3, 0], nl + 1 if nl > 1 else 1
-        for j in range(count):
-            at = (done + j) % len(pairs)
-            u, cells, lookups, _ = unit_def(sp, *pairs[at])
-            assert len(cells) == lay.num_cells
-            col = j % 3
-            units.append((col, rows[col], 2 * (k + 1) * at, 2 * (k + 1) * at + k + 1))
-            defs.append((u, cells, lookups))
-            slots_.append(slot)
-            rows[col] += len(cells) + (j % 2)
-            slot += len(lookups) + (j % 2)
-        done += count
-        rows_n = max(max(rows), -(-slot // nl)) + 9
-        where = lookup_positions(slot, nl)
-        d_vals = ctx.to_device(fr(vals))
-        try:
-            for with_ranges in (False, True):
-                want = [np.tile(SENTINEL, (rows_n, 1)) for _ in range(3)]
-                want_lk = [np.tile(SENTINEL, (rows_n, 1)) for _ in range(nl)]
-                want_res = np.tile(SENTINEL, (count * nres + 2, 1))
-                d_cols = [ctx.to_device(c) for c in want]
-                d_lk = [ctx.to_device(c) for c in want_lk]
-                d_res = ctx.to_device(want_res)
-                for j, ((col, row, _a, _b), (u, cells, lookups), s) in enumerate(zip(units, defs, slots_)):
-                    keep = np.ones(len(cells), dtype=bool) if with_ranges else own_mask(u)
-                    want[col][row:row + len(cells)][keep] = fr(cells)[keep]
-                    want_res[j * nres:(j + 1) * nres] = fr(u.results)
-                    if with_ranges:
-                        for i, v in enumerate(fr(lookups)):
-                            c, r = where[s + i]
-                            want_lk[c][r] = v
-                try:
-                    if with_ranges:
-                        PL.fp_mul_fill_with_ranges(ctx, d_cols, rows_n - 2, None, d_lk, sp.params(), d_vals, len(vals), d_res, count * nres, units, slots_)
-                    else:
-                        PL.fp_mul_fill(ctx, d_cols, rows_n - 2, None, sp.params(), d_vals, len(vals), d_res, count * nres, units)
-                    ctx.sync()
-                    what = "(n, k, lb) = (%d, %d, %d), %s, count = %d, nl = %d, ranges = %s" % (n, k, lb, modulus, count, nl, with_ranges)
-                    _compare(ctx, d_cols, want, what + " (gate columns)")
-                    _compare(ctx, d_lk, want_lk, what + " (lookup columns)")
-                    _compare(ctx, [d_res], [want_res], what + " (results)")
-                finally:
-                    for ptr in d_cols + d_lk + [d_res]:
-                        ctx.free(ptr)
-        finally:
-            ctx.free(d_vals)
+    FH.check_fill(ctx, FpMul(sp), operand_pairs(sp, seed) if pairs is None else pairs, count, nl)
 
 
 def check_chained(ctx, n, k, lb, modulus, count=5, seed=0xC4):
@@ -407,7 +317,7 @@ def check_chained(ctx, n, k, lb, modulus, count=5, seed=0xC4):
             for i, v in enumerate(fr(lookups)):
                 want_lk[where[s + i][1]] = v
         what = "chained calls, (n, k, lb) = (%d, %d, %d), %s" % (n, k, lb, modulus)
-        _compare(ctx, d_cols + [d_lk, d_res1, d_res2], want + [want_lk] + want_res, what)
+        compare(ctx, d_cols + [d_lk, d_res1, d_res2], want + [want_lk] + want_res, what)
     finally:
         for ptr in d_cols + [d_lk, d_vals, d_res1, d_res2]:
             ctx.free(ptr)
@@ -416,19 +326,7 @@ def check_chained(ctx, n, k, lb, modulus, count=5, seed=0xC4):
 def check_results_null(ctx):
     """results_dev = NULL: the same own cells"""
     sp = Spec(88, 3, 8, SECP_P)
-    u, cells, _, _ = unit_def(sp, sp.crt(SECP_P - 3), sp.crt(12345))
-    want = np.tile(SENTINEL, (len(cells) + 9, 1))
-    own = own_mask(u)
-    want[2:2 + len(cells)][own] = fr(cells)[own]
-    d_col = ctx.to_device(np.tile(SENTINEL, (len(cells) + 9, 1)))
-    d_vals = ctx.to_device(fr(sp.crt(SECP_P - 3) + sp.crt(12345)))
-    try:
-        PL.fp_mul_fill(ctx, [d_col], len(cells) + 8, None, sp.params(), d_vals, 8, None, 0, [(0, 2, 0, 4)])
-        ctx.sync()
-        _compare(ctx, [d_col], [want], "results_dev = NULL")
-    finally:
-        ctx.free(d_col)
-        ctx.free(d_vals)
+    FH.check_no_results(ctx, FpMul(sp), [(sp.crt(SECP_P - 3), sp.crt(12345))], 9, 1)
 
 
 # ------------------------------------------------------------------------------------------------ B: column breaks
@@ -450,59 +348,20 @@ def _break_cells(sp):
 BREAK_CASES = ["s1_running_sum", "s3_prod", "last_own_before_a_gap", "last_cell_of_a_gap", "out_native", "unit_last"]
 
 
-def check_breaks(ctx, case, ncols):
-    """one thread (plain cells, then (88, 3, 8) units back to back, each reading witnesses of its own) laid into ncols columns of about
-    1,500 usable rows by virtual_region.assign_witnesses and by fp_mul_fill_with_ranges from each unit's first cell, from the same break
-    points; the lookup column by LookupAnyManager.assign_raw and by the fill.  Every break falls on the cell the case names."""
+def check_mul_breaks(ctx, case, ncols):
+    """the harness's check_breaks over (88, 3, 8) units in ncols columns of about 1,500 usable rows, through fp_mul_fill_with_ranges: the
+    first break at row 1450, every later one 3 units further down the thread, each on the cell the case names"""
     sp = Spec(88, 3, 8, SECP_P)
-    k, usable = sp.k, 1500
+    usable = 1500
     cell = _break_cells(sp)[case]
-    lay = PL.fp_mul_layout(sp.params(), ctx.lib)
-    ncells = lay.num_cells
-    filler = 1450 - 2 * ncells - cell                  # the first break at row 1450, every later one 3 units further down the thread
+    ncells = PL.fp_mul_layout(sp.params(), ctx.lib).num_cells
+    filler = 1450 - 2 * ncells - cell
     assert filler >= 5
     targets = [(2 + 3 * b, cell) for b in range(ncols - 1)]
-    idx = [filler + unit * ncells + c for unit, c in targets]
-    bps = [idx[0]] + [b - a for a, b in zip(idx, idx[1:])]
+    bps = FH.break_points(filler, ncells, targets)
     assert all(1200 < b < usable for b in bps), bps
-    nunits = targets[-1][0] + 2
     pairs = operand_pairs(sp, 0xB7)
-    vals = [v for j in range(nunits) for x in pairs[(5 * j) % len(pairs)] for v in x]
-    thread, chip, _ = _thread()
-    thread.advice += list(range(100, 100 + filler))
-    thread.selector += [False] * filler
-    pos, units, slots_ = place(0, 0, filler, bps, ncols)[1], [], []
-    for j in range(nunits):
-        a_vals, b_vals = pairs[(5 * j) % len(pairs)]
-        u = fp_mul(thread, chip, sp, _operand(a_vals, 2 * j), _operand(b_vals, 2 * j + 1))
-        assert u.end - u.start == ncells
-        units.append((pos[0], pos[1], 2 * (k + 1) * j, 2 * (k + 1) * j + k + 1))
-        slots_.append(u.queue)
-        pos = place(pos[0], pos[1], ncells, bps, ncols)[1]
-    for (unit, c), b, col in zip(targets, bps, range(ncols)):   # the break cell is the cell the case names
-        cells_at = place(units[unit][0], units[unit][1], ncells, bps, ncols)[0]
-        assert (c, col, b) in cells_at and (c, col + 1, 0) in cells_at, (case, unit, c)
-    region = VR.Region(usable + 9, ncols + 1)
-    VR.assign_witnesses([thread], list(range(ncols)), region, bps)
-    chip.lookup_manager.witness_gen_only = True
-    chip.lookup_manager.assign_raw([ncols], region)
-    want = [np.tile(SENTINEL, (usable + 9, 1)) for _ in range(ncols + 1)]
-    for c in range(ncols + 1):
-        rows = sorted(region.advice[c])
-        want[c][rows] = fr([region.advice[c][r] for r in rows])
-    start = [np.tile(SENTINEL, (usable + 9, 1)) for _ in range(ncols + 1)]
-    start[0][:filler] = want[0][:filler]
-    d_cols = [ctx.to_device(c) for c in start]
-    d_vals = ctx.to_device(fr(vals))
-    d_res = ctx.to_device(np.tile(SENTINEL, (nunits * (3 * k + 1), 1)))
-    try:
-        PL.fp_mul_fill_with_ranges(ctx, d_cols[:ncols], usable, bps, d_cols[ncols:], sp.params(), d_vals, len(vals), d_res, nunits * (3 * k + 1),
-                                   units, slots_)
-        ctx.sync()
-        _compare(ctx, d_cols, want, "breaks (%s, %d columns)" % (case, ncols))
-    finally:
-        for ptr in d_cols + [d_vals, d_res]:
-            ctx.free(ptr)
+    FH.check_breaks(ctx, FpMul(sp), [pairs[(5 * j) % len(pairs)] for j in range(targets[-1][0] + 2)], targets, filler, usable, ncols)
 
 
 # ------------------------------------------------------------------------------------------------ C: the refusals
@@ -511,82 +370,25 @@ def check_rejections(ctx):
     results); then count == 0 and a good call from the same context"""
     sp = Spec(88, 3, 8, SECP_P)
     k, nres = sp.k, 10
-    lay = PL.fp_mul_layout(sp.params(), ctx.lib)
+    kind = FpMul(sp)
+    lay = kind.layout(ctx.lib)
     ncells = lay.num_cells
-    n_rows, usable, nv = 2 * ncells + 60, 2 * ncells + 50, 24
     ops = [sp.crt(SECP_P - 5), sp.crt(77), sp.crt(SECP_N), sp.crt(1 << 200), sp.crt(3), sp.crt(9)]
     vals = [v for x in ops for v in x]
-    assert len(vals) == nv
-    sent, sent_res = np.tile(SENTINEL, (n_rows, 1)), np.tile(SENTINEL, (4 * nres, 1))
-    d_cols = [ctx.to_device(sent) for _ in range(3)]
-    d_vals = ctx.to_device(fr(vals))
-    d_res = ctx.to_device(sent_res)
-    good = sp.params()
-    ok = (0, 0, 0, 4)
-    try:
-        def refused(what, reason, call):
-            try:
-                call()
-            except H.H2HipError as e:
-                assert e.code == ERR_INVALID, (what, e.code)
-                msg = ctx.lib.h2hip_last_error().decode()
-                assert reason in msg, (what, msg)
-            else:
-                raise AssertionError("%s was accepted" % what)
-            ctx.sync()
-            for ptr in d_cols:
-                assert np.array_equal(ctx.download(ptr, (n_rows, 4)), sent), "%s: a cell was written" % what
-            assert np.array_equal(ctx.download(d_res, (4 * nres, 4)), sent_res), "%s: a result was written" % what
-
-        def fill(units, cols=None, usable_rows=usable, bps=None, params=good, vdev=None, vlen=nv, rdev=None, rlen=4 * nres):
-            return lambda: PL.fp_mul_fill(ctx, d_cols if cols is None else cols, usable_rows, bps, params, d_vals if vdev is None else vdev, vlen,
-                                          d_res if rdev is None else rdev, rlen, units)
-
-        par = lambda n=88, k_=3, lb=8, p=SECP_P, flags=0: PL.fp_params(n, k_, lb, p, flags)
-        cols = (_vp * 3)(*[_vp(int(ptr)) for ptr in d_cols])
-        tab = C.cast(PL.fp_mul_table([ok]), _vp)
-        pp = C.cast(C.pointer(good), _vp)
-        raw = lambda c, p_, v, t, cnt=1: (lambda: ctx._chk(ctx.lib.h2hip_fp_mul_fill_dev(ctx.handle, c, 3, usable, None, p_, v, nv, _vp(int(d_res)), 4 * nres, t, cnt)))
-        refused("columns NULL", "NULL argument", raw(None, pp, _vp(int(d_vals)), tab))
-        refused("params NULL", "NULL argument", raw(cols, None, _vp(int(d_vals)), tab))
-        refused("values NULL", "NULL argument", raw(cols, pp, None, tab))
-        refused("units NULL", "NULL argument", raw(cols, pp, _vp(int(d_vals)), None))
-        refused("flags != 0", "flags", fill([ok], params=par(flags=1)))
-        refused("limb_bits 63", "limb_bits outside", fill([ok], params=par(n=63, k_=4, p=(1 << 252) - 1)))
-        refused("limb_bits 128", "limb_bits outside", fill([ok], params=par(n=128, k_=2)))
-        refused("num_limbs 1", "num_limbs outside", fill([ok], params=par(k_=1)))
-        refused("num_limbs 5", "num_limbs outside", fill([ok], params=par(n=64, k_=5)))
-        refused("n k > 320", "> 320", fill([ok], params=par(n=107, k_=3, p=(1 << 320) - 1)))
-        refused("log2 k + 2 n > 252", "> 252", fill([ok], params=par(n=126, k_=2, p=(1 << 252) - 1)))
-        refused("p == 0", "zero", fill([ok], params=par(p=0)))
-        refused("p < 2^(n (k - 1))", "exactly num_limbs", fill([ok], params=par(p=(1 << 176) - 1)))
-        refused("p >= 2^(n k)", "exactly num_limbs", fill([ok], params=par(p=1 << 264)))
-        refused("quot_max_bits >= n k", "quot_max_bits", fill([ok], params=par(p=(1 << 252) - 1)))
-        refused("a limb of p equal to 1", "equals 1", fill([ok], params=par(p=(1 << 255) + (1 << 88) + 12345)))
-        refused("lookup_bits 0", "lookup_bits", fill([ok], params=par(lb=0)))
-        refused("lookup_bits 64", "lookup_bits", fill([ok], params=par(lb=64)))
-        refused("column index out of range", "column index", fill([ok, (3, 0, 8, 12)]))
-        refused("a NULL column", "column index", fill([ok, (1, 0, 8, 12)], cols=[d_cols[0], 0, d_cols[2]]))
-        refused("a run that leaves the usable rows", "usable rows", fill([ok, (1, usable - ncells + 1, 8, 12)]))
-        refused("a run that leaves the last column", "last column", fill([ok, (2, usable - ncells + 1, 8, 12)], bps=[usable - 1, usable - 1]))
-        refused("a break point >= usable_rows", "break point", fill([ok], bps=[10, usable]))
-        refused("an operand past values_len", "outside values_len", fill([ok, (1, 0, nv - k, 0)]))
+    assert len(vals) == 24
+    with FH.RefusalBench(ctx, kind, vals, (0, 4), (8, 12), ncells, slots(3), 4 * nres) as b:
+        usable, nv, fill, refused = b.usable, b.nv, b.fill, b.refused
+        b.refuse_nulls()
+        b.refuse_params(behind={"n k > 320": [("log2 k + 2 n > 252", "> 252", dict(n=126, k_=2, p=(1 << 252) - 1))]})
+        b.refuse_placement()
+        refused("an operand past values_len", "outside values_len", fill([b.ok, (1, 0, nv - k, 0)]))
         refused("the right operand past values_len", "outside values_len", fill([(1, 0, 0, (1 << 64) - 2)]))
-        refused("results_len too small", "results_len", fill([ok, (1, 0, 8, 12)], rlen=2 * nres - 1))
-        refused("count (4 k + 3) > 2^32", "2^32", raw(cols, pp, _vp(int(d_vals)), tab, cnt=(1 << 32) // 15 + 1))
-        refused("two units' cells overlap", "cells overlap", fill([ok, (0, ncells - 1, 8, 12)]))
-        refused("a unit inside another's gap", "cells overlap", fill([ok, (0, lay.ranges[0][0], 8, 12)]))
-        refused("a break copy inside another unit", "cells overlap", fill([(1, 0, 0, 4), (0, 20, 8, 12)], bps=[25, usable - 1]))
-        refused("an operand inside cells this call writes", "operand range", fill([(1, 0, 5, 300)], vdev=d_cols[1], vlen=usable))
-        refused("the results inside cells this call writes", "results overlap", fill([(1, 0, 0, 4)], rdev=d_cols[1] + 32 * 10, rlen=nres))
-        refused("the results over operands of the call", "operand range", fill([ok], rdev=d_vals, rlen=nv))
-        for what, prm in (("layout: flags", par(flags=2)), ("layout: p", par(p=0)), ("layout: lookup_bits", par(lb=64))):
-            try:
-                PL.fp_mul_layout(prm, ctx.lib)
-            except H.H2HipError as e:
-                assert e.code == ERR_INVALID, what
-            else:
-                raise AssertionError(what + " was accepted")
+        b.refuse_results_len()
+        b.refuse_count()
+        b.refuse_overlaps(lay.ranges[0][0])
+        b.refuse_aliasing((5, 300))
+        for what, prm in (("layout: flags", FH.par(flags=2)), ("layout: p", FH.par(p=0)), ("layout: lookup_bits", FH.par(lb=64))):
+            FH.layout_refused(what, lambda: PL.fp_mul_layout(prm, ctx.lib))
         # count == 0 needs nothing
         ctx._chk(ctx.lib.h2hip_fp_mul_fill_dev(ctx.handle, None, 0, 0, None, None, None, 0, None, 0, None, 0))
         # the largest run that still fits (its last cell on row usable - 1), an operand that ends with values_len, a unit that ends on its
@@ -595,49 +397,24 @@ def check_rejections(ctx):
         bps = [usable - 1, 30 + ncells - 1]
         fill(units, bps=bps, rlen=2 * nres)()
         ctx.sync()
-        want = [np.tile(SENTINEL, (n_rows, 1)) for _ in range(3)]
+        want = [np.tile(SENTINEL, (b.n_rows, 1)) for _ in range(3)]
         want_res = np.tile(SENTINEL, (4 * nres, 1))
-        for j, (col, row, a, b) in enumerate(units):
-            u, cells, _, _ = unit_def(sp, vals[a:a + k + 1], vals[b:b + k + 1])
+        for j, (col, row, a, b_) in enumerate(units):
+            u, cells, _, _ = unit_def(sp, vals[a:a + k + 1], vals[b_:b_ + k + 1])
             own = own_mask(u)
             for i, c, r in place(col, row, ncells, bps, 3)[0]:
                 if own[i]:
                     want[c][r] = fr([cells[i]])[0]
             want_res[j * nres:(j + 1) * nres] = fr(u.results)
-        _compare(ctx, d_cols + [d_res], want + [want_res], "after the refusals")
-    finally:
-        for ptr in d_cols + [d_vals, d_res]:
-            ctx.free(ptr)
+        compare(ctx, b.d_cols + [b.d_res], want + [want_res], "after the refusals")
 
 
 # ------------------------------------------------------------------------------------------------ D: the structs in every layer
 def check_struct_layout():
-    """h2hip_fp_params and h2hip_fp_mul: the same fields in the header, the Rust sys crate and ctypes; 64 and 24 bytes; every function named in
-    the C++ mirror and the safe Rust wrapper"""
-    hdr = open(os.path.join(ROOT, "include", "h2hip.h")).read()
-    rs = open(os.path.join(ROOT, "ffi", "rust", "h2hip-sys", "src", "lib.rs")).read()
-    cmap = {"uint32_t": "u32", "uint64_t": "u64", "uint8_t": "u8"}
-    pymap = {C.c_uint32: "u32", C.c_uint64: "u64"}
-    for name, py, size in (("h2hip_fp_params", PL.FpParamsStruct, 64), ("h2hip_fp_mul", PL.FpMulStruct, 24), ("h2hip_fp_mul_range", PL.FpMulRangeStruct, 16)):
-        body = re.search(r"typedef struct %s\s*\{(.*?)\}\s*%s\s*;" % (name, name), hdr, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        c_fields = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if decl:
-                ty, names = decl.split(None, 1)
-                for nm in names.split(","):
-                    arr = re.fullmatch(r"(\w+)\[(\d+)\]", nm.strip())
-                    c_fields.append((arr.group(1), "[%s; %s]" % (cmap[ty], arr.group(2))) if arr else (nm.strip(), cmap[ty]))
-        rs_body = re.search(r"pub struct %s\s*\{(.*?)\}" % name, rs, flags=re.S).group(1)
-        rs_fields = re.findall(r"pub ([a-z_]+): (\[[a-z0-9]+; \d+\]|[a-z0-9]+)", rs_body)
-        py_fields = [(nm, pymap[ty] if ty in pymap else "[u8; %d]" % ty._length_) for nm, ty in py._fields_]
-        assert c_fields == rs_fields == py_fields, (name, c_fields, rs_fields, py_fields)
-        assert C.sizeof(py) == size, name
-    for layer in ("halo2-lib_amd/host/halo2_proofs.hpp", "ffi/rust/h2hip-sys/src/safe.rs"):
-        src = open(os.path.join(ROOT, layer)).read()
-        for fn in ("h2hip_fp_mul_fill_dev", "h2hip_fp_mul_layout", "h2hip_trace_seek"):
-            assert fn in src, (layer, fn)
+    """h2hip_fp_params, h2hip_fp_mul and h2hip_fp_mul_range: the same fields in the header, the Rust sys crate and ctypes; 64, 24 and 16
+    bytes; every function named in the C++ mirror and the safe Rust wrapper"""
+    FH.check_names(structs=[("h2hip_fp_params", PL.FpParamsStruct, 64), ("h2hip_fp_mul", PL.FpMulStruct, 24), ("h2hip_fp_mul_range", PL.FpMulRangeStruct, 16)],
+                   mirrored=("h2hip_fp_mul_fill_dev", "h2hip_fp_mul_layout", "h2hip_trace_seek"))
 
 
 # ------------------------------------------------------------------------------------------------ E: inside a proof
@@ -677,55 +454,20 @@ def check_proof(ctx, kk, seed, nl=1, xs=None, truncated=False):
     lay = PL.fp_mul_layout(sp.params(), ctx.lib)
     n = 1 << kk
     reps = -(-13 * n // (10 * 2 * lay.num_cells))      # 1.3 columns of cells and more
-    na = 2
-    while True:                                        # the number of gate columns the layout fills (an empty one would have a disjoint selector)
-        sh = P.Shape(kk, na, nl, 1, 1, lb)
-        kb = VR.BaseCircuitBuilder(False)
-        calls_k = _fp_program(kb, sp, xs, reps)
-        advice_k, fixed, copies, instances, bps = kb.synthesize(sh)
-        if len(bps) == na - 1:
-            break
-        na = len(bps) + 1
-    assert na >= 2 and len(bps) >= 1
-    pb = VR.BaseCircuitBuilder(True)
-    pb.break_points = bps
-    calls = _fp_program(pb, sp, xs, reps)
-    advice, _, _, _, _ = pb.synthesize(sh)
-    assert all(np.array_equal(a, b) for a, b in zip(advice, advice_k))
-    nloaded = 3 * (k + 1)
-    total = sum(len(t.advice) for t in pb.threads)
-    cells_at, _ = place(0, 0, total, bps, na)
-    first = {}
-    for i, c, r in cells_at:
-        first.setdefault(i, (c, r))
-    assert all(first[i] == (0, i) for i in range(nloaded))          # the witnesses: flat index i of the gate allocation
-    assert any(first[s][0] != first[s + lay.num_cells - 1][0] for call in calls for s, _q, _u in call), "no break falls inside a unit"
-    kzg, srs_params = srs(ctx, kk, seed)
-    gpk = PL.keygen(kzg, PL.BaseCircuitParams.new(kk, na, nl, 1, 1, lb), fixed, copies)
-    budget = rng_budget(sh)
-    # one device buffer: [gate columns][results of the first call][results of the second], so that a unit of the second call finds one operand
-    # in the first call's results and the other among the loaded witnesses
-    host = np.zeros((na * n + 2 * reps * nres, 4), dtype=np.uint64)
-    host[:nloaded] = advice[0][:nloaded]
-    d_gate = ctx.to_device(host)
-    d_lookup = ctx.to_device(np.zeros((nl * n, 4), dtype=np.uint64))
-    d_cols = [d_gate + 32 * n * c for c in range(na)]
-    d_lks = [d_lookup + 32 * n * c for c in range(nl)]
-    res_at = [na * n, na * n + reps * nres]
-    tables = [[first[s] + (0, k + 1) for s, _q, _u in calls[0]],
-              [first[s] + (res_at[0] + j * nres, 2 * (k + 1)) for j, (s, _q, _u) in enumerate(calls[1])]]
-
-    def fill_all():
+    with FH.ProofBench(ctx, kk, nl, lb, seed, lambda builder: _fp_program(builder, sp, xs, reps), num_advice=2) as pb:
+        calls, first = pb.calls, pb.first
+        assert any(first[s][0] != first[s + lay.num_cells - 1][0] for call in calls for s, _q, _u in call), "no break falls inside a unit"
+        # one device buffer: [gate columns][results of the first call][results of the second], so that a unit of the second call finds one
+        # operand in the first call's results and the other among the loaded witnesses
+        res_at = pb.buffers(2 * reps * nres, [range(3 * (k + 1))])
+        res_at = [res_at, res_at + reps * nres]
+        tables = [[first[s] + (0, k + 1) for s, _q, _u in calls[0]],
+                  [first[s] + (res_at[0] + j * nres, 2 * (k + 1)) for j, (s, _q, _u) in enumerate(calls[1])]]
         for c in range(2):
-            PL.fp_mul_fill_with_ranges(ctx, d_cols, sh.usable_rows, bps, d_lks, sp.params(), d_gate, len(host), d_gate + 32 * res_at[c], reps * nres,
-                                       tables[c], [q for _s, q, _u in calls[c]])
+            PL.fp_mul_fill_with_ranges(ctx, pb.d_cols, pb.sh.usable_rows, pb.bps, pb.d_lks, sp.params(), pb.d_gate, len(pb.host), pb.d_gate + 32 * res_at[c],
+                                       reps * nres, tables[c], [q for _s, q, _u in calls[c]])
         ctx.sync()
-
-    try:
-        fill_all()
-        got_cols = np.concatenate([ctx.download(d_gate, (na, n, 4)), ctx.download(d_lookup, (nl, n, 4))])
-        for c in range(na + nl):
-            assert np.array_equal(got_cols[c], advice[c]), "advice column %d differs from the Python-computed advice" % c
+        pb.check_columns()
         if truncated:
             # 2^(n k) - 1 squared: Q = 2^272 + 2^48 + ... has more than k limbs and its low k limbs are small, so every range check holds and
             # what fails is S9's native identity, the gate on out_native, over the truncated quot_native.  With 3 2^254 + 12345 as the second
@@ -733,29 +475,17 @@ def check_proof(ctx, kk, seed, nl=1, xs=None, truncated=False):
             s, _q, u1 = calls[0][0]
             improper = not isinstance(xs[0], int)
             assert improper or (u1.quot.bit_length() > sp.quot_max_bits and (xs[1] != top or u1.quot >> (sp.n * k))), "Q is within its bound"
-            total_f, fails = PL.check_witness(gpk, d_cols + d_lks, instances, max_failures=4096, advice_on_device=True)
+            total_f, fails = pb.check_witness(max_failures=4096)
             s9_fails = [f for f in fails if f.kind == "gate" and (f.column, f.row) == first[s + u1.out_offsets[k]]]
             assert total_f >= 1 and (improper or bool(s9_fails) == (xs[1] == top)), fails[:8]
             lk_rows = set(lookup_positions(sum(u.lookups for call in calls for _s, _q, u in call), nl))
             lookup_fails = [f for f in fails if f.kind == "lookup" and (f.column, f.row) in lk_rows]
             assert improper or bool(lookup_fails) == (xs[1] != top), fails[:8]
             return
-        want = PL.create_proof(gpk, advice, instances, PreDrawnRng(budget, 2000 + seed))
-        got = PL.create_proof(gpk, d_cols + d_lks, instances, PreDrawnRng(budget, 2000 + seed), advice_on_device=True)
-        assert got == want, "the proof over device-filled field multiplications differs from the one over the Python-computed advice"
-        assert PL.verify_proof(gpk, instances, got), "h2hip_plonk_verify_proof rejects the proof"
-        assert P.verify_proof(srs_params, vk_from_gpu(sh, gpk), [_ints(v) for v in instances], got), "the test verifier rejects the proof"
-        total_f, fails = PL.check_witness(gpk, d_cols + d_lks, instances, advice_on_device=True)
-        assert total_f == 0, fails
+        pb.check_proof()
         # ---- the q_1 cell of S3_1 (ip(q_0, q_1; m_1, m_0): 0 q_0 m_1 s_0 [q_1] m_0 prod_1) changed on the device: the gate on s_0, one row up
         s, u = next((s, u) for s, _q, u in calls[1]
                     if first[s + u.quot_cell_offset + 2] == (first[s + u.quot_cell_offset - 1][0], first[s + u.quot_cell_offset - 1][1] + 3))   # (no break cuts the gate)
-        (c, r), (c0, r0) = first[s + u.quot_cell_offset], first[s + u.quot_cell_offset - 1]
-        ctx.upload(d_cols[c] + 32 * r, fr([(_ints(advice[c][r:r + 1])[0] + 1) % R]))
-        total_f, fails = PL.check_witness(gpk, d_cols + d_lks, instances, max_failures=64, advice_on_device=True)
+        c0, r0 = first[s + u.quot_cell_offset - 1]
+        total_f, fails = pb.changed(s + u.quot_cell_offset)
         assert total_f >= 1 and any(f.kind == "gate" and f.column == c0 and f.row == r0 for f in fails), fails
-    finally:
-        ctx.free(d_gate)
-        ctx.free(d_lookup)
-        gpk.free()
-        kzg.free()

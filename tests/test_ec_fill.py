@@ -32,7 +32,7 @@ def test_layout_and_range_tables_equal_the_definition():
 @pytest.mark.parametrize("modulus", sorted(K.MODULI))
 @pytest.mark.parametrize("n,k,lb", K.PARAMS, ids=["%d_%d_%d" % p for p in K.PARAMS])
 def test_fill_against_its_definition(ctx, n, k, lb, modulus, op):
-    K.check_fill(ctx, n, k, lb, modulus, K.OPS[op], 5)
+    K.check_op_fill(ctx, n, k, lb, modulus, K.OPS[op], 5)
 
 
 @pytest.mark.parametrize("op", sorted(K.OPS))
@@ -40,13 +40,13 @@ def test_fill_against_its_definition(ctx, n, k, lb, modulus, op):
 def test_one_unit_per_call(ctx, n, k, lb, op):
     sp = K.Spec(n, k, lb, K.SECP_P)
     pool = K.operand_pool(sp, "secp256k1_p")
-    K.check_fill(ctx, n, k, lb, "secp256k1_p", K.OPS[op], 1, pool=pool[:2] + pool[6:10] + pool[-3:])
+    K.check_op_fill(ctx, n, k, lb, "secp256k1_p", K.OPS[op], 1, pool=pool[:2] + pool[6:10] + pool[-3:])
 
 
 @pytest.mark.parametrize("op", sorted(K.OPS))
 @pytest.mark.parametrize("n,k,lb", [(88, 3, 8), (64, 4, 8)])
 def test_lookup_cells_over_two_columns(ctx, n, k, lb, op):
-    K.check_fill(ctx, n, k, lb, "secp256k1_n", K.OPS[op], 5, nl=2)
+    K.check_op_fill(ctx, n, k, lb, "secp256k1_n", K.OPS[op], 5, nl=2)
 
 
 def test_reductions_with_different_carry_widths(ctx):
@@ -61,7 +61,7 @@ def test_points_read_from_a_previous_calls_results(ctx, n, k, lb):
 @pytest.mark.parametrize("ncols", [2, 3])
 @pytest.mark.parametrize("case", K.BREAK_CASES)
 def test_column_breaks_as_assign_witnesses_makes_them(ctx, case, ncols):
-    K.check_breaks(ctx, case, ncols)
+    K.check_op_breaks(ctx, case, ncols)
 
 
 def test_rejections(ctx):

@@ -20,7 +20,7 @@ def ctx():
 @pytest.mark.parametrize("modulus", sorted(K.MODULI))
 @pytest.mark.parametrize("n,k,lb", K.PARAMS, ids=["%d_%d_%d" % p for p in K.PARAMS])
 def test_fill_against_its_definition(ctx, n, k, lb, modulus, op):
-    K.check_fill(ctx, n, k, lb, modulus, K.OPS[op], 5)
+    K.check_op_fill(ctx, n, k, lb, modulus, K.OPS[op], 5)
 
 
 @pytest.mark.parametrize("op", sorted(K.OPS))
@@ -28,13 +28,13 @@ def test_fill_against_its_definition(ctx, n, k, lb, modulus, op):
 def test_one_unit_per_call(ctx, n, k, lb, op):
     sp = K.Spec(n, k, lb, K.SECP_P)
     pool = K.operand_pool(sp, "secp256k1_p")
-    K.check_fill(ctx, n, k, lb, "secp256k1_p", K.OPS[op], 1, pool=pool[:2] + pool[6:10] + pool[-3:])
+    K.check_op_fill(ctx, n, k, lb, "secp256k1_p", K.OPS[op], 1, pool=pool[:2] + pool[6:10] + pool[-3:])
 
 
 @pytest.mark.parametrize("op", sorted(K.OPS))
 @pytest.mark.parametrize("n,k,lb", [(88, 3, 8), (64, 4, 8)])
 def test_lookup_cells_over_two_columns(ctx, n, k, lb, op):
-    K.check_fill(ctx, n, k, lb, "secp256k1_n", K.OPS[op], 5, nl=2)
+    K.check_op_fill(ctx, n, k, lb, "secp256k1_n", K.OPS[op], 5, nl=2)
 
 
 def test_reductions_with_different_carry_widths(ctx):
@@ -49,7 +49,7 @@ def test_points_read_from_a_previous_calls_results(ctx, n, k, lb):
 @pytest.mark.parametrize("op", sorted(K.OPS))
 @pytest.mark.parametrize("count", [K.SOLVE_BLOCK - 1, K.SOLVE_BLOCK, K.SOLVE_BLOCK + 1], ids=["one_before", "on_the_edge", "one_past"])
 def test_units_around_the_solving_workgroup(ctx, count, op):
-    K.check_fill(ctx, 88, 3, 18, "secp256k1_p", K.OPS[op], count)
+    K.check_op_fill(ctx, 88, 3, 18, "secp256k1_p", K.OPS[op], count)
 
 
 @pytest.mark.parametrize("op", sorted(K.OPS))
@@ -59,13 +59,13 @@ def test_units_around_the_placing_workgroup(ctx, edge, op):
     slots = K.segments(3, K.OPS[op])
     count = edge * pow(slots, -1, K.PLACE_BLOCK) % K.PLACE_BLOCK or K.PLACE_BLOCK
     assert (count * slots - edge) % K.PLACE_BLOCK == 0 and count * slots > K.PLACE_BLOCK
-    K.check_fill(ctx, 88, 3, 8, "secp256k1_p", K.OPS[op], count)
+    K.check_op_fill(ctx, 88, 3, 8, "secp256k1_p", K.OPS[op], count)
 
 
 @pytest.mark.parametrize("ncols", [2, 3])
 @pytest.mark.parametrize("case", K.BREAK_CASES)
 def test_column_breaks_as_assign_witnesses_makes_them(ctx, case, ncols):
-    K.check_breaks(ctx, case, ncols)
+    K.check_op_breaks(ctx, case, ncols)
 
 
 def test_rejections(ctx):

@@ -57,7 +57,7 @@ def test_one_unit_per_call_and_no_results(ctx):
 def test_column_breaks_as_assign_witnesses_makes_them(ctx, name, case, ncols):
     if case == "two" and ncols == 2:
         ncols = 3   # (two breaks in one unit need three columns: the case runs there under both ids)
-    S.check_breaks(ctx, name, case, ncols)
+    S.check_select_breaks(ctx, name, case, ncols)
 
 
 @pytest.mark.parametrize("curve", sorted(S.CURVES))

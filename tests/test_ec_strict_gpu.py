@@ -89,7 +89,7 @@ def test_strict_addition_reads_a_subtractions_results(ctx, n, k, lb):
 @pytest.mark.parametrize("ncols", [2, 3])
 @pytest.mark.parametrize("case", S.BREAK_CASES)
 def test_column_breaks_as_assign_witnesses_makes_them(ctx, case, ncols):
-    S.check_breaks(ctx, case, ncols)
+    S.check_strict_breaks(ctx, case, ncols)
 
 
 def test_rejections(ctx):

@@ -31,18 +31,18 @@ def test_trace_seek_equals_assign_witnesses_placement_on_an_exhaustive_grid():
 @pytest.mark.parametrize("modulus", sorted(K.MODULI))
 @pytest.mark.parametrize("n,k,lb", K.PARAMS, ids=["%d_%d_%d" % p for p in K.PARAMS])
 def test_fill_against_its_definition(ctx, n, k, lb, modulus):
-    K.check_fill(ctx, n, k, lb, modulus, 5)
+    K.check_mul_fill(ctx, n, k, lb, modulus, 5)
 
 
 @pytest.mark.parametrize("n,k,lb", K.PARAMS, ids=["%d_%d_%d" % p for p in K.PARAMS])
 def test_one_unit_per_call(ctx, n, k, lb):
     sp = K.Spec(n, k, lb, K.SECP_P)
-    K.check_fill(ctx, n, k, lb, "secp256k1_p", 1, pairs=K.operand_pairs(sp, 0xF9)[14:22] + K.operand_pairs(sp, 0xF9)[-2:])
+    K.check_mul_fill(ctx, n, k, lb, "secp256k1_p", 1, pairs=K.operand_pairs(sp, 0xF9)[14:22] + K.operand_pairs(sp, 0xF9)[-2:])
 
 
 @pytest.mark.parametrize("n,k,lb", [(88, 3, 8), (64, 4, 8)])
 def test_lookup_cells_over_two_columns(ctx, n, k, lb):
-    K.check_fill(ctx, n, k, lb, "secp256k1_n", 5, nl=2)
+    K.check_mul_fill(ctx, n, k, lb, "secp256k1_n", 5, nl=2)
 
 
 @pytest.mark.parametrize("n,k,lb", [(88, 3, 8), (64, 4, 8)])
@@ -57,7 +57,7 @@ def test_results_may_be_null(ctx):
 @pytest.mark.parametrize("ncols", [2, 3])
 @pytest.mark.parametrize("case", K.BREAK_CASES)
 def test_column_breaks_as_assign_witnesses_makes_them(ctx, case, ncols):
-    K.check_breaks(ctx, case, ncols)
+    K.check_mul_breaks(ctx, case, ncols)
 
 
 def test_rejections(ctx):
