@@ -918,11 +918,15 @@ static int msm_reserve(h2hip_ctx *ctx, const MsmPlan &p, XYZZ29 *ext_buckets, Ms
 static int zero_or_await_buckets(h2hip_ctx *ctx, const MsmPlan &p, XYZZ29 *buckets, bool external, bool external_zeroed) {
     if (external) {
         if (!external_zeroed) H2_HIPCHK(hipMemsetAsync(buckets, 0, p.buckets_bytes, ctx->stream));
-    } else if (buckets_prezeroed(ctx, 0, buckets, p.buckets_bytes)) {
-        H2_HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->clean_ev, 0));
-    } else {
-        H2_HIPCHK(hipMemsetAsync(buckets, 0, p.buckets_bytes, ctx->stream));
+        return H2HIP_OK;
     }
+    // a fill of THIS buffer may still be pending on the clean stream even when it covered fewer bytes than this MSM needs (a small MSM before a
+    // larger one): it is ordered behind the previous reduction only, so the stream waits for it either way, or it could land behind the fill
+    // below and wipe partial sums in the head of the array (the batch's shared array: fill_pending, msm_batch.hip)
+    const bool fill_pending = ctx->clean_ev && ctx->clean_ptr[0] == buckets;
+    const bool zeroed = buckets_prezeroed(ctx, 0, buckets, p.buckets_bytes);
+    if (zeroed || fill_pending) H2_HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->clean_ev, 0));
+    if (!zeroed) H2_HIPCHK(hipMemsetAsync(buckets, 0, p.buckets_bytes, ctx->stream));
     return H2HIP_OK;
 }
 // digits, histogram, its scans, scatter: s.sval holds the entries in bucket order, s.offsets the buckets' boundaries

@@ -20,44 +20,91 @@ def ints(hexes):
     return [int(h, 16) for h in hexes]
 
 
-def check_backend_against_golden(ctx):
+def golden_steps():
+    """the committed small cases as named steps, in the order check_backend_against_golden runs them: [(name, step(ctx))].  Every step carries its
+    own expected values and asserts them itself, so the steps can run in any order on one context (tests/context_state_checks.py does)"""
     g = load("hotpath_small_cases.json")
+    steps = []
+
+    def step(f):
+        steps.append((f.__name__, f))
+        return f
+
     # MSM
     m = g["msm"]
     pts = [(int(x, 16), int(y, 16)) for x, y in m["bases_xy"]]
-    want = (int(m["result_xy"][0], 16), int(m["result_xy"][1], 16))
-    for flags in (0, 1):
+    want_msm = (int(m["result_xy"][0], 16), int(m["result_xy"][1], 16))
+
+    def msm(ctx, flags):
         b = ctx.bases_upload(O.points_to_limbs(pts), flags)
-        got = ctx.msm(b, fr(ints(m["scalars"])), H.POINT_AFFINE)
-        assert O.limbs_to_points(got)[0] == want
-        b.free()
+        try:
+            got = ctx.msm(b, fr(ints(m["scalars"])), H.POINT_AFFINE)
+            assert O.limbs_to_points(got)[0] == want_msm
+        finally:
+            b.free()
+
+    @step
+    def msm_plain_bases(ctx):
+        msm(ctx, 0)
+
+    @step
+    def msm_precomputed_bases(ctx):
+        msm(ctx, 1)
+
     # NTT family
     t = g["ntt"]
     k, ek, a, w = t["k"], t["extended_k"], fr(ints(t["input"])), int(t["omega"], 16)
-    assert O.limbs_to_ints(ctx.best_fft(a, fr([w]), k), R) == ints(t["best_fft"])
-    assert O.limbs_to_ints(ctx.ifft(a, fr([O.inv_mod(w, R)]), k, fr([O.inv_mod(1 << k, R)])), R) == ints(t["ifft"])
-    ext_w = O.omega_for(ek)
-    ext = ctx.coeff_to_extended(a, k, ek, fr([ext_w]), fr([O.ZETA]))
-    assert O.limbs_to_ints(ext, R) == ints(t["coeff_to_extended"])
-    back = ctx.extended_to_coeff(ext, ek, fr([O.inv_mod(ext_w, R)]), fr([O.inv_mod(1 << ek, R)]), fr([O.ZETA * O.ZETA % R]))
-    assert O.limbs_to_ints(back[: 1 << k], R) == ints(t["input"]) and not back[1 << k:].any()
+
+    @step
+    def best_fft(ctx):
+        assert O.limbs_to_ints(ctx.best_fft(a, fr([w]), k), R) == ints(t["best_fft"])
+
+    @step
+    def ifft(ctx):
+        assert O.limbs_to_ints(ctx.ifft(a, fr([O.inv_mod(w, R)]), k, fr([O.inv_mod(1 << k, R)])), R) == ints(t["ifft"])
+
+    @step
+    def coeff_to_extended_and_back(ctx):
+        ext_w = O.omega_for(ek)
+        ext = ctx.coeff_to_extended(a, k, ek, fr([ext_w]), fr([O.ZETA]))
+        assert O.limbs_to_ints(ext, R) == ints(t["coeff_to_extended"])
+        back = ctx.extended_to_coeff(ext, ek, fr([O.inv_mod(ext_w, R)]), fr([O.inv_mod(1 << ek, R)]), fr([O.ZETA * O.ZETA % R]))
+        assert O.limbs_to_ints(back[: 1 << k], R) == ints(t["input"]) and not back[1 << k:].any()
+
     # pointwise
     p = g["poly"]
     c, x = fr(ints(p["coeffs"])), fr([int(p["x"], 16)])
-    assert O.limbs_to_ints(ctx.fr_eval_polynomial(c, x), R) == [int(p["eval"], 16)]
-    assert O.limbs_to_ints(ctx.fr_kate_division(c, x), R) == ints(p["kate_division"])
     cv = ints(p["coeffs"])
-    assert O.limbs_to_ints(ctx.fr_batch_invert(fr(cv[:8] + [0])), R) == ints(p["batch_invert"])
-    assert O.limbs_to_ints(ctx.fr_grand_product(fr(cv[:16]), fr(cv[16:32])), R) == ints(p["grand_product"])
+
+    @step
+    def eval_polynomial(ctx):
+        assert O.limbs_to_ints(ctx.fr_eval_polynomial(c, x), R) == [int(p["eval"], 16)]
+
+    @step
+    def kate_division(ctx):
+        assert O.limbs_to_ints(ctx.fr_kate_division(c, x), R) == ints(p["kate_division"])
+
+    @step
+    def batch_invert(ctx):
+        assert O.limbs_to_ints(ctx.fr_batch_invert(fr(cv[:8] + [0])), R) == ints(p["batch_invert"])
+
+    @step
+    def grand_product(ctx):
+        assert O.limbs_to_ints(ctx.fr_grand_product(fr(cv[:16]), fr(cv[16:32])), R) == ints(p["grand_product"])
+
     # lookup permutation
     lk = g["lookup_permute"]
-    ap, sp = ctx.lookup_permute(fr(lk["input"]), fr(lk["table"]), len(lk["input"]))
-    assert O.limbs_to_ints(ap, R) == lk["permuted_input"] and O.limbs_to_ints(sp, R) == lk["permuted_table"]
+
+    @step
+    def lookup_permute(ctx):
+        ap, sp = ctx.lookup_permute(fr(lk["input"]), fr(lk["table"]), len(lk["input"]))
+        assert O.limbs_to_ints(ap, R) == lk["permuted_input"] and O.limbs_to_ints(sp, R) == lk["permuted_table"]
+
     # Poseidon: the reference's own KATs
     kats = load("poseidon_reference_kats.json")
     from oracle.poseidon import Spec
 
-    for key in ("t3", "t5"):
+    def poseidon(ctx, key):
         kat = kats[key]
         spec = Spec(kat["t"], kat["r_f"], kat["r_p"])
         if "mds" in kat:
@@ -65,6 +112,21 @@ def check_backend_against_golden(ctx):
         ctx.poseidon_set_spec(kat["t"], kat["r_f"], kat["r_p"], fr([v for row in spec.constants for v in row]), fr([v for row in spec.mds for v in row]))
         out = ctx.poseidon_permute(fr(kat["state_in"]).reshape(1, kat["t"], 4), fr(kat["inputs"]).reshape(1, -1, 4))
         assert O.limbs_to_ints(out.reshape(-1, 4), R) == [int(v) for v in kat["state_out"]]
+
+    @step
+    def poseidon_t3(ctx):
+        poseidon(ctx, "t3")
+
+    @step
+    def poseidon_t5(ctx):
+        poseidon(ctx, "t5")
+
+    return steps
+
+
+def check_backend_against_golden(ctx):
+    for _name, step in golden_steps():
+        step(ctx)
 
 
 def check_c_oracle_against_golden():
