@@ -123,11 +123,30 @@ class ConstraintSystemShape(C.Structure):
                 ("usable_rows", C.c_uint32), ("quotient_pieces", C.c_uint32), ("num_commitments", C.c_uint32), ("num_evals", C.c_uint32)]
 
 
+class _Kind(NamedTuple):
+    """what differs between the circuit kinds on the way into libh2hip"""
+    id: int                   # H2HIP_CIRCUIT_*
+    shape_of: str             # the per-kind entries' names
+    keygen: str
+    verify_proof: str
+    phased: bool              # the advice is committed phase by phase: create_proof takes phase 0's columns and a phase_witness
+    verify_instances: bool    # the verify entry takes instance columns
+    batched: bool             # h2hip_plonk_verify_batch serves the kind
+
+
+_KIND_OF = {
+    BaseCircuitParams: _Kind(0, "h2hip_plonk_shape_of", "h2hip_plonk_keygen", "h2hip_plonk_verify_proof", False, True, True),
+    DynLookupCircuitParams: _Kind(1, "h2hip_plonk_shape_of_dyn", "h2hip_plonk_keygen_dyn", "h2hip_plonk_verify_proof_dyn", False, False, True),
+    PhasedCircuitParams: _Kind(2, "h2hip_plonk_shape_of_phased", "h2hip_plonk_keygen_phased", "h2hip_plonk_verify_proof_phased", True, True, True),
+    RlcCircuitParams: _Kind(3, "h2hip_plonk_shape_of_rlc", "h2hip_plonk_keygen_rlc", "h2hip_plonk_verify_proof_rlc", True, True, False),
+}
+_CIRCUIT_KINDS = {t: k.id for t, k in _KIND_OF.items() if k.batched}   # the kinds h2hip_plonk_verify_batch takes (RLC keys: not batched)
+_CIRCUIT_RLC = _KIND_OF[RlcCircuitParams].id   # H2HIP_CIRCUIT_RLC: h2hip_plonk_verify_proof_transcript only
+
+
 def shape_of(ctx: Context, params) -> ConstraintSystemShape:
     out = ConstraintSystemShape()
-    fn = {DynLookupCircuitParams: ctx.lib.h2hip_plonk_shape_of_dyn, PhasedCircuitParams: ctx.lib.h2hip_plonk_shape_of_phased,
-          RlcCircuitParams: ctx.lib.h2hip_plonk_shape_of_rlc}.get(type(params), ctx.lib.h2hip_plonk_shape_of)
-    ctx._chk(fn(C.byref(params), C.byref(out)))
+    ctx._chk(getattr(ctx.lib, _KIND_OF[type(params)].shape_of)(C.byref(params), C.byref(out)))
     return out
 
 
@@ -383,11 +402,45 @@ def keygen(kzg: ParamsKZG, params, fixed: Sequence[np.ndarray], copies) -> Provi
     copies = np.ascontiguousarray(copies, dtype=np.uint32).reshape(-1, 4)
     arr = (_vp * len(cols))(*[_vp(c.ctypes.data) for c in cols])
     out = _vp()
-    fn = {DynLookupCircuitParams: ctx.lib.h2hip_plonk_keygen_dyn, PhasedCircuitParams: ctx.lib.h2hip_plonk_keygen_phased,
-          RlcCircuitParams: ctx.lib.h2hip_plonk_keygen_rlc}.get(type(params), ctx.lib.h2hip_plonk_keygen)
-    ctx._chk(fn(ctx.handle, C.byref(params), kzg.g.handle, kzg.g_lagrange.handle, arr, _vp(copies.ctypes.data), len(copies),
-                                        C.byref(out)))
+    fn = getattr(ctx.lib, _KIND_OF[type(params)].keygen)
+    ctx._chk(fn(ctx.handle, C.byref(params), kzg.g.handle, kzg.g_lagrange.handle, arr, _vp(copies.ctypes.data), len(copies), C.byref(out)))
     return ProvingKey(ctx, out, params, shape, kzg)
+
+
+# ---- argument groups several entries share: (the arguments, the arrays they point into)
+def _advice_args(who: str, advice: Sequence, n: int, on_device: bool):
+    """the advice column pointer array over host (n,4) arrays or device pointers"""
+    if on_device:
+        return (_vp * len(advice))(*[_vp(int(p)) for p in advice]), None
+    keep = [_fe(c) for c in advice]
+    if any(len(c) != n for c in keep):
+        raise ValueError("%s: advice columns must have 2^k elements" % who)
+    return (_vp * len(keep))(*[_vp(c.ctypes.data) for c in keep]), keep
+
+
+def _column_arrays(cols: Sequence[np.ndarray]):
+    """the pointer and length arrays over host columns"""
+    return (_vp * max(len(cols), 1))(*[_vp(c.ctypes.data) for c in cols]), (C.c_size_t * max(len(cols), 1))(*[len(c) for c in cols])
+
+
+def _instance_args(who: str, params, instances: Sequence[np.ndarray]):
+    inst = [_fe(c) for c in instances]
+    if len(inst) != params.num_instance:
+        raise ValueError("%s: need %d instance columns" % (who, params.num_instance))
+    return _column_arrays(inst), inst
+
+
+def _vk_args(who: str, pk: ProvingKey):
+    """the verifying key as the verify entries take it: fixed and permutation commitments, transcript_repr, g[0], g2, s_g2"""
+    ctx, kzg = pk.ctx, pk.kzg
+    if len(kzg.g2_raw) != 256:
+        raise ValueError("%s: the ParamsKZG carries no G2 elements (g2_raw)" % who)
+    if not hasattr(kzg, "_g0"):
+        kzg._g0 = ctx.bases_download(kzg.g)[:1].copy()
+    g2 = np.frombuffer(kzg.g2_raw, dtype=np.uint8).copy()
+    pc = pk.permutation_commitments if len(pk.permutation_commitments) else np.zeros((1, 8), dtype=np.uint64)
+    keep = [np.ascontiguousarray(pk.fixed_commitments), np.ascontiguousarray(pc), fr_limbs(pk.transcript_repr), kzg._g0, g2]
+    return tuple(_ptr(a) for a in keep[:4]) + (_vp(g2.ctypes.data), _vp(g2.ctypes.data + 128)), keep
 
 
 def create_proof(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarray], rng, timings: Optional[dict] = None,
@@ -404,25 +457,14 @@ def create_proof(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarra
     has it, else None.  An exception raised inside a method aborts the proof and is re-raised here."""
     ctx, sh = pk.ctx, pk.shape
     n = 1 << pk.params.k
-    phased = isinstance(pk.params, (PhasedCircuitParams, RlcCircuitParams))
+    phased = _KIND_OF[type(pk.params)].phased
     if phase_witness is not None and phase_witness_dev is not None:
         raise ValueError("create_proof: give phase_witness or phase_witness_dev, not both")
     want = len(pk.params.phase_columns()[0]) if phased else sh.num_advice_total
     if len(advice) != want:
         raise ValueError("create_proof: need %d advice columns" % want)
-    keep = None
-    if advice_on_device:
-        adv = (_vp * len(advice))(*[_vp(int(p)) for p in advice])
-    else:
-        keep = [_fe(c) for c in advice]
-        if any(len(c) != n for c in keep):
-            raise ValueError("create_proof: advice columns must have 2^k elements")
-        adv = (_vp * len(keep))(*[_vp(c.ctypes.data) for c in keep])
-    inst = [_fe(c) for c in instances]
-    if len(inst) != pk.params.num_instance:
-        raise ValueError("create_proof: need %d instance columns" % pk.params.num_instance)
-    ip = (_vp * max(len(inst), 1))(*[_vp(c.ctypes.data) for c in inst])
-    il = (C.c_size_t * max(len(inst), 1))(*[len(c) for c in inst])
+    adv, keep = _advice_args("create_proof", advice, n, advice_on_device)
+    (ip, il), inst = _instance_args("create_proof", pk.params, instances)
     err = []
 
     def _fill(_user, out, count):
@@ -508,9 +550,6 @@ def _phase_witness_trampoline(ctx: Context, n: int, phase_witness, err: list, ph
     return _PhaseWitness(C.cast(cb, _vp), None), cb
 
 
-_CIRCUIT_RLC = 3   # H2HIP_CIRCUIT_RLC: h2hip_plonk_verify_proof_transcript only
-
-
 def verify_proof(pk: ProvingKey, instances: Sequence[np.ndarray], proof: Optional[bytes] = None, transcript=None, want_accumulator: bool = False):
     """verify_proof with the key's verifying half (VerifierSHPLONK, SingleStrategy) — check_proof of halo2-base/src/utils/testing.rs:64-88.
     Host code inside libh2hip; needs the G2 half of the SRS (ParamsKZG.g2_raw).
@@ -519,70 +558,34 @@ def verify_proof(pk: ProvingKey, instances: Sequence[np.ndarray], proof: Optiona
     returns a bad value, rejects the proof (the exception is dropped: a malformed proof is not an error); an exception in common_scalar or
     squeeze_challenge is re-raised.  If the object has exhausted(), input left over rejects the proof.  want_accumulator: return (accepted,
     acc) with acc the (2, 8) uint64 pair (W', outer) the pairing decides (zeros when the proof is malformed)."""
-    ctx, kzg = pk.ctx, pk.kzg
     if transcript is not None:
         if proof is not None:
             raise ValueError("verify_proof: give proof or transcript, not both")
         return _verify_proof_transcript(pk, instances, transcript, want_accumulator)
     if want_accumulator:
         raise ValueError("verify_proof: want_accumulator needs transcript=")
-    if len(kzg.g2_raw) != 256:
-        raise ValueError("verify_proof: the ParamsKZG carries no G2 elements (g2_raw)")
-    inst = [_fe(c) for c in instances]
-    if len(inst) != pk.params.num_instance:
-        raise ValueError("verify_proof: need %d instance columns" % pk.params.num_instance)
-    ip = (_vp * max(len(inst), 1))(*[_vp(c.ctypes.data) for c in inst])
-    il = (C.c_size_t * max(len(inst), 1))(*[len(c) for c in inst])
-    g0 = ctx.bases_download(kzg.g)[:1].copy() if not hasattr(kzg, "_g0") else kzg._g0
-    kzg._g0 = g0
-    g2 = np.frombuffer(kzg.g2_raw, dtype=np.uint8).copy()
+    ctx, kind = pk.ctx, _KIND_OF[type(pk.params)]
+    vk, keep = _vk_args("verify_proof", pk)
+    (ip, il), inst = _instance_args("verify_proof", pk.params, instances)
     buf = np.frombuffer(bytes(proof), dtype=np.uint8).copy()
     ok = C.c_int(0)
-    pc = pk.permutation_commitments if len(pk.permutation_commitments) else np.zeros((1, 8), dtype=np.uint64)
-    if isinstance(pk.params, RlcCircuitParams):
-        ctx._chk(ctx.lib.h2hip_plonk_verify_proof_rlc(C.byref(pk.params), _ptr(np.ascontiguousarray(pk.fixed_commitments)), _ptr(np.ascontiguousarray(pc)),
-                                                      _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128), ip, il,
-                                                      _vp(buf.ctypes.data), len(buf), C.byref(ok)))
-        return bool(ok.value)
-    if isinstance(pk.params, PhasedCircuitParams):
-        ctx._chk(ctx.lib.h2hip_plonk_verify_proof_phased(C.byref(pk.params), _ptr(np.ascontiguousarray(pk.fixed_commitments)), _ptr(np.ascontiguousarray(pc)),
-                                                         _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128), ip, il,
-                                                         _vp(buf.ctypes.data), len(buf), C.byref(ok)))
-        return bool(ok.value)
-    if isinstance(pk.params, DynLookupCircuitParams):
-        ctx._chk(ctx.lib.h2hip_plonk_verify_proof_dyn(C.byref(pk.params), _ptr(np.ascontiguousarray(pk.fixed_commitments)), _ptr(np.ascontiguousarray(pc)),
-                                                      _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128),
-                                                      _vp(buf.ctypes.data), len(buf), C.byref(ok)))
-        return bool(ok.value)
-    ctx._chk(ctx.lib.h2hip_plonk_verify_proof(C.byref(pk.params), _ptr(np.ascontiguousarray(pk.fixed_commitments)), _ptr(np.ascontiguousarray(pc)),
-                                              _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128), ip, il,
-                                              _vp(buf.ctypes.data), len(buf), C.byref(ok)))
+    ctx._chk(getattr(ctx.lib, kind.verify_proof)(C.byref(pk.params), *vk, *((ip, il) if kind.verify_instances else ()), _vp(buf.ctypes.data), len(buf),
+                                                 C.byref(ok)))
+    del keep
     return bool(ok.value)
 
 
 def _verify_proof_transcript(pk: ProvingKey, instances, transcript, want_accumulator: bool):
-    ctx, kzg = pk.ctx, pk.kzg
-    if len(kzg.g2_raw) != 256:
-        raise ValueError("verify_proof: the ParamsKZG carries no G2 elements (g2_raw)")
-    inst = [_fe(c) for c in instances]
-    if len(inst) != pk.params.num_instance:
-        raise ValueError("verify_proof: need %d instance columns" % pk.params.num_instance)
-    ip = (_vp * max(len(inst), 1))(*[_vp(c.ctypes.data) for c in inst])
-    il = (C.c_size_t * max(len(inst), 1))(*[len(c) for c in inst])
-    g0 = ctx.bases_download(kzg.g)[:1].copy() if not hasattr(kzg, "_g0") else kzg._g0
-    kzg._g0 = g0
-    g2 = np.frombuffer(kzg.g2_raw, dtype=np.uint8).copy()
-    pc = pk.permutation_commitments if len(pk.permutation_commitments) else np.zeros((1, 8), dtype=np.uint64)
-    kind = _CIRCUIT_RLC if isinstance(pk.params, RlcCircuitParams) else _CIRCUIT_KINDS[type(pk.params)]
+    ctx = pk.ctx
+    vk, keep_vk = _vk_args("verify_proof", pk)
+    (ip, il), inst = _instance_args("verify_proof", pk.params, instances)
     err = []
     tr, keep = _transcript_trampolines(transcript, err)
     ok = C.c_int(0)
     acc = np.zeros((2, 8), dtype=np.uint64)
-    rc = ctx.lib.h2hip_plonk_verify_proof_transcript(kind, C.cast(C.byref(pk.params), _vp), _ptr(np.ascontiguousarray(pk.fixed_commitments)),
-                                                     _ptr(np.ascontiguousarray(pc)), _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data),
-                                                     _vp(g2.ctypes.data + 128), ip if inst else None, il if inst else None, C.byref(tr),
-                                                     C.byref(ok), _ptr(acc))
-    del keep
+    rc = ctx.lib.h2hip_plonk_verify_proof_transcript(_KIND_OF[type(pk.params)].id, C.cast(C.byref(pk.params), _vp), *vk, ip if inst else None,
+                                                     il if inst else None, C.byref(tr), C.byref(ok), _ptr(acc))
+    del keep, keep_vk
     if rc != 0 and err:   # the transcript failed where no proof byte is involved
         raise err[0]
     ctx._chk(rc)
@@ -592,34 +595,26 @@ def _verify_proof_transcript(pk: ProvingKey, instances, transcript, want_accumul
     return (accepted, acc) if want_accumulator else accepted
 
 
-_CIRCUIT_KINDS = {BaseCircuitParams: 0, DynLookupCircuitParams: 1, PhasedCircuitParams: 2}   # H2HIP_CIRCUIT_BASE / _DYN / _PHASED (RLC keys: not batched)
-
-
 def verify_batch(pk: ProvingKey, instances_per_proof: Sequence, proofs: Sequence[bytes], rng=None, want_rejected: bool = False,
                  want_acc: bool = False, kind: Optional[int] = None):
     """h2hip_plonk_verify_batch: every proof of `proofs` under pk's verifying key with one pairing; the points are decompressed and the scalar
     multiplications run on the GPU.  -> (accepted, rejected: list[bool] or None, acc: (2, 8) uint64 array (L, R) or None).  rng draws one
     combiner per proof in one call: ArrayRng / ChaChaRng / any object with fill_into(dst, n); None = a ChaChaRng seeded from os.urandom, host
     draws."""
-    ctx, kzg = pk.ctx, pk.kzg
-    if len(kzg.g2_raw) != 256:
-        raise ValueError("verify_batch: the ParamsKZG carries no G2 elements (g2_raw)")
+    ctx = pk.ctx
+    if kind is None:
+        kind = _CIRCUIT_KINDS[type(pk.params)]
+    vk, keep_vk = _vk_args("verify_batch", pk)
     if len(instances_per_proof) != len(proofs):
         raise ValueError("verify_batch: need one list of instance columns per proof")
     ni, count = pk.params.num_instance, len(proofs)
     inst = [[_fe(c) for c in cols] for cols in instances_per_proof]
     if any(len(cols) != ni for cols in inst):
         raise ValueError("verify_batch: need %d instance columns per proof" % ni)
-    flat = [c for cols in inst for c in cols]
-    ip = (_vp * max(len(flat), 1))(*[_vp(c.ctypes.data) for c in flat])
-    il = (C.c_size_t * max(len(flat), 1))(*[len(c) for c in flat])
+    ip, il = _column_arrays([c for cols in inst for c in cols])
     bufs = [np.frombuffer(bytes(p), dtype=np.uint8).copy() if len(p) else np.zeros(1, dtype=np.uint8) for p in proofs]
     pp = (_vp * max(count, 1))(*[_vp(b.ctypes.data) for b in bufs])
     pl = (C.c_size_t * max(count, 1))(*[len(p) for p in proofs])
-    g0 = ctx.bases_download(kzg.g)[:1].copy() if not hasattr(kzg, "_g0") else kzg._g0
-    kzg._g0 = g0
-    g2 = np.frombuffer(kzg.g2_raw, dtype=np.uint8).copy()
-    pc = pk.permutation_commitments if len(pk.permutation_commitments) else np.zeros((1, 8), dtype=np.uint64)
     if rng is None:
         import os
 
@@ -637,11 +632,10 @@ def verify_batch(pk: ProvingKey, instances_per_proof: Sequence, proofs: Sequence
     ok = C.c_int(0)
     rejected = np.zeros(max(count, 1), dtype=np.uint8) if want_rejected else None
     acc = np.zeros((2, 8), dtype=np.uint64) if want_acc else None
-    rc = ctx.lib.h2hip_plonk_verify_batch(ctx.handle, _CIRCUIT_KINDS[type(pk.params)] if kind is None else kind, C.cast(C.byref(pk.params), _vp),
-                                          _ptr(np.ascontiguousarray(pk.fixed_commitments)), _ptr(np.ascontiguousarray(pc)),
-                                          _ptr(fr_limbs(pk.transcript_repr)), _ptr(g0), _vp(g2.ctypes.data), _vp(g2.ctypes.data + 128), count,
-                                          ip if ni else None, il if ni else None, pp, pl, C.cast(cb, _vp), None, C.byref(ok),
-                                          _ptr(rejected) if want_rejected else None, _ptr(acc) if want_acc else None)
+    rc = ctx.lib.h2hip_plonk_verify_batch(ctx.handle, kind, C.cast(C.byref(pk.params), _vp), *vk, count, ip if ni else None, il if ni else None, pp, pl,
+                                          C.cast(cb, _vp), None, C.byref(ok), _ptr(rejected) if want_rejected else None,
+                                          _ptr(acc) if want_acc else None)
+    del keep_vk
     if err:
         raise err[0]
     ctx._chk(rc)
@@ -699,19 +693,8 @@ def check_witness(pk: ProvingKey, advice: Sequence, instances: Sequence[np.ndarr
     n = 1 << pk.params.k
     if len(advice) != sh.num_advice_total:
         raise ValueError("check_witness: need %d advice columns" % sh.num_advice_total)
-    keep = None
-    if advice_on_device:
-        adv = (_vp * len(advice))(*[_vp(int(p)) for p in advice])
-    else:
-        keep = [_fe(c) for c in advice]
-        if any(len(c) != n for c in keep):
-            raise ValueError("check_witness: advice columns must have 2^k elements")
-        adv = (_vp * len(keep))(*[_vp(c.ctypes.data) for c in keep])
-    inst = [_fe(c) for c in instances]
-    if len(inst) != pk.params.num_instance:
-        raise ValueError("check_witness: need %d instance columns" % pk.params.num_instance)
-    ip = (_vp * max(len(inst), 1))(*[_vp(c.ctypes.data) for c in inst])
-    il = (C.c_size_t * max(len(inst), 1))(*[len(c) for c in inst])
+    adv, keep = _advice_args("check_witness", advice, n, advice_on_device)
+    (ip, il), inst = _instance_args("check_witness", pk.params, instances)
     out = (WitnessFailureStruct * max(max_failures, 1))()
     total = C.c_size_t(0)
     if challenges is not None:

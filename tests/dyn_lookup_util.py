@@ -1,5 +1,5 @@
 """Shared by the dynamic-lookup tests (CPU-emulated and GPU): a RAMCircuit (virtual_region/tests/lookups/memory.rs:30-158) proven by libh2hip and
-by the test-side CPU prover (tests/dyn_lookup_oracle.py) on the same SRS and RNG stream."""
+by the test-side CPU prover (tests/shape_oracle.py) on the same SRS and RNG stream."""
 import numpy as np
 
 from halo2_lib_amd import halo2_proofs as HP
@@ -7,7 +7,7 @@ from halo2_lib_amd import plonk as PL
 from halo2_lib_amd import virtual_region as V
 from oracle import bn254 as O
 from oracle import plonk as P
-from tests import dyn_lookup_oracle as D
+from tests import shape_oracle as SO
 from tests.util import PreDrawnRng, R
 
 
@@ -29,7 +29,7 @@ def rng_budget(sh):
 
 
 def oracle_shape(params):
-    return D.Shape.dyn(params.k, params.num_advice, params.num_fixed, params.key_cols, params.lu_sets)
+    return SO.Shape.dyn(params.k, params.num_advice, params.num_fixed, params.key_cols, params.lu_sets)
 
 
 def srs(ctx, k, seed):
@@ -52,10 +52,7 @@ def vk_from_gpu(sh, gpk):
 
 
 def oracle_verify(params, vk, proof):
-    try:
-        return D.verify_proof(params, vk, [], proof)
-    except P.VerifyError:
-        return False
+    return SO.oracle_verify(params, vk, [], proof)
 
 
 def prove_both(ctx, k, accesses, mem_len, key_cols, lu_sets, seed, threads=2, oracle_prover=True):
@@ -74,7 +71,7 @@ def prove_both(ctx, k, accesses, mem_len, key_cols, lu_sets, seed, threads=2, or
     if oracle_prover:
         pk = oracle_pk(sh, params, fixed, copies, threads)
         assert pk.vk.transcript_repr == gpk.transcript_repr, "verifying keys differ (fixed / permutation commitments)"
-        want = D.create_proof(params, pk, advice, [], PreDrawnRng(budget, 1000 + seed), threads)
+        want = SO.create_proof(params, pk, advice, [], PreDrawnRng(budget, 1000 + seed), threads)
         vk = pk.vk
     else:
         vk = vk_from_gpu(sh, gpk)

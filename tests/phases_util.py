@@ -1,5 +1,5 @@
 """Shared by the multi-phase tests (CPU-emulated and GPU): a BaseConfig circuit whose later phases hold RLC chains over the earlier phases'
-cells, proven by libh2hip (h2hip_plonk_create_proof_phased) and by the test-side CPU prover (tests/phased_oracle.py) on the same SRS and RNG
+cells, proven by libh2hip (h2hip_plonk_create_proof_phased) and by the test-side CPU prover (tests/shape_oracle.py) on the same SRS and RNG
 stream.
 
 Layout of the circuit (every gate column is enabled on row 0, so keygen's selector rule holds):
@@ -13,9 +13,9 @@ import numpy as np
 
 from halo2_lib_amd import plonk as PL
 from oracle import bn254 as O
-from oracle import plonk as P
-from tests import phased_oracle as PO
+from tests import shape_oracle as SO
 from tests.dyn_lookup_util import oracle_pk, rng_budget, srs, vk_from_gpu
+from tests.shape_oracle import oracle_verify
 from tests.util import PreDrawnRng, R
 
 NO_CHALLENGE_GAMMA = 7
@@ -24,7 +24,7 @@ NO_CHALLENGE_GAMMA = 7
 class PhasedCircuit:
     def __init__(self, params: PL.PhasedCircuitParams, seed: int, instance: bool = False, bad_lookup: bool = False):
         self.params, self.seed, self.bad_lookup = params, seed, bad_lookup
-        self.sh = PO.Shape.phased(params)
+        self.sh = SO.Shape.phased(params)
         sh = self.sh
         self.n, self.u = sh.n, sh.usable_rows
         self.blocks = self.u // 4
@@ -128,33 +128,31 @@ class PhasedCircuit:
         return [O.ints_to_limbs(v, R) for v in self.instances]
 
 
-def prove_both(ctx, params, seed, instance=False, rng_seed=None, oracle_prover=True, threads=2, witness=None):
-    """keygen + create_proof on libh2hip and (oracle_prover) on the test prover.  -> dict(gpk, kzg, params, vk, got, want, circ, budget)"""
-    circ = PhasedCircuit(params, seed, instance=instance)
+def prove_both(ctx, params, seed, instance=False, rng_seed=None, oracle_prover=True, threads=2, witness=None, circuit=PhasedCircuit):
+    """keygen + create_proof on libh2hip and (oracle_prover) on the test prover, for a circuit class with PhasedCircuit's interface
+    (rlc_checks.RlcCircuit).  -> dict(gpk, kzg, params, vk, got, want, circ, budget, seen, seed)"""
+    circ = circuit(params, seed, instance=instance)
     kzg, srs_params = srs(ctx, params.k, seed)
     gpk = PL.keygen(kzg, params, circ.fixed, circ.copies)
-    budget = rng_budget(circ.sh)
+    sh, gs = circ.sh, gpk.shape
+    assert (gs.degree, gs.extended_k, gs.blinding_factors, gs.usable_rows, gs.num_perm_sets, gs.num_fixed_total, gs.num_advice_total, gs.num_lookups,
+            gs.num_perm_columns) == (sh.degree, sh.extended_k, 6, sh.usable_rows, sh.num_perm_sets, sh.num_fixed_total, sh.num_advice_total,
+                                     len(sh.lookups), len(sh.perm_columns))
+    budget = rng_budget(sh)
     rs = 1000 + seed if rng_seed is None else rng_seed
     got = PL.create_proof(gpk, circ.advice0(), circ.instance_arrays(), PreDrawnRng(budget, rs), phase_witness=witness or circ.witness)
     lib_seen = list(circ.gamma_seen)
     want, vk = None, None
     if oracle_prover:
-        pk = oracle_pk(circ.sh, srs_params, circ.fixed, circ.copies, threads)
+        pk = oracle_pk(sh, srs_params, circ.fixed, circ.copies, threads)
         assert pk.vk.transcript_repr == gpk.transcript_repr, "verifying keys differ (fixed / permutation commitments)"
         circ.gamma_seen.clear()
-        want = PO.create_proof(srs_params, pk, circ.advice0(), circ.instances, PreDrawnRng(budget, rs), threads, phase_witness=circ.witness)
+        want = SO.create_proof(srs_params, pk, circ.advice0(), circ.instances, PreDrawnRng(budget, rs), threads, phase_witness=circ.witness)
         assert circ.gamma_seen == lib_seen, "the witness callback saw different challenges (%s vs %s)" % (lib_seen, circ.gamma_seen)
         vk = pk.vk
     else:
-        vk = vk_from_gpu(circ.sh, gpk)
-    return dict(gpk=gpk, kzg=kzg, params=srs_params, vk=vk, got=got, want=want, circ=circ, budget=budget, seen=lib_seen)
-
-
-def oracle_verify(params, vk, instances, proof):
-    try:
-        return PO.verify_proof(params, vk, instances, proof)
-    except P.VerifyError:
-        return False
+        vk = vk_from_gpu(sh, gpk)
+    return dict(gpk=gpk, kzg=kzg, params=srs_params, vk=vk, got=got, want=want, circ=circ, budget=budget, seen=lib_seen, seed=seed)
 
 
 def first_phase1_commitment(circ) -> int:

@@ -3,7 +3,7 @@ challenge 0), shared by tests/test_rlc.py (the CPU-emulated build) and tests/tes
 
   - the device fill h2hip_rlc_fill_chains_dev and the quotient kernel h2hip_quotient_rlc_gate_batch_dev against their definitions, computed here
     in Python integers;
-  - RlcCircuit: the multi-phase test circuit of tests/phases_util.py with RLC columns, proven by libh2hip and by tests/rlc_oracle.py on the
+  - RlcCircuit: the multi-phase test circuit of tests/phases_util.py with RLC columns, proven by libh2hip and by tests/shape_oracle.py on the
     same SRS and RNG stream;
   - soundness (a phase-1 witness computed from another gamma), the refusals, and that multi-phase keys prove as before.
 """
@@ -13,10 +13,11 @@ import numpy as np
 
 from halo2_lib_amd import plonk as PL
 from oracle import bn254 as O
-from oracle import plonk as P
-from tests import rlc_oracle as RO
-from tests.dyn_lookup_util import oracle_pk, rng_budget, srs, vk_from_gpu
+from tests import phases_util as PU
+from tests import shape_oracle as SO
+from tests.dyn_lookup_util import rng_budget, srs, vk_from_gpu
 from tests.phases_util import PhasedCircuit
+from tests.shape_oracle import oracle_verify
 from tests.util import PreDrawnRng, R, fr, full_range_fr, rand_fr
 
 _vp = C.c_void_p
@@ -215,7 +216,7 @@ class RlcCircuit(PhasedCircuit):
         super().__init__(params.base, seed, instance=instance)
         self.rparams = params
         self.params = params
-        self.sh = RO.Shape.rlc(params)
+        self.sh = SO.Shape.rlc(params)
         self.phase_cols = self.sh.phase_cols
         self.nr = params.num_rlc_advice
         self.rlc = list(self.sh.rlc_advice)
@@ -321,38 +322,6 @@ def shape_b(k, lookup_bits):
     return PL.RlcCircuitParams.new(k, [2, 1], [1, 1], 1, 1, lookup_bits, [1], 2), True
 
 
-def oracle_verify(params, vk, instances, proof):
-    try:
-        return RO.verify_proof(params, vk, instances, proof)
-    except P.VerifyError:
-        return False
-
-
-def prove_both(ctx, params, seed, instance=False, threads=2, oracle_prover=True, witness=None):
-    """keygen + create_proof on libh2hip and on tests/rlc_oracle.py -> dict(gpk, kzg, params, vk, got, want, circ, budget, seen)"""
-    circ = RlcCircuit(params, seed, instance=instance)
-    kzg, srs_params = srs(ctx, params.k, seed)
-    gpk = PL.keygen(kzg, params, circ.fixed, circ.copies)
-    sh, gs = circ.sh, gpk.shape
-    assert (gs.degree, gs.extended_k, gs.blinding_factors, gs.usable_rows, gs.num_perm_sets, gs.num_fixed_total, gs.num_advice_total, gs.num_lookups,
-            gs.num_perm_columns) == (sh.degree, sh.extended_k, 6, sh.usable_rows, sh.num_perm_sets, sh.num_fixed_total, sh.num_advice_total,
-                                     len(sh.lookups), len(sh.perm_columns))
-    budget = rng_budget(sh)
-    got = PL.create_proof(gpk, circ.advice0(), circ.instance_arrays(), PreDrawnRng(budget, 1000 + seed), phase_witness=witness or circ.witness)
-    seen = list(circ.gamma_seen)
-    want = None
-    if oracle_prover:
-        pk = oracle_pk(sh, srs_params, circ.fixed, circ.copies, threads)
-        assert pk.vk.transcript_repr == gpk.transcript_repr, "verifying keys differ (fixed / permutation commitments)"
-        circ.gamma_seen.clear()
-        want = RO.create_proof(srs_params, pk, circ.advice0(), circ.instances, PreDrawnRng(budget, 1000 + seed), threads, phase_witness=circ.witness)
-        assert circ.gamma_seen == seen, "the witness callback saw different challenges"
-        vk = pk.vk
-    else:
-        vk = vk_from_gpu(sh, gpk)
-    return dict(gpk=gpk, kzg=kzg, params=srs_params, vk=vk, got=got, want=want, circ=circ, budget=budget, seen=seen, seed=seed)
-
-
 def free(r):
     r["gpk"].free()
     r["kzg"].free()
@@ -360,10 +329,10 @@ def free(r):
 
 def check_proof_bytes(ctx, params, instance, seed, threads=2):
     """check 3: the library's proof equals the test prover's byte for byte; both verifiers accept it and reject a flipped bit"""
-    r = prove_both(ctx, params, seed, instance=instance, threads=threads)
+    r = PU.prove_both(ctx, params, seed, instance=instance, threads=threads, circuit=RlcCircuit)
     try:
         circ, got = r["circ"], r["got"]
-        assert got == r["want"], "proof bytes differ from tests/rlc_oracle.py's"
+        assert got == r["want"], "proof bytes differ from tests/shape_oracle.py's"
         assert r["seen"][0][0] == 1 and len(r["seen"][0][1]) >= 1
         inst = circ.instance_arrays()
         assert oracle_verify(r["params"], r["vk"], circ.instances, got), "the test verifier rejects the proof"
@@ -497,8 +466,6 @@ def check_limits(ctx, k, lookup_bits, seed):
 
 def check_phased_keys_unmoved(ctx, k, lookup_bits):
     """check 6: a multi-phase key (h2hip_plonk_keygen_phased) proven before and after RLC proofs on the same context: identical bytes"""
-    from tests import phases_util as PU
-
     pparams, _ = PU.shape_params("a", k, lookup_bits)
     pc = PU.PhasedCircuit(pparams, 31)
     kzg, _ = srs(ctx, k, 31)
@@ -508,7 +475,7 @@ def check_phased_keys_unmoved(ctx, k, lookup_bits):
         before = PL.create_proof(ppk, pc.advice0(), [], PreDrawnRng(budget, 12), phase_witness=pc.witness)
         assert PL.verify_proof(ppk, [], before)
         for params, inst in (shape_a(k, lookup_bits), shape_b(k, lookup_bits)):
-            r = prove_both(ctx, params, 40 + params.num_rlc_advice, instance=inst, oracle_prover=False)
+            r = PU.prove_both(ctx, params, 40 + params.num_rlc_advice, instance=inst, oracle_prover=False, circuit=RlcCircuit)
             try:
                 assert PL.verify_proof(r["gpk"], r["circ"].instance_arrays(), r["got"])
             finally:
@@ -531,27 +498,11 @@ def _phased_advice(pc):
     return cols
 
 
-def check_oracle_reduces_to_phased_oracle(k=6):
-    """tests/rlc_oracle.py without RLC gates is tests/phased_oracle.py, byte for byte (no ctx: both are CPU provers)"""
-    from tests import phased_oracle as PO
-    from tests import phases_util as PU
-
-    pparams, _ = PU.shape_params("a", k, 4)
-    pc = PU.PhasedCircuit(pparams, 17)
-    sp = P.Params.setup(k, 0xBEEF12345 + k)
-    pk = oracle_pk(pc.sh, sp, pc.fixed, pc.copies, 2)
-    budget = rng_budget(pc.sh)
-    want = PO.create_proof(sp, pk, pc.advice0(), [], PreDrawnRng(budget, 4), 2, phase_witness=pc.witness)
-    got = RO.create_proof(sp, pk, pc.advice0(), [], PreDrawnRng(budget, 4), 2, phase_witness=pc.witness)
-    assert got == want
-    assert RO.verify_proof(sp, pk.vk, [], got)
-
-
 def check_device_fill_proof(ctx, k, lookup_bits, seed):
     """shape B with phase 1 written on the device — the RLC columns by rlc_fill_chains from values resident before the proof, the other
     phase-1 columns uploaded in place — gives the bytes of the same proof with host-computed columns"""
     params, inst = shape_b(k, lookup_bits)
-    r = prove_both(ctx, params, seed, instance=inst, oracle_prover=False)
+    r = PU.prove_both(ctx, params, seed, instance=inst, oracle_prover=False, circuit=RlcCircuit)
     circ, gpk = r["circ"], r["gpk"]
     d_vals = ctx.to_device(fr(circ.values))
     calls = []

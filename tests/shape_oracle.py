@@ -1,11 +1,20 @@
 """
-TEST INFRASTRUCTURE ONLY.  A CPU create_proof / verify_proof for multi-phase BaseConfig circuits: FlexGateConfig with SecondPhase /
-ThirdPhase gate columns and RangeConfig with later-phase lookup-advice columns (reference halo2-base/src/gates/flex_gate/mod.rs:62-70,121-137,
-gates/range/mod.rs:87-108,131-150), with the challenges a circuit declares after each phase.  The prover commits the advice phase by phase
-and obtains every later phase's witness from a phase_witness(phase, challenges) callback, like libh2hip's h2hip_plonk_create_proof_phased.
-Built from oracle.plonk's keygen, Domain and SHPLONK and tests/dyn_lookup_oracle.py's expression-list lookups; the two functions below are
-dyn_lookup_oracle's create_proof / verify_proof with the advice step generalised.  Pinned to the established oracle: a single-phase shape
-(Shape.from_base) reproduces oracle.plonk.create_proof byte for byte (tests/test_phases.py).
+TEST INFRASTRUCTURE ONLY.  The one CPU create_proof / verify_proof of the proof tests, for the four circuit kinds libh2hip proves: one Shape
+with a constructor per kind, one prover and one verifier that read nothing but the Shape.  They are oracle.plonk's create_proof /
+verify_proof (whose keygen, Domain and SHPLONK they use, over oracle.c_oracle's vector primitives) generalised in three steps:
+
+  - lookups are lists of column expressions compressed by theta (upstream's compress_expressions: acc * theta + e), as halo2-base's dynamic
+    lookup table needs them (BasicDynLookupConfig, reference halo2-base/src/virtual_region/lookups/basic.rs:38-199).  An expression is a
+    list of (kind, column) factors, queried at the current row; a lookup is (input expressions, table expressions);
+  - the advice is committed phase by phase (Shape.phase_cols), each phase's challenges (Shape.phase_challenges) squeezed behind its
+    commitments and every later phase's witness obtained from a phase_witness(phase, challenges) callback, like libh2hip's
+    h2hip_plonk_create_proof_phased: multi-phase BaseConfig, i.e. FlexGateConfig with SecondPhase / ThirdPhase gate columns and RangeConfig
+    with later-phase lookup-advice columns (reference halo2-base/src/gates/flex_gate/mod.rs:62-70,121-137, gates/range/mod.rs:87-108,131-150);
+  - RLC columns (Shape.rlc_gates): phase-1 advice columns with a selector each and the vertical gate q_rlc * (a[r] * gamma + a[r+1] -
+    a[r+2]), gamma = challenge 0, folded behind the flex gates (the layout include/h2hip.h states for h2hip_rlc_circuit_params).
+
+Pinned twice (tests/test_shape_oracle.py): for BaseConfig shapes (Shape.from_base) it reproduces oracle.plonk.create_proof byte for byte, and
+for dynamic-lookup, multi-phase and RLC circuits it reproduces the recorded digests of tests/golden/test_prover_proof_digests.json.
 """
 from __future__ import annotations
 
@@ -20,21 +29,62 @@ from oracle import c_oracle as CO
 from oracle import pairing as PR
 from oracle import plonk as P
 from oracle.transcript import Blake2bRead, Blake2bWrite
-from tests import dyn_lookup_oracle as D
-from tests.dyn_lookup_oracle import compress, compress_evals
 
 R = O.R_MOD
 fr1, to_int = P.fr1, P.to_int
 
 
-class Shape(D.Shape):
-    """dyn_lookup_oracle.Shape plus the phase layout: phase_cols (advice columns of each used phase) and phase_challenges"""
+class Shape:
+    """the attributes oracle.plonk's keygen and the prover below read: lookups as expression lists, phase_cols (the advice columns of each
+    used phase), phase_challenges (how many are squeezed after each) and rlc_gates ((q_rlc fixed column, RLC advice column) pairs)"""
 
     @classmethod
     def from_base(cls, base: P.Shape) -> "Shape":
-        s = super().from_base(base)
-        s.phase_cols = [list(range(base.num_advice_total))]
-        s.phase_challenges = [0]
+        s = cls()
+        s.__dict__.update(base.__dict__)
+        s._pinned = base.pinned()
+        s.lookups = [([[("advice", a)] if q is None else [("fixed", q), ("advice", a)]], [[("fixed", t)]]) for (q, a, t) in base.lookups]
+        s._one_phase()
+        return s
+
+    def _one_phase(self):
+        self.phase_cols, self.phase_challenges, self.rlc_gates = [list(range(self.num_advice_total))], [0], []
+
+    def _derive(self, degree: int):
+        """what follows from the columns, gates and lookups of a configuration with gates of 4 rotations"""
+        self.degree = degree
+        self.blinding_factors = max(3, 4) + 2
+        self.usable_rows = self.n - (self.blinding_factors + 1)
+        self.chunk_len = self.degree - 2
+        self.quotient_poly_degree = self.degree - 1
+        ek = self.k
+        while (1 << ek) < self.n * self.quotient_poly_degree:
+            ek += 1
+        self.extended_k = ek
+        self.num_perm_sets = (len(self.perm_columns) + self.chunk_len - 1) // self.chunk_len
+
+    @classmethod
+    def dyn(cls, k: int, num_advice: int, num_fixed: int, key_cols: int, lu_sets: int) -> "Shape":
+        """BasicDynLookupConfig::new(meta, || FirstPhase, lu_sets) + FlexGateConfig::configure, in the layout include/h2hip.h states"""
+        s = cls()
+        m, L = key_cols, lu_sets
+        ndyn = m * (1 + L)
+        s.k, s.n, s.num_instance, s.num_fixed = k, 1 << k, 0, num_fixed
+        s.gate_advice = list(range(ndyn, ndyn + num_advice))
+        s.num_advice_total = ndyn + num_advice
+        s.constant_cols = list(range(1 + L, 1 + L + num_fixed))
+        s.q_enable_cols = list(range(1 + L + num_fixed, 1 + L + num_fixed + num_advice))
+        s.num_fixed_total = 1 + L + num_fixed + num_advice
+        s.gates = list(zip(s.q_enable_cols, s.gate_advice))
+        s.lookups = [([[("advice", m * (1 + j) + i)] for i in range(m)] + [[("fixed", 1 + j)]],
+                      [[("advice", i)] for i in range(m)] + [[("fixed", 0)]]) for j in range(L)]
+        s.perm_columns = [("advice", c) for c in range(ndyn)] + [("fixed", c) for c in s.constant_cols] + [("advice", a) for a in s.gate_advice]
+        s.advice_queries = [(c, 0) for c in range(ndyn)] + [(a, r) for a in s.gate_advice for r in range(4)]
+        s.fixed_queries = [(c, 0) for c in range(s.num_fixed_total)]
+        s.instance_queries = []
+        s._derive(4)
+        s._one_phase()
+        s._pinned = PL.describe(PL.DynLookupCircuitParams.new(k, num_advice, num_fixed, m, L))   # the description transcript_repr hashes
         return s
 
     @classmethod
@@ -74,27 +124,75 @@ class Shape(D.Shape):
         s.fixed_queries = [(c, 0) for c in s.constant_cols] + ([(table, 0)] if rng else []) + ([(qcol, 0)] if q else []) + \
                           [(c, 0) for c in s.q_enable_cols]
         s.instance_queries = [(i, 0) for i in range(params.num_instance)]
-        s.degree = max([3] + [max(4, 2 + (2 if (q and i == 0) else 1) + 1) for i in range(len(s.lookups))])
-        s.blinding_factors = max(3, 4) + 2
-        s.usable_rows = s.n - (s.blinding_factors + 1)
-        s.chunk_len = s.degree - 2
-        s.quotient_poly_degree = s.degree - 1
-        ek = k
-        while (1 << ek) < s.n * s.quotient_poly_degree:
-            ek += 1
-        s.extended_k = ek
-        s.num_perm_sets = (len(s.perm_columns) + s.chunk_len - 1) // s.chunk_len
+        s._derive(max([3] + [max(4, 2 + (2 if (q and i == 0) else 1) + 1) for i in range(len(s.lookups))]))
         s.table_col, s.q_lookup_col = table, qcol
         s.phase_cols = phase_cols
         s.phase_challenges = list(params.num_challenges_per_phase)[: len(phase_cols)]
+        s.rlc_gates = []
         s._pinned = PL.describe(params)   # the description transcript_repr hashes (halo2_lib_amd.plonk.describe)
         return s
+
+    @classmethod
+    def rlc(cls, params: "PL.RlcCircuitParams") -> "Shape":
+        """BaseConfig::configure(params.base), then the RLC columns: last advice indices (phase 1), their selectors behind every fixed column,
+        their permutation columns behind the instance columns, rotations 0, 1, 2"""
+        s = cls.phased(params.base)
+        nr = params.num_rlc_advice
+        a0, f0 = s.num_advice_total, s.num_fixed_total
+        s.rlc_advice = list(range(a0, a0 + nr))
+        s.q_rlc_cols = list(range(f0, f0 + nr))
+        s.num_advice_total, s.num_fixed_total = a0 + nr, f0 + nr
+        s.rlc_gates = list(zip(s.q_rlc_cols, s.rlc_advice))
+        s.perm_columns = s.perm_columns + [("advice", a) for a in s.rlc_advice]
+        s.advice_queries = s.advice_queries + [(a, r) for a in s.rlc_advice for r in range(3)]
+        s.fixed_queries = s.fixed_queries + [(c, 0) for c in s.q_rlc_cols]
+        s.num_perm_sets = (len(s.perm_columns) + s.chunk_len - 1) // s.chunk_len
+        s.phase_cols = [list(c) for c in s.phase_cols]
+        while len(s.phase_cols) < 2:
+            s.phase_cols.append([])
+        s.phase_cols[1] = s.phase_cols[1] + s.rlc_advice
+        ch = list(params.base.num_challenges_per_phase)
+        s.phase_challenges = ch[: len(s.phase_cols)]
+        assert s.phase_challenges[0] >= 1
+        s._pinned = PL.describe(params)
+        return s
+
+    def pinned(self) -> str:
+        return self._pinned
+
+
+def compress(exprs, columns: dict, theta: int, T: int = 1) -> np.ndarray:
+    """Horner in theta over the expressions' values (columns: kind -> list of arrays, Lagrange or extended domain alike)"""
+    acc = None
+    for factors in exprs:
+        e = columns[factors[0][0]][factors[0][1]]
+        for kind, idx in factors[1:]:
+            e = CO.fr_mul_mt(e, columns[kind][idx], T)
+        acc = np.array(e, dtype=np.uint64) if acc is None else CO.fr_lincomb(acc, fr1(theta), e, None, None, T)
+    return acc
+
+
+def compress_evals(exprs, col_eval, theta: int) -> int:
+    acc = 0
+    for factors in exprs:
+        e = 1
+        for kind, idx in factors:
+            e = e * col_eval(kind, idx) % R
+        acc = (acc * theta + e) % R
+    return acc
+
+
+def rlc_gate(acc, q, a, gamma: int, y, step: int, T: int = 1):
+    """acc * y + q * (a * gamma + a[i + step] - a[i + 2 step]) over the extended domain (indices wrap)"""
+    t = CO.fr_lincomb(a, fr1(gamma), np.ascontiguousarray(np.roll(a, -step, axis=0)), None, None, T)
+    t = CO.fr_lincomb(t, None, np.ascontiguousarray(np.roll(a, -2 * step, axis=0)), fr1(R - 1), None, T)
+    return CO.fr_axpy(CO.fr_mul_mt(q, t, T), y, acc, T)
 
 
 def create_proof(params: P.Params, pk: P.ProvingKey, advice: List[np.ndarray], instances: List[List[int]], rng, threads: int = 1, timings: dict = None,
                  phase_witness=None) -> bytes:
-    """dyn_lookup_oracle.create_proof with the advice committed phase by phase (Shape.phase_cols): `advice` holds phase 0's columns,
-    phase_witness(phase, challenges) -> columns the later phases'"""
+    """oracle.plonk.create_proof over a Shape of this module: `advice` holds phase 0's columns (every column of a one-phase shape),
+    phase_witness(phase, challenges) -> columns the later phases' (phase 1's list ends with the RLC columns)"""
     import time as _time
 
     sh = pk.vk.shape
@@ -229,6 +327,8 @@ def create_proof(params: P.Params, pk: P.ProvingKey, advice: List[np.ndarray], i
     acc = np.tile(fr1(0)[0], (ne, 1))
     for (qcol, acol) in sh.gates:
         CO.quotient_gate(acc, pk.fixed_cosets[qcol], adv_cosets[acol], Y, dom.step, T)
+    for (qcol, acol) in sh.rlc_gates:
+        acc = rlc_gate(acc, pk.fixed_cosets[qcol], adv_cosets[acol], challenges[0], Y, dom.step, T)
     lap("quotient_gates")
     if perm_polys:
         perm_cosets = [dom.coeff_to_extended(p, T) for p in perm_polys]
@@ -323,7 +423,8 @@ def create_proof(params: P.Params, pk: P.ProvingKey, advice: List[np.ndarray], i
 
 
 def verify_proof(params: P.Params, vk: P.VerifyingKey, instances: List[List[int]], proof: bytes) -> bool:
-    """dyn_lookup_oracle.verify_proof with the advice commitments read phase by phase, each phase's challenges squeezed after them"""
+    """oracle.plonk.verify_proof over a Shape of this module: the advice commitments read phase by phase, each phase's challenges squeezed
+    after them, and the RLC gates' terms (challenge 0 of the replay) in the quotient identity"""
     sh = vk.shape
     dom = P.Domain(sh)
     n, bf = sh.n, sh.blinding_factors
@@ -337,11 +438,12 @@ def verify_proof(params: P.Params, vk: P.VerifyingKey, instances: List[List[int]
             for v_ in vals:
                 tr.common_scalar(v_)
         advice_comm = [None] * sh.num_advice_total
+        challenges = []
         for ph, pcols in enumerate(sh.phase_cols):
             for c in pcols:
                 advice_comm[c] = tr.read_point()
             for _ in range(sh.phase_challenges[ph]):
-                tr.squeeze_challenge()
+                challenges.append(tr.squeeze_challenge())
         theta = tr.squeeze_challenge()
         lk_perm_comm = [(tr.read_point(), tr.read_point()) for _ in sh.lookups]
         beta = tr.squeeze_challenge()
@@ -379,6 +481,8 @@ def verify_proof(params: P.Params, vk: P.VerifyingKey, instances: List[List[int]
     exprs = []
     for (qcol, acol) in sh.gates:
         exprs.append(f_eval[(qcol, 0)] * (a_eval[(acol, 0)] + a_eval[(acol, 1)] * a_eval[(acol, 2)] - a_eval[(acol, 3)]) % R)
+    for (qcol, acol) in sh.rlc_gates:
+        exprs.append(f_eval[(qcol, 0)] * (a_eval[(acol, 0)] * challenges[0] + a_eval[(acol, 1)] - a_eval[(acol, 2)]) % R)
     if sh.num_perm_sets:
         exprs.append(l_0 * (1 - perm_evals[0][0]) % R)
         zl = perm_evals[-1][0]
@@ -472,3 +576,11 @@ def verify_proof(params: P.Params, vk: P.VerifyingKey, instances: List[List[int]
     outer = O.g1_add(outer, O.g1_mul(h2, u))
     # DualMSM::check: e(left, s_g2) * e(-right, g2) == 1  with left = h2, right = outer
     return PR.pairing_product_is_one([(h2, params.s_g2), (O.g1_neg(outer), params.g2)])
+
+
+def oracle_verify(params: P.Params, vk: P.VerifyingKey, instances: List[List[int]], proof: bytes) -> bool:
+    """verify_proof with a malformed proof counted as a rejected one"""
+    try:
+        return verify_proof(params, vk, instances, proof)
+    except P.VerifyError:
+        return False

@@ -1,44 +1,14 @@
 """Proofs of circuits with a dynamic lookup table (BasicDynLookupConfig, reference halo2-base/src/virtual_region/lookups/basic.rs:38-199) on the
-CPU: the test-side prover against the established oracle, libh2hip's emulated build against the test prover, and the host mirror's layout."""
+CPU: libh2hip's emulated build against the test prover (itself pinned by tests/test_shape_oracle.py), and the host mirror's layout."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from halo2_lib_amd import plonk as PL
-from halo2_lib_amd import testing as T
 from halo2_lib_amd import virtual_region as V
-from oracle import c_oracle as CO
-from oracle import plonk as P
-from tests import dyn_lookup_oracle as D
+from tests import shape_oracle as SO
 from tests.dyn_lookup_util import PreDrawnRng, R, oracle_verify, prove_both, ram_circuit, rng_budget, oracle_shape, srs
-
-
-class _OracleBackend:
-    mul = staticmethod(CO.fr_mul)
-    add = staticmethod(CO.fr_add)
-
-
-# ---- 1. the test prover is the oracle for BaseConfig shapes
-@pytest.mark.parametrize("shape", [(6, 1, 0, 1, 0, None), (6, 1, 1, 1, 0, 4), (7, 2, 1, 1, 1, 5), (5, 6, 4, 1, 1, 3)],
-                         ids=["no_lookups", "q_lookup", "lookup_advice", "k5_wide"])
-def test_test_prover_reproduces_oracle_on_base_shapes(shape):
-    k = shape[0]
-    sh = P.Shape(*shape)
-    params = P.Params.setup(k, 0xABCDEF12345 + k)
-    circ = T.build_circuit(sh, 5, _OracleBackend)
-    asm = P.PermutationAssembly(sh)
-    for l, r in circ.copies:
-        asm.copy(l, r)
-    pk = P.keygen(params, sh, circ.fixed, asm, 2)
-    inst = [[int(v) for v in CO_ints(c)] for c in circ.instances]
-    budget = rng_budget(sh)
-    want = P.create_proof(params, pk, circ.advice, inst, PreDrawnRng(budget, 77), 2)
-    dsh = D.Shape.from_base(sh)
-    pk.vk.shape = dsh
-    got = D.create_proof(params, pk, circ.advice, inst, PreDrawnRng(budget, 77), 2)
-    assert got == want
-    assert D.verify_proof(params, pk.vk, inst, got)
 
 
 def CO_ints(col):
@@ -148,7 +118,7 @@ def test_shape_of_dyn_layout():
     # advice: 2 table + 2 x 2 key + 3 gate; fixed: table_is_enabled, 2 key_is_enabled, 1 constant, 3 q_enable
     assert (out.num_advice_total, out.num_fixed_total, out.table_col, out.q_lookup_col, out.first_constant_col, out.first_q_enable_col) == (9, 7, -1, -1, 3, 4)
     assert (out.num_lookups, out.num_perm_columns, out.degree, out.blinding_factors, out.usable_rows, out.quotient_pieces) == (2, 10, 4, 6, 1017, 3)
-    sh = D.Shape.dyn(10, 3, 1, 2, 2)
+    sh = SO.Shape.dyn(10, 3, 1, 2, 2)
     assert out.num_perm_sets == sh.num_perm_sets and out.extended_k == sh.extended_k
     evals = len(sh.advice_queries) + len(sh.fixed_queries) + 1 + len(sh.perm_columns) + 3 * sh.num_perm_sets - 1 + 5 * len(sh.lookups)
     assert out.num_evals == evals

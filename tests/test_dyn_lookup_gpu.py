@@ -1,5 +1,5 @@
 """Proofs with a dynamic lookup table (BasicDynLookupConfig) on the GPU: reference-sized RAM circuits against the test-side prover
-(tests/dyn_lookup_oracle.py), a table near the usable rows (the bitonic sort's global passes), the failed-access error, and a BaseConfig
+(tests/shape_oracle.py), a table near the usable rows (the bitonic sort's global passes), the failed-access error, and a BaseConfig
 proof before and after a dynamic one on the same context."""
 import numpy as np
 import pytest

@@ -1,6 +1,6 @@
 """Multi-phase BaseConfig circuits (SecondPhase / ThirdPhase gate and lookup-advice columns, challenges; reference
-halo2-base/src/gates/flex_gate/mod.rs:62-70,121-137, gates/range/mod.rs:87-108) on the CPU: the test-side prover against the established
-oracle, libh2hip's emulated build against the test prover, the layout, the refusals and the error paths."""
+halo2-base/src/gates/flex_gate/mod.rs:62-70,121-137, gates/range/mod.rs:87-108) on the CPU: libh2hip's emulated build
+against the test prover (itself pinned by tests/test_shape_oracle.py), the layout, the refusals and the error paths."""
 import ctypes as C
 import os
 import re
@@ -10,10 +10,9 @@ import pytest
 
 from halo2_lib_amd import plonk as PL
 from halo2_lib_amd import testing as T
-from oracle import bn254 as O
 from oracle import c_oracle as CO
 from oracle import plonk as P
-from tests import phased_oracle as PO
+from tests import shape_oracle as SO
 from tests.dyn_lookup_util import rng_budget
 from tests.phases_util import PhasedCircuit, PreDrawnRng, R, first_phase1_commitment, oracle_verify, prove_both, shape_params
 
@@ -21,10 +20,6 @@ from tests.phases_util import PhasedCircuit, PreDrawnRng, R, first_phase1_commit
 class _OracleBackend:
     mul = staticmethod(CO.fr_mul)
     add = staticmethod(CO.fr_add)
-
-
-def _ints(col):
-    return O.limbs_to_ints(np.ascontiguousarray(col, dtype=np.uint64).reshape(-1, 4), R)
 
 
 @pytest.fixture(scope="module")
@@ -39,27 +34,6 @@ def ctx():
 def _free(r):
     r["gpk"].free()
     r["kzg"].free()
-
-
-# ---- 1. the test prover is the oracle for single-phase BaseConfig shapes
-@pytest.mark.parametrize("shape", [(6, 1, 0, 1, 0, None), (6, 1, 1, 1, 0, 4), (7, 2, 1, 1, 1, 5), (5, 6, 4, 1, 1, 3)],
-                         ids=["no_lookups", "q_lookup", "lookup_advice", "k5_wide"])
-def test_test_prover_reproduces_oracle_on_base_shapes(shape):
-    k = shape[0]
-    sh = P.Shape(*shape)
-    params = P.Params.setup(k, 0xBEEF12345 + k)
-    circ = T.build_circuit(sh, 5, _OracleBackend)
-    asm = P.PermutationAssembly(sh)
-    for l, r in circ.copies:
-        asm.copy(l, r)
-    pk = P.keygen(params, sh, circ.fixed, asm, 2)
-    inst = [_ints(c) for c in circ.instances]
-    budget = rng_budget(sh)
-    want = P.create_proof(params, pk, circ.advice, inst, PreDrawnRng(budget, 77), 2)
-    pk.vk.shape = PO.Shape.from_base(sh)
-    got = PO.create_proof(params, pk, circ.advice, inst, PreDrawnRng(budget, 77), 2)
-    assert got == want
-    assert PO.verify_proof(params, pk.vk, inst, got)
 
 
 # ---- 2. libh2hip (emulated build) against the test prover
@@ -298,7 +272,7 @@ def test_shape_of_phased_layout():
     rc, out = _shape(lib, 10, [2, 3], [1, 1], 0, 0, None, [2])
     assert rc == 0 and (out.num_advice_total, out.table_col, out.num_lookups, out.num_fixed_total) == (5, -1, 0, 5)
     for p in (PL.PhasedCircuitParams.new(10, [1, 1], [1, 1], 1, 0, 8, [1]), PL.PhasedCircuitParams.new(10, [2, 1, 1], [1, 0, 1], 2, 1, 8, [1, 1])):
-        sh = PO.Shape.phased(p)
+        sh = SO.Shape.phased(p)
         rc, out = _shape(lib, 10, list(p.num_advice_per_phase), list(p.num_lookup_advice_per_phase), p.num_fixed, p.num_instance,
                          p.lookup_bits, list(p.num_challenges_per_phase))
         assert (out.num_advice_total, out.num_fixed_total, out.num_lookups, out.num_perm_sets, out.degree, out.extended_k) == (

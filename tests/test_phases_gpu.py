@@ -1,4 +1,4 @@
-"""Multi-phase BaseConfig proofs on the GPU: shape (a) at k = 10 against the test-side prover (tests/phased_oracle.py) with phase-0 advice on
+"""Multi-phase BaseConfig proofs on the GPU: shape (a) at k = 10 against the test-side prover (tests/shape_oracle.py) with phase-0 advice on
 the host and on the device and later phases written by h2hip_upload and from a device tensor, a k = 17 two-phase circuit with range lookups
 in both phases, and a BaseConfig k = 19 proof before and after multi-phase proofs on the same context."""
 import numpy as np

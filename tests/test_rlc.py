@@ -1,5 +1,5 @@
 """RLC circuits on the CPU-emulated build: the device fill and the quotient kernel against their definitions, proof bytes against the test-side
-prover (tests/rlc_oracle.py), soundness, the refusals, and multi-phase keys before and after.  The checks live in tests/rlc_checks.py and run
+prover (tests/shape_oracle.py), soundness, the refusals, and multi-phase keys before and after.  The checks live in tests/rlc_checks.py and run
 on the GPU from tests/test_rlc_gpu.py."""
 import pytest
 
@@ -14,10 +14,6 @@ def ctx():
     c = emu_context()
     yield c
     c.close()
-
-
-def test_oracle_without_rlc_gates_is_the_phased_oracle():
-    RC.check_oracle_reduces_to_phased_oracle()
 
 
 @pytest.mark.parametrize("gamma", RC.FILL_GAMMAS, ids=["zero", "one", "r_minus_1", "random"])

@@ -5,7 +5,7 @@ Two transcripts, both plain Python:
   T1  oracle.transcript.Blake2bWrite / Blake2bRead themselves: through the callbacks they must give the built-in entries' bytes;
   T2  a transcript the library has never seen: a sponge over oracle/poseidon.py's Spec(3, 8, 57) that absorbs a point as the four 128-bit
       halves of x and y and a scalar as itself, squeezes a full-width Fr, and serialises points uncompressed (64 B, big-endian) and scalars
-      big-endian.  It claims no upstream format.  The four Python provers build their transcript through the module-level names Blake2bWrite /
+      big-endian.  It claims no upstream format.  The two Python provers (oracle.plonk and tests/shape_oracle.py) build their transcript through the module-level names Blake2bWrite /
       Blake2bRead, so pytest's monkeypatch makes them prove and verify over T2: exact equalities, no recalled statement.
 """
 import ctypes as C
@@ -22,10 +22,8 @@ from oracle import c_oracle as CO
 from oracle import plonk as P
 from oracle import poseidon as PS
 from oracle.transcript import Blake2bRead, Blake2bWrite
-from tests import dyn_lookup_oracle as D
-from tests import phased_oracle as PO
 from tests import rlc_checks as RC
-from tests import rlc_oracle as RO
+from tests import shape_oracle as SO
 from tests.dyn_lookup_util import oracle_pk, oracle_shape, ram_circuit, rng_budget, srs
 from tests.phases_util import PhasedCircuit, shape_params
 from tests.util import PreDrawnRng, R, fr
@@ -199,15 +197,15 @@ def make_case(ctx, name, k):
         return _base_case(ctx, name, k, 2, 1, 1, 1, lb, 12)
     if name == "dyn":      # dynamic lookup: key_cols 2, 2 sets
         _, dp, advice, fixed, copies = ram_circuit(k, 40, 16, 2, 2, seed=13)
-        return Case(ctx, name, D, dp, oracle_shape(dp), fixed, copies, advice, [], 13)
+        return Case(ctx, name, SO, dp, oracle_shape(dp), fixed, copies, advice, [], 13)
     if name == "phased":   # two phases [1, 1] / [1, 1] with one challenge
         params, inst = shape_params("a", k, lb)
         circ = PhasedCircuit(params, 14, instance=inst)
-        return Case(ctx, name, PO, params, circ.sh, circ.fixed, circ.copies, circ.advice0(), circ.instances, 14, witness=circ.witness, num_challenges=1)
+        return Case(ctx, name, SO, params, circ.sh, circ.fixed, circ.copies, circ.advice0(), circ.instances, 14, witness=circ.witness, num_challenges=1)
     if name == "rlc":      # RLC shape B
         params, inst = RC.shape_b(k, lb)
         circ = RC.RlcCircuit(params, 15, instance=inst)
-        return Case(ctx, name, RO, params, circ.sh, circ.fixed, circ.copies, circ.advice0(), circ.instances, 15, witness=circ.witness, num_challenges=1)
+        return Case(ctx, name, SO, params, circ.sh, circ.fixed, circ.copies, circ.advice0(), circ.instances, 15, witness=circ.witness, num_challenges=1)
     raise ValueError(name)
 
 

@@ -1,7 +1,7 @@
 """Test-side checker of h2hip_plonk_check_witness's contract (include/h2hip.h): MockProver's verdict for the one gate form and the lookup forms
 of BaseConfig, the dynamic lookup table and multi-phase BaseConfig, in plain Python integers.
 
-Shapes: oracle.plonk.Shape (BaseConfig), tests.dyn_lookup_oracle.Shape.dyn and tests.phased_oracle.Shape.phased.  All three carry `gates`
+Shapes: oracle.plonk.Shape (BaseConfig), tests.shape_oracle.Shape.dyn and Shape.phased.  All three carry `gates`
 [(q_enable fixed column, advice column)], `perm_columns` [(kind, index)] and `usable_rows`; their lookups are (q, advice, table) triples
 (BaseConfig) or (input expressions, table expressions) with every expression a product of (kind, index) factors.
 

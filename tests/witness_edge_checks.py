@@ -551,10 +551,10 @@ def check_rlc_gate_edge(ctx, k, lookup_bits):
     (values that do) is written out by hand from the contract."""
     import halo2_lib_amd as H
     from tests import rlc_checks as RC
-    from tests import rlc_oracle as RO
+    from tests import shape_oracle as SO
 
     params, _ = RC.shape_a(k, lookup_bits)
-    sh = RO.Shape.rlc(params)
+    sh = SO.Shape.rlc(params)
     n, u = sh.n, sh.usable_rows
     one = fr([1])[0]
     gate_adv, rlc_adv = 0, sh.rlc_advice[0]

@@ -17,9 +17,9 @@ TR = "halo2-lib_amd/csrc/transcript.h"   # the transcript interface and its buil
 OP, OT, OB = "oracle/plonk.py", "oracle/transcript.py", "oracle/bn254.py"
 HP, VR, PL = "halo2-lib_amd/halo2_proofs.py", "halo2-lib_amd/virtual_region.py", "halo2-lib_amd/plonk.py"
 RG, OC = "halo2-lib_amd/csrc/rng.hip", "oracle/chacha.py"
-PO = "tests/phased_oracle.py"
+SO = "tests/shape_oracle.py"   # the test-side prover of the four circuit kinds
 VB = "halo2-lib_amd/csrc/verify_batch.hip"
-RL, RO = "halo2-lib_amd/csrc/rlc.hip", "tests/rlc_oracle.py"
+RL = "halo2-lib_amd/csrc/rlc.hip"
 
 # (item, what is assumed about upstream, [(file, anchor)] product, [(file, anchor)] oracle, how to flip)
 ITEMS = [
@@ -73,14 +73,14 @@ ITEMS = [
      [(VR, 'region.constrain_equal(self.copy_manager.assigned_advices[inst.cell], (("instance", col), i))'), (VR, "copy_manager.constant_equalities.sort(key=lambda t: (t[0], t[1]))")], [],
      "`virtual_region.py` (and `host/halo2_proofs.hpp`); affects the sigma polynomials (verifying key), not validity"),
     ("multi-phase advice order", "after the instances, per phase in order: the blinding rows of the phase's advice columns (column by column, index order), one blind per column, the phase's commitments in index order, then the challenges `challenge_usable_after(phase)` squeezed (Challenge255); the next phase's witness is synthesised with them; theta follows the last phase.  The advice commitments in the proof are grouped by phase, not in column order; the RNG draws the same number of values before the random polynomial",
-     [(PP, "// Multi-phase keys [UPSTREAM-RECALL: create_proof's per-phase loop]")], [(PO, "# ---- advice, phase by phase [UPSTREAM-RECALL")],
+     [(PP, "// Multi-phase keys [UPSTREAM-RECALL: create_proof's per-phase loop]")], [(SO, "# ---- advice, phase by phase [UPSTREAM-RECALL")],
      "`ProofRun::round1_phased` (and `blind_phase`) with the phase loop of `derive` (verifier.hip), which replays it over the same `Shape::phase_cols`, and the oracle's block"),
     ("batch verification", "`BatchVerifier::finalize` / `AccumulatorStrategy` combine the proofs' final pairing inputs with random scalars into ONE `DualMSM` check; only the verdict is shared with upstream (no bytes), and which random scalars upstream draws, and from what, is not relied on",
      [(VB, "upstream's BatchVerifier / AccumulatorStrategy seam [UPSTREAM-RECALL")], [],
      "nothing to flip for correctness: any non-zero combiners decide the same batches except with probability ~ N/r; the combiners come through the caller's `h2hip_rng_fill_fn`"),
     ("RLC configuration (downstream's `RlcConfig` / `RlcChip`, not in the reference tree)", "`RlcConfig::configure` runs after `BaseConfig::configure`: per RLC column a SecondPhase advice column with equality enabled, a selector `q_rlc`, and the gate `q_rlc * (a * gamma + a_next - a_next2)` at rotations 0, 1, 2 with gamma = the first challenge usable after FirstPhase; so the RLC columns take the last advice indices, their selectors the last fixed columns, their permutation columns come last, and their gates fold into h(X) behind the flex gates.  `compute_rlc_fixed_len` lays a chain out as v_0, v_1, r_1, v_2, r_2, ... with r_i = r_(i-1) * gamma + v_i, and a chain that crosses a column break repeats the break cell at the top of the next column",
      [(PI, "int init_rlc(const h2hip_rlc_circuit_params &rp) {"), (PP, "if (sh.num_rlc) {   // the RLC gates follow the flex gates"), (RL, "// the cells: a head piece's v_0, v_1, r_1, v_2, r_2, ...")],
-     [(RO, "def rlc(cls, params: \"PL.RlcCircuitParams\") -> \"Shape\":"), (RO, "def rlc_gate(acc, q, a, gamma: int, y, step: int, T: int = 1):")],
+     [(SO, "def rlc(cls, params: \"PL.RlcCircuitParams\") -> \"Shape\":"), (SO, "def rlc_gate(acc, q, a, gamma: int, y, step: int, T: int = 1):")],
      "`Shape::layout`'s `num_rlc` lines (column numbering, query and permutation order: the one place, prover and verifier read it); the fold position is the RLC call inside `ProofRun::quotient_pass` with the `rlc_gates()` loop of `derive`; the cell order is `rlc_place_kernel`'s index arithmetic"),
 ]
 
